@@ -13,6 +13,12 @@ whose SrcIP hashes to it and processes its own 100M-packet shard stream (weak
 scaling, no data-path collective); after the timed region the ranks
 all-gather their heavy-hitter candidates (the per-window exchange).
 
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs DIR is given, and prints the line.  --full adds what
+else the bench measures and checks after the timed steps: the configs[3] window
+cycle, the flow-dictionary reclaim, the heavy-hitter lists, the CPU baselines
+and the bit-exact parity leg against the sequential oracle.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -232,11 +238,12 @@ def bench_superspread(args, torch, dist, world, rank, local):
             traffic = json.load(open(tfile)).get(dom)
         except Exception:
             traffic = None
-    hh = ss.heavy_hitters()  # first call sizes the list's buffers; the next three are timed
-    t_hh = time.perf_counter()
-    for _ in range(3):
-        hh_n = len(ss.heavy_hitters_arrays()[1])
-    t_hh = (time.perf_counter() - t_hh) / 3
+    if args.full:
+        hh = ss.heavy_hitters()  # first call sizes the list's buffers; the next three are timed
+        t_hh = time.perf_counter()
+        for _ in range(3):
+            hh_n = len(ss.heavy_hitters_arrays()[1])
+        t_hh = (time.perf_counter() - t_hh) / 3
     line = {
         "metric": "Mpackets/s SuperSpread update (device-resident, d=2 w=32768 m=128)",
         "value": round(n * args.steps * world / elapsed / 1e6, 2), "unit": "Mpackets/s", "n_gpus": world,
@@ -251,12 +258,14 @@ def bench_superspread(args, torch, dist, world, rank, local):
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "bytes_per_packet": BYTES_PER_PKT, "kernel_avg_ms": round(avg_ms, 4)},
         "stage_ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in stages.items()},
-        "heavy_hitters": len(hh.Count), "engine_counters": ss.counters(),
-        "heavy_hitters_ms": round(t_hh * 1e3, 3),
-        "heavy_hitters_how": f"{hh_n} flows; device list (candidates, per-flow max, radix order), one D2H; "
-                             "mean of 3 calls after the sizing call, after the timed steps",
+        "engine_counters": ss.counters(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full:
+        line["heavy_hitters"] = len(hh.Count)
+        line["heavy_hitters_ms"] = round(t_hh * 1e3, 3)
+        line["heavy_hitters_how"] = (f"{hh_n} flows; device list (candidates, per-flow max, radix order), one D2H; "
+                                     "mean of 3 calls after the sizing call, after the timed steps")
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         ph, pw = syn.generate(8_000_000)
         base, orc_ss, done = cpu_baseline_ss(ph, pw)
         line["cpu_baseline"] = base
@@ -359,7 +368,7 @@ def bench_exact(args, torch, dist, world, rank, local):
         "stage_ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in stages.items()},
         "engine_counters": task.agg.counters(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline_exact(hdr, wl, ts)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -658,7 +667,7 @@ def bench_c1(args, torch, dist, world, rank, local):
                    "insert_only_rate": round(n * K / t_gpu / 1e6, 2)},
         "note": "not the headline metric; the reference pcap-analyzer is a CPU path (BASELINE configs[0])",
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         o = orc.CountMin(W, D, 1 << 20, 1000, 37, seeds)
         t0 = time.perf_counter()
         o.insert_hdr64(hb.hdr, hb.wirelen, FIELDS)
@@ -744,6 +753,48 @@ def bench_windows(args, torch, dist, world, cm, timed_step, n):
             if world > 1 else "none (one shard: the device list is already the global one)"}
 
 
+# --dump-outputs sample sizes: 2 x 2^21 counters (f64) + 2 x 2^15 fingerprint rows (f32) + the
+# heavy-hitter lists (<= 2^19 values, <= 2^15 flows each) stay under 64 MB for every geometry
+DUMP_COUNTERS, DUMP_ROWS, DUMP_HH_VALUES = 1 << 21, 1 << 15, 1 << 19
+DUMP_SEED = 0x5EED0D0
+DUMP_FP_HOST_BYTES = 1 << 30  # fingerprints are exported whole before sampling; skipped above this
+
+
+def dump_outputs(cm, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as
+    DIR/<name>.npy (rank r > 0 of an N-rank run: <name>.rank<r>.npy).  Counter rows C and S
+    (float64, exact for u32), the two fingerprint arrays (float32 of the key bytes) and the
+    two heavy-hitter lists in the engine's canonical order.  Arrays larger than their share
+    of the 64 MB are sampled at fixed, seeded, sorted positions (the same positions for C and
+    S, and the same rows for both fingerprint arrays); the lists keep their head."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = cm.depth * cm.width
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def pick(total, k):
+        return np.arange(total) if total <= k else np.sort(rng.choice(total, k, replace=False))
+
+    ci, ri = pick(n, DUMP_COUNTERS), pick(n, DUMP_ROWS)
+    out = {}
+    if 2 * n * max(cm.key_bytes, 1) <= DUMP_FP_HOST_BYTES:
+        C, S, Fc, Fs = cm.export_state()
+        out["fingerprints_count"] = Fc[ri].astype(np.float32)
+        out["fingerprints_size"] = Fs[ri].astype(np.float32)
+    else:
+        C, S = cm.export_counters()
+    out["counters_count"] = C[ci].astype(np.float64)
+    out["counters_size"] = S[ci].astype(np.float64)
+    cf, cv, sf, sv = cm.heavy_hitters_arrays()
+    out["heavy_lengths"] = np.array([len(cv), len(sv)], np.float64)
+    out["heavy_count_values"] = cv[:DUMP_HH_VALUES].astype(np.float64)
+    out["heavy_size_values"] = sv[:DUMP_HH_VALUES].astype(np.float64)
+    out["heavy_count_flows"] = cf[:DUMP_ROWS, : cm.key_bytes].astype(np.float32)
+    out["heavy_size_flows"] = sf[:DUMP_ROWS, : cm.key_bytes].astype(np.float32)
+    suffix = f".rank{rank}" if world > 1 and rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -751,7 +802,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--packets", type=int, default=PACKETS)
     ap.add_argument("--batch", type=int, default=0, help="device batch (packets); 0 = whole step")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the configs[3] "
+                         "window cycle (--windows), the flow-dictionary reclaim cost, the heavy-hitter lists, the "
+                         "CPU baselines and the bit-exact parity leg (--no-cpu drops the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the Count-Min path holds after its last step (counter "
+                         "rows, fingerprints, heavy-hitter lists; fixed seeded samples of the large arrays) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines and the parity leg")
     ap.add_argument("--width", type=int, default=WIDTH, help="Count-Min width (2^24 = configs[4] geometry)")
     ap.add_argument("--depth", type=int, default=DEPTH, help="Count-Min depth (8 = configs[4] geometry)")
     ap.add_argument("--config", choices=["c1", "c2"], default="c2",
@@ -766,7 +825,7 @@ def main():
     ap.add_argument("--ex-max-flows", type=int, default=1 << 21,
                     help="exact aggregator flow dictionary capacity (--sketch exact / hybrid)")
     ap.add_argument("--windows", type=int, default=3,
-                    help="after the timed steps: W timed windows of insert + device heavy hitters + "
+                    help="--full, after the timed steps: W timed windows of insert + device heavy hitters + "
                          "all-gather of every shard's list (configs[3] per-window exchange); 0 = off")
     ap.add_argument("--window-steps", type=int, default=10,
                     help="steps per window (fresh 100M-packet windows; configs[3] says a 1 s window)")
@@ -785,6 +844,8 @@ def main():
                          "hitters (PCIe-inclusive rate, for DESIGN.md): 64-B header records or 41-B PacketInfo "
                          "tuples (the live path's pre-parsed form)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.config != "c2" or args.sketch != "countmin"):
+        ap.error("--dump-outputs writes the Count-Min path's outputs (--config c2 --sketch countmin)")
 
     import torch
     import torch.distributed as dist
@@ -960,27 +1021,31 @@ def main():
     stages = {k: v for k, v in cm.stage_times().items() if v[1]}
     counters = cm.counters()
 
-    window = None
-    if args.windows > 0 and not args.host_input and not route:
+    if args.dump_outputs:  # the state the last timed step left, before anything below inserts again
+        dump_outputs(cm, args.dump_outputs, rank, world)
+
+    window = dictionary = hh = None
+    if args.full and args.windows > 0 and not args.host_input and not route:
         window = bench_windows(args, torch, dist, world, cm, timed_step, n)
 
-    # flow dictionary: reclaims during the run, and the cost of one reclaim at a
-    # window boundary with this run's live set (untimed; inserts reclaim on their
-    # own when the dictionary reaches max_flows)
-    dict_run = cm.dict_stats()
-    torch.cuda.synchronize()
-    t_r = time.perf_counter()
-    cm.reclaim()
-    reclaim_ms = (time.perf_counter() - t_r) * 1e3
-    dict_after = cm.dict_stats()
-    dictionary = {"max_flows": args.max_flows, "reclaims_during_run": dict_run["reclaims"],
-                  "retried_batches": dict_run["retried_batches"], "claimed_before_reclaim": dict_run["claimed"],
-                  "live_flows": dict_after["live"], "one_reclaim_ms": round(reclaim_ms, 3)}
+    if args.full:
+        # flow dictionary: reclaims during the run, and the cost of one reclaim at a
+        # window boundary with this run's live set (untimed; inserts reclaim on their
+        # own when the dictionary reaches max_flows)
+        dict_run = cm.dict_stats()
+        torch.cuda.synchronize()
+        t_r = time.perf_counter()
+        cm.reclaim()
+        reclaim_ms = (time.perf_counter() - t_r) * 1e3
+        dict_after = cm.dict_stats()
+        dictionary = {"max_flows": args.max_flows, "reclaims_during_run": dict_run["reclaims"],
+                      "retried_batches": dict_run["retried_batches"], "claimed_before_reclaim": dict_run["claimed"],
+                      "live_flows": dict_after["live"], "one_reclaim_ms": round(reclaim_ms, 3)}
 
-    hh = cm.heavy_hitters()
-    if world > 1:
-        from go2netspectra_amd.dist import allgather_heavy
-        hh = allgather_heavy(hh, world)
+        hh = cm.heavy_hitters()
+        if world > 1:
+            from go2netspectra_amd.dist import allgather_heavy
+            hh = allgather_heavy(hh, world)
 
     total_pkts = n * args.steps * world
     value = total_pkts / elapsed / 1e6
@@ -1019,10 +1084,11 @@ def main():
                      "pipeline_frac_b": round((BYTES_PER_PKT + args.depth * 64) * n * args.steps / elapsed / 1e9
                                               / HBM_PEAK_GBS, 4)},
         "stage_ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in stages.items()},
-        "heavy_hitters": {"count": len(hh.Count), "size": len(hh.Size or [])},
         "engine_counters": counters,
-        "flow_dictionary": dictionary,
     }
+    if args.full:
+        line["heavy_hitters"] = {"count": len(hh.Count), "size": len(hh.Size or [])}
+        line["flow_dictionary"] = dictionary
     if window is not None:
         line["window_exchange"] = window
     if (args.width, args.depth) != (WIDTH, DEPTH):
@@ -1048,7 +1114,7 @@ def main():
                           "counter rows and heavy hitters), d=4 w=2^20" % args.host_input)
         line["note"] = "not the headline metric: inputs start in pinned host memory, outputs end in host memory"
         line["config"]["host_input"] = args.host_input
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         # CPU legs on a bounded prefix of window 0, then the parity check: the same
         # prefix through a fresh engine handle must equal the sequential oracle
         m = min(n, 24_000_000)

@@ -13,7 +13,7 @@ mkdir -p $O
 run() {  # name, seconds, bench args...
     local n=$1 t=$2
     shift 2
-    echo "== $n" && timeout -k 10 "$t" python3 bench.py "$@" > $O/$n.json 2> $O/$n.err || { echo "FAIL $n rc=$?"; tail -5 $O/$n.err; exit 1; }
+    echo "== $n" && timeout -k 10 "$t" python3 bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { echo "FAIL $n rc=$?"; tail -5 $O/$n.err; exit 1; }
     tail -c 700 $O/$n.json
 }
 prof() {  # name, seconds, bench args...
