@@ -13,6 +13,7 @@ from .factory import Manager, TaskGroup, create, register_aggregator
 from .packets import (HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
 from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread
+from .spread import ExactSpread
 from .task import New, SketchTask, decode_flow
 
 __all__ = [
@@ -20,5 +21,5 @@ __all__ = [
     "TaskGroup", "create", "register_aggregator", "HeaderBatch", "PacketBatch", "SyntheticTraffic",
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
-    "NewExact", "SnapshotData",
+    "NewExact", "SnapshotData", "ExactSpread",
 ]

@@ -43,6 +43,9 @@ EXPORTED = [
     "gns_pack_pcap_compact16", "gns_compact_headers16",
     "gns_route_owner_fields", "gns_route_create_keyed", "gns_route_owner_layout", "gns_route_owner_keys",
     "gns_device_alloc", "gns_device_free", "gns_cm_heavy_rows", "gns_hh_order_rows",
+    "gns_exs_create", "gns_exs_destroy", "gns_exs_insert_keys", "gns_exs_insert_tuples", "gns_exs_insert_headers",
+    "gns_exs_flush", "gns_exs_query", "gns_exs_query_device", "gns_exs_heavy_hitters", "gns_exs_snapshot",
+    "gns_exs_reset", "gns_exs_counters", "gns_exs_dict_stats", "gns_exs_set_timing", "gns_exs_stage_times",
 ]
 
 
@@ -93,6 +96,12 @@ class SsParams(ct.Structure):
 
 class ExParams(ct.Structure):
     _fields_ = [("key", Layout), ("max_flows", ct.c_uint64), ("batch_packets", ct.c_uint64), ("device", ct.c_int)]
+
+
+class ExsParams(ct.Structure):
+    _fields_ = [("flow", Layout), ("elem", Layout), ("flow_bytes", ct.c_uint32), ("elem_bytes", ct.c_uint32),
+                ("max_flows", ct.c_uint64), ("max_pairs", ct.c_uint64), ("batch_packets", ct.c_uint64),
+                ("device", ct.c_int)]
 
 
 class SynthParams(ct.Structure):
@@ -180,6 +189,15 @@ def load() -> ct.CDLL:
         "gns_device_alloc": ([u64, i32, vp], i32), "gns_device_free": ([vp, i32], i32),
         "gns_cm_heavy_rows": ([vp, vp, vp, vp, vp], i32),
         "gns_hh_order_rows": ([vp, u32, u64, vp, i32], i32),
+        "gns_exs_create": ([vp, vp], i32), "gns_exs_destroy": ([vp], i32),
+        "gns_exs_insert_keys": ([vp, vp, u32, vp, u32, u64, i32], i32),
+        "gns_exs_insert_tuples": ([vp, vp, u64, i32], i32),
+        "gns_exs_insert_headers": ([vp, vp, vp, u64, i32], i32),
+        "gns_exs_flush": ([vp], i32), "gns_exs_query": ([vp, vp, u32, u64, vp], i32),
+        "gns_exs_query_device": ([vp, vp, u32, u64, vp], i32),
+        "gns_exs_heavy_hitters": ([vp, u32, vp, vp, vp], i32), "gns_exs_snapshot": ([vp, vp, vp, vp], i32),
+        "gns_exs_reset": ([vp], i32), "gns_exs_counters": ([vp, vp], i32), "gns_exs_dict_stats": ([vp, vp], i32),
+        "gns_exs_set_timing": ([vp, i32], i32), "gns_exs_stage_times": ([vp, vp, vp, i32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,877 @@
+// gns_spread.hip -- exact distinct-element (spread) aggregator: the device
+// ground truth of SuperSpread (ss_test.go:49-66,86-136 keep a
+// map[flow]map[elem]bool; spread(flow) = len of the inner map).
+//
+// Semantics: spread(flow) = number of distinct element keys inserted together
+// with that flow key since create / the last reset.  Exact: pairs are compared by
+// their bytes, a pair is counted once however its duplicates are spread over
+// lanes, waves, workgroups, device batches and calls, and the result does not
+// depend on packet order.
+//
+// State:
+//   pair table  open addressing, keyed by the pair's own bytes flow ‖ elem
+//               (<= 74): records {tag, key words} of 16 or 32 words, the tag and
+//               epoch protocol of the flow dictionary (gns_keys.cuh).  Flow ids
+//               are not part of the key, so a growing flow table never forces a
+//               rehash of the pairs.
+//   flow table  a DictDev over the flow bytes; spread[slot] is the flow's count.
+//
+// One device batch:
+//   E1 k_exs_pass<FIRST>   parse, flow and pair key words, probe the pair table.
+//        committed equal record -> duplicate, done (one line read, no write)
+//        claimed an empty slot  -> NEW pair: find-or-claim the flow, spread += 1
+//                                  (folded per workgroup in LDS: a hot flow costs
+//                                  one global add per workgroup)
+//        slot claimed in this launch (its bytes are not visible yet) -> parked
+//   E2 k_exs_pass<!FIRST>  the parked packets re-probe from where they stopped,
+//        under a new epoch (the kernel boundary committed the claims); a NEW pair
+//        whose flow slot was pending is parked as "count only".  Repeats until
+//        no packet is parked; the first repeat is queued blind, then one host
+//        read per round (rarely more than one).
+// The NEW outcome is unique per pair (one CAS wins the empty slot), and only it
+// counts: that is the whole exactness argument.
+//
+// Growth: decided BEFORE a batch from host-known bounds.  A batch of m packets
+// claims at most m pair slots and m flow slots, so both tables are grown (pair
+// table: rehash of its own records; flow table: dict_rebuild with every flow
+// live, spread[] permuted by its remap) until claimed + m <= 3/4 of the slots.
+// No batch can overflow a table, so none is aborted or re-run and nothing can be
+// counted twice (DESIGN.md §4e states why this replaces the abort-and-retry of
+// the sketches).
+#include <cstdlib>
+#include <cstring>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "gns_common.hpp"
+#include "gns_ctl.cuh"
+#include "gns_hh.hpp"
+
+namespace gns {
+
+constexpr int kExsThreads = 256;
+constexpr uint32_t kExsChunk = 4096;   // packets per workgroup; a parked entry keeps 12 bits of packet index
+constexpr uint32_t kExsFold = 512;     // LDS (flow id, new pairs) entries per workgroup
+constexpr uint64_t kExsMaxPairSlots = 1ull << 31;
+
+struct PairDev {
+    uint32_t *rec;   // slots * RW words: tag (0 empty, else claim epoch), key words
+    uint32_t mask;   // slots - 1
+    uint32_t RW;     // 16 or 32 (one or two 64-byte lines, never straddling)
+    uint32_t seed;
+    uint32_t K;      // pair key bytes
+};
+
+enum { PAIR_DUP = 0, PAIR_NEW = 1, PAIR_PENDING = 2, PAIR_FULL = 3 };
+
+// LW uint4 loads cover the tag and the key words the kernel's word count can hold
+template <int LW>
+__device__ __forceinline__ void pair_load(const PairDev &P, uint32_t slot, uint32_t (&r)[4 * LW]) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(P.rec + (size_t)slot * P.RW);
+#pragma unroll
+    for (int i = 0; i < LW; i++) {
+        const uint4 v = (4u * i < P.RW) ? q[i] : make_uint4(0, 0, 0, 0);
+        r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+    }
+}
+
+// dict_find_or_claim (gns_keys.cuh) for pair keys of NW words.  Every probe
+// sequence ends: the host keeps claimed < slots, so an empty slot exists.
+template <int NW>
+__device__ __forceinline__ int pair_find_or_claim(const PairDev &P, const uint32_t (&kw)[NW], uint32_t slot,
+                                                  uint32_t epoch, uint32_t *out) {
+    constexpr int LW = NW <= 8 ? 3 : 5;  // 8 key words + tag; 19 key words (74 bytes) + tag
+    const uint32_t nkw = (P.K + 3) >> 2;
+    for (uint32_t probe = 0; probe <= P.mask; probe++) {
+        uint32_t r[4 * LW];
+        pair_load<LW>(P, slot, r);
+        uint32_t tag = r[0];
+        if (tag == 0) {
+            uint32_t *tp = P.rec + (size_t)slot * P.RW;
+            const uint32_t old = atomicCAS(tp, 0u, epoch);
+            if (old == 0) {
+#pragma unroll
+                for (int i = 0; i < NW; i++)
+                    if ((uint32_t)i < nkw) tp[1 + i] = kw[i];
+                *out = slot;
+                return PAIR_NEW;
+            }
+            tag = old;
+            if (tag != epoch) pair_load<LW>(P, slot, r);  // committed earlier: need its key words
+        }
+        if (tag == epoch) { *out = slot; return PAIR_PENDING; }
+        bool eq = true;
+#pragma unroll
+        for (int i = 0; i < NW; i++)
+            if ((uint32_t)i < nkw && 1 + i < 4 * LW) eq = eq && (r[1 + i] == kw[i]);
+        if (eq) { *out = slot; return PAIR_DUP; }
+        slot = (slot + 1u) & P.mask;
+    }
+    return PAIR_FULL;
+}
+
+struct ExsArgs {
+    InputDesc in;
+    uint64_t n;
+    KeyPlanN kpf, kpm;
+    uint32_t Kf, Km;
+    PairDev P;
+    DictDev F;
+    uint32_t epoch;
+    uint32_t *spread;
+    uint32_t *nclaim;            // [0] flow slots, [1] pair slots claimed since the last reset
+    const uint64_t *pend_in;     // parked: stage << 63 | (packet - chunk start) << 32 | slot to resume at
+    const uint32_t *cnt_in;      // [chunk]
+    uint64_t *pend_out;
+    uint32_t *cnt_out, *total_out;
+    unsigned long long *stats;   // 0 inserted, 1 dropped, 2 unsupported, 3 probe overflow (cannot), 4 new pairs
+};
+
+// flow key (kwf) and pair key flow ‖ elem (kwm) of packet p: the bytes SuperSpread
+// hashes (EncodeFlow, task.go:265-300; super_spread.go:183-190)
+template <int KIND, int MF, int MM, int NW>
+__device__ __forceinline__ int exs_keys(const ExsArgs &a, const uint8_t *s_srcf, const uint8_t *s_srcm, uint64_t p,
+                                        uint32_t (&kwf)[GNS_KWMAX], uint32_t (&kwm)[NW]) {
+    if constexpr (KIND == IN_KEYS) {
+        const uint8_t *f = a.in.keys + p * a.in.stride;
+        const uint8_t *e = a.in.keys2 + p * a.in.stride2;
+        load_key_bytes<GNS_KWMAX>(f, a.Kf, false, kwf);
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const uint32_t j = 4 * i + b;
+                uint32_t byte = 0;
+                if (j < a.Kf) byte = f[j];
+                else if (j < a.Km) byte = e[j - a.Kf];
+                v |= byte << (8 * b);
+            }
+            kwm[i] = v;
+        }
+        return PARSE_OK;
+    } else {
+        uint32_t tw[10];
+        const int st = load_tuple<KIND>(a.in, p, tw);
+        if (st != PARSE_OK) return st;
+        make_key_m<MF, GNS_KWMAX>(a.Kf, s_srcf, tw, kwf);
+        make_key_m<MM, NW>(a.Km, s_srcm, tw, kwm);
+        return PARSE_OK;
+    }
+}
+
+// One pass over a chunk of kExsChunk packets per workgroup: FIRST = every packet
+// of the chunk from its hash slot, else the chunk's parked packets.
+template <int KIND, int MF, int MM, int NW, bool FIRST>
+__global__ __launch_bounds__(kExsThreads) void k_exs_pass(ExsArgs a) {
+    __shared__ uint8_t s_srcf[80], s_srcm[80];
+    __shared__ uint32_t s_fid[kExsFold], s_fcnt[kExsFold];
+    __shared__ uint32_t s_cnt, s_new, s_fclaim, s_full, s_ok, s_drop, s_unsup;
+    const uint32_t tid = threadIdx.x, ch = blockIdx.x;
+    for (uint32_t j = tid; j < 80; j += kExsThreads) { s_srcf[j] = a.kpf.src[j]; s_srcm[j] = a.kpm.src[j]; }
+    for (uint32_t j = tid; j < kExsFold; j += kExsThreads) { s_fid[j] = GNS_ID_NONE; s_fcnt[j] = 0; }
+    if (tid == 0) { s_cnt = 0; s_new = 0; s_fclaim = 0; s_full = 0; s_ok = 0; s_drop = 0; s_unsup = 0; }
+    __syncthreads();
+    const uint64_t beg = (uint64_t)ch * kExsChunk;
+    const uint32_t cnt = FIRST ? (uint32_t)min((uint64_t)kExsChunk, a.n - beg) : a.cnt_in[ch];
+    for (uint32_t i = tid; i < cnt; i += kExsThreads) {
+        uint32_t rel = i, slot = 0, stage = 0;
+        if (!FIRST) {
+            const uint64_t v = a.pend_in[beg + i];
+            stage = (uint32_t)(v >> 63);
+            rel = (uint32_t)(v >> 32) & (kExsChunk - 1);
+            slot = (uint32_t)v;
+        }
+        uint32_t kwf[GNS_KWMAX], kwm[NW];
+        const int st = exs_keys<KIND, MF, MM, NW>(a, s_srcf, s_srcm, beg + rel, kwf, kwm);
+        if (st != PARSE_OK) {  // only in the first pass: a parked packet parsed OK
+            if (FIRST) atomicAdd(st == PARSE_DROP ? &s_drop : &s_unsup, 1u);
+            continue;
+        }
+        if (FIRST) {
+            atomicAdd(&s_ok, 1u);
+            slot = mm3_n<NW>(kwm, a.Km, a.P.seed) & a.P.mask;
+        }
+        if (stage == 0) {
+            uint32_t at;
+            const int res = pair_find_or_claim<NW>(a.P, kwm, slot, a.epoch, &at);
+            if (res == PAIR_DUP) continue;
+            if (res == PAIR_PENDING) {
+                a.pend_out[beg + atomicAdd(&s_cnt, 1u)] = (uint64_t)rel << 32 | at;
+                continue;
+            }
+            if (res == PAIR_FULL) { atomicAdd(&s_full, 1u); continue; }
+            atomicAdd(&s_new, 1u);
+            slot = mm3_n<GNS_KWMAX>(kwf, a.Kf, a.F.seed) & a.F.mask;
+        }
+        // the packet holds a NEW pair: its flow's count goes up by one, exactly once
+        uint32_t id;
+        const int fr = dict_find_or_claim(a.F, kwf, slot, a.epoch, &id);
+        if (fr == DICT_CLAIMED) atomicAdd(&s_fclaim, 1u);
+        if (fr == DICT_FOUND || fr == DICT_CLAIMED) {
+            const uint32_t h = (id * 0x9E3779B1u) >> 23;  // kExsFold = 2^9 entries
+            const uint32_t old = atomicCAS(&s_fid[h], GNS_ID_NONE, id);
+            if (old == GNS_ID_NONE || old == id) atomicAdd(&s_fcnt[h], 1u);
+            else atomicAdd(&a.spread[id], 1u);
+        } else if (fr == DICT_PENDING) {
+            a.pend_out[beg + atomicAdd(&s_cnt, 1u)] = 1ull << 63 | (uint64_t)rel << 32 | id;
+        } else {
+            atomicAdd(&s_full, 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = tid; j < kExsFold; j += kExsThreads)
+        if (s_fcnt[j]) atomicAdd(&a.spread[s_fid[j]], s_fcnt[j]);
+    if (tid == 0) {
+        a.cnt_out[ch] = s_cnt;
+        if (s_cnt) atomicAdd(a.total_out, s_cnt);
+        if (s_fclaim) atomicAdd(&a.nclaim[0], s_fclaim);
+        if (s_new) {
+            atomicAdd(&a.nclaim[1], s_new);
+            atomicAdd(&a.stats[4], (unsigned long long)s_new);
+        }
+        if (s_full) atomicAdd(&a.stats[3], (unsigned long long)s_full);
+        if (s_ok) atomicAdd(&a.stats[0], (unsigned long long)s_ok);
+        if (s_drop) atomicAdd(&a.stats[1], (unsigned long long)s_drop);
+        if (s_unsup) atomicAdd(&a.stats[2], (unsigned long long)s_unsup);
+    }
+}
+
+// pair-table growth: every record of the old table into the (zeroed) new one;
+// keys are distinct, so the first empty slot from the home slot is its place
+template <int NW>
+__global__ __launch_bounds__(256) void k_exs_rehash(PairDev O, uint64_t old_slots, PairDev N, uint32_t *fail) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= old_slots) return;
+    const uint32_t *r = O.rec + (size_t)s * O.RW;
+    const uint32_t tag = r[0];
+    if (tag == 0) return;
+    const uint32_t nkw = (O.K + 3) >> 2;
+    uint32_t kw[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) kw[i] = (uint32_t)i < nkw ? r[1 + i] : 0u;
+    uint32_t slot = mm3_n<NW>(kw, N.K, N.seed) & N.mask;
+    for (uint32_t probe = 0; probe <= N.mask; probe++) {
+        uint32_t *tp = N.rec + (size_t)slot * N.RW;
+        if (atomicCAS(tp, 0u, tag) == 0u) {
+#pragma unroll
+            for (int i = 0; i < NW; i++)
+                if ((uint32_t)i < nkw) tp[1 + i] = kw[i];
+            return;
+        }
+        slot = (slot + 1u) & N.mask;
+    }
+    atomicAdd(fail, 1u);
+}
+
+// flow-table growth: spread[] follows each record to its new slot (gns_dict.hip remap)
+__global__ __launch_bounds__(256) void k_exs_permute(const uint32_t *spread, uint64_t slots, const uint32_t *remap,
+                                                     uint32_t *out) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= slots) return;
+    const uint32_t t = remap[s];
+    if (t < kDictMarked) out[t] = spread[s];
+}
+
+__global__ __launch_bounds__(256) void k_exs_iota(uint32_t *ids, uint64_t n) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s < n) ids[s] = (uint32_t)s;
+}
+
+__global__ __launch_bounds__(256) void k_exs_query(const uint8_t *flows, uint32_t stride, uint64_t n, DictDev F,
+                                                   const uint32_t *spread, uint64_t *out) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    uint32_t kw[GNS_KWMAX];
+    load_key_bytes<GNS_KWMAX>(flows + p * stride, F.K, false, kw);
+    const uint32_t id = dict_lookup(F, kw);
+    out[p] = id != GNS_ID_NONE ? (uint64_t)spread[id] : 0ull;
+}
+
+// snapshot: the occupied flow slots (at most cap; the host knows the exact count)
+__global__ __launch_bounds__(256) void k_exs_list(DictDev F, uint64_t slots, uint32_t *ids, uint32_t cap, uint32_t *count) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = s < slots && F.rec[s * F.RW] != 0u;
+    const uint64_t m = __ballot(live);
+    if (m == 0) return;
+    const uint32_t lane = __lane_id();
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    const uint32_t j = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (live && j < cap) ids[j] = (uint32_t)s;
+}
+
+__global__ __launch_bounds__(256) void k_exs_gather(const uint32_t *ids, uint64_t n, DictDev F, const uint32_t *spread,
+                                                    uint8_t *keys, uint32_t *vals) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t id = ids[p];
+    uint32_t r[12];
+    load_record(F, id, r);
+    for (uint32_t j = 0; j < F.K; j++) keys[p * F.K + j] = (uint8_t)(r[1 + (j >> 2)] >> (8 * (j & 3)));
+    vals[p] = spread[id];
+}
+
+}  // namespace gns
+
+// ===========================================================================
+// Host side
+// ===========================================================================
+using namespace gns;
+
+struct gns_exs {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    KeyPlanN kpf{}, kpm{};
+    uint32_t Kf = 0, Km = 0;
+    bool has_layout = false;     // tuples / headers need the field layouts
+    PairDev P{};
+    DictDev F{};
+    uint64_t pslots = 0, fslots = 0;
+    uint64_t pclaimed = 0, fclaimed = 0;  // claimed slots as of the last batch
+    uint32_t *spread = nullptr;  // [fslots]
+    uint32_t *ident = nullptr;   // [fslots] = slot: the rebuild's mark list and the heavy list's ids
+    uint32_t *ctl = nullptr;     // [0..1] flow table claimed / abort (DictDev.ctl), [4] flow, [5] pair claims
+    uint32_t *ptotal = nullptr;  // [2] parked totals (ping-pong)
+    uint64_t *pend[2] = {nullptr, nullptr};
+    uint32_t *pcnt[2] = {nullptr, nullptr};
+    unsigned long long *stats = nullptr;
+    uint32_t *h_pin = nullptr;
+    uint32_t epoch = 0;
+    uint64_t bmax = 0, pkt = 0, n_batches = 0;
+    uint64_t n_fgrow = 0, n_pgrow = 0;
+    double grow_ms = 0.0;
+    DictScratch dsc;
+    uint8_t *stage = nullptr;
+    size_t stage_bytes = 0;
+    StageTimer timer;
+    CmScratch *hh = nullptr;
+};
+
+namespace {
+
+int exs_set_dev(gns_exs *h) {
+    (void)hipGetLastError();  // clear a stale error of an earlier runtime call on this thread
+    GNS_HIP(hipSetDevice(h->device));
+    return GNS_OK;
+}
+
+void exs_free_all(gns_exs *h) {
+    dfree(h->P.rec); dfree(h->F.rec); dfree(h->spread); dfree(h->ident); dfree(h->ctl); dfree(h->ptotal);
+    dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); dfree(h->stage);
+    h->dsc.free_all();
+    gns::hh_scratch_free(h->hh);
+    h->hh = nullptr;
+    if (h->h_pin) (void)hipHostFree(h->h_pin);
+    h->timer.destroy();
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+}
+
+// empty tables (create, reset); the tables keep the size they have grown to
+int exs_clear(gns_exs *h) {
+    hipStream_t s = h->stream;
+    GNS_HIP(hipMemsetAsync(h->P.rec, 0, h->pslots * h->P.RW * 4, s));
+    GNS_HIP(hipMemsetAsync(h->F.rec, 0, h->fslots * h->F.RW * 4, s));
+    GNS_HIP(hipMemsetAsync(h->spread, 0, h->fslots * 4, s));
+    GNS_HIP(hipMemsetAsync(h->ctl, 0, 32, s));
+    h->pclaimed = h->fclaimed = 0;
+    return GNS_OK;
+}
+
+unsigned exs_grid(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+int exs_alloc_flow_side(uint64_t slots, hipStream_t s, uint32_t **spread, uint32_t **ident) {
+    *spread = *ident = nullptr;
+    int rc;
+    if ((rc = dalloc_t(spread, slots)) || (rc = dalloc_t(ident, slots))) {
+        dfree(*spread);
+        *spread = nullptr;
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(*spread, 0, slots * 4, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_exs_iota, dim3(exs_grid(slots)), dim3(256), 0, s, *ident, slots);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        dfree(*spread); dfree(*ident);
+        *spread = *ident = nullptr;
+        set_error("spread flow state: %s", hipGetErrorString(e));
+        return GNS_E_HIP;
+    }
+    return GNS_OK;
+}
+
+int exs_grow_pairs(gns_exs *h, uint64_t new_slots) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s = h->stream;
+    PairDev N = h->P;
+    GNS_TRY(dalloc_t(&N.rec, new_slots * N.RW));
+    N.mask = (uint32_t)(new_slots - 1);
+    hipError_t e = hipMemsetAsync(N.rec, 0, new_slots * N.RW * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->ptotal, 0, 8, s);
+    if (e == hipSuccess) {
+        if (h->Km <= 32) hipLaunchKernelGGL(k_exs_rehash<8>, dim3(exs_grid(h->pslots)), dim3(256), 0, s, h->P, h->pslots, N, h->ptotal);
+        else hipLaunchKernelGGL(k_exs_rehash<20>, dim3(exs_grid(h->pslots)), dim3(256), 0, s, h->P, h->pslots, N, h->ptotal);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_pin, h->ptotal, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess || h->h_pin[0]) {
+        dfree(N.rec);
+        set_error("pair table growth: %s", e != hipSuccess ? hipGetErrorString(e) : "records lost");
+        return GNS_E_HIP;
+    }
+    dfree(h->P.rec);
+    h->P = N;
+    h->pslots = new_slots;
+    h->n_pgrow++;
+    h->grow_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GNS_OK;
+}
+
+int exs_grow_flows(gns_exs *h, uint64_t new_slots) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s = h->stream;
+    uint32_t *nspread = nullptr, *nident = nullptr;
+    GNS_TRY(exs_alloc_flow_side(new_slots, s, &nspread, &nident));
+    const uint64_t old_slots = h->fslots;
+    DictIds all{h->ident, old_slots};  // every occupied record is a live flow
+    uint64_t slots = old_slots, live = 0;
+    const int rc = dict_rebuild(h->F, slots, &all, 1, nullptr, nullptr, 0, new_slots, s, h->dsc, &live, nullptr);
+    if (rc != GNS_OK) { dfree(nspread); dfree(nident); return rc; }
+    hipLaunchKernelGGL(k_exs_permute, dim3(exs_grid(old_slots)), dim3(256), 0, s, h->spread, old_slots, h->dsc.remap, nspread);
+    GNS_HIP(hipGetLastError());
+    GNS_HIP(hipStreamSynchronize(s));
+    dfree(h->spread); dfree(h->ident);
+    h->spread = nspread;
+    h->ident = nident;
+    h->fslots = slots;
+    h->fclaimed = live;
+    h->n_fgrow++;
+    h->grow_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GNS_OK;
+}
+
+// Both tables take the m claims the next batch can make at most, at a load of
+// at most 3/4 (grown to at most 1/2).
+int exs_reserve(gns_exs *h, uint64_t m) {
+    const uint64_t need_p = h->pclaimed + m, need_f = h->fclaimed + m;
+    if (need_p > h->pslots - h->pslots / 4) {
+        uint64_t ns = h->pslots;
+        while (need_p > ns / 2) ns *= 2;
+        if (ns > kExsMaxPairSlots) {
+            set_error("pair table: %llu pairs exceed the device (%llu-slot limit)", (unsigned long long)need_p,
+                      (unsigned long long)kExsMaxPairSlots);
+            return GNS_E_OOM;
+        }
+        ScopedStage st(h->timer, 2);
+        GNS_TRY(exs_grow_pairs(h, ns));
+    }
+    if (need_f > h->fslots - h->fslots / 4) {
+        uint64_t ns = h->fslots;
+        while (need_f > ns / 2) ns *= 2;
+        if (ns > kDictMaxSlots) {
+            set_error("flow table: %llu flows exceed the device (%llu-slot limit)", (unsigned long long)need_f,
+                      (unsigned long long)kDictMaxSlots);
+            return GNS_E_OOM;
+        }
+        ScopedStage st(h->timer, 2);
+        GNS_TRY(exs_grow_flows(h, ns));
+    }
+    return GNS_OK;
+}
+
+template <int KIND, int MF, int MM, int NW>
+int exs_run_batch(gns_exs *h, const InputDesc &in, uint64_t n) {
+    hipStream_t s = h->stream;
+    ScopedStage total_stage(h->timer, 5);
+    const uint32_t nch = (uint32_t)((n + kExsChunk - 1) / kExsChunk);
+    ExsArgs a{};
+    a.in = in; a.n = n; a.kpf = h->kpf; a.kpm = h->kpm; a.Kf = h->Kf; a.Km = h->Km;
+    a.P = h->P; a.F = h->F; a.spread = h->spread; a.nclaim = h->ctl + 4; a.stats = h->stats;
+    GNS_HIP(hipMemsetAsync(h->ptotal, 0, 8, s));
+    int cur = 0;  // the parked list the next round reads
+    for (int round = 0;; round++) {
+        if (++h->epoch == 0) h->epoch = 1;
+        a.epoch = h->epoch;
+        if (round == 0) {
+            ScopedStage st(h->timer, 0);
+            a.pend_out = h->pend[0]; a.cnt_out = h->pcnt[0]; a.total_out = h->ptotal;
+            hipLaunchKernelGGL((k_exs_pass<KIND, MF, MM, NW, true>), dim3(nch), dim3(kExsThreads), 0, s, a);
+            GNS_HIP(hipGetLastError());
+            continue;  // the first resolve round is queued blind (an empty parked list makes it a no-op)
+        }
+        {
+            ScopedStage st(h->timer, 1);
+            a.pend_in = h->pend[cur]; a.cnt_in = h->pcnt[cur];
+            a.pend_out = h->pend[cur ^ 1]; a.cnt_out = h->pcnt[cur ^ 1]; a.total_out = h->ptotal + (cur ^ 1);
+            hipLaunchKernelGGL((k_exs_pass<KIND, MF, MM, NW, false>), dim3(nch), dim3(kExsThreads), 0, s, a);
+            GNS_HIP(hipGetLastError());
+            cur ^= 1;
+        }
+        CtlRead rd;  // the batch's one host round trip: still parked, claims, the cannot-happen word
+        rd.add(h->ptotal + cur, 4, 0);
+        rd.add(h->ctl + 4, 8, 1);
+        rd.add(h->stats + 3, 8, 4);
+        GNS_HIP(ctl_read(rd, h->h_pin, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        h->fclaimed = h->h_pin[1];
+        h->pclaimed = h->h_pin[2];
+        if (h->h_pin[4] | h->h_pin[5]) {
+            set_error("spread tables: a probe found no free slot (%llu pair / %llu flow slots)",
+                      (unsigned long long)h->pslots, (unsigned long long)h->fslots);
+            return GNS_E_FULL;
+        }
+        if (h->h_pin[0] == 0) break;
+        if (round > 65536) { set_error("spread resolve did not converge"); return GNS_E_HIP; }
+        GNS_HIP(hipMemsetAsync(h->ptotal + (cur ^ 1), 0, 4, s));
+    }
+    h->pkt += n;
+    h->n_batches++;
+    return GNS_OK;
+}
+
+template <int KIND>
+int exs_batch(gns_exs *h, const InputDesc &d, uint64_t m) {
+    if (m == 0) return GNS_OK;
+    GNS_TRY(exs_reserve(h, m));
+    const bool narrow = h->Km <= 32;
+    if constexpr (KIND == IN_KEYS) {
+        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m)
+                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m);
+    } else if (plan_mode(h->kpf) == PLAN_SLICE0 && plan_mode(h->kpm) == PLAN_SLICE0) {
+        return narrow ? exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 8>(h, d, m)
+                      : exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 20>(h, d, m);
+    } else {
+        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m)
+                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m);
+    }
+}
+
+InputDesc exs_advance(const InputDesc &in, uint64_t off) {
+    InputDesc d = in;
+    if (d.hdr) d.hdr += off * 16;
+    if (d.src16) d.src16 += off * 16;
+    if (d.dst16) d.dst16 += off * 16;
+    if (d.sport) d.sport += off;
+    if (d.dport) d.dport += off;
+    if (d.proto) d.proto += off;
+    if (d.keys) d.keys += off * d.stride;
+    if (d.keys2) d.keys2 += off * d.stride2;
+    if (d.sizes) d.sizes += off;
+    return d;
+}
+
+template <int KIND>
+int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where) {
+    GNS_TRY(exs_set_dev(h));
+    for (uint64_t off = 0; off < n; off += h->bmax) {
+        const uint64_t m = std::min<uint64_t>(h->bmax, n - off);
+        InputDesc d = exs_advance(in, off);
+        if (where != GNS_MEM_DEVICE) {  // stage the piece on the device
+            const void *src[9] = {d.hdr, d.src16, d.dst16, d.sport, d.dport, d.proto, d.keys, d.keys2, d.sizes};
+            const size_t bytes[9] = {d.hdr ? m * 64 : 0, d.src16 ? m * 16 : 0, d.dst16 ? m * 16 : 0,
+                                     d.sport ? m * 2 : 0, d.dport ? m * 2 : 0, d.proto ? m : 0,
+                                     d.keys ? m * d.stride : 0, d.keys2 ? m * d.stride2 : 0, d.sizes ? m * 4 : 0};
+            size_t tot = 0;
+            for (int i = 0; i < 9; i++) tot += (bytes[i] + 15) & ~size_t(15);
+            if (h->stage_bytes < tot) {
+                dfree(h->stage);
+                h->stage = nullptr;
+                h->stage_bytes = 0;
+                GNS_TRY(dalloc(reinterpret_cast<void **>(&h->stage), tot));
+                h->stage_bytes = tot;
+            }
+            uint8_t *p = h->stage;
+            const void **dst[9] = {(const void **)&d.hdr, (const void **)&d.src16, (const void **)&d.dst16,
+                                   (const void **)&d.sport, (const void **)&d.dport, (const void **)&d.proto,
+                                   (const void **)&d.keys, (const void **)&d.keys2, (const void **)&d.sizes};
+            for (int i = 0; i < 9; i++) {
+                if (!bytes[i]) continue;
+                GNS_HIP(hipMemcpyAsync(p, src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
+                *dst[i] = p;
+                p += (bytes[i] + 15) & ~size_t(15);
+            }
+        }
+        GNS_TRY(exs_batch<KIND>(h, d, m));
+    }
+    return GNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gns_exs_create(const gns_exs_params *p, gns_exs **out) {
+    if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
+    *out = nullptr;
+    // the layouts first: a bad one is an argument error with or without a device
+    KeyPlanN kpf, kpe, kpm;
+    if (p->flow.n_fields > 8 || p->elem.n_fields > 8) { set_error("layout has more than 8 fields"); return GNS_E_ARG; }
+    GNS_TRY(make_plan(p->flow, p->flow_bytes, &kpf));
+    GNS_TRY(make_plan(p->elem, p->elem_bytes, &kpe));
+    if (kpf.K == 0 || kpe.K == 0) {
+        set_error("flow key of %u bytes, element key of %u bytes: both must be 1..37", kpf.K, kpe.K);
+        return GNS_E_ARG;
+    }
+    const bool has_layout = p->flow.n_fields && p->elem.n_fields;
+    if (has_layout) {
+        GNS_TRY(make_plan2(p->flow, p->elem, &kpm));
+    } else {
+        memset(&kpm, 0, sizeof(kpm));
+        kpm.K = kpf.K + kpe.K;
+        kpm.woff = -1;
+    }
+    if (p->max_flows > kDictMaxSlots / 2 || p->max_pairs > kExsMaxPairSlots / 2) {
+        set_error("max_flows > 2^29 or max_pairs > 2^30");
+        return GNS_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        set_error("no HIP device available");
+        return GNS_E_NODEV;
+    }
+    if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return GNS_E_ARG; }
+    gns_exs *h = new gns_exs();
+    h->device = p->device;
+    h->kpf = kpf; h->kpm = kpm; h->Kf = kpf.K; h->Km = kpm.K; h->has_layout = has_layout;
+    int rc = GNS_OK;
+    do {
+        if ((rc = exs_set_dev(h)) != GNS_OK) break;
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+            set_error("hipStreamCreate failed"); rc = GNS_E_HIP; break;
+        }
+        h->timer.stream = h->stream;
+        const uint64_t mf = p->max_flows ? p->max_flows : (1ull << 20);
+        const uint64_t mp = p->max_pairs ? p->max_pairs : (4ull << 20);
+        h->fslots = 16; h->pslots = 16;
+        while (h->fslots < 2 * mf) h->fslots <<= 1;
+        while (h->pslots < 2 * mp) h->pslots <<= 1;
+        h->bmax = p->batch_packets ? p->batch_packets : (4ull << 20);
+        h->bmax = std::min<uint64_t>(h->bmax, 1ull << 26);
+        const uint64_t nch = (h->bmax + kExsChunk - 1) / kExsChunk;
+        const uint32_t nkw = (h->Km + 3) / 4;
+        h->P.RW = 1 + nkw <= 16 ? 16u : 32u;
+        h->P.mask = (uint32_t)(h->pslots - 1);
+        h->P.seed = 0x9E3779B9u;
+        h->P.K = h->Km;
+        h->F.mask = (uint32_t)(h->fslots - 1);
+        h->F.K = h->Kf;
+        h->F.RW = dict_record_words(h->Kf);
+        h->F.seed = 0x2545F491u;
+        h->F.cap = 0xFFFFFFFFu;  // never reached: exs_reserve grows the table before a batch
+        if ((rc = dalloc_t(&h->P.rec, h->pslots * h->P.RW)) || (rc = dalloc_t(&h->F.rec, h->fslots * h->F.RW)) ||
+            (rc = exs_alloc_flow_side(h->fslots, h->stream, &h->spread, &h->ident)) ||
+            (rc = dalloc_t(&h->ctl, 8)) || (rc = dalloc_t(&h->ptotal, 2)) ||
+            (rc = dalloc_t(&h->pend[0], nch * kExsChunk)) || (rc = dalloc_t(&h->pend[1], nch * kExsChunk)) ||
+            (rc = dalloc_t(&h->pcnt[0], nch)) || (rc = dalloc_t(&h->pcnt[1], nch)) || (rc = dalloc_t(&h->stats, 8)))
+            break;
+        h->F.ctl = h->ctl;
+        if (hipHostMalloc(reinterpret_cast<void **>(&h->h_pin), 64, 0) != hipSuccess) {
+            set_error("hipHostMalloc failed"); rc = GNS_E_OOM; break;
+        }
+        if (hipMemsetAsync(h->stats, 0, 64, h->stream) != hipSuccess) { rc = GNS_E_HIP; break; }
+        if ((rc = exs_clear(h)) != GNS_OK) break;
+        if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("create: stream error"); rc = GNS_E_HIP; break; }
+    } while (0);
+    if (rc != GNS_OK) {
+        exs_free_all(h);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return GNS_OK;
+}
+
+int gns_exs_destroy(gns_exs *h) {
+    if (!h) return GNS_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    exs_free_all(h);
+    delete h;
+    return GNS_OK;
+}
+
+int gns_exs_insert_keys(gns_exs *h, const uint8_t *flows, uint32_t fstride, const uint8_t *elems, uint32_t estride,
+                        uint64_t n, gns_mem where) {
+    if (!h || (n && (!flows || !elems))) { set_error("null argument"); return GNS_E_ARG; }
+    if (fstride < h->Kf || estride < h->Km - h->Kf) { set_error("stride smaller than key"); return GNS_E_ARG; }
+    InputDesc in{};
+    in.keys = flows; in.stride = fstride; in.keys2 = elems; in.stride2 = estride;
+    return exs_insert<IN_KEYS>(h, in, n, where);
+}
+
+int gns_exs_insert_tuples(gns_exs *h, const gns_tuples *t, uint64_t n, gns_mem where) {
+    if (!h || !t) { set_error("null argument"); return GNS_E_ARG; }
+    if (!h->has_layout) { set_error("handle created without field layouts: keys input only"); return GNS_E_ARG; }
+    if (n && (!t->src16 || !t->dst16 || !t->sport || !t->dport || !t->proto)) { set_error("null tuple array"); return GNS_E_ARG; }
+    InputDesc in{};
+    in.src16 = t->src16; in.dst16 = t->dst16; in.sport = t->sport; in.dport = t->dport; in.proto = t->proto;
+    return exs_insert<IN_TUPLE>(h, in, n, where);
+}
+
+int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n, gns_mem where) {
+    if (!h || (n && (!hdr || !wirelen))) { set_error("null argument"); return GNS_E_ARG; }
+    if (!h->has_layout) { set_error("handle created without field layouts: keys input only"); return GNS_E_ARG; }
+    InputDesc in{};
+    in.hdr = reinterpret_cast<const uint32_t *>(hdr);
+    in.sizes = wirelen;
+    return exs_insert<IN_HDR>(h, in, n, where);
+}
+
+int gns_exs_flush(gns_exs *h) {
+    if (!h) return GNS_E_ARG;
+    GNS_TRY(exs_set_dev(h));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    return GNS_OK;
+}
+
+static int exs_query_impl(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
+    if (!h || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
+    if (n == 0) return GNS_OK;
+    if (stride < h->Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
+    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
+    GNS_TRY(exs_set_dev(h));
+    uint8_t *dk = nullptr;
+    uint64_t *dout = nullptr;
+    if (dev) {
+        dk = const_cast<uint8_t *>(flows);
+        dout = out;
+    } else {
+        GNS_TRY(dalloc(reinterpret_cast<void **>(&dk), n * stride));
+        int rc = dalloc(reinterpret_cast<void **>(&dout), n * 8);
+        if (rc) { dfree(dk); return rc; }
+    }
+    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(dk, flows, n * stride, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_exs_query, dim3(exs_grid(n)), dim3(256), 0, h->stream, dk, stride, n, h->F, h->spread, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && !dev) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (!dev) {
+        dfree(dk);
+        dfree(dout);
+    }
+    if (e != hipSuccess) { set_error("spread query: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+int gns_exs_query(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
+    return exs_query_impl(h, flows, stride, n, out, false);
+}
+
+int gns_exs_query_device(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
+    return exs_query_impl(h, flows, stride, n, out, true);
+}
+
+// The flows with spread >= threshold through the shared list code (gns_hh.hpp):
+// the cell array is spread[] itself, one cell per flow-table slot, whose id is the
+// slot.  A list longer than the caller's buffers is reported and not written.
+int gns_exs_heavy_hitters(gns_exs *h, uint32_t threshold, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(exs_set_dev(h));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    if (!h->hh) h->hh = gns::hh_scratch_new();
+    const uint64_t cap = *n_io;
+    std::vector<uint8_t> tf(flows ? cap * h->Kf : 0);
+    std::vector<uint32_t> tv(spreads ? cap : 0);
+    uint64_t n = cap;
+    // a seen flow has spread >= 1, so threshold 0 lists the same flows as 1 (empty slots hold 0)
+    GNS_TRY(gns::hh_heavy_list(h->hh, h->stream, h->F, h->fslots, h->Kf, h->fslots, h->spread, h->ident,
+                               std::max(threshold, 1u), flows ? tf.data() : nullptr, spreads ? tv.data() : nullptr, &n));
+    *n_io = n;
+    if (n <= cap && n) {
+        if (flows) memcpy(flows, tf.data(), n * h->Kf);
+        if (spreads) memcpy(spreads, tv.data(), n * 4);
+    }
+    return GNS_OK;
+}
+
+int gns_exs_snapshot(gns_exs *h, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(exs_set_dev(h));
+    hipStream_t s = h->stream;
+    GNS_HIP(hipStreamSynchronize(s));
+    const uint64_t cap = *n_io, nf = h->fclaimed;  // every claimed flow slot holds a seen flow
+    *n_io = nf;
+    if (nf == 0 || nf > cap || (!flows && !spreads)) return GNS_OK;
+    uint32_t *ids = nullptr, *dv = nullptr;
+    uint8_t *dk = nullptr;
+    int rc;
+    if ((rc = dalloc_t(&ids, nf)) || (rc = dalloc_t(&dv, nf)) || (rc = dalloc(reinterpret_cast<void **>(&dk), nf * h->Kf))) {
+        dfree(ids); dfree(dv);
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(h->ptotal, 0, 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ids, 0, nf * 4, s);  // every id the gather reads names a slot
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_exs_list, dim3(exs_grid(h->fslots)), dim3(256), 0, s, h->F, h->fslots, ids, (uint32_t)nf, h->ptotal);
+        hipLaunchKernelGGL(k_exs_gather, dim3(exs_grid(nf)), dim3(256), 0, s, ids, nf, h->F, h->spread, dk, dv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_pin, h->ptotal, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && flows) e = hipMemcpyAsync(flows, dk, nf * h->Kf, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && spreads) e = hipMemcpyAsync(spreads, dv, nf * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dfree(ids); dfree(dv); dfree(dk);
+    if (e != hipSuccess) { set_error("spread snapshot: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    if (h->h_pin[0] != nf) {
+        set_error("spread snapshot: %u occupied flow slots, %llu claimed", h->h_pin[0], (unsigned long long)nf);
+        return GNS_E_HIP;
+    }
+    return GNS_OK;
+}
+
+int gns_exs_reset(gns_exs *h) {
+    if (!h) return GNS_E_ARG;
+    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(exs_clear(h));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    return GNS_OK;
+}
+
+int gns_exs_counters(gns_exs *h, uint64_t out[8]) {
+    if (!h || !out) return GNS_E_ARG;
+    GNS_TRY(exs_set_dev(h));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    unsigned long long st[8];
+    GNS_HIP(hipMemcpy(st, h->stats, sizeof(st), hipMemcpyDeviceToHost));
+    out[0] = st[0]; out[1] = st[1]; out[2] = st[2]; out[3] = st[3]; out[4] = st[4];
+    out[5] = h->fclaimed; out[6] = h->pkt; out[7] = h->n_batches;
+    return GNS_OK;
+}
+
+int gns_exs_dict_stats(gns_exs *h, uint64_t out[8]) {
+    if (!h || !out) return GNS_E_ARG;
+    out[0] = h->n_fgrow; out[1] = h->n_pgrow; out[2] = h->fslots; out[3] = h->fclaimed;
+    out[4] = h->pslots; out[5] = h->pclaimed; out[6] = (uint64_t)(h->grow_ms * 1000.0); out[7] = 0;
+    return GNS_OK;
+}
+
+int gns_exs_set_timing(gns_exs *h, int on) {
+    if (!h) return GNS_E_ARG;
+    set_timing_arg(h->timer, on);
+    return GNS_OK;
+}
+
+int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset) {
+    if (!h) return GNS_E_ARG;
+    GNS_TRY(exs_set_dev(h));
+    h->timer.collect();
+    for (int i = 0; i < 8; i++) {
+        if (ms) ms[i] = h->timer.ms[i];
+        if (launches) launches[i] = h->timer.launches[i];
+    }
+    if (reset) for (int i = 0; i < 8; i++) { h->timer.ms[i] = 0; h->timer.launches[i] = 0; }
+    return GNS_OK;
+}
+
+}  // extern "C"

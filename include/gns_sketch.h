@@ -469,6 +469,74 @@ int gns_ex_set_timing(gns_ex *ex, int on);
 /* stages: 0 extract, 1 resolve, 2 aggregate, 3 timestamps, 5 total */
 int gns_ex_stage_times(gns_ex *ex, double ms[8], uint64_t launches[8], int reset);
 
+/* ------------------------------------------------------------------ */
+/* Exact spread: the device ground truth of SuperSpread                */
+/* ------------------------------------------------------------------ */
+/* spread(flow) = the number of DISTINCT element keys inserted together with that
+ * flow key since create / the last reset: len(spreadMap[key]) of the reference's
+ * SuperSpread test (ss_test.go:49-66,86-136).  Exact: pairs are compared by their
+ * bytes (never by a hash), a pair is counted once however its duplicates are
+ * spread over lanes, workgroups, device batches and calls, and the result does
+ * not depend on packet order.
+ *   - Keys: flow and element keys are the EncodeFlow bytes SuperSpread uses for
+ *     the same layout: task.go:265-300, IPv4 = 4 bytes + 12 zero bytes.  So a
+ *     flow key taken from this engine is byte-for-byte a key gns_ss_query accepts
+ *     and a Flow gns_ss_heavy_hitters returns.  This is deliberately NOT the exact
+ *     aggregator's To16 form (gns_ex_*: ::ffff:a.b.c.d).
+ *   - Records: gns_exs_insert_headers keeps, drops or counts a record as
+ *     unsupported by the rules of gns_ss_insert_headers (the same parser); for the
+ *     same input counters [0..2] equal SuperSpread's.
+ *   - No traffic-dependent failure: the flow table and the pair table grow before
+ *     a device batch that could fill them (max_flows / max_pairs are only the
+ *     initial capacities); GNS_E_OOM only when the device cannot hold them (pair
+ *     table limit 2^31 slots, flow table 2^30).
+ *   - GNS_E_ARG at create: flow_bytes == 0, elem_bytes == 0, either above 37, more
+ *     than 8 fields in a layout (checked before any device call).  With empty
+ *     layouts (flow_bytes / elem_bytes alone) only gns_exs_insert_keys is usable.
+ *   - Deviation from SuperSpread.Query (super_spread.go:238-258, minimum 1): a
+ *     flow never seen answers 0. */
+typedef struct gns_exs gns_exs;
+typedef struct gns_exs_params {
+    gns_layout flow, elem;   /* FlowFields / ElementFields */
+    uint32_t flow_bytes, elem_bytes;
+    uint64_t max_flows;      /* initial flow-table capacity (grows); 0 -> 1M */
+    uint64_t max_pairs;      /* initial pair-table capacity (grows); 0 -> 4M */
+    uint64_t batch_packets;  /* device batch; longer inserts are split; 0 -> 4M */
+    int device;
+} gns_exs_params;
+int gns_exs_create(const gns_exs_params *p, gns_exs **out);
+int gns_exs_destroy(gns_exs *h);
+int gns_exs_insert_keys(gns_exs *h, const uint8_t *flows, uint32_t fstride, const uint8_t *elems,
+                        uint32_t estride, uint64_t n, gns_mem where);
+int gns_exs_insert_tuples(gns_exs *h, const gns_tuples *t, uint64_t n, gns_mem where);
+int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n,
+                           gns_mem where);
+int gns_exs_flush(gns_exs *h);
+/* out[i] = spread of flow i (0 if never seen) */
+int gns_exs_query(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
+/* device keys / answers, as gns_ss_query_device */
+int gns_exs_query_device(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
+/* The flows with spread >= threshold, spread descending, ties by flow bytes
+ * ascending (the shared list code of gns_cm_heavy_hitters).  *n = capacity in
+ * (rows), full list length out; a list longer than its buffers is reported and
+ * not written.  A threshold of 0 lists every seen flow (as 1 does). */
+int gns_exs_heavy_hitters(gns_exs *h, uint32_t threshold, uint8_t *flows, uint32_t *spreads, uint64_t *n);
+/* Every seen flow and its spread, in unspecified order; *n as above; NULL
+ * buffers ask for the count only. */
+int gns_exs_snapshot(gns_exs *h, uint8_t *flows, uint32_t *spreads, uint64_t *n);
+/* empties both tables (they keep the size they have grown to); counters [0..4], [6], [7] keep counting */
+int gns_exs_reset(gns_exs *h);
+/* out[8]: inserted, dropped, unsupported, 0 (a probe without a free slot: cannot
+ * happen), new pairs, flows now, records, device batches */
+int gns_exs_counters(gns_exs *h, uint64_t out[8]);
+/* [0] flow-table growths, [1] pair-table growths, [2] flow slots, [3] flow slots
+ * claimed, [4] pair slots, [5] pair slots claimed, [6] growth time (us, host clock
+ * incl. the device work), [7] 0 */
+int gns_exs_dict_stats(gns_exs *h, uint64_t out[8]);
+int gns_exs_set_timing(gns_exs *h, int on);
+/* stages: 0 insert (first pass), 1 resolve rounds, 2 table growth, 5 total */
+int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset);
+
 /* Device buffers for callers without a device allocator of their own (the cgo
  * binding's ThriftDecoder: gns_thrift_decode writes device records that
  * gns_*_insert_headers then reads with GNS_MEM_DEVICE). */
