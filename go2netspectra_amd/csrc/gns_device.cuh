@@ -88,9 +88,11 @@ __device__ __forceinline__ void set_ports(uint32_t (&tw)[10], uint32_t sport, ui
 // gopacket v1.1.19 keeps a layer whose decode fails with the fields it set
 // before the failing check (decodeIPv4 / decodeIPv6 / decodeTCP / decodeUDP
 // call p.AddLayer before returning the error), and parser.go:38-61 reads them:
-//   IPv4 data < 20 bytes       -> IPv4 layer with nil IPs: counted, zero IPs, proto 0
+//   no byte after the L2 header -> NextDecoder does nothing on an empty payload:
+//                                 no IP layer, "not an IP packet" (DROP, parser.go:48-49)
+//   IPv4 data 1..19 bytes      -> IPv4 layer with nil IPs: counted, zero IPs, proto 0
 //   IPv4 Length < 20, IHL < 5, IHL*4 > Length -> IPs + protocol, ports 0
-//   IPv6 data < 40 bytes       -> nil IPs, NextHeader 0
+//   IPv6 data 1..39 bytes      -> nil IPs, NextHeader 0
 //   IPv6 Length 0 (no HBH)     -> IPs + NextHeader, ports 0
 //   TCP < 20 bytes / UDP < 8   -> the layer with ports 0; a TCP data offset < 5 or
 //                                 beyond the data errs after the ports are read
@@ -103,6 +105,7 @@ __device__ __forceinline__ int parse_l3(const uint32_t (&w)[16], uint32_t type, 
     const uint32_t l2hdr = 14u + 4u * nv;
     const uint32_t lim = 64u - 4u * nv;
     const uint32_t l2len = wirelen > l2hdr ? wirelen - l2hdr : 0u;
+    if ((type == 0x0800u || type == 0x86DDu) && l2len == 0) return PARSE_DROP;  // NextDecoder: no IP layer
     if (type == 0x0800u) {  // gopacket IPv4.DecodeFromBytes
         if (l2len < 20) return PARSE_OK;  // nil IPs (version bytes 0), protocol 0, no ports
         const uint32_t ihl = rec_byte<OFF>(w) & 15u;

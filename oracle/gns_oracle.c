@@ -90,7 +90,10 @@ int or_parse_hdr64_len(const uint8_t *r, uint32_t wirelen, or_tuple *t) {
     uint32_t l2len = wirelen > off ? wirelen - off : 0; /* bytes after the L2 header */
     /* gopacket v1.1.19 decodeIPv4 / decodeIPv6 / decodeTCP / decodeUDP add the
      * layer before returning a decode error, with the fields DecodeFromBytes set
-     * before the failing check; parser.go:38-61 reads those fields. */
+     * before the failing check; parser.go:38-61 reads those fields.  With no
+     * byte after the L2 header NextDecoder never calls the IP decoder: no IP
+     * layer, parser.go:48-49 "not an IP packet". */
+    if ((type == 0x0800 || type == 0x86DD) && l2len == 0) return OR_PARSE_DROP;
     if (type == 0x0800) { /* gopacket IPv4.DecodeFromBytes */
         const uint8_t *ip = r + off;
         if (l2len < 20) return OR_PARSE_OK; /* "Invalid ip4 header": nil IPs, Protocol 0 */

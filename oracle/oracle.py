@@ -128,6 +128,25 @@ def parse_hdr64(rec: bytes, wirelen: int):
     return st, bytes(t.src), bytes(t.dst), t.sport, t.dport, t.proto
 
 
+def parse_hdr64_batch(hdr: np.ndarray, wirelen: np.ndarray) -> dict:
+    """or_parse_hdr64_len per record -> arrays: status, src16, dst16, sport, dport, proto,
+    sver / dver (IP version of the source / destination address: 4, 6 or 0)."""
+    hdr = np.ascontiguousarray(hdr, np.uint8)
+    wirelen = np.ascontiguousarray(wirelen, np.uint32)
+    n = len(wirelen)
+    out = dict(status=np.zeros(n, np.uint8), src16=np.zeros((n, 16), np.uint8), dst16=np.zeros((n, 16), np.uint8),
+               sport=np.zeros(n, np.uint16), dport=np.zeros(n, np.uint16), proto=np.zeros(n, np.uint8),
+               sver=np.zeros(n, np.uint8), dver=np.zeros(n, np.uint8))
+    L, t = lib(), TupleRec()
+    base = hdr.ctypes.data
+    for i in range(n):
+        out["status"][i] = L.or_parse_hdr64_len(base + 64 * i, int(wirelen[i]), ct.byref(t))
+        out["src16"][i], out["dst16"][i] = t.src, t.dst
+        out["sport"][i], out["dport"][i], out["proto"][i] = t.sport, t.dport, t.proto
+        out["sver"][i], out["dver"][i] = t.ipver, t.dst_ipver
+    return out
+
+
 def field_ids(fields) -> np.ndarray:
     return np.array([FIELD_IDS.get(f, 0) for f in fields] or [0], dtype=np.uint8)
 

@@ -175,6 +175,17 @@ PARSE = [
      None, None, 0, 0, 0),
     ("mpls_unsupported", frame(src=V4S, dst=V4D, sport=0, dport=0, proto=0, ethertype=0x8847), 60, UNSUP,
      None, None, 0, 0, 0),
+    # empty-L3 rule: no byte on the wire after the L2 header -> NextDecoder never runs the IP
+    # decoder, no IP layer exists, parser.go:48-49 rejects the packet
+    ("ipv4_no_l3_bytes_dropped", frame(src=V4S, dst=V4D, sport=1, dport=2, proto=6), 14, DROP, None, None, 0, 0, 0),
+    ("vlan_ipv4_no_l3_bytes_dropped", frame(src=V4S, dst=V4D, sport=1, dport=2, proto=6, vlans=1), 18, DROP,
+     None, None, 0, 0, 0),
+    ("ipv6_no_l3_bytes_dropped", frame(src=V6S, dst=V6D, sport=1, dport=2, proto=6, v6=True), 14, DROP,
+     None, None, 0, 0, 0),
+    ("ipv4_wirelen_13_dropped", frame(src=V4S, dst=V4D, sport=1, dport=2, proto=6), 13, DROP, None, None, 0, 0, 0),
+    # one byte of L3 is enough for decodeIPv4 to run and add its (nil) layer
+    ("ipv4_one_l3_byte_nil_ips", frame(src=V4S, dst=V4D, sport=1, dport=2, proto=6), 15, OK,
+     bytes(4), bytes(4), 0, 0, 0),
 ]
 
 
@@ -214,7 +225,12 @@ def main():
     json.dump({"bucket": "w=1 d=1 key_bytes=4 (every update hits the same bucket)",
                "state_fields": ["C", "FPc", "S", "FPs"], "traces": CM_TRACES},
               open(os.path.join(HERE, "cm_traces.json"), "w"), indent=1)
-    # --- parse vectors ---
+    write_parse_vectors()
+    write_streams()
+    print("golden fixtures written")
+
+
+def write_parse_vectors():
     vecs = []
     for name, rec, wl, st, s, d, sp, dp, pr in PARSE + [("preparsed_escape", preparsed(), 300, OK, V4S, V4D,
                                                           4444, 5555, 6)]:
@@ -229,7 +245,9 @@ def main():
                      "sport": sp, "dport": dp, "proto": pr})
     json.dump({"status": {"0": "ok", "1": "dropped (not IP, parser.go:48-49)", "2": "outside fast-parse subset"},
                "vectors": vecs}, open(os.path.join(HERE, "parse_vectors.json"), "w"), indent=1)
-    # --- stream fixture ---
+
+
+def write_streams():
     from helpers import sizes_u32, zipf_keys
     rng = np.random.default_rng(20260424)
     keys, _, _ = zipf_keys(rng, 4096, 300, 16)
@@ -273,7 +291,6 @@ def main():
                         hh=np.array([v for _, v in sh], np.uint32),
                         params=np.array([64, 2, 20, 32, 5, 16, 16], np.uint32),
                         fparams=np.array([0.5, 1.08]), seeds64=np.array([0xABCDEF, 0x13579], np.uint64))
-    print("golden fixtures written")
 
 
 if __name__ == "__main__":

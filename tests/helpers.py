@@ -35,6 +35,18 @@ def assert_same_list(got: list, want: list, what: str = "list") -> None:
     raise AssertionError(f"{what}: lengths differ: got {len(got)} want {len(want)}")
 
 
+def owner_of_records(oracle, hdr, wl, G):
+    """Host owner shard per record: parse with the oracle; records it does not count go to 0."""
+    from go2netspectra_amd.dist import shard_of
+    src = np.zeros((len(wl), 16), np.uint8)
+    ok = np.zeros(len(wl), bool)
+    for i in range(len(wl)):
+        st, s16, _, _, _, _ = oracle.parse_hdr64(bytes(hdr[i]), int(wl[i]))
+        ok[i] = st == 0
+        src[i] = np.frombuffer(s16, np.uint8)
+    return np.where(ok, shard_of(src, G), 0)
+
+
 def zipf_index(rng, n: int, nflows: int, s: float = 1.1) -> np.ndarray:
     p = np.arange(1, nflows + 1, dtype=np.float64) ** -s
     cdf = np.cumsum(p)
@@ -338,6 +350,57 @@ def thrift_messages(rng, n, nflows=500, bad_frac=0.1, v6_frac=0.3):
                 m = bytes(rng.integers(0, 256, int(rng.integers(1, 80)), dtype=np.uint8))
         msgs.append(m)
     return msgs
+
+
+# The device decoder's fast path takes a 70-byte message after checking these 34 header
+# bytes of MarshalPacketInfo's IPv4 layout (field types and ids, the two address lengths,
+# the two STOP bytes).
+THRIFT_HEADER_BYTES = (0, 1, 2, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 25, 26, 27, 28, 29, 30, 31, 36, 37, 38,
+                       43, 44, 45, 50, 51, 52, 57, 58, 59, 60, 69)
+THRIFT_NEAR_VALUES = (0, 1, 2, 3, 4, 5, 8, 0x0A, 0x0B, 0x0C, 0x10, 0x7F, 0x80, 0xFF)
+
+
+def thrift_near_misses():
+    """70-byte messages around the canonical IPv4 PacketInfo: (valid, invalid).
+    valid: [(name, message, (ts, src, dst, sport, dport, proto, length))], messages of 70
+    bytes that are not the canonical layout (or are it: "ft_345") and decode.
+    invalid: [(name, message)], the canonical message with one checked header byte replaced."""
+    import itertools
+    ts, ln = 0x0102030405060708, 0x1112131415161718
+    src, dst, sp, dp, pr = bytes([10, 20, 30, 40]), bytes([50, 60, 70, 80]), 0x1234, 0x5678, 0x11
+    want = (ts, src, dst, sp, dp, pr, ln)
+
+    def fs(fid, b):
+        return b"\x0b\x00" + bytes([fid]) + struct.pack(">i", len(b)) + b
+
+    def fi(fid, v):
+        return b"\x08\x00" + bytes([fid]) + struct.pack(">i", v)
+
+    f1 = b"\x0a\x00\x01" + struct.pack(">q", ts)
+    f3 = b"\x0a\x00\x03" + struct.pack(">q", ln)
+    ints = {3: fi(3, sp), 4: fi(4, dp), 5: fi(5, pr)}
+
+    def msg(top="123", ips="12", order=(3, 4, 5), s=src, d=dst):
+        ip = {"1": fs(1, s), "2": fs(2, d)}
+        ft = b"\x0c\x00\x02" + b"".join(ip[c] for c in ips) + b"".join(ints[i] for i in order) + b"\x00"
+        return b"".join({"1": f1, "2": ft, "3": f3}[c] for c in top) + b"\x00"
+
+    canonical = msg()
+    from go2netspectra_amd.thrift import marshal_packet_info
+    assert canonical == marshal_packet_info(ts, src, dst, sp, dp, pr, ln) and len(canonical) == 70
+    valid = [("top_321", msg(top="321"), want), ("ips_21", msg(ips="21"), want)]
+    for order in itertools.permutations((3, 4, 5)):
+        valid.append(("ft_" + "".join(map(str, order)), msg(order=order), want))
+    for a, b in ((3, 5), (5, 3), (0, 8), (8, 0)):
+        s, d = bytes(range(0xA1, 0xA1 + a)), bytes(range(0xB1, 0xB1 + b))
+        valid.append((f"iplen_{a}_{b}", msg(s=s, d=d), (ts, s, d, sp, dp, pr, ln)))
+    assert all(len(m) == 70 for _, m, _ in valid)
+    invalid = []
+    for pos in THRIFT_HEADER_BYTES:
+        for v in THRIFT_NEAR_VALUES:
+            if canonical[pos] != v:
+                invalid.append((f"byte{pos}_{v:02x}", canonical[:pos] + bytes([v]) + canonical[pos + 1:]))
+    return valid, invalid
 
 
 def pcapgen_records(rng, n: int):

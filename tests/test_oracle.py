@@ -241,3 +241,24 @@ def test_thrift_decode_c_vs_python(oracle):
         assert (out["sport"][i], out["dport"][i], out["proto"][i]) == (sp, dp, pr)
         assert out["sver"][i] == {4: 4, 16: 6}.get(len(s), 0)
     assert 2500 < nok < 3900
+
+
+def test_thrift_near_misses_c_vs_python(oracle):
+    """CPU twin of test_thrift_gpu.py::test_fast_path_near_misses: on the 70-byte messages
+    around the device fast path the two CPU restatements agree; the valid variants decode
+    to their own fields and every one-byte header replacement is rejected."""
+    from go2netspectra_amd.thrift import pack_messages
+    from helpers import py_thrift_decode, thrift_near_misses
+    valid, invalid = thrift_near_misses()
+    assert len(valid) == 12 and len(invalid) == 34 * 14 - 34  # every checked byte is one of the 14 values
+    msgs = [m for _, m, _ in valid] + [m for _, m in invalid]
+    out = oracle.thrift_decode(*pack_messages(msgs))
+    for i, (name, m, want) in enumerate(valid):
+        assert py_thrift_decode(m) == want, name
+        ts, s, d, sp, dp, pr, ln = want
+        assert out["ok"][i] and out["ts"][i] == ts and out["length"][i] == ln, name
+        assert bytes(out["src16"][i]) == s + bytes(16 - len(s)) and bytes(out["dst16"][i]) == d + bytes(16 - len(d)), name
+        assert (out["sport"][i], out["dport"][i], out["proto"][i]) == (sp, dp, pr), name
+        assert (out["sver"][i], out["dver"][i]) == ({4: 4}.get(len(s), 0), {4: 4}.get(len(d), 0)), name
+    for i, (name, m) in enumerate(invalid, len(valid)):
+        assert py_thrift_decode(m) is None and not out["ok"][i], name

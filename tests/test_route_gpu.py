@@ -6,23 +6,11 @@ stable filter of the unsharded stream."""
 import numpy as np
 import pytest
 
-from helpers import assert_same_list, frames_from_tuples, random_tuples
+from helpers import assert_same_list, frames_from_tuples, owner_of_records, random_tuples
 
 pytestmark = pytest.mark.gpu
 
 FIVE = ["SrcIP", "DstIP", "SrcPort", "DstPort", "Protocol"]
-
-
-def owner_of_records(oracle, hdr, wl, G):
-    """Host owner shard per record: parse with the oracle; records it does not count go to 0."""
-    from go2netspectra_amd.dist import shard_of
-    src = np.zeros((len(wl), 16), np.uint8)
-    ok = np.zeros(len(wl), bool)
-    for i in range(len(wl)):
-        st, s16, _, _, _, _ = oracle.parse_hdr64(bytes(hdr[i]), int(wl[i]))
-        ok[i] = st == 0
-        src[i] = np.frombuffer(s16, np.uint8)
-    return np.where(ok, shard_of(src, G), 0)
 
 
 @pytest.mark.parametrize("G", [1, 3, 8, 64])

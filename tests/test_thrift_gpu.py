@@ -49,6 +49,56 @@ def test_decode_parity(gpu, oracle):
     assert np.array_equal(hb.ts.cpu().numpy(), ts)
 
 
+def assert_decode_is_oracle(oracle, msgs, what):
+    from go2netspectra_amd.thrift import decode_messages, pack_messages
+    buf, offs = pack_messages(msgs)
+    hb, nbad = decode_messages(buf, offs)
+    out = oracle.thrift_decode(buf, offs)
+    rec, wl, ts = expected_records(out)
+    assert nbad == int((out["ok"] == 0).sum()), what
+    got = hb.hdr.cpu().numpy()
+    bad = np.nonzero((got != rec).any(axis=1))[0]
+    assert len(bad) == 0, f"{what}: record of message {bad[:5]} (offset {offs[bad[:5]]}) differs from the oracle's"
+    assert np.array_equal(hb.wirelen.cpu().numpy().view(np.uint32), wl), what
+    assert np.array_equal(hb.ts.cpu().numpy(), ts), what
+    return out, got
+
+
+def test_fast_path_near_misses(gpu, oracle):
+    """The 70-byte fast path of k_thrift_decode takes a message after checking 34 header
+    bytes.  Valid 70-byte messages that are not the canonical layout must decode with
+    every value in its own field, and the canonical message with any one checked byte
+    replaced must come out as the full decoder has it (rejected): at each alignment of
+    the message in the buffer, and as the last message of a buffer of every length
+    mod 16 (the fast path's over-read guard)."""
+    from helpers import thrift_near_misses
+    valid, invalid = thrift_near_misses()
+    msgs = [m for _, m, _ in valid] + [m for _, m in invalid]
+    # every message at every alignment: a rejected message of 0..3 bytes in front of it
+    batch, at, pos = [], [], 0
+    for m in msgs:
+        for k in range(4):
+            pad = b"\x7f" * ((k - pos) & 3)
+            batch += [pad, m]
+            pos += len(pad) + len(m)
+            at.append(len(batch) - 1)
+            assert ((pos - len(m)) & 3) == k
+    out, got = assert_decode_is_oracle(oracle, batch, "alignments")
+    at = np.array(at).reshape(len(msgs), 4)
+    assert not out["ok"][at - 1].any()  # the pads
+    assert out["ok"][at[:len(valid)]].all() and not out["ok"][at[len(valid):]].any()
+    for (name, m, want), rows in zip(valid, at):
+        ts, s, d, sp, dp, pr, ln = want
+        for i in rows:
+            assert bytes(got[i, 16:32]) == s + bytes(16 - len(s)) and bytes(got[i, 32:48]) == d + bytes(16 - len(d)), name
+            assert bytes(got[i, 48:53]) == bytes([sp >> 8, sp & 255, dp >> 8, dp & 255, pr]), name
+            assert (got[i, 15], got[i, 53]) == ({4: 4}.get(len(s), 0), {4: 4}.get(len(d), 0)), name
+    # last message of the buffer, buffer length mod 16 = 0..15
+    for name, m in [(n, m) for n, m, _ in valid] + invalid:
+        for r in range(16):
+            assert_decode_is_oracle(oracle, [b"\x7f" * ((r - len(m)) & 15), m], f"{name} last, length mod 16 = {r}")
+
+
 def test_records_drive_all_engines(gpu, oracle):
     import torch
     from go2netspectra_amd import CountMin, ExactTask, SuperSpread
