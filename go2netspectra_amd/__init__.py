@@ -8,7 +8,8 @@ behind the C ABI in include/gns_sketch.h (libgns_sketch.so).
 """
 from ._lib import GnsError, build, load
 from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_config
-from .exact import ExactAggregator, ExactTask, NewExact, SnapshotData
+from .exact import (ExactAggregator, ExactTask, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
+                    TaskSummary, make_filter, merge_summaries)
 from .factory import Manager, TaskGroup, create, register_aggregator
 from .packets import (HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
@@ -21,5 +22,6 @@ __all__ = [
     "TaskGroup", "create", "register_aggregator", "HeaderBatch", "PacketBatch", "SyntheticTraffic",
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
-    "NewExact", "SnapshotData", "ExactSpread",
+    "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
+    "make_filter", "merge_summaries",
 ]

@@ -46,6 +46,7 @@ EXPORTED = [
     "gns_exs_create", "gns_exs_destroy", "gns_exs_insert_keys", "gns_exs_insert_tuples", "gns_exs_insert_headers",
     "gns_exs_flush", "gns_exs_query", "gns_exs_query_device", "gns_exs_heavy_hitters", "gns_exs_snapshot",
     "gns_exs_reset", "gns_exs_counters", "gns_exs_dict_stats", "gns_exs_set_timing", "gns_exs_stage_times",
+    "gns_ex_aggregate", "gns_ex_heavy_hitters",
 ]
 
 
@@ -96,6 +97,17 @@ class SsParams(ct.Structure):
 
 class ExParams(ct.Structure):
     _fields_ = [("key", Layout), ("max_flows", ct.c_uint64), ("batch_packets", ct.c_uint64), ("device", ct.c_int)]
+
+
+class ExFilter(ct.Structure):  # gns_ex_filter: 44 bytes
+    _fields_ = [("mask", ct.c_uint32), ("src16", ct.c_uint8 * 16), ("dst16", ct.c_uint8 * 16),
+                ("sport", ct.c_uint16), ("dport", ct.c_uint16), ("proto", ct.c_uint8), ("_pad", ct.c_uint8 * 3)]
+
+
+class ExSummary(ct.Structure):  # gns_ex_summary: 56 bytes
+    _fields_ = [("flows", ct.c_uint64), ("packets", ct.c_uint64), ("bytes", ct.c_uint64),
+                ("first_ns", ct.c_int64), ("last_ns", ct.c_int64),
+                ("max_packets", ct.c_uint64), ("max_bytes", ct.c_uint64)]
 
 
 class ExsParams(ct.Structure):
@@ -198,6 +210,8 @@ def load() -> ct.CDLL:
         "gns_exs_heavy_hitters": ([vp, u32, vp, vp, vp], i32), "gns_exs_snapshot": ([vp, vp, vp, vp], i32),
         "gns_exs_reset": ([vp], i32), "gns_exs_counters": ([vp, vp], i32), "gns_exs_dict_stats": ([vp, vp], i32),
         "gns_exs_set_timing": ([vp, i32], i32), "gns_exs_stage_times": ([vp, vp, vp, i32], i32),
+        "gns_ex_aggregate": ([vp, vp, u32, vp], i32),
+        "gns_ex_heavy_hitters": ([vp, i32, u64, u64, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -32,6 +32,8 @@
 //                      workgroup, which merges each of its flows once
 //   T   k_ex_times     StartTime / EndTime of the flows the batch touched
 //   D   k_exh_*        designate the next batch's heavy flows
+//   Q   k_exq_aggregate  filtered aggregates of the resident table (gns_ex_aggregate)
+//   HH  k_exq_hh_*     flows above a threshold, ordered, cut to a limit (gns_ex_heavy_hitters)
 // A Zipf batch touches a flow in many places; per-block LDS aggregation of
 // every flow left the tail flows to global atomics, three per packet; sorting
 // every packet (rocPRIM radix sort of 100M words) made the sort the largest
@@ -41,6 +43,8 @@
 #include <chrono>
 #include <cstring>
 #include <vector>
+
+#include <rocprim/device/device_merge_sort.hpp>
 
 #include "gns_common.hpp"
 #include "gns_xcd.cuh"
@@ -980,6 +984,241 @@ __global__ __launch_bounds__(256) void k_ex_gather(const uint32_t *ids, uint64_t
     start[p] = f.start[id]; end[p] = f.end[id]; pkts[p] = f.pkts[id]; bytes[p] = f.bytes[id];
 }
 
+// ---------------------------------------------------------------------------
+// Query plane (gns_ex_aggregate / gns_ex_heavy_hitters): the Querier's questions
+// (internal/query/querier.go) answered by scans of the resident table.
+// ---------------------------------------------------------------------------
+// Q: filtered aggregates.  A filter is equality on some key fields
+// (appendAggregationFilters, querier.go:143-188).  The host turns it into one
+// (mask, value) pair per little-endian key word of the record -- fields lie at
+// the byte offsets of the handle's layout, aligned or not -- so a lane tests a
+// filter with nkw AND / compare pairs on the key words it already holds.  One
+// pass answers up to kQBatch filters: a lane loads its slot's tag, key words
+// and state words once and tests every filter of the batch against them.  A
+// filter some lane of the wave matches is reduced across the wave, merged into
+// the workgroup's LDS partials, and leaves the CU as one set of global updates
+// per workgroup and filter.  All of it is integer add / min / max: bit-exact in
+// any order.  StartTime / EndTime are signed: they are reduced as unsigned
+// words with the sign bit flipped, which keeps their order.
+constexpr uint32_t kQBatch = 64;
+#ifndef GNS_EXQ_NARROW
+#define GNS_EXQ_NARROW 4
+#endif
+constexpr uint32_t kQNarrow = GNS_EXQ_NARROW;  // a batch of at most this many filters reduces each match across the wave
+static_assert(kQBatch == 64, "the wide scan gives every lane of a wave one filter of the batch");
+constexpr uint32_t kQAcc = 7;  // flows, packets, bytes, min start, max end, max packets, max bytes
+constexpr unsigned long long kQSign = 1ull << 63;
+struct ExQFilter {
+    uint32_t m[GNS_KWMAX], v[GNS_KWMAX];  // match: (key word & m) == v for every key word
+};
+__host__ __device__ inline unsigned long long exq_acc_init(uint32_t j) { return j == 3 ? ~0ull : 0ull; }
+
+extern "C" __device__ unsigned long long __ockl_wfred_min_u64(unsigned long long);
+extern "C" __device__ unsigned long long __ockl_wfred_max_u64(unsigned long long);
+
+// value of wave-uniform lane j
+__device__ __forceinline__ unsigned long long exq_lane_u64(unsigned long long v, uint32_t j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j);
+    return (unsigned long long)hi << 32 | lo;
+}
+
+// WIDE = false (a few filters): a filter some lane matches is reduced across the wave
+// at once (six 64-bit wave reductions) into the workgroup's partials.
+// WIDE = true: those reductions, per filter and table row of the wave, cost several
+// times the filter tests themselves once a dozen filters match most flows.  So the wave
+// is turned: lane q owns filter q of the batch (kQBatch = the wave width) and keeps its
+// partials in registers for the whole scan; per row of 64 slots it gets the ballot of
+// the lanes filter q matched, then walks the slots any filter matched -- their state
+// words broadcast from the owning lane -- and merges those its ballot names.  One walk
+// serves all 64 filters, and nothing is reduced before the scan ends.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots, FlowState f,
+                                                       const ExQFilter *__restrict__ flt, uint32_t nf,
+                                                       unsigned long long *__restrict__ acc) {
+    __shared__ unsigned long long s_a[kQBatch][kQAcc];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t i = tid; i < nf * kQAcc; i += 256) s_a[i / kQAcc][i % kQAcc] = exq_acc_init(i % kQAcc);
+    __syncthreads();
+    const uint32_t nkw = (D.K + 3) >> 2;
+    unsigned long long a_n = 0, a_pk = 0, a_by = 0, a_st = ~0ull, a_en = 0, a_mp = 0, a_mb = 0;  // WIDE: filter `lane`
+    for (uint64_t s0 = (uint64_t)blockIdx.x * 256; s0 < slots; s0 += (uint64_t)gridDim.x * 256) {  // block-uniform
+        const uint64_t s = s0 + tid;
+        uint32_t r[12];
+        unsigned long long pk = 0, by = 0, st = ~0ull, en = 0;
+        bool occ = false;
+        if (s < slots) {
+            load_record(D, (uint32_t)s, r);
+            pk = f.pkts[s]; by = f.bytes[s];
+            st = (unsigned long long)f.start[s] ^ kQSign; en = (unsigned long long)f.end[s] ^ kQSign;
+            occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
+        }
+        if (!__ballot(occ)) continue;  // wave-uniform
+        unsigned long long mine = 0;   // WIDE: the lanes filter `lane` matched
+        bool any = false;
+        for (uint32_t q = 0; q < nf; q++) {
+            // the filter's words are wave-uniform: scalar loads, operands from scalar registers
+            const ExQFilter *fq = flt + q;
+            bool hit = occ;
+#pragma unroll
+            for (int i = 0; i < GNS_KWMAX; i++) {
+                const uint32_t m = fq->m[i], v = fq->v[i];
+                // every key word, open ones (m = v = 0) too: skipping them on a uniform branch
+                // measured 30% slower than the two vector instructions it saves
+                if ((uint32_t)i < nkw) hit = hit && ((r[1 + i] & m) == v);
+            }
+            const uint64_t hm = __ballot(hit);
+            if constexpr (WIDE) {
+                mine = lane == q ? hm : mine;
+                any = any || hit;
+            } else {
+                if (!hm) continue;  // wave-uniform: every lane takes part in the reductions below
+                const unsigned long long tp = __ockl_wfred_add_u64(hit ? pk : 0ull);
+                const unsigned long long tb = __ockl_wfred_add_u64(hit ? by : 0ull);
+                const unsigned long long ts = __ockl_wfred_min_u64(hit ? st : ~0ull);
+                const unsigned long long te = __ockl_wfred_max_u64(hit ? en : 0ull);
+                const unsigned long long mp = __ockl_wfred_max_u64(hit ? pk : 0ull);
+                const unsigned long long mb = __ockl_wfred_max_u64(hit ? by : 0ull);
+                if (lane == 0) {
+                    atomicAdd(&s_a[q][0], (unsigned long long)__popcll(hm));
+                    atomicAdd(&s_a[q][1], tp);
+                    atomicAdd(&s_a[q][2], tb);
+                    atomicMin(&s_a[q][3], ts);
+                    atomicMax(&s_a[q][4], te);
+                    atomicMax(&s_a[q][5], mp);
+                    atomicMax(&s_a[q][6], mb);
+                }
+            }
+        }
+        if constexpr (WIDE) {
+            uint64_t todo = __ballot(any);  // slots some filter matched (wave-uniform walk)
+            while (todo) {
+                const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1);
+                todo &= todo - 1;
+                const unsigned long long pj = exq_lane_u64(pk, j), bj = exq_lane_u64(by, j);
+                const unsigned long long sj = exq_lane_u64(st, j), ej = exq_lane_u64(en, j);
+                if (mine >> j & 1ull) {
+                    a_n += 1; a_pk += pj; a_by += bj;
+                    a_st = min(a_st, sj); a_en = max(a_en, ej);
+                    a_mp = max(a_mp, pj); a_mb = max(a_mb, bj);
+                }
+            }
+        }
+    }
+    if constexpr (WIDE) {
+        if (lane < nf && a_n != 0ull) {
+            atomicAdd(&s_a[lane][0], a_n);
+            atomicAdd(&s_a[lane][1], a_pk);
+            atomicAdd(&s_a[lane][2], a_by);
+            atomicMin(&s_a[lane][3], a_st);
+            atomicMax(&s_a[lane][4], a_en);
+            atomicMax(&s_a[lane][5], a_mp);
+            atomicMax(&s_a[lane][6], a_mb);
+        }
+    }
+    __syncthreads();
+    if (tid < nf && s_a[tid][0] != 0ull) {
+        unsigned long long *a = acc + (uint64_t)tid * kQAcc;
+        atomicAdd(&a[0], s_a[tid][0]);
+        atomicAdd(&a[1], s_a[tid][1]);
+        atomicAdd(&a[2], s_a[tid][2]);
+        atomicMin(&a[3], s_a[tid][3]);
+        atomicMax(&a[4], s_a[tid][4]);
+        atomicMax(&a[5], s_a[tid][5]);
+        atomicMax(&a[6], s_a[tid][6]);
+    }
+}
+
+// HH: the flows with value >= threshold in (value desc, key bytes asc) order, cut to
+// `limit` rows.  Values are 64-bit and a row is a flow, so the 32-bit fingerprint
+// list of gns_hh.hpp does not fit; as the hot-flow designation above (k_exh_*), a
+// histogram over 1/8-octave bands of the value picks the lowest band the cut can
+// reach, only the flows from that band up are compacted into rows (every flow
+// below it is lighter than all of them, and equal values share a band, so ties at
+// the cut are all candidates), and only those rows are ordered.
+//   HH1 k_exq_hh_hist     band histogram of the qualifying flows (its sum = list length)
+//   HH2 k_exq_hh_collect  rows {value, key words byte-swapped: word compare = byte compare}
+//   HH3 rocprim::merge_sort of the rows by (value desc, key asc)
+//   HH4 k_exq_hh_out      the first rows -> key bytes, values
+constexpr uint32_t kQBands = 512;
+__device__ __forceinline__ uint32_t exq_band(unsigned long long v) {
+    if (v < 8) return 0;
+    const uint32_t lz = 63u - (uint32_t)__clzll((long long)v);
+    return lz * 8u + (uint32_t)((v >> (lz - 3)) & 7u);  // <= 63 * 8 + 7
+}
+struct ExHhRow {
+    unsigned long long v;
+    uint32_t k[GNS_KWMAX];
+};
+struct ExHhLess {
+    __host__ __device__ bool operator()(const ExHhRow &a, const ExHhRow &b) const {
+        if (a.v != b.v) return a.v > b.v;
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++)
+            if (a.k[i] != b.k[i]) return a.k[i] < b.k[i];
+        return false;
+    }
+};
+__device__ __forceinline__ bool exq_hh_take(const DictDev &D, const FlowState &f, uint64_t s, uint64_t slots, int metric,
+                                            unsigned long long thr, unsigned long long &v) {
+    if (s >= slots) return false;
+    const unsigned long long pk = f.pkts[s];
+    v = metric ? f.bytes[s] : pk;
+    return D.rec[s * D.RW] != 0u && pk != 0ull && v >= thr;
+}
+__global__ __launch_bounds__(256) void k_exq_hh_hist(DictDev D, uint64_t slots, FlowState f, int metric,
+                                                     unsigned long long thr, uint32_t *hist) {
+    __shared__ uint32_t h[kQBands];
+    for (uint32_t i = threadIdx.x; i < kQBands; i += 256) h[i] = 0;
+    __syncthreads();
+    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * 256) {
+        unsigned long long v;
+        if (exq_hh_take(D, f, s, slots, metric, thr, v)) atomicAdd(&h[exq_band(v)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kQBands; i += 256)
+        if (h[i]) atomicAdd(&hist[i], h[i]);
+}
+__global__ __launch_bounds__(256) void k_exq_hh_collect(DictDev D, uint64_t slots, FlowState f, int metric,
+                                                        unsigned long long thr, uint32_t band, ExHhRow *rows,
+                                                        uint32_t *cnt, uint32_t cap) {
+    const uint32_t lane = __lane_id();
+    for (uint64_t s0 = (uint64_t)blockIdx.x * 256; s0 < slots; s0 += (uint64_t)gridDim.x * 256) {  // block-uniform
+        const uint64_t s = s0 + threadIdx.x;
+        unsigned long long v = 0;
+        const bool take = exq_hh_take(D, f, s, slots, metric, thr, v) && exq_band(v) >= band;
+        const uint64_t m = __ballot(take);
+        if (!m) continue;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        uint32_t base = 0;
+        if ((int)lane == leader) base = atomicAdd(cnt, (uint32_t)__popcll(m));
+        base = __shfl(base, leader);
+        const uint32_t q = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (take && q < cap) {  // (cap = the histogram's count of these bands: never exceeded)
+            uint32_t r[12];
+            load_record(D, (uint32_t)s, r);
+            ExHhRow row;
+            row.v = v;
+#pragma unroll
+            for (int i = 0; i < GNS_KWMAX; i++) row.k[i] = __builtin_bswap32(r[1 + i] & tail_mask(D.K, i));
+            rows[q] = row;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_exq_hh_out(const ExHhRow *rows, uint64_t n, uint32_t K, uint8_t *keys,
+                                                    unsigned long long *vals) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const ExHhRow row = rows[p];
+    for (uint32_t j = 0; j < K; j++) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++) w = (j >> 2) == (uint32_t)i ? row.k[i] : w;
+        keys[p * K + j] = (uint8_t)(w >> (8u * (3u - (j & 3u))));
+    }
+    vals[p] = row.v;
+}
+
 // table growth: per-flow state follows its record to the new slot (gns_dict.hip remap)
 __global__ __launch_bounds__(256) void k_ex_permute(FlowState o, uint64_t slots, const uint32_t *remap, FlowState f) {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1573,6 +1812,152 @@ int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_n
     dfree(ids);
     dfree(cnt);
     if (e != hipSuccess) { set_error("exact snapshot: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
+    if (!ex || (nf && (!filters || !out))) { set_error("null argument"); return GNS_E_ARG; }
+    constexpr uint32_t kFieldBits = (1u << GNS_F_SRCIP) | (1u << GNS_F_DSTIP) | (1u << GNS_F_SRCPORT) |
+                                    (1u << GNS_F_DSTPORT) | (1u << GNS_F_PROTO);
+    for (uint32_t i = 0; i < nf; i++)
+        if (filters[i].mask & ~kFieldBits) {
+            set_error("filter %u: mask 0x%x has bits outside the five key fields", i, filters[i].mask);
+            return GNS_E_ARG;
+        }
+    if (nf == 0) return GNS_OK;
+    GNS_TRY(ex_set_dev(ex));
+    // per filter: the 37 tuple bytes (make_plan's numbering) and which of them are masked;
+    // the layout's byte plan carries them to their place in the record's key words
+    static const struct { uint32_t base, len; } kSpan[6] = {{0, 0}, {0, 16}, {16, 16}, {32, 2}, {34, 2}, {36, 1}};
+    std::vector<ExQFilter> hf(nf);
+    std::vector<unsigned long long> ha((size_t)nf * kQAcc);
+    for (uint32_t i = 0; i < nf; i++) {
+        const gns_ex_filter &q = filters[i];
+        uint8_t tb[40] = {0}, tm[40] = {0};
+        memcpy(tb, q.src16, 16);
+        memcpy(tb + 16, q.dst16, 16);
+        tb[32] = (uint8_t)(q.sport >> 8); tb[33] = (uint8_t)q.sport;
+        tb[34] = (uint8_t)(q.dport >> 8); tb[35] = (uint8_t)q.dport;
+        tb[36] = q.proto;
+        for (uint32_t fld = GNS_F_SRCIP; fld <= GNS_F_PROTO; fld++)
+            if (q.mask >> fld & 1u) memset(tm + kSpan[fld].base, 0xFF, kSpan[fld].len);
+        ExQFilter &w = hf[i];
+        memset(&w, 0, sizeof(w));
+        uint8_t seen[40] = {0};
+        for (uint32_t j = 0; j < ex->K; j++) {
+            const uint32_t t = ex->kp.src[j];
+            if (t >= 37 || !tm[t]) continue;
+            seen[t] = 1;
+            w.m[j >> 2] |= 0xFFu << (8 * (j & 3));
+            w.v[j >> 2] |= (uint32_t)tb[t] << (8 * (j & 3));
+        }
+        // a masked field outside the key is a NULL column (writer_clickhouse.go:142-148):
+        // `NULL = ?` selects nothing -> a pair no word satisfies
+        for (uint32_t t = 0; t < 37; t++)
+            if (tm[t] && !seen[t]) { w.m[0] = 0u; w.v[0] = 1u; break; }
+        for (uint32_t j = 0; j < kQAcc; j++) ha[(size_t)i * kQAcc + j] = exq_acc_init(j);
+    }
+    hipStream_t s = ex->stream;
+    ExQFilter *df = nullptr;
+    unsigned long long *da = nullptr;
+    GNS_TRY(dalloc_t(&df, nf));
+    int rc = dalloc_t(&da, (size_t)nf * kQAcc);
+    if (rc) { dfree(df); return rc; }
+    hipError_t e = hipMemcpyAsync(df, hf.data(), (size_t)nf * sizeof(ExQFilter), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(da, ha.data(), ha.size() * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        ScopedStage stg(ex->timer, 6);
+        const unsigned grid = (unsigned)std::min<uint64_t>((ex->slots + 255) / 256, 2048);
+        for (uint32_t p0 = 0; p0 < nf; p0 += kQBatch) {
+            const uint32_t nb = std::min(kQBatch, nf - p0);
+            if (nb > kQNarrow)
+                hipLaunchKernelGGL(k_exq_aggregate<true>, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, df + p0,
+                                   nb, da + (size_t)p0 * kQAcc);
+            else
+                hipLaunchKernelGGL(k_exq_aggregate<false>, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, df + p0,
+                                   nb, da + (size_t)p0 * kQAcc);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ha.data(), da, ha.size() * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dfree(df);
+    dfree(da);
+    if (e != hipSuccess) { set_error("exact aggregate: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    for (uint32_t i = 0; i < nf; i++) {
+        const unsigned long long *a = &ha[(size_t)i * kQAcc];
+        gns_ex_summary &o = out[i];
+        memset(&o, 0, sizeof(o));
+        if (a[0] == 0) continue;
+        o.flows = a[0]; o.packets = a[1]; o.bytes = a[2];
+        o.first_ns = (int64_t)(a[3] ^ kQSign); o.last_ns = (int64_t)(a[4] ^ kQSign);
+        o.max_packets = a[5]; o.max_bytes = a[6];
+    }
+    return GNS_OK;
+}
+
+int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit, uint8_t *keys,
+                         uint64_t *values, uint64_t *n_io) {
+    if (!ex || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
+    GNS_TRY(ex_set_dev(ex));
+    hipStream_t s = ex->stream;
+    const unsigned grid = (unsigned)std::min<uint64_t>((ex->slots + 255) / 256, 2048);
+    uint32_t *dh = nullptr;  // [0..kQBands) band histogram, [kQBands] rows collected
+    GNS_TRY(dalloc_t(&dh, kQBands + 1));
+    std::vector<uint32_t> hist(kQBands);
+    hipError_t e = hipMemsetAsync(dh, 0, (kQBands + 1) * 4, s);
+    if (e == hipSuccess) {
+        ScopedStage stg(ex->timer, 6);
+        hipLaunchKernelGGL(k_exq_hh_hist, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, metric,
+                           (unsigned long long)threshold, dh);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), dh, kQBands * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { dfree(dh); set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < kQBands; b++) total += hist[b];
+    const uint64_t cap = *n_io, len = limit ? std::min<uint64_t>(limit, total) : total;
+    *n_io = len;
+    if (len == 0 || len > cap || (!keys && !values)) { dfree(dh); return GNS_OK; }
+    // the lowest band the first `len` rows can reach, and the rows from it up
+    uint32_t band = kQBands - 1;
+    uint64_t nrows = hist[band];
+    while (band > 0 && nrows < len) nrows += hist[--band];
+    ExHhRow *rows[2] = {nullptr, nullptr};
+    void *tmp = nullptr;
+    uint8_t *dk = nullptr;
+    unsigned long long *dv = nullptr;
+    size_t tmp_bytes = 0;
+    int rc = GNS_OK;
+    ExHhRow *sorted = nullptr;
+    if (rocprim::merge_sort(nullptr, tmp_bytes, rows[0], rows[1], (size_t)nrows, ExHhLess(), s) != hipSuccess) e = hipErrorUnknown;
+    if (e == hipSuccess && ((rc = dalloc_t(&rows[0], nrows)) || (rc = dalloc_t(&rows[1], nrows)) ||
+                            (rc = dalloc(&tmp, tmp_bytes)) ||
+                            (rc = dalloc(reinterpret_cast<void **>(&dk), len * std::max<uint32_t>(ex->K, 1))) ||
+                            (rc = dalloc_t(&dv, len)))) {
+        dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk); dfree(dv);
+        return rc;
+    }
+    if (e == hipSuccess) {
+        ScopedStage stg(ex->timer, 6);
+        hipLaunchKernelGGL(k_exq_hh_collect, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, metric,
+                           (unsigned long long)threshold, band, rows[0], dh + kQBands, (uint32_t)nrows);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = rocprim::merge_sort(tmp, tmp_bytes, rows[0], rows[1], (size_t)nrows, ExHhLess(), s);
+        sorted = rows[1];
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_exq_hh_out, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, sorted, len, ex->K,
+                               dk, dv);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess && keys) e = hipMemcpyAsync(keys, dk, len * ex->K, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && values) e = hipMemcpyAsync(values, dv, len * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk); dfree(dv);
+    if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
     return GNS_OK;
 }
 

@@ -3,13 +3,16 @@
 Reference: exact/task.go -- New (:83-103), ProcessPacket (:124-149), Snapshot
 (:153-191), Reset (:194-210), AlerterMsg (:213-282), Query (:298-326),
 generateKeyAndFields (:330-366); exact/statistic/flow.go (Flow, Shard,
-SnapshotData).  The device engine (csrc/gns_exact.hip, C ABI gns_ex_*) keys
+SnapshotData); internal/query/querier.go (AggregateFlows, TraceFlow,
+QueryHeavyHitters: answered from the device table, gns_ex_aggregate /
+gns_ex_heavy_hitters).  The device engine (csrc/gns_exact.hip, C ABI gns_ex_*) keys
 flows by canonical bytes (IP fields in 16-byte To16 form); the Go key string
 and the Fields map are rebuilt here from those bytes for snapshots.
 """
 from __future__ import annotations
 
 import ctypes as ct
+import ipaddress
 import struct
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
@@ -43,6 +46,146 @@ class Shard:
 class SnapshotData:
     TaskName: str
     Shards: List[Shard]
+
+
+@dataclass
+class Summary:  # gns_ex_summary: one filter's answer
+    flows: int = 0        # COUNT(*)
+    packets: int = 0      # SUM(PacketCount) mod 2^64
+    bytes: int = 0        # SUM(ByteCount) mod 2^64
+    first_ns: int = 0     # min(StartTime), signed; 0 when flows == 0
+    last_ns: int = 0      # max(EndTime)
+    max_packets: int = 0  # max(PacketCount)
+    max_bytes: int = 0    # max(ByteCount)
+
+
+@dataclass
+class TaskSummary:  # query.TaskSummary (querier.go:29-34)
+    TaskName: str
+    TotalBytes: int
+    TotalPackets: int
+    FlowCount: int
+
+
+@dataclass
+class FlowLifecycle:  # query.FlowLifecycle (querier.go:49-54); times in ns since the epoch
+    FirstSeen: int
+    LastSeen: int
+    TotalPackets: int
+    TotalBytes: int
+
+
+@dataclass
+class HeavyHitter:  # query.HeavyHitter (querier.go:65-68); Flow = the Go key string
+    Flow: str
+    Value: int
+
+
+FLOW_KEYS = ("SrcIP", "DstIP", "SrcPort", "DstPort", "Protocol")  # traceFlowKeys, querier.go:94-100
+_FIELD_MASK = sum(1 << _lib.FIELD_IDS[f] for f in FLOW_KEYS)
+
+
+def ip_to16(ip) -> bytes:
+    """net.ParseIP(ip).To16(): the form the engine stores (IPv4 as ::ffff:a.b.c.d).
+    "1.2.3.4" and "::ffff:1.2.3.4" give the same bytes, as does any spelling of an
+    IPv6 address; 4 or 16 raw bytes are taken as a net.IP."""
+    if isinstance(ip, (bytes, bytearray, np.ndarray)):
+        ip = bytes(ip)
+        if len(ip) not in (4, 16):
+            raise ValueError(f"an IP of {len(ip)} bytes")
+        return (bytes(10) + b"\xff\xff" + ip) if len(ip) == 4 else ip
+    a = ipaddress.ip_address(ip)
+    return (bytes(10) + b"\xff\xff" + a.packed) if a.version == 4 else a.packed
+
+
+def _small_int(name: str, v, hi: int) -> int:
+    v = int(v)
+    if not 0 <= v <= hi:
+        raise ValueError(f"{name} {v} outside 0..{hi}")
+    return v
+
+
+def make_filter(src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None) -> "_lib.ExFilter":
+    """gns_ex_filter of an AggregationRequest (querier.go:19-26, :143-170): every field
+    given must equal the flow's; None (and "" for an IP, as the reference) leaves it open."""
+    f = _lib.ExFilter()
+    for name, ip, dst in (("SrcIP", src_ip, f.src16), ("DstIP", dst_ip, f.dst16)):
+        if ip is None or (isinstance(ip, str) and ip == ""):
+            continue
+        dst[:] = list(ip_to16(ip))
+        f.mask |= 1 << _lib.FIELD_IDS[name]
+    if src_port is not None:
+        f.sport = _small_int("SrcPort", src_port, 0xFFFF)
+        f.mask |= 1 << _lib.FIELD_IDS["SrcPort"]
+    if dst_port is not None:
+        f.dport = _small_int("DstPort", dst_port, 0xFFFF)
+        f.mask |= 1 << _lib.FIELD_IDS["DstPort"]
+    if protocol is not None:
+        f.proto = _small_int("Protocol", protocol, 0xFF)
+        f.mask |= 1 << _lib.FIELD_IDS["Protocol"]
+    return f
+
+
+_FLOW_KEY_ARG = {"SrcIP": "src_ip", "DstIP": "dst_ip", "SrcPort": "src_port", "DstPort": "dst_port",
+                 "Protocol": "protocol"}
+
+
+def filter_from_flow_keys(flow_keys) -> "_lib.ExFilter":
+    """gns_ex_filter of TraceFlowRequest.FlowKeys (appendTraceFlowFilters, querier.go:172-188)."""
+    for k in sorted(flow_keys):
+        if k not in _FLOW_KEY_ARG:
+            raise ValueError(f"unsupported flow key: {k}")
+    return make_filter(**{_FLOW_KEY_ARG[k]: v for k, v in flow_keys.items()})
+
+
+def check_filter(f) -> None:
+    if int(f.mask) & ~_FIELD_MASK:
+        raise ValueError(f"filter mask {int(f.mask):#x} has bits outside the five key fields")
+
+
+def filter_fields(f) -> List[str]:
+    """Names of the fields a filter constrains."""
+    return [n for n in FLOW_KEYS if int(f.mask) >> _lib.FIELD_IDS[n] & 1]
+
+
+def filter_key_bytes(f, key_fields: Sequence[str]):
+    """(mask, value) uint8 arrays over the canonical key bytes of ``key_fields``: a flow
+    matches iff key & mask == value.  None when the filter constrains a field that is not
+    part of the key: such a column is NULL in the reference (writer_clickhouse.go:142-148)
+    and `NULL = ?` selects nothing."""
+    check_filter(f)
+    want = set(filter_fields(f))
+    if not want <= set(key_fields):
+        return None
+    vals = {"SrcIP": bytes(f.src16), "DstIP": bytes(f.dst16), "SrcPort": struct.pack(">H", f.sport),
+            "DstPort": struct.pack(">H", f.dport), "Protocol": bytes([f.proto])}
+    mask, value = bytearray(), bytearray()
+    for name in key_fields:
+        size = _lib.FIELD_SIZE.get(name, 0)
+        mask += (b"\xff" if name in want else b"\x00") * size
+        value += vals[name] if name in want else bytes(size)
+    return np.frombuffer(bytes(mask), np.uint8), np.frombuffer(bytes(value), np.uint8)
+
+
+def merge_summaries(parts: Sequence[Summary]) -> Summary:
+    """One Summary of shards that hold DISJOINT flows (the router's owner-key rule):
+    sum, sum, sum (mod 2^64), min, max, max, max.  A shard without matching flows carries
+    0 timestamps that are not observations and does not contribute them."""
+    out = Summary()
+    m64 = (1 << 64) - 1
+    for p in parts:
+        if p.flows == 0:
+            continue
+        first = p.first_ns if out.flows == 0 else min(out.first_ns, p.first_ns)
+        last = p.last_ns if out.flows == 0 else max(out.last_ns, p.last_ns)
+        out = Summary((out.flows + p.flows) & m64, (out.packets + p.packets) & m64, (out.bytes + p.bytes) & m64,
+                      first, last, max(out.max_packets, p.max_packets), max(out.max_bytes, p.max_bytes))
+    return out
+
+
+def _no_end_time(end_time) -> None:
+    if end_time is not None:
+        raise ValueError("end_time is not supported: a live handle holds one point in time, no history of snapshots")
 
 
 def _ptr(a):
@@ -138,6 +281,41 @@ class ExactAggregator:
         m = min(m, n2.value)
         return keys[:m, : self.key_bytes], st[:m], en[:m], pk[:m], by[:m]
 
+    def aggregate(self, filters) -> List[Summary]:
+        """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
+        arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
+        flt = [f if isinstance(f, _lib.ExFilter) else make_filter(**f) for f in filters]
+        for f in flt:
+            check_filter(f)
+        n = len(flt)
+        if n == 0:
+            return []
+        arr = (_lib.ExFilter * n)(*flt)
+        out = (_lib.ExSummary * n)()
+        check(self._L.gns_ex_aggregate(self._h, arr, n, out))
+        return [Summary(int(o.flows), int(o.packets), int(o.bytes), int(o.first_ns), int(o.last_ns),
+                        int(o.max_packets), int(o.max_bytes)) for o in out]
+
+    def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0):
+        """gns_ex_heavy_hitters: (keys [n, K] canonical bytes, values uint64 [n]) of the flows
+        with PacketCount (metric 0) / ByteCount (metric 1) >= threshold, value descending, ties
+        by key bytes ascending, cut to ``limit`` rows when limit != 0."""
+        if metric not in (0, 1):
+            raise ValueError(f"metric {metric}: 0 (PacketCount) or 1 (ByteCount)")
+        if threshold < 0 or limit < 0:
+            raise ValueError("threshold and limit are unsigned")
+        n = ct.c_uint64(limit if 0 < limit <= 1 << 16 else 0)
+        if n.value == 0:  # the list's length first
+            check(self._L.gns_ex_heavy_hitters(self._h, metric, threshold, limit, None, None, ct.byref(n)))
+        cap = n.value
+        K = max(self.key_bytes, 1)
+        keys, vals = np.zeros((max(cap, 1), K), np.uint8), np.zeros(max(cap, 1), np.uint64)
+        if cap:
+            check(self._L.gns_ex_heavy_hitters(self._h, metric, threshold, limit, keys.ctypes.data, vals.ctypes.data,
+                                               ct.byref(n)))
+        m = min(cap, n.value)
+        return keys[:m, : self.key_bytes], vals[:m]
+
     def reset(self) -> None:
         check(self._L.gns_ex_reset(self._h))
 
@@ -156,7 +334,7 @@ class ExactAggregator:
     def set_timing(self, on: bool = True, stages=None) -> None:
         check(self._L.gns_ex_set_timing(self._h, _lib.timing_arg(on, stages, self.STAGES)))
 
-    STAGES = ["extract", "resolve", "partition", "aggregate", "hot", "total"]
+    STAGES = ["extract", "resolve", "partition", "aggregate", "hot", "total", "query"]
 
     def stage_times(self, reset: bool = False) -> dict:
         ms = (ct.c_double * 8)()
@@ -246,11 +424,50 @@ class ExactTask:
     def flush(self) -> None:
         self.agg.flush()
 
+    # --- query.Querier (internal/query/querier.go) on the live table ---
+    def aggregate_flows_many(self, requests) -> List[TaskSummary]:
+        """AggregateFlows (querier.go:251-319) for a batch of AggregationRequests in ONE device
+        call.  A request is a dict of src_ip / dst_ip / src_port / dst_port / protocol (absent or
+        None: no constraint); an end_time raises ValueError."""
+        flt = []
+        for req in requests:
+            req = dict(req)
+            _no_end_time(req.pop("end_time", None))
+            flt.append(make_filter(**req))
+        return [TaskSummary(self.name_, s.bytes, s.packets, s.flows) for s in self.agg.aggregate(flt)]
+
+    def aggregate_flows(self, src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None,
+                        end_time=None) -> TaskSummary:
+        return self.aggregate_flows_many([dict(src_ip=src_ip, dst_ip=dst_ip, src_port=src_port, dst_port=dst_port,
+                                               protocol=protocol, end_time=end_time)])[0]
+
+    def trace_flow(self, flow_keys, end_time=None) -> FlowLifecycle:
+        """TraceFlow (querier.go:322-372): min(StartTime), max(EndTime), max(PacketCount),
+        max(ByteCount) of the flows equal to ``flow_keys`` on every key given (all zero when
+        none is)."""
+        flt = filter_from_flow_keys(flow_keys)
+        _no_end_time(end_time)
+        s = self.agg.aggregate([flt])[0]
+        return FlowLifecycle(s.first_ns, s.last_ns, s.max_packets, s.max_bytes)
+
+    def heavy_hitters(self, type: int, limit: int, end_time=None) -> List[HeavyHitter]:
+        """QueryHeavyHitters (querier.go:191-248): Type 0 PacketCount, 1 ByteCount, ORDER BY value
+        DESC LIMIT ``limit`` (ties by key bytes; LIMIT 0 and an unknown Type select no row, as
+        in the reference)."""
+        _no_end_time(end_time)
+        if limit < 0:
+            raise ValueError("negative limit")
+        if type not in (0, 1) or limit == 0:
+            return []
+        keys, vals = self.agg.heavy_hitters(type, 0, limit)
+        return [HeavyHitter(key_string(bytes(k), self.key_fields)[0], int(v)) for k, v in zip(keys, vals)]
+
     def alerter_msg(self, rules) -> str:
-        """AlerterMsg (task.go:213-282): total_packets / total_bytes / total_flows."""
-        keys, st, en, pk, by = self.agg.snapshot_arrays()
-        totals = {"total_packets": (float(int(pk.sum())), "packets"), "total_bytes": (float(int(by.sum())), "bytes"),
-                  "total_flows": (float(len(pk)), "flows")}
+        """AlerterMsg (task.go:213-282): total_packets / total_bytes / total_flows, the one
+        unfiltered aggregate of the device table."""
+        t = self.agg.aggregate([make_filter()])[0]
+        totals = {"total_packets": (float(t.packets), "packets"), "total_bytes": (float(t.bytes), "bytes"),
+                  "total_flows": (float(t.flows), "flows")}
         msgs = []
         for rule in rules:
             if rule.get("task_name") != self.name_:
@@ -274,6 +491,9 @@ class ExactTask:
     Snapshot = snapshot
     Reset = reset
     AlerterMsg = alerter_msg
+    AggregateFlows = aggregate_flows
+    TraceFlow = trace_flow
+    QueryHeavyHitters = heavy_hitters
 
 
 def NewExact(name: str, key_fields: Sequence[str], num_shards: int = 0, **kw) -> ExactTask:  # exact/task.go:83

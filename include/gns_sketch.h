@@ -466,8 +466,47 @@ int gns_ex_counters(gns_ex *ex, uint64_t out[8]);
  * [5] batches re-run after a dictionary overflow, [6] slots, [7] growths */
 int gns_ex_dict_stats(gns_ex *ex, uint64_t out[8]);
 int gns_ex_set_timing(gns_ex *ex, int on);
-/* stages: 0 extract, 1 resolve, 2 aggregate, 3 timestamps, 5 total */
+/* stages: 0 extract, 1 resolve, 2 partition, 3 aggregate, 4 hot flows + timestamps, 5 total
+ * (of an insert batch), 6 query (the device work of gns_ex_aggregate / gns_ex_heavy_hitters) */
 int gns_ex_stage_times(gns_ex *ex, double ms[8], uint64_t launches[8], int reset);
+
+/* Query plane: the three questions of query.Querier (internal/query/querier.go)
+ * answered from the live flow table instead of ClickHouse.  Both calls are
+ * ordered after pending insert batches exactly as gns_ex_snapshot is, and see
+ * exactly the flows gns_ex_snapshot lists.
+ *
+ * A filter is appendAggregationFilters / appendTraceFlowFilters
+ * (querier.go:143-188): equality on the masked fields, AND-ed.  A masked field
+ * that is not part of the handle's key layout matches no flow: the reference
+ * stores such a column as NULL (getNullableField, exact/writer_clickhouse.go:142-148)
+ * and `NULL = ?` selects nothing.  mask == 0 matches every flow: the totals of
+ * AlerterMsg (exact/task.go:224-233). */
+typedef struct gns_ex_filter {
+    uint32_t mask;        /* OR of (1u << gns_field): that field must equal the value below */
+    uint8_t  src16[16];   /* net.IP.To16() form: IPv4 as ::ffff:a.b.c.d, the form keys are stored in */
+    uint8_t  dst16[16];
+    uint16_t sport, dport;  /* host order */
+    uint8_t  proto, _pad[3];
+} gns_ex_filter;
+/* AggregateFlows' row (querier.go:251-319) and TraceFlow's (querier.go:322-372) in one */
+typedef struct gns_ex_summary {
+    uint64_t flows, packets, bytes;     /* COUNT(*), SUM(PacketCount), SUM(ByteCount), mod 2^64 */
+    int64_t  first_ns, last_ns;         /* min(StartTime), max(EndTime), signed; 0, 0 when flows == 0 */
+    uint64_t max_packets, max_bytes;    /* TraceFlow's max(PacketCount), max(ByteCount); 0 when flows == 0 */
+} gns_ex_summary;
+/* out[i] = the summary of the flows matching filters[i] (host arrays).  One pass
+ * over the table answers 64 filters; a longer batch takes ceil(nf / 64) passes.
+ * nf == 0 is a no-op.  GNS_E_ARG: a null pointer, mask bits outside the five fields. */
+int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out /* [nf] */);
+/* QueryHeavyHitters ... ORDER BY LatestValue DESC LIMIT ? (querier.go:191-248), and the
+ * truth side of Count-Min's heavy hitters (cm_test.go:124-137).
+ * metric 0: PacketCount, 1: ByteCount.  Flows with value >= threshold, in the canonical list order
+ * (value descending, key bytes ascending), cut to the first `limit` rows when limit != 0.
+ * *n_io: capacity in, list length (after the cut) out; a list longer than the capacity is
+ * reported and not written (as gns_exs_heavy_hitters).  keys[n*key_bytes] in the layout of
+ * gns_ex_snapshot, values 64-bit.  threshold 0 lists every flow.  keys / values may be NULL. */
+int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit,
+                         uint8_t *keys, uint64_t *values, uint64_t *n_io);
 
 /* ------------------------------------------------------------------ */
 /* Exact spread: the device ground truth of SuperSpread                */

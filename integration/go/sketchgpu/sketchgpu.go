@@ -27,6 +27,7 @@ import (
 	"errors"
 	"fmt"
 	"log"
+	"net"
 	"sync"
 	"unsafe"
 
@@ -647,6 +648,102 @@ func (e *Exact) Flows() (keys []byte, start, end []int64, pkts, bytes []uint64, 
 		(*C.uint64_t)(unsafe.Pointer(&bytes[0])), &n))
 	m = int(n)
 	return keys[:m*e.keyBytes], start[:m], end[:m], pkts[:m], bytes[:m], err
+}
+
+// ExactFilter is the equality filter of query.AggregationRequest and of
+// TraceFlowRequest.FlowKeys (internal/query/querier.go:19-26, :143-188): a nil field is open,
+// every other field must equal the flow's.  A field that is not part of the task's key
+// matches no flow (the reference stores that column as NULL).
+type ExactFilter struct {
+	SrcIP, DstIP     net.IP
+	SrcPort, DstPort *uint16
+	Protocol         *uint8
+}
+
+// ExactSummary is gns_ex_summary: AggregateFlows' COUNT / SUM columns (querier.go:251-319)
+// and TraceFlow's min / max columns (querier.go:322-372) of the flows one filter matches.
+type ExactSummary struct {
+	Flows, Packets, Bytes uint64
+	FirstNs, LastNs       int64 // time.Unix(0, ns); 0, 0 when Flows == 0
+	MaxPackets, MaxBytes  uint64
+}
+
+func exactFilterIP(dst *[16]C.uint8_t, ip net.IP) error {
+	ip16 := ip.To16()
+	if ip16 == nil {
+		return fmt.Errorf("sketchgpu: IP of %d bytes in an exact filter", len(ip))
+	}
+	for i := 0; i < 16; i++ {
+		dst[i] = C.uint8_t(ip16[i])
+	}
+	return nil
+}
+
+// Aggregate answers every filter from one device scan per 64 filters (gns_ex_aggregate):
+// AggregateFlows and TraceFlow on the live table, without a snapshot leaving the GPU.
+func (e *Exact) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cf := make([]C.gns_ex_filter, n)
+	for i, f := range filters {
+		if f.SrcIP != nil {
+			if err := exactFilterIP(&cf[i].src16, f.SrcIP); err != nil {
+				return nil, err
+			}
+			cf[i].mask |= 1 << C.GNS_F_SRCIP
+		}
+		if f.DstIP != nil {
+			if err := exactFilterIP(&cf[i].dst16, f.DstIP); err != nil {
+				return nil, err
+			}
+			cf[i].mask |= 1 << C.GNS_F_DSTIP
+		}
+		if f.SrcPort != nil {
+			cf[i].sport = C.uint16_t(*f.SrcPort)
+			cf[i].mask |= 1 << C.GNS_F_SRCPORT
+		}
+		if f.DstPort != nil {
+			cf[i].dport = C.uint16_t(*f.DstPort)
+			cf[i].mask |= 1 << C.GNS_F_DSTPORT
+		}
+		if f.Protocol != nil {
+			cf[i].proto = C.uint8_t(*f.Protocol)
+			cf[i].mask |= 1 << C.GNS_F_PROTO
+		}
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_aggregate(e.h, &cf[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	out := make([]ExactSummary, n)
+	for i, s := range cs {
+		out[i] = ExactSummary{Flows: uint64(s.flows), Packets: uint64(s.packets), Bytes: uint64(s.bytes),
+			FirstNs: int64(s.first_ns), LastNs: int64(s.last_ns),
+			MaxPackets: uint64(s.max_packets), MaxBytes: uint64(s.max_bytes)}
+	}
+	return out, nil
+}
+
+// HeavyHitters is QueryHeavyHitters (querier.go:191-248) on the live table (gns_ex_heavy_hitters):
+// the flows with PacketCount (metric 0) or ByteCount (metric 1) >= threshold, value descending,
+// ties by key bytes ascending, cut to limit rows when limit != 0.  keys holds len(values) keys
+// of the task's key bytes each, in the layout of Flows.
+func (e *Exact) HeavyHitters(metric int, threshold, limit uint64) (keys []byte, values []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_heavy_hitters(e.h, C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		nil, nil, &n)); err != nil || n == 0 {
+		return nil, nil, err
+	}
+	m := int(n)
+	keys, values = make([]byte, m*e.keyBytes+1), make([]uint64, m)
+	err = lastErr(C.gns_ex_heavy_hitters(e.h, C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		(*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint64_t)(unsafe.Pointer(&values[0])), &n))
+	if err == nil && int(n) != m {
+		err = fmt.Errorf("sketchgpu: heavy-hitter list changed length between calls (%d, %d)", m, int(n))
+	}
+	return keys[:m*e.keyBytes], values, err
 }
 
 // Reset is exact.Task.Reset (task.go:194-210).
