@@ -22,10 +22,8 @@
 //                   sequential replay for the buckets where it is not.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <mutex>
-#include <sys/resource.h>
 #include <vector>
 
 #include "gns_common.hpp"
@@ -3359,7 +3357,7 @@ __global__ __launch_bounds__(1024) void k_hot_table(CmGeom g, uint32_t *hot_ids,
 }
 
 // ---------------------------------------------------------------------------
-// Query (count_min.go:160-174), export, heavy-hitter candidates
+// Query (count_min.go:160-174)
 // ---------------------------------------------------------------------------
 struct QueryArgs {
     const uint8_t *keys;
@@ -3389,248 +3387,6 @@ __global__ __launch_bounds__(256) void k_query(QueryArgs a) {
     a.out[p] = (uint64_t)ct << 32 | sz;
 }
 
-// flow ids -> key bytes (GNS_ID_NONE -> zero bytes, the reference's reset FP)
-__global__ __launch_bounds__(256) void k_ids_to_bytes(const uint32_t *ids, uint64_t n, DictDev D,
-                                                      uint8_t *out) {
-    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const uint32_t id = ids[p];
-    uint32_t r[12];
-    if (id != GNS_ID_NONE) load_record(D, id, r);
-    for (uint32_t j = 0; j < D.K; j++) {
-        const uint32_t w = id != GNS_ID_NONE ? r[1 + (j >> 2)] : 0u;
-        out[p * D.K + j] = (uint8_t)(w >> (8 * (j & 3)));
-    }
-}
-
-// cells whose counter >= thr -> (value<<32 | id) candidate list
-// kHhItems cells per lane; one global atomic per workgroup reserves the
-// candidates' slots (a per-lane atomic on the one counter serialized every
-// candidate: 0.59 ms per call at the bench geometry).  Order is irrelevant:
-// the host dedupes and sorts.
-constexpr uint32_t kHhItems = 8;
-// Device-side heavy-hitter list (count_min.go:178-247 HeavyHitters), all
-// hand-written (no library sort):
-//   candidates   cells with value >= threshold (one global atomic per workgroup);
-//   per-flow max every candidate atomicMax'es (epoch << 32 | value) into a dense
-//                per-flow-id word, then the one candidate per flow that carries the
-//                max and wins the flow's mark emits (id, max) -- the dedupe of
-//                count_min.go:214-228's map, order-free, O(candidates);
-//   order        a stable LSD radix sort of the unique entries (8-bit digits,
-//                device-wide passes: block histograms, the K2 scan, stable
-//                ballot-multisplit scatter) by the primary key (value desc, key
-//                bytes 0..3); only when two entries tie on it (the same value and
-//                the same first four key bytes) is the list re-sorted by the whole
-//                key (bytes K-1..4 first, then the primary key).  A pass whose
-//                digit is the same for every entry (IPv4 slots' zero padding) only
-//                copies.  Canonical order: value desc, flow bytes asc.
-// A candidate whose id is not a dictionary slot (a corrupt fingerprint word) is
-// skipped and raises *bad: the host then fails the call with GNS_E_HIP instead of
-// letting the per-flow words be indexed out of bounds.
-__global__ __launch_bounds__(256) void k_hh_best(const uint64_t *cand, uint32_t n, unsigned long long *best,
-                                                 uint32_t epoch, uint64_t slots, uint32_t *bad) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t c = cand[i];  // value << 32 | id
-    if ((uint32_t)c >= slots) { atomicOr(bad, 1u); return; }
-    atomicMax(&best[(uint32_t)c], (unsigned long long)epoch << 32 | (c >> 32));
-}
-
-__global__ __launch_bounds__(256) void k_hh_emit(const uint64_t *cand, uint32_t n, const unsigned long long *best,
-                                                 uint32_t *mark, uint32_t epoch, uint64_t slots, uint32_t *uid,
-                                                 uint32_t *uval, uint32_t *nu) {
-    __shared__ uint32_t s_n, s_base;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    bool out = false;
-    uint32_t id = 0, v = 0;
-    if (i < n) {
-        const uint64_t c = cand[i];
-        id = (uint32_t)c;
-        v = (uint32_t)(c >> 32);
-        out = id < slots && (uint32_t)best[id] == v && atomicExch(&mark[id], epoch) != epoch;  // one per flow
-    }
-    const uint32_t off = out ? atomicAdd(&s_n, 1u) : 0u;
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = s_n ? atomicAdd(nu, s_n) : 0u;
-    __syncthreads();
-    if (out) {
-        uid[s_base + off] = id;
-        uval[s_base + off] = v;
-    }
-}
-
-// A heavy-hitter list on the device: entry e has flow bytes ub[e*stride .. +K) and
-// a value, uval[e] -- or, for packed rows [flow | u32 value] (uval null), the
-// little-endian word at ub[e*stride + K].
-struct HhSrc {
-    const uint32_t *uval;
-    const uint8_t *ub;
-    uint32_t K, stride;
-};
-__device__ __forceinline__ uint32_t hh_val(const HhSrc &h, uint32_t e) {
-    if (h.uval) return h.uval[e];
-    const uint8_t *q = h.ub + (uint64_t)e * h.stride + h.K;
-    return (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
-}
-__device__ __forceinline__ uint32_t hh_byte(const HhSrc &h, uint32_t e, uint32_t b) {
-    return b < h.K ? (uint32_t)h.ub[(uint64_t)e * h.stride + b] : 0u;
-}
-
-// One radix pass's digit of entry e: mode 0 = byte `b` of the value, inverted
-// (descending); mode 1 = key byte b (0 beyond K).
-struct RsDigit {
-    uint32_t mode, b;
-    HhSrc src;
-};
-__device__ __forceinline__ uint32_t rs_digit(const RsDigit &r, uint32_t e) {
-    if (r.mode == 0) return 255u - ((hh_val(r.src, e) >> (8u * r.b)) & 255u);
-    return hh_byte(r.src, e, r.b);
-}
-
-constexpr uint32_t kRsPer = 16;                 // entries per thread
-constexpr uint32_t kRsBlock = 256 * kRsPer;     // entries per block of a pass
-
-__global__ __launch_bounds__(256) void k_rs_hist(const uint32_t *perm, uint32_t n, RsDigit r, uint32_t *hist) {
-    __shared__ uint32_t s_h[256];
-    const uint32_t tid = threadIdx.x;
-    s_h[tid] = 0;
-    __syncthreads();
-    const uint32_t beg = blockIdx.x * kRsBlock;
-#pragma unroll 4
-    for (uint32_t k = 0; k < kRsPer; k++) {
-        const uint32_t j = beg + k * 256 + tid;
-        if (j < n) atomicAdd(&s_h[rs_digit(r, perm[j])], 1u);
-    }
-    __syncthreads();
-    hist[(uint64_t)blockIdx.x * 256 + tid] = s_h[tid];
-}
-
-// Stable scatter of one pass: entries of a block in (round, wave, lane) order =
-// position order; per wave-instruction the lanes of one digit are found by
-// eight ballots (no reliance on LDS-atomic lane order).  offs = the scanned
-// block-major histogram (global start of every (block, digit) run); tot / total
-// = the digit totals' exclusive scan: a digit holding every entry makes the pass
-// a copy (the order cannot change).
-__global__ __launch_bounds__(256) void k_rs_scatter(const uint32_t *perm, uint32_t n, RsDigit r, const uint32_t *offs,
-                                                    const uint32_t *tot, const uint32_t *total, uint32_t *out) {
-    __shared__ uint32_t s_base[256];
-    __shared__ uint32_t s_wave[4][256];
-    __shared__ uint32_t s_copy;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t beg = blockIdx.x * kRsBlock;
-    if (tid == 0) {
-        const uint32_t d0 = rs_digit(r, perm[0]);
-        const uint32_t hi = d0 < 255u ? tot[d0 + 1] : *total;
-        s_copy = hi - tot[d0] == n;
-    }
-    s_base[tid] = offs[(uint64_t)blockIdx.x * 256 + tid];
-    __syncthreads();
-    if (s_copy) {  // block-uniform
-        for (uint32_t k = 0; k < kRsPer; k++) {
-            const uint32_t j = beg + k * 256 + tid;
-            if (j < n) out[j] = perm[j];
-        }
-        return;
-    }
-    const uint64_t lt = lane ? (~0ull >> (64u - lane)) : 0ull;
-    for (uint32_t k = 0; k < kRsPer; k++) {
-        if (beg + k * 256 >= n) break;  // block-uniform
-        const uint32_t j = beg + k * 256 + tid;
-        const bool valid = j < n;
-        const uint32_t e = valid ? perm[j] : 0u;
-        const uint32_t dg = valid ? rs_digit(r, e) : 0u;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (uint32_t bit = 0; bit < 8; bit++) {
-            const uint64_t m = __ballot(valid && ((dg >> bit) & 1u));
-            peers &= ((dg >> bit) & 1u) ? m : ~m;
-        }
-        s_wave[0][tid] = 0; s_wave[1][tid] = 0; s_wave[2][tid] = 0; s_wave[3][tid] = 0;
-        __syncthreads();
-        const uint32_t rank = (uint32_t)__popcll(peers & lt);
-        if (valid && rank == 0) s_wave[wave][dg] = (uint32_t)__popcll(peers);
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = s_base[dg] + rank;
-            for (uint32_t w = 0; w < wave; w++) pos += s_wave[w][dg];
-            out[pos] = e;
-        }
-        __syncthreads();
-        s_base[tid] += s_wave[0][tid] + s_wave[1][tid] + s_wave[2][tid] + s_wave[3][tid];
-        __syncthreads();
-    }
-}
-
-// Whether two neighbours of the primary order tie on (value, key bytes 0..3):
-// only then does the list need the whole-key order.
-__global__ __launch_bounds__(256) void k_hh_ties(const uint32_t *perm, uint32_t n, HhSrc h, uint32_t *flag) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x + 1;
-    if (j >= n) return;
-    const uint32_t a = perm[j - 1], b = perm[j];
-    if (hh_val(h, a) != hh_val(h, b)) return;
-    bool eq = true;
-    for (uint32_t t = 0; t < 4 && t < h.K; t++) eq = eq && hh_byte(h, a, t) == hh_byte(h, b, t);
-    if (eq) atomicOr(flag, 1u);
-}
-
-__global__ __launch_bounds__(256) void k_hh_iota(uint32_t *perm, uint32_t n) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j < n) perm[j] = j;
-}
-
-// ordered output: flow bytes and values in list order (one D2H each), or packed
-// rows [flow | u32 value] (rows non-null: the multi-GPU exchange keeps them on the device)
-__global__ __launch_bounds__(256) void k_hh_gather(const uint32_t *perm, HhSrc h, uint32_t n, uint8_t *ob,
-                                                   uint32_t *ov, uint8_t *rows) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t u = perm[j], K = h.K;
-    const uint32_t v = hh_val(h, u);
-    if (rows) {
-        uint8_t *o = rows + (uint64_t)j * (K + 4);
-        for (uint32_t t = 0; t < K; t++) o[t] = hh_byte(h, u, t);
-        o[K] = (uint8_t)v; o[K + 1] = (uint8_t)(v >> 8); o[K + 2] = (uint8_t)(v >> 16); o[K + 3] = (uint8_t)(v >> 24);
-        return;
-    }
-    for (uint32_t t = 0; t < K; t++) ob[(uint64_t)j * K + t] = hh_byte(h, u, t);
-    ov[j] = v;
-}
-
-__global__ __launch_bounds__(256) void k_hh_candidates(const uint32_t *val, const uint32_t *fp,
-                                                       uint64_t cells, uint32_t thr,
-                                                       uint64_t *cand, uint32_t *ncand, uint32_t cap) {
-    __shared__ uint32_t s_n, s_base;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const uint64_t c0 = (uint64_t)blockIdx.x * 256 * kHhItems + threadIdx.x;
-    uint64_t cv[kHhItems];
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kHhItems; i++) {
-        const uint64_t c = c0 + (uint64_t)i * 256;
-        cv[i] = 0;
-        if (c < cells) {
-            const uint32_t v = val[c];
-            if (v > 0 && v >= thr) { cv[i] = (uint64_t)v << 32 | fp[c]; cnt++; }
-        }
-    }
-    const uint32_t off = cnt ? atomicAdd(&s_n, cnt) : 0u;
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = s_n ? atomicAdd(ncand, s_n) : 0u;
-    __syncthreads();
-    uint32_t q = s_base + off;
-#pragma unroll
-    for (uint32_t i = 0; i < kHhItems; i++)
-        if (cv[i]) { if (q < cap) cand[q] = cv[i]; q++; }
-}
-
-__global__ void k_fill_u32(uint32_t *p, uint64_t n, uint32_t v) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        p[i] = v;
-}
-
 }  // namespace gns
 
 // ===========================================================================
@@ -3638,89 +3394,35 @@ __global__ void k_fill_u32(uint32_t *p, uint64_t n, uint32_t v) {
 // ===========================================================================
 using namespace gns;
 
-// Grow-only device buffers of the read side (heavy hitters, queries, id -> key
-// bytes): no allocation or free -- hipFree synchronizes the device -- once
-// warm, so a snapshot view can query while the handle ingests.
-struct CmScratch {
-    uint64_t *cand = nullptr;
-    uint32_t *ncand = nullptr;
-    uint64_t cap = 0;               // candidates sc.cand holds
-    uint32_t *ids = nullptr;
-    uint64_t ids_n = 0;
-    uint8_t *bytes = nullptr;
-    uint64_t bytes_n = 0;
+// Grow-only device buffers of the read side: the heavy-hitter list's (gns_hh.hpp,
+// also id -> key bytes) and the staging of host queries.  No allocation or free
+// -- hipFree synchronizes the device -- once warm, so a snapshot view can query
+// while the handle ingests.
+struct CmRead {
+    HhScratch hh;
     uint8_t *qkeys = nullptr;
     uint64_t qkeys_n = 0;
     uint64_t *qout = nullptr;
     uint64_t qout_n = 0;
-    // device heavy-hitter list: per-flow-id max / mark words (dense over the dictionary's
-    // slots, epoch-tagged so they are never cleared), unique (id, value), order indices,
-    // radix-pass histograms (block-major) and their scan
-    unsigned long long *best = nullptr;
-    uint32_t *mark = nullptr;
-    uint64_t best_n = 0, mark_n = 0;
-    uint32_t hh_epoch = 0;
-    uint32_t *u32a = nullptr, *u32b = nullptr, *u32c = nullptr, *u32d = nullptr;
-    uint64_t u32a_n = 0, u32b_n = 0, u32c_n = 0, u32d_n = 0;
-    uint32_t *rsh = nullptr;    // [blocks][256] histograms, then [ngrp][256] group sums, [256] totals, total, tie flag
-    uint64_t rsh_n = 0;
-    uint8_t *obytes = nullptr;  // heavy hitters: ordered flow bytes
-    uint64_t obytes_n = 0;
-    uint8_t *hpin = nullptr;    // pinned host staging of the heavy-hitter rows (D2H into pageable
-    uint64_t hpin_n = 0;        // caller memory went through the runtime's slow path)
-    uint32_t *hsm = nullptr;    // pinned host words for the list's small read-backs (lengths, flags):
-                                // a 4-byte D2H into a pageable stack word took 28-35 ms now and then
     void free_all() {
-        dfree(obytes); obytes = nullptr; obytes_n = 0;
-        if (hpin) (void)hipHostFree(hpin);
-        hpin = nullptr; hpin_n = 0;
-        if (hsm) (void)hipHostFree(hsm);
-        hsm = nullptr;
-        dfree(cand); dfree(ncand); dfree(ids); dfree(bytes); dfree(qkeys); dfree(qout);
-        dfree(best); dfree(mark); dfree(u32a); dfree(u32b); dfree(u32c); dfree(u32d); dfree(rsh);
-        cand = nullptr; ncand = nullptr; ids = nullptr; bytes = nullptr; qkeys = nullptr; qout = nullptr;
-        best = nullptr; mark = nullptr; u32a = u32b = u32c = u32d = nullptr; rsh = nullptr;
-        cap = 0; ids_n = bytes_n = qkeys_n = qout_n = 0;
-        best_n = mark_n = u32a_n = u32b_n = u32c_n = u32d_n = rsh_n = 0; hh_epoch = 0;
+        hh.free_all();
+        dfree(qkeys); dfree(qout);
+        qkeys = nullptr; qout = nullptr;
+        qkeys_n = qout_n = 0;
     }
 };
 
-// Grows to twice the request: heavy-hitter lists grow window by window over a
-// period, and every reallocation (hipFree synchronizes the device) cost more
-// than the whole device-side list build.
-template <typename T>
-static int grow_buf(T **p, uint64_t &have, uint64_t need) {
-    if (need <= have && *p) return GNS_OK;
-    dfree(*p);
-    *p = nullptr;
-    have = 0;
-    const uint64_t n = std::max<uint64_t>(2 * need, 1);
-    GNS_TRY(dalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-    have = n;
-    return GNS_OK;
-}
-
-struct gns_cm {
+struct gns_cm : FlowDict {
     int device = 0;
     hipStream_t stream = nullptr;
     CmGeom g{};
     KeyPlanN kp{};
     uint32_t K = 0, st = 0, ct = 0;
     uint32_t *C = nullptr, *S = nullptr, *Fc = nullptr, *Fs = nullptr;
-    CmScratch rd;                 // read-side buffers of the handle's own queries (grow-only)
+    CmRead rd;                    // read-side buffers of the handle's own queries (grow-only)
     std::atomic<uint32_t> period{0};  // bumped by reset: snapshot views taken before it are stale
     std::mutex views_mu;              // guards `views` (view create/destroy vs reset / dictionary reclaim)
     std::vector<gns_cm_view *> views; // live snapshot views: reset and reclaim wait for their calls
-    DictDev D{};
-    uint64_t dict_slots = 0;
-    uint64_t max_flows = 0;               // proactive reclaim once this many slots are claimed
-    uint64_t claimed = 0;                 // D.ctl[0] as of the last batch
-    bool full = false;                    // live flows + one 16K-packet batch exceed the dictionary (sticky)
-    uint32_t *dctl = nullptr;             // D.ctl: [0] claimed slots, [1] abort flag
-    DictScratch dsc;                      // rebuild scratch (grow-only)
-    unsigned long long *stats_bak = nullptr;  // [3] counters before the running batch (undone on abort)
-    uint64_t n_reclaim = 0, n_dropped = 0, last_live = 0, n_retry = 0, n_grow = 0;
-    double reclaim_ms = 0.0;
     uint32_t epoch = 0;
     uint64_t bmax = 0;
     uint32_t nblk_max = 0;
@@ -3763,8 +3465,7 @@ struct gns_cm {
     uint32_t *h_pin = nullptr;            // pinned host mirror of small counters
     // staging for host inputs: two device buffers; batch i+1's H2D copies run on
     // cstream while batch i computes on `stream` (events order the reuse)
-    uint8_t *stage[2] = {nullptr, nullptr};
-    size_t stage_bytes[2] = {0, 0};
+    HostStage stage[2];
     uint32_t *side_dev = nullptr;         // staged side records of a compact host insert
     uint64_t side_n = 0;
     hipStream_t cstream = nullptr;
@@ -3777,7 +3478,7 @@ struct gns_cm_view {
     hipStream_t stream = nullptr;
     hipEvent_t ready = nullptr;
     uint32_t *C = nullptr, *S = nullptr, *Fc = nullptr, *Fs = nullptr;
-    CmScratch rd;
+    CmRead rd;
     std::mutex mu;          // refresh vs queries: a refresh waits for the query in progress
     uint32_t period = ~0u;  // handle period of the snapshot (~0: never refreshed)
 };
@@ -3796,39 +3497,13 @@ struct ViewsQuiesced {
 
 namespace {
 
-int stage_reserve(gns_cm *cm, int b, size_t bytes) {
-    if (!cm->cstream) {
-        GNS_HIP(hipStreamCreateWithFlags(&cm->cstream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            GNS_HIP(hipEventCreateWithFlags(&cm->ev_copied[i], hipEventDisableTiming));
-            GNS_HIP(hipEventCreateWithFlags(&cm->ev_used[i], hipEventDisableTiming));
-        }
-    }
-    if (cm->stage_bytes[b] >= bytes) return GNS_OK;
-    GNS_HIP(hipEventSynchronize(cm->ev_used[b]));  // the batch that read it is done
-    dfree(cm->stage[b]);
-    cm->stage[b] = nullptr;
-    cm->stage_bytes[b] = 0;
-    GNS_TRY(dalloc(reinterpret_cast<void **>(&cm->stage[b]), bytes));
-    cm->stage_bytes[b] = bytes;
-    return GNS_OK;
-}
-
-int set_dev(gns_cm *cm) {
-    (void)hipGetLastError();  // a stale error of an earlier runtime call on this thread (e.g. the
-                              // host framework's) must not fail this call's launch checks
-    GNS_HIP(hipSetDevice(cm->device));
-    return GNS_OK;
-}
-
 int cm_free_all(gns_cm *cm) {
     dfree(cm->C); dfree(cm->S); dfree(cm->Fc); dfree(cm->Fs); cm->rd.free_all();
-    dfree(cm->D.rec);
     dfree(cm->keyid); dfree(cm->idx); dfree(cm->scnt);  // hstr lives in idx
     dfree(cm->pend[0]); dfree(cm->pend[1]); dfree(cm->pcnt[0]); dfree(cm->pcnt[1]);
     dfree(cm->ptotal); dfree(cm->hist); dfree(cm->part); dfree(cm->total); dfree(cm->order);
     dfree(cm->entries); dfree(cm->entries2); dfree(cm->rseg); dfree(cm->rec_sizes); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
-    dfree(cm->stage[0]); dfree(cm->stage[1]); dfree(cm->side_dev);
+    cm->stage[0].free_all(); cm->stage[1].free_all(); dfree(cm->side_dev);
     for (int i = 0; i < 2; i++) {
         if (cm->ev_copied[i]) (void)hipEventDestroy(cm->ev_copied[i]);
         if (cm->ev_used[i]) (void)hipEventDestroy(cm->ev_used[i]);
@@ -3838,7 +3513,7 @@ int cm_free_all(gns_cm *cm) {
     dfree(cm->hot_ids); dfree(cm->segtot); dfree(cm->hflag); dfree(cm->hhist); dfree(cm->hthr); dfree(cm->hcnt);
     dfree(cm->hcand); dfree(cm->hcn);
     dfree(cm->hsum); dfree(cm->hflag2); dfree(cm->hres); dfree(cm->chk); dfree(cm->hot_tab);
-    dfree(cm->dctl); dfree(cm->stats_bak); cm->dsc.free_all();
+    cm->FlowDict::free_all();
     if (cm->h_pin) (void)hipHostFree(cm->h_pin);
     cm->timer.destroy();
     if (cm->stream) (void)hipStreamDestroy(cm->stream);
@@ -3873,11 +3548,6 @@ int cm_reset_state(gns_cm *cm) {
 // before; a stale view (taken before a reset) names nothing: it answers
 // GNS_E_ARG until refreshed, which overwrites its ids.  The table doubles
 // while the live flows exceed a quarter of it, and to at least min_slots.
-void cm_dict_limits(gns_cm *cm) {
-    cm->D.cap = (uint32_t)(cm->dict_slots - cm->dict_slots / 4);  // claims beyond 3/4 load abort the batch
-    cm->max_flows = std::max<uint64_t>(cm->max_flows, cm->dict_slots / 2);  // proactive reclaim at load 1/2
-}
-
 int cm_reclaim(gns_cm *cm, uint64_t min_slots = 0) {
     ViewsQuiesced q(cm);
     const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
@@ -3885,20 +3555,7 @@ int cm_reclaim(gns_cm *cm, uint64_t min_slots = 0) {
     const uint32_t period = cm->period.load();
     for (gns_cm_view *v : cm->views)
         if (v->period == period) { ids.push_back({v->Fc, cells}); ids.push_back({v->Fs, cells}); }
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t before = cm->claimed, slots0 = cm->dict_slots;
-    uint64_t live = 0;
-    GNS_TRY(dict_rebuild(cm->D, cm->dict_slots, ids.data(), (int)ids.size(), nullptr, ids.data(), (int)ids.size(),
-                         std::min(kDictMaxSlots, std::max(cm->dict_slots, min_slots)), cm->stream, cm->dsc, &live,
-                         nullptr, kDictMaxSlots));
-    cm->reclaim_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    cm->n_reclaim++;
-    if (cm->dict_slots != slots0) cm->n_grow++;
-    cm_dict_limits(cm);
-    cm->n_dropped += before > live ? before - live : 0;
-    cm->claimed = live;
-    cm->last_live = live;
-    return GNS_OK;
+    return cm->reclaim(ids.data(), (int)ids.size(), min_slots, cm->stream);
 }
 
 // One device batch: n <= bmax packets, inputs already device-resident.
@@ -4151,20 +3808,6 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
     return GNS_OK;
 }
 
-InputDesc advance(const InputDesc &in, uint64_t off) {
-    InputDesc d = in;
-    if (d.hdr) d.hdr += off * 16;
-    if (d.src16) d.src16 += off * 16;
-    if (d.dst16) d.dst16 += off * 16;
-    if (d.sport) d.sport += off;
-    if (d.dport) d.dport += off;
-    if (d.proto) d.proto += off;
-    if (d.keys) d.keys += off * d.stride;
-    if (d.rec16) d.rec16 += off * 4;
-    if (d.sizes) d.sizes += off;
-    return d;
-}
-
 template <int KIND>
 int cm_batch(gns_cm *cm, const InputDesc &d, uint64_t m) {
     if constexpr (KIND == IN_KEYS) {
@@ -4178,60 +3821,16 @@ int cm_batch(gns_cm *cm, const InputDesc &d, uint64_t m) {
     }
 }
 
-// One device batch (device-resident inputs) with dictionary recovery: a batch
-// whose new flows overflow the dictionary is aborted before it changes the
-// sketch, its counters are undone and its claims dropped with
-// the dead flows (reclaim); it is re-run as is once, then in halves.  A piece
-// of <= kChunk packets that does not fit a freshly rebuilt dictionary doubles
-// the table instead, so the engine keeps counting whatever the stream brings,
-// as the reference's fixed table of key bytes does (count_min.go:66-81,94-157):
-// live ids are bounded by 2*d*w, the table by kDictMaxSlots.  fresh: the
-// dictionary was rebuilt right before this batch.
+// One device batch with dictionary recovery (DictRecovery): the
+// engine keeps counting whatever the stream brings, as the reference's fixed table
+// of key bytes does (count_min.go:66-81,94-157); live ids are bounded by 2*d*w.
 template <int KIND>
-int cm_batch_recover(gns_cm *cm, const InputDesc &d, uint64_t m, bool fresh) {
-    if (m == 0) return GNS_OK;
-    if (cm->full) {
-        set_error("flow dictionary full (%llu slots, %llu live flows)",
-                  (unsigned long long)cm->dict_slots, (unsigned long long)cm->last_live);
-        return GNS_E_FULL;
-    }
-    if (cm->claimed >= cm->max_flows) {  // proactive: keep the load <= ~1/2
-        GNS_TRY(cm_reclaim(cm));
-        fresh = true;
-    }
-    for (;;) {
-        GNS_HIP(hipMemcpyAsync(cm->stats_bak, cm->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                               cm->stream));
-        const int rc = cm_batch<KIND>(cm, d, m);
-        if (rc != GNS_E_FULL) return rc;
-        // not applied: undo its counters, drop its claims and the dead flows
-        GNS_HIP(hipMemcpyAsync(cm->stats, cm->stats_bak, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                               cm->stream));
-        GNS_HIP(hipMemsetAsync(cm->stats + 3, 0, sizeof(unsigned long long), cm->stream));
-        cm->n_retry++;
-        if (!fresh) {  // the flows that died since the last rebuild may be room enough
-            GNS_TRY(cm_reclaim(cm));
-            fresh = true;
-            continue;
-        }
-        if (m > kChunk) {  // split: each half meets a fresh dictionary
-            GNS_TRY(cm_reclaim(cm));
-            break;
-        }
-        if (cm->dict_slots >= kDictMaxSlots) {  // cannot happen below 2*d*w + kChunk ~ 3/4 * 2^30 live flows
-            GNS_TRY(cm_reclaim(cm));
-            cm->full = true;
-            const unsigned long long one = 1;
-            GNS_HIP(hipMemcpy(cm->stats + 3, &one, sizeof(one), hipMemcpyHostToDevice));
-            set_error("flow dictionary full: %llu live flows plus one %u-packet batch exceed %llu slots",
-                      (unsigned long long)cm->last_live, kChunk, (unsigned long long)cm->dict_slots);
-            return GNS_E_FULL;
-        }
-        GNS_TRY(cm_reclaim(cm, cm->dict_slots * 2));  // grow, then re-run the piece
-    }
-    const uint64_t h = ((m / 2 + kChunk - 1) / kChunk) * kChunk;
-    GNS_TRY(cm_batch_recover<KIND>(cm, d, h, true));
-    return cm_batch_recover<KIND>(cm, advance(d, h), m - h, false);
+int cm_batch_recover(gns_cm *cm, const InputDesc &d, uint64_t m) {
+    static const std::string piece = std::to_string(kChunk) + "-packet batch";
+    const DictRecovery r{*cm, cm->stats, cm->stream, kChunk, piece.c_str(),
+                         [cm](const InputDesc &pd, uint64_t pm) { return cm_batch<KIND>(cm, pd, pm); },
+                         [cm](uint64_t min_slots) { return cm_reclaim(cm, min_slots); }};
+    return r.batch(d, m, false);
 }
 
 // 16-byte compact records: the wire lengths (word 3 bits 16..31) as the batch's size array
@@ -4243,41 +3842,26 @@ __global__ __launch_bounds__(256) void k_rec_sizes(const uint32_t *rec16, uint64
 // Host input: stage batch [off, off+m) into device buffer b on the copy stream,
 // after the batch that last read b has finished; d points into the buffer.
 int stage_host_batch(gns_cm *cm, int b, const InputDesc &in, uint64_t off, uint64_t m, InputDesc &d) {
-    d = in;
-    constexpr int NA = 8;
-    const void *src[NA] = {in.hdr ? (const void *)(in.hdr + off * 16) : nullptr,
-                           in.src16 ? (const void *)(in.src16 + off * 16) : nullptr,
-                           in.dst16 ? (const void *)(in.dst16 + off * 16) : nullptr,
-                           in.sport ? (const void *)(in.sport + off) : nullptr,
-                           in.dport ? (const void *)(in.dport + off) : nullptr,
-                           in.proto ? (const void *)(in.proto + off) : nullptr,
-                           in.keys ? (const void *)(in.keys + off * in.stride) : nullptr,
-                           in.rec16 ? (const void *)(in.rec16 + off * 4) : nullptr};
-    const size_t bytes[NA] = {in.hdr ? m * 64 : 0, in.src16 ? m * 16 : 0, in.dst16 ? m * 16 : 0,
-                              in.sport ? m * 2 : 0, in.dport ? m * 2 : 0, in.proto ? m : 0,
-                              in.keys ? m * in.stride : 0, in.rec16 ? m * 16 : 0};
-    size_t tot = (m * 4 + 15) & ~size_t(15);
-    for (int i = 0; i < NA; i++) tot += (bytes[i] + 15) & ~size_t(15);
-    GNS_TRY(stage_reserve(cm, b, tot));
+    if (!cm->cstream) {
+        GNS_HIP(hipStreamCreateWithFlags(&cm->cstream, hipStreamNonBlocking));
+        for (int i = 0; i < 2; i++) {
+            GNS_HIP(hipEventCreateWithFlags(&cm->ev_copied[i], hipEventDisableTiming));
+            GNS_HIP(hipEventCreateWithFlags(&cm->ev_used[i], hipEventDisableTiming));
+        }
+    }
+    StageList l;
+    d = advance(in, off);
+    stage_input(l, d, m);
+    if (in.rec_len) stage_add<uint32_t>(l, nullptr, m * 4, &d.sizes);  // room for the sizes of the staged records
+    HostStage &sg = cm->stage[b];
+    if (sg.cap < HostStage::need(l)) GNS_HIP(hipEventSynchronize(cm->ev_used[b]));  // the batch that read it is done
     GNS_HIP(hipStreamWaitEvent(cm->cstream, cm->ev_used[b], 0));
-    uint8_t *p = cm->stage[b];
-    const void **dst[NA] = {(const void **)&d.hdr, (const void **)&d.src16, (const void **)&d.dst16,
-                            (const void **)&d.sport, (const void **)&d.dport, (const void **)&d.proto,
-                            (const void **)&d.keys, (const void **)&d.rec16};
-    for (int i = 0; i < NA; i++) {
-        if (!bytes[i]) continue;
-        GNS_HIP(hipMemcpyAsync(p, src[i], bytes[i], hipMemcpyHostToDevice, cm->cstream));
-        *dst[i] = p;
-        p += (bytes[i] + 15) & ~size_t(15);
-    }
-    if (in.rec_len) {  // sizes from the staged records
+    GNS_TRY(sg.copy(l, cm->cstream));
+    if (in.rec_len) {
         hipLaunchKernelGGL(k_rec_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, cm->cstream, d.rec16, m,
-                           reinterpret_cast<uint32_t *>(p));
+                           const_cast<uint32_t *>(d.sizes));
         GNS_HIP(hipGetLastError());
-    } else {
-        GNS_HIP(hipMemcpyAsync(p, in.sizes + off, m * 4, hipMemcpyHostToDevice, cm->cstream));
     }
-    d.sizes = reinterpret_cast<const uint32_t *>(p);
     if (d.keys) d.aligned = (d.stride % 4 == 0 && d.stride >= ((cm->K + 3) & ~3u)) ? 1u : 0u;
     GNS_HIP(hipEventRecord(cm->ev_copied[b], cm->cstream));
     return GNS_OK;
@@ -4285,7 +3869,7 @@ int stage_host_batch(gns_cm *cm, int b, const InputDesc &in, uint64_t off, uint6
 
 template <int KIND>
 int cm_insert(gns_cm *cm, InputDesc in, uint64_t n, gns_mem where) {
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     // batch sizes: a cold handle's small first batch designates the heavy buckets early
     auto batch_len = [&](uint64_t off, bool warm) {
         const uint64_t m = std::min<uint64_t>(cm->bmax, n - off);
@@ -4302,7 +3886,7 @@ int cm_insert(gns_cm *cm, InputDesc in, uint64_t n, gns_mem where) {
                 GNS_HIP(hipGetLastError());
                 d.sizes = cm->rec_sizes;
             }
-            GNS_TRY(cm_batch_recover<KIND>(cm, d, m, false));
+            GNS_TRY(cm_batch_recover<KIND>(cm, d, m));
         }
         return GNS_OK;
     }
@@ -4319,7 +3903,7 @@ int cm_insert(gns_cm *cm, InputDesc in, uint64_t n, gns_mem where) {
         InputDesc nd;
         if (nm) GNS_TRY(stage_host_batch(cm, b ^ 1, in, noff, nm, nd));
         GNS_HIP(hipStreamWaitEvent(cm->stream, cm->ev_copied[b], 0));
-        const int rc = cm_batch_recover<KIND>(cm, d, m, false);
+        const int rc = cm_batch_recover<KIND>(cm, d, m);
         GNS_HIP(hipEventRecord(cm->ev_used[b], cm->stream));
         if (rc != GNS_OK) {
             (void)hipStreamSynchronize(cm->cstream);  // no copy may outlive the caller's arrays
@@ -4338,23 +3922,15 @@ int cm_insert(gns_cm *cm, InputDesc in, uint64_t n, gns_mem where) {
 
 extern "C" {
 
-static int heavy_reserve(CmScratch &sc, uint64_t cells, uint64_t slots, uint32_t K, hipStream_t st);
-
 int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
     if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return GNS_E_ARG; }
+    GNS_TRY(check_device(p->device));
     gns_cm *cm = new gns_cm();
     cm->device = p->device;
     int rc = GNS_OK;
     do {
-        if ((rc = set_dev(cm)) != GNS_OK) break;
+        if ((rc = set_device(cm->device)) != GNS_OK) break;
         // count_min.go:48-59 defaults
         CmGeom &g = cm->g;
         g.w = p->width ? p->width : (1u << 20);
@@ -4428,7 +4004,7 @@ int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
         if ((rc = dalloc_t(&cm->D.rec, slots * cm->D.RW)) != GNS_OK) break;
         if ((rc = dalloc_t(&cm->dctl, 4)) != GNS_OK || (rc = dalloc_t(&cm->stats_bak, 3)) != GNS_OK) break;
         cm->D.ctl = cm->dctl;
-        cm_dict_limits(cm);
+        cm->limits();
         // batch buffers
         cm->bmax = p->batch_packets ? p->batch_packets : (16ull << 20);
         cm->bmax = ((cm->bmax + kChunk - 1) / kChunk) * kChunk;
@@ -4501,7 +4077,7 @@ int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
             }
         }
         // the read side's heavy-hitter buffers (a window's first call allocates nothing)
-        if ((rc = heavy_reserve(cm->rd, (uint64_t)cm->g.d * cm->g.w, cm->dict_slots, cm->K, cm->stream)) != GNS_OK) break;
+        if ((rc = hh_reserve(cm->rd.hh, (uint64_t)cm->g.d * cm->g.w, cm->dict_slots, cm->K, cm->stream)) != GNS_OK) break;
         if (hipStreamSynchronize(cm->stream) != hipSuccess) { set_error("sync failed"); rc = GNS_E_HIP; break; }
     } while (0);
     if (rc != GNS_OK) {
@@ -4565,7 +4141,7 @@ int gns_cm_insert_compact(gns_cm *cm, const uint8_t *rec16, const uint32_t *wire
     if (where == GNS_MEM_HOST && n_side) {
         // the side records of the whole call, staged once (escapes index them globally);
         // the batches of the previous call may still read the buffer
-        GNS_TRY(set_dev(cm));
+        GNS_TRY(set_device(cm->device));
         GNS_HIP(hipStreamSynchronize(cm->stream));
         if (cm->side_n < n_side) {
             dfree(cm->side_dev);
@@ -4582,7 +4158,7 @@ int gns_cm_insert_compact(gns_cm *cm, const uint8_t *rec16, const uint32_t *wire
 
 int gns_cm_flush(gns_cm *cm) {
     if (!cm) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     {  // stats words 4..9 into the pinned mirror behind the stream's work: one round trip
         CtlRead rd;
         rd.add(cm->stats + 4, 48, 0);
@@ -4606,7 +4182,7 @@ int gns_cm_flush(gns_cm *cm) {
 // Query (count_min.go:160-174) of n keys against state (C, Fc, S, Fs) on stream st:
 // host keys / answers (staged through the grow-only scratch), or device keys /
 // answers (dev: no copies; the call returns once the answers are written).
-static int cm_query_impl(gns_cm *cm, hipStream_t st, CmScratch &sc, const uint32_t *C, const uint32_t *Fc,
+static int cm_query_impl(gns_cm *cm, hipStream_t st, CmRead &sc, const uint32_t *C, const uint32_t *Fc,
                          const uint32_t *S, const uint32_t *Fs, const uint8_t *keys, uint32_t stride, uint64_t n,
                          uint64_t *out, bool dev = false) {
     if (!dev) {
@@ -4636,7 +4212,7 @@ int gns_cm_query(gns_cm *cm, const uint8_t *keys, uint32_t stride, uint64_t n, u
     if (!cm || (n && (!keys || !out))) { set_error("null argument"); return GNS_E_ARG; }
     if (n == 0) return GNS_OK;
     if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     return cm_query_impl(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->S, cm->Fs, keys, stride, n, out);
 }
 
@@ -4645,326 +4221,32 @@ int gns_cm_query_device(gns_cm *cm, const uint8_t *keys, uint32_t stride, uint64
     if (n == 0) return GNS_OK;
     if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
     if (((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     return cm_query_impl(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->S, cm->Fs, keys, stride, n, out, true);
-}
-
-// ids -> key bytes on stream `st`: through the grow-only scratch when small
-// (heavy-hitter lists), a temporary buffer for whole-state exports.
-static int cm_ids_to_host_bytes(gns_cm *cm, hipStream_t st, CmScratch &sc, const uint32_t *d_ids, uint64_t n,
-                                uint8_t *host) {
-    if (n == 0 || cm->K == 0) return GNS_OK;
-    const uint64_t nb = n * cm->K;
-    const bool tmp = nb > (64ull << 20);
-    uint8_t *d = nullptr;
-    if (tmp) GNS_TRY(dalloc(reinterpret_cast<void **>(&d), nb));
-    else { GNS_TRY(grow_buf(&sc.bytes, sc.bytes_n, nb)); d = sc.bytes; }
-    hipLaunchKernelGGL(k_ids_to_bytes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_ids, n, cm->D, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host, d, nb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (tmp) dfree(d);
-    if (e != hipSuccess) { set_error("ids_to_bytes: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
 }
 
 int gns_cm_export_state(gns_cm *cm, uint32_t *C, uint32_t *S, uint8_t *FPc, uint8_t *FPs) {
     if (!cm) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     GNS_HIP(hipStreamSynchronize(cm->stream));
     const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
     if (C) GNS_HIP(hipMemcpy(C, cm->C, cells * 4, hipMemcpyDeviceToHost));
     if (S) GNS_HIP(hipMemcpy(S, cm->S, cells * 4, hipMemcpyDeviceToHost));
-    if (FPc) GNS_TRY(cm_ids_to_host_bytes(cm, cm->stream, cm->rd, cm->Fc, cells, FPc));
-    if (FPs) GNS_TRY(cm_ids_to_host_bytes(cm, cm->stream, cm->rd, cm->Fs, cells, FPs));
+    if (FPc) GNS_TRY(hh_ids_to_host_bytes(cm->rd.hh, cm->stream, cm->D, cm->Fc, cells, FPc));
+    if (FPs) GNS_TRY(hh_ids_to_host_bytes(cm->rd.hh, cm->stream, cm->D, cm->Fs, cells, FPs));
     return GNS_OK;
 }
 
-// HeavyHitters (count_min.go:178-247): a flow's max over its buckets reaches the
-// threshold iff one of its buckets does, so only cells >= threshold are
-// candidates; dedupe by fingerprint keeping the max; sort value desc.
-// the per-flow-id words cover every slot of the dictionary (zeroed when (re)allocated:
-// the epochs of the calls start at 1); bump: a new call's epoch
-static int heavy_flow_words(CmScratch &sc, uint64_t slots, hipStream_t st, bool bump) {
-    if (sc.best_n < slots || !sc.best || sc.mark_n < slots || !sc.mark) {
-        dfree(sc.best); dfree(sc.mark);
-        sc.best = nullptr; sc.mark = nullptr; sc.best_n = sc.mark_n = 0;
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&sc.best), slots * 8));
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&sc.mark), slots * 4));
-        sc.best_n = sc.mark_n = slots;
-        GNS_HIP(hipMemsetAsync(sc.best, 0, slots * 8, st));
-        GNS_HIP(hipMemsetAsync(sc.mark, 0, slots * 4, st));
-        sc.hh_epoch = 0;
-    }
-    if (bump && ++sc.hh_epoch == 0) {  // wrapped: clear, restart at 1
-        GNS_HIP(hipMemsetAsync(sc.best, 0, sc.best_n * 8, st));
-        GNS_HIP(hipMemsetAsync(sc.mark, 0, sc.mark_n * 4, st));
-        sc.hh_epoch = 1;
-    }
-    return GNS_OK;
-}
-
-// Read-side buffers of the heavy-hitter list sized up front (gns_cm_create /
-// gns_cm_view_create), so a window's first call allocates nothing: candidates
-// for min(cells, 4M) buckets, the per-flow words for the dictionary's slots,
-// unique entries and their order for 1M flows.  Larger lists still grow them.
-static int small_pin(CmScratch &sc) {
-    if (!sc.hsm) GNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&sc.hsm), 64, hipHostMallocDefault));
-    return GNS_OK;
-}
-
-static int heavy_reserve(CmScratch &sc, uint64_t cells, uint64_t slots, uint32_t K, hipStream_t st) {
-    GNS_TRY(heavy_flow_words(sc, slots, st, false));
-    if (!sc.ncand) GNS_TRY(dalloc(reinterpret_cast<void **>(&sc.ncand), 16));
-    if (!sc.cand) {
-        const uint64_t want = std::min<uint64_t>(cells, 1ull << 22);
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&sc.cand), want * 8));
-        sc.cap = want;
-    }
-    const uint64_t nu = std::min<uint64_t>(std::min(cells, slots), 1ull << 20);
-    GNS_TRY(grow_buf(&sc.u32a, sc.u32a_n, nu / 2));
-    GNS_TRY(grow_buf(&sc.u32b, sc.u32b_n, nu / 2 + 1));
-    GNS_TRY(grow_buf(&sc.u32c, sc.u32c_n, nu));
-    GNS_TRY(grow_buf(&sc.u32d, sc.u32d_n, nu / 2));
-    GNS_TRY(grow_buf(&sc.bytes, sc.bytes_n, nu / 2 * std::max<uint32_t>(K, 1)));
-    GNS_TRY(grow_buf(&sc.obytes, sc.obytes_n, nu / 2 * std::max<uint32_t>(K, 1)));
-    if (!sc.hpin) {
-        const uint64_t want = nu * (std::max<uint32_t>(K, 1) + 4);
-        GNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&sc.hpin), want, hipHostMallocDefault));
-        sc.hpin_n = want;
-    }
-    // the order's pass histograms and the small pinned read-back words for nu entries too:
-    // a window's first list then allocates nothing (an allocation inside one list call was
-    // followed by an 18-36 ms dispatch stall of a LATER call, profiles/r06_hh_spikes.txt)
-    const uint64_t nblk = (nu + kRsBlock - 1) / kRsBlock, ngrp = (nblk + kTGrp - 1) / kTGrp;
-    GNS_TRY(grow_buf(&sc.rsh, sc.rsh_n, (nblk + ngrp + 1) * 256 + 4));
-    return small_pin(sc);
-}
-
-// GNS_HH_TRACE=1: the heavy-hitter list's phases timed on stderr (each mark
-// synchronizes the stream first; diagnostics only, never on by default).
-struct HhTrace {
-    bool on;
-    hipStream_t st;
-    std::chrono::steady_clock::time_point t;
-    explicit HhTrace(hipStream_t s) : on(getenv("GNS_HH_TRACE") != nullptr), st(s), t(std::chrono::steady_clock::now()) {}
-    void mark(const char *what, uint64_t n, bool sync = true) {
-        if (!on) return;
-        if (sync) (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        struct rusage ru;
-        getrusage(RUSAGE_THREAD, &ru);
-        fprintf(stderr, "[hh] %-12s n=%-9llu %8.3f ms  nivcsw=%ld nvcsw=%ld\n", what, (unsigned long long)n,
-                std::chrono::duration<double, std::milli>(now - t).count(), ru.ru_nivcsw, ru.ru_nvcsw);
-        t = now;
-    }
-};
-
-// One stable LSD radix pass over perm (n entries) by digit r: in -> out.
-static int rs_pass(CmScratch &sc, hipStream_t st, const uint32_t *in, uint32_t *out, uint32_t n, const RsDigit &r) {
-    const uint32_t nblk = (n + kRsBlock - 1) / kRsBlock;
-    const uint32_t ngrp = (nblk + kTGrp - 1) / kTGrp;
-    uint32_t *hist = sc.rsh, *part = hist + (size_t)nblk * 256, *tot = part + (size_t)ngrp * 256, *total = tot + 256;
-    hipLaunchKernelGGL(k_rs_hist, dim3(nblk), dim3(256), 0, st, in, n, r, hist);
-    hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, st, hist, nblk, 256u, part);
-    hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, st, part, ngrp, 256u, tot);
-    hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, st, tot, 256u, total);
-    hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, st, hist, nblk, 256u, part, tot);
-    hipLaunchKernelGGL(k_rs_scatter, dim3(nblk), dim3(256), 0, st, in, n, r, hist, tot, total, out);
-    GNS_HIP(hipGetLastError());
-    return GNS_OK;
-}
-
-// Canonical order of n entries of a device list (value desc, flow bytes asc) -> *perm_out
-// (a device array of sc's): stable LSD radix passes by (value desc, key bytes 0..3), and by
-// the whole key only when two neighbours tie on that.
-static int hh_sort(CmScratch &sc, hipStream_t st, const HhSrc &src, uint32_t n, uint32_t **perm_out) {
-    const unsigned g = (n + 255) / 256;
-    const uint32_t K = src.K;
-    GNS_TRY(grow_buf(&sc.u32c, sc.u32c_n, (uint64_t)n * 2));
-    const uint32_t nblk = (n + kRsBlock - 1) / kRsBlock, ngrp = (nblk + kTGrp - 1) / kTGrp;
-    GNS_TRY(grow_buf(&sc.rsh, sc.rsh_n, (uint64_t)(nblk + ngrp + 1) * 256 + 4));
-    uint32_t *tie = sc.rsh + (size_t)(nblk + ngrp + 1) * 256 + 1;
-    uint32_t *p[2] = {sc.u32c, sc.u32c + n};
-    int cur = 0;
-    // LSD: key bytes hi-1..0 (the last first), then the value (least significant byte first,
-    // inverted: descending) -> (value desc, key bytes 0..hi-1 asc)
-    auto sort_by = [&](uint32_t hi) -> int {
-        hipLaunchKernelGGL(k_hh_iota, dim3(g), dim3(256), 0, st, p[0], n);
-        cur = 0;
-        RsDigit r{1, 0, src};
-        for (int b = (int)hi - 1; b >= 0; b--) {
-            r.b = (uint32_t)b;
-            GNS_TRY(rs_pass(sc, st, p[cur], p[cur ^ 1], n, r));
-            cur ^= 1;
-        }
-        r.mode = 0;
-        for (uint32_t b = 0; b < 4; b++) {
-            r.b = b;
-            GNS_TRY(rs_pass(sc, st, p[cur], p[cur ^ 1], n, r));
-            cur ^= 1;
-        }
-        return GNS_OK;
-    };
-    HhTrace tr(st);
-    GNS_TRY(sort_by(std::min<uint32_t>(K, 4)));
-    tr.mark("sort_primary", n);
-    if (K > 4) {
-        GNS_TRY(small_pin(sc));
-        GNS_HIP(hipMemsetAsync(tie, 0, 4, st));
-        hipLaunchKernelGGL(k_hh_ties, dim3(g), dim3(256), 0, st, p[cur], n, src, tie);
-        GNS_HIP(hipMemcpyAsync(sc.hsm + 4, tie, 4, hipMemcpyDeviceToHost, st));
-        GNS_HIP(hipStreamSynchronize(st));
-        const uint32_t tflag = sc.hsm[4];
-        tr.mark(tflag ? "ties:yes" : "ties:no", n);
-        if (tflag) GNS_TRY(sort_by(K));  // the whole key: bytes K-1..0, then the value
-        if (tflag) tr.mark("sort_full", n);
-    }
-    *perm_out = p[cur];
-    return GNS_OK;
-}
-
-// rows_dev non-null: the ordered list as packed device rows [flow | u32 value] (capacity
-// *n_io rows), no host copy; else flows / vals on the host.
-// The list of one (value, fingerprint id) cell array of `cells` cells whose ids are
-// slots of dictionary D: Count-Min's count and size lists, and SuperSpread's list
-// (gns_ss.hip through gns::hh_heavy_list).
-static int heavy_list(CmScratch &sc, hipStream_t st, const DictDev &Dd, uint64_t dict_slots, uint32_t K,
-                      uint64_t cells, const uint32_t *val, const uint32_t *fp, uint32_t thr, uint8_t *flows,
-                      uint32_t *vals, uint64_t *n_io, uint8_t *rows_dev = nullptr) {
-    struct {
-        uint64_t dict_slots;
-        DictDev D;
-    } cmv{dict_slots, Dd}, *cm = &cmv;
-    HhTrace tr(st);
-    GNS_TRY(heavy_reserve(sc, cells, cm->dict_slots, K, st));
-    GNS_TRY(small_pin(sc));
-    tr.mark("reserve", cells);
-    // candidate buffer: grows to the number of cells at or above the threshold
-    // (no cap: a low threshold can make every bucket a candidate, d*w < 2^32)
-    uint32_t nc = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        // [0] candidates, [1] unique, [2] bad-id flag: zeroed by a kernel on the list's stream
-        tr.mark("pre_launch", 0, false);
-        hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(64), 0, st, sc.ncand, (uint64_t)3, 0u);
-        tr.mark("launched", 0, false);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_hh_candidates, dim3((unsigned)((cells + 256 * kHhItems - 1) / (256 * kHhItems))), dim3(256), 0,
-                               st, val, fp, cells, thr, sc.cand, sc.ncand, (uint32_t)sc.cap);
-            e = hipGetLastError();
-        }
-        tr.mark("cand_kernel", cells);
-        if (e == hipSuccess) e = hipMemcpyAsync(sc.hsm, sc.ncand, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { set_error("heavy: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-        nc = sc.hsm[0];
-        tr.mark("candidates", nc);
-        if (nc <= sc.cap) break;
-        // more candidates than the buffer holds: grow to the count and run again
-        dfree(sc.cand);
-        sc.cand = nullptr;
-        sc.cap = 0;
-        const uint64_t want = std::min<uint64_t>(cells, (uint64_t)nc + nc / 8);
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&sc.cand), want * 8));
-        sc.cap = want;
-    }
-    const uint64_t *cand = sc.cand;
-    // on the device: the max per flow over its buckets, one entry per flow
-    uint32_t nu = 0;
-    if (nc) {
-        const unsigned g = (nc + 255) / 256;
-        GNS_TRY(heavy_flow_words(sc, cm->dict_slots, st, true));
-        GNS_TRY(grow_buf(&sc.u32a, sc.u32a_n, nc));
-        GNS_TRY(grow_buf(&sc.u32b, sc.u32b_n, nc + 1));
-        uint32_t *d_nu = sc.ncand + 1, *d_bad = sc.ncand + 2;
-        const uint64_t slots = cm->dict_slots;
-        hipLaunchKernelGGL(k_hh_best, dim3(g), dim3(256), 0, st, cand, nc, sc.best, sc.hh_epoch, slots, d_bad);
-        hipLaunchKernelGGL(k_hh_emit, dim3(g), dim3(256), 0, st, cand, nc, sc.best, sc.mark, sc.hh_epoch, slots,
-                           sc.u32a, sc.u32b, d_nu);
-        GNS_HIP(hipGetLastError());
-        GNS_HIP(hipMemcpyAsync(sc.hsm + 1, d_nu, 8, hipMemcpyDeviceToHost, st));
-        GNS_HIP(hipStreamSynchronize(st));
-        nu = sc.hsm[1];
-        if (sc.hsm[2]) {
-            set_error("heavy hitters: a bucket fingerprint names no dictionary slot (corrupt state)");
-            return GNS_E_HIP;
-        }
-        tr.mark("dedupe", nu);
-    }
-    const uint64_t capn = *n_io;
-    *n_io = nu;
-    if (nu) {
-        const unsigned g = (nu + 255) / 256;
-        const uint32_t Kb = K ? K : 1;
-        GNS_TRY(grow_buf(&sc.bytes, sc.bytes_n, (uint64_t)nu * Kb));
-        GNS_TRY(grow_buf(&sc.obytes, sc.obytes_n, (uint64_t)nu * Kb));
-        GNS_TRY(grow_buf(&sc.u32d, sc.u32d_n, (uint64_t)nu));
-        tr.mark("grow", nu);
-        if (K) hipLaunchKernelGGL(k_ids_to_bytes, dim3(g), dim3(256), 0, st, sc.u32a, (uint64_t)nu, cm->D, sc.bytes);
-        tr.mark("ids_to_bytes", nu);
-        const HhSrc src{sc.u32b, sc.bytes, K, K};
-        uint32_t *perm = nullptr;
-        GNS_TRY(hh_sort(sc, st, src, nu, &perm));
-        tr.mark("sorted", nu);
-        if (rows_dev) {
-            if (nu <= capn) {
-                hipLaunchKernelGGL(k_hh_gather, dim3(g), dim3(256), 0, st, perm, src, nu, nullptr, nullptr, rows_dev);
-                GNS_HIP(hipGetLastError());
-                GNS_HIP(hipStreamSynchronize(st));
-            }
-            return GNS_OK;
-        }
-        hipLaunchKernelGGL(k_hh_gather, dim3(g), dim3(256), 0, st, perm, src, nu, sc.obytes, sc.u32d, nullptr);
-        GNS_HIP(hipGetLastError());
-        const uint64_t m = std::min<uint64_t>(nu, capn);
-        const uint64_t fb = (flows && K) ? m * K : 0, vb = vals ? m * 4 : 0;
-        if (fb + vb > sc.hpin_n) {
-            if (sc.hpin) (void)hipHostFree(sc.hpin);
-            sc.hpin = nullptr; sc.hpin_n = 0;
-            const uint64_t want = 2 * (fb + vb);
-            GNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&sc.hpin), want, hipHostMallocDefault));
-            sc.hpin_n = want;
-        }
-        if (fb) GNS_HIP(hipMemcpyAsync(sc.hpin, sc.obytes, fb, hipMemcpyDeviceToHost, st));
-        if (vb) GNS_HIP(hipMemcpyAsync(sc.hpin + fb, sc.u32d, vb, hipMemcpyDeviceToHost, st));
-        GNS_HIP(hipStreamSynchronize(st));
-        tr.mark("gather_d2h", m);
-        if (fb) memcpy(flows, sc.hpin, fb);
-        if (vb) memcpy(vals, sc.hpin + fb, vb);
-        tr.mark("host_copy", m);
-    }
-    return GNS_OK;
-}
-
-static int cm_heavy_one(gns_cm *cm, hipStream_t st, CmScratch &sc, const uint32_t *val, const uint32_t *fp,
+static int cm_heavy_one(gns_cm *cm, hipStream_t st, CmRead &sc, const uint32_t *val, const uint32_t *fp,
                         uint32_t thr, uint8_t *flows, uint32_t *vals, uint64_t *n_io, uint8_t *rows_dev = nullptr) {
-    return heavy_list(sc, st, cm->D, cm->dict_slots, cm->K, (uint64_t)cm->g.d * cm->g.w, val, fp, thr, flows, vals,
+    return hh_heavy_list(sc.hh, st, cm->D, cm->dict_slots, cm->K, (uint64_t)cm->g.d * cm->g.w, val, fp, thr, flows, vals,
                       n_io, rows_dev);
 }
-
-}  // extern "C"
-
-namespace gns {
-CmScratch *hh_scratch_new() { return new CmScratch(); }
-void hh_scratch_free(CmScratch *sc) {
-    if (!sc) return;
-    sc->free_all();
-    delete sc;
-}
-int hh_heavy_list(CmScratch *sc, hipStream_t st, const DictDev &D, uint64_t dict_slots, uint32_t K, uint64_t cells,
-                  const uint32_t *val, const uint32_t *fp, uint32_t thr, uint8_t *flows, uint32_t *vals,
-                  uint64_t *n_io) {
-    return heavy_list(*sc, st, D, dict_slots, K, cells, val, fp, thr, flows, vals, n_io);
-}
-}  // namespace gns
-
-extern "C" {
 
 int gns_cm_heavy_hitters(gns_cm *cm, uint8_t *count_flows, uint32_t *counts, uint64_t *n_count,
                          uint8_t *size_flows, uint32_t *sizes, uint64_t *n_size) {
     if (!cm || !n_count || !n_size) { set_error("null argument"); return GNS_E_ARG; }
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     GNS_HIP(hipStreamSynchronize(cm->stream));
     GNS_TRY(cm_heavy_one(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->ct, count_flows, counts, n_count));
     GNS_TRY(cm_heavy_one(cm, cm->stream, cm->rd, cm->S, cm->Fs, cm->st, size_flows, sizes, n_size));
@@ -4975,7 +4257,7 @@ int gns_cm_heavy_rows(gns_cm *cm, uint8_t *count_rows, uint64_t *n_count, uint8_
     if (!cm || !n_count || !n_size || (*n_count && !count_rows) || (*n_size && !size_rows)) {
         set_error("null argument"); return GNS_E_ARG;
     }
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     GNS_HIP(hipStreamSynchronize(cm->stream));
     uint8_t dummy_c = 0, dummy_s = 0;  // a zero-capacity call only reports the lengths
     GNS_TRY(cm_heavy_one(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->ct, nullptr, nullptr, n_count,
@@ -4984,36 +4266,6 @@ int gns_cm_heavy_rows(gns_cm *cm, uint8_t *count_rows, uint64_t *n_count, uint8_
                          size_rows ? size_rows : &dummy_s));
     return GNS_OK;
 }
-
-// per device, per host thread: the sort scratch of gns_hh_order_rows (grow-only; it lives as long
-// as the thread -- freeing device memory from a thread-exit destructor could run after the HIP
-// runtime's own teardown at process exit)
-static thread_local std::vector<CmScratch *> t_hh_scratch;
-
-int gns_hh_order_rows(const uint8_t *rows, uint32_t key_bytes, uint64_t n, uint8_t *out_rows, int device) {
-    if ((n && (!rows || !out_rows)) || key_bytes > 37) { set_error("bad argument"); return GNS_E_ARG; }
-    if (n >= (1ull << 31)) { set_error("%llu rows (max 2^31 - 1)", (unsigned long long)n); return GNS_E_RANGE; }
-    if (n == 0) return GNS_OK;
-    (void)hipGetLastError();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError(); set_error("device %d not available", device); return GNS_E_NODEV;
-    }
-    GNS_HIP(hipSetDevice(device));
-    if ((int)t_hh_scratch.size() <= device) t_hh_scratch.resize(device + 1, nullptr);
-    if (!t_hh_scratch[device]) t_hh_scratch[device] = new CmScratch();
-    CmScratch &sc = *t_hh_scratch[device];
-    hipStream_t st = nullptr;  // the legacy stream: ordered after the caller's device writes
-    const HhSrc src{nullptr, rows, key_bytes, key_bytes + 4};
-    uint32_t *perm = nullptr;
-    GNS_TRY(hh_sort(sc, st, src, (uint32_t)n, &perm));
-    hipLaunchKernelGGL(k_hh_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, perm, src, (uint32_t)n,
-                       nullptr, nullptr, out_rows);
-    GNS_HIP(hipGetLastError());
-    GNS_HIP(hipStreamSynchronize(st));
-    return GNS_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Snapshot views: heavy hitters and queries concurrent with ingest
 // (BASELINE configs[4]; the reference's snapshotter reads the live buckets
@@ -5030,7 +4282,7 @@ static void view_free(gns_cm_view *v) {
 int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
     if (!cm || !out) { set_error("null argument"); return GNS_E_ARG; }
     *out = nullptr;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     gns_cm_view *v = new gns_cm_view();
     v->cm = cm;
     const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
@@ -5047,7 +4299,7 @@ int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
             hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess) {
             set_error("view stream/event"); rc = GNS_E_HIP; break;
         }
-        if ((rc = heavy_reserve(v->rd, cells, cm->dict_slots, cm->K, v->stream)) != GNS_OK) break;
+        if ((rc = hh_reserve(v->rd.hh, cells, cm->dict_slots, cm->K, v->stream)) != GNS_OK) break;
         if (hipStreamSynchronize(v->stream) != hipSuccess) { set_error("view sync"); rc = GNS_E_HIP; break; }
     } while (0);
     if (rc) { view_free(v); delete v; return rc; }
@@ -5079,7 +4331,7 @@ int gns_cm_view_destroy(gns_cm_view *v) {
 int gns_cm_view_refresh(gns_cm_view *v) {
     if (!v) { set_error("null argument"); return GNS_E_ARG; }
     gns_cm *cm = v->cm;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     std::lock_guard<std::mutex> lk(v->mu);  // no view query is reading the snapshot
     const uint64_t bytes = (uint64_t)cm->g.d * cm->g.w * 4;
     // copies on the handle's stream: the snapshot is the state after every insert
@@ -5104,7 +4356,7 @@ int gns_cm_view_heavy_hitters(gns_cm_view *v, uint8_t *count_flows, uint32_t *co
                               uint8_t *size_flows, uint32_t *sizes, uint64_t *n_size) {
     if (!v || !n_count || !n_size) { set_error("null argument"); return GNS_E_ARG; }
     gns_cm *cm = v->cm;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(view_check(v));
     GNS_TRY(cm_heavy_one(cm, v->stream, v->rd, v->C, v->Fc, cm->ct, count_flows, counts, n_count));
@@ -5117,7 +4369,7 @@ int gns_cm_view_query(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint
     if (n == 0) return GNS_OK;
     gns_cm *cm = v->cm;
     if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(view_check(v));
     return cm_query_impl(cm, v->stream, v->rd, v->C, v->Fc, v->S, v->Fs, keys, stride, n, out);
@@ -5125,7 +4377,7 @@ int gns_cm_view_query(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint
 
 int gns_cm_reset(gns_cm *cm) {
     if (!cm) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     // a view call that passed its period check still reads the dictionary: wait
     // for it before the dictionary is cleared (views answer GNS_E_ARG afterwards)
     ViewsQuiesced q(cm);
@@ -5137,7 +4389,7 @@ int gns_cm_reset(gns_cm *cm) {
 
 int gns_cm_stats(gns_cm *cm, uint64_t stats[4]) {
     if (!cm || !stats) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     GNS_HIP(hipStreamSynchronize(cm->stream));
     unsigned long long h[8];
     GNS_HIP(hipMemcpy(h, cm->stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -5159,7 +4411,7 @@ int gns_cm_stats(gns_cm *cm, uint64_t stats[4]) {
 
 int gns_cm_counters(gns_cm *cm, uint64_t out[8]) {
     if (!cm || !out) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     GNS_HIP(hipStreamSynchronize(cm->stream));
     unsigned long long h[kStatsProf + 16];
     GNS_HIP(hipMemcpy(h, cm->stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -5190,7 +4442,7 @@ int gns_cm_counters(gns_cm *cm, uint64_t out[8]) {
 
 int gns_cm_reclaim(gns_cm *cm) {
     if (!cm) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     return cm_reclaim(cm);
 }
 
@@ -5210,7 +4462,7 @@ int gns_cm_set_timing(gns_cm *cm, int on) {
 
 int gns_cm_stage_times(gns_cm *cm, double ms[8], uint64_t launches[8], int reset) {
     if (!cm) return GNS_E_ARG;
-    GNS_TRY(set_dev(cm));
+    GNS_TRY(set_device(cm->device));
     cm->timer.collect();
     for (int i = 0; i < 8; i++) {
         if (ms) ms[i] = cm->timer.ms[i];

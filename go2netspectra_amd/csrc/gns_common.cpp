@@ -1,6 +1,7 @@
 // gns_common.cpp -- host plumbing (see gns_common.hpp).
 #include "gns_common.hpp"
 
+#include <chrono>
 #include <mutex>
 
 namespace gns {
@@ -30,6 +31,161 @@ int dalloc(void **p, size_t bytes) {
 
 void dfree(void *p) {
     if (p) (void)hipFree(p);
+}
+
+int check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        set_error("no HIP device available");
+        return GNS_E_NODEV;
+    }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range", device); return GNS_E_ARG; }
+    return GNS_OK;
+}
+
+int set_device(int device) {
+    (void)hipGetLastError();
+    GNS_HIP(hipSetDevice(device));
+    return GNS_OK;
+}
+
+InputDesc advance(const InputDesc &in, uint64_t off) {
+    InputDesc d = in;
+    if (d.hdr) d.hdr += off * 16;
+    if (d.src16) d.src16 += off * 16;
+    if (d.dst16) d.dst16 += off * 16;
+    if (d.sport) d.sport += off;
+    if (d.dport) d.dport += off;
+    if (d.proto) d.proto += off;
+    if (d.keys) d.keys += off * d.stride;
+    if (d.keys2) d.keys2 += off * d.stride2;
+    if (d.rec16) d.rec16 += off * 4;
+    if (d.sizes) d.sizes += off;
+    return d;
+}
+
+void stage_input(StageList &l, InputDesc &d, uint64_t m) {
+    stage_add(l, d.hdr, d.hdr ? m * 64 : 0, &d.hdr);
+    stage_add(l, d.src16, d.src16 ? m * 16 : 0, &d.src16);
+    stage_add(l, d.dst16, d.dst16 ? m * 16 : 0, &d.dst16);
+    stage_add(l, d.sport, d.sport ? m * 2 : 0, &d.sport);
+    stage_add(l, d.dport, d.dport ? m * 2 : 0, &d.dport);
+    stage_add(l, d.proto, d.proto ? m : 0, &d.proto);
+    stage_add(l, d.keys, d.keys ? m * d.stride : 0, &d.keys);
+    stage_add(l, d.keys2, d.keys2 ? m * d.stride2 : 0, &d.keys2);
+    stage_add(l, d.rec16, d.rec16 ? m * 16 : 0, &d.rec16);
+    stage_add(l, d.sizes, d.sizes ? m * 4 : 0, &d.sizes);
+}
+
+size_t HostStage::need(const StageList &l) {
+    size_t tot = 0;
+    for (const StageItem &it : l) tot += (it.bytes + 15) & ~size_t(15);
+    return tot;
+}
+
+int HostStage::copy(const StageList &l, hipStream_t s) {
+    const size_t tot = need(l);
+    if (cap < tot) {
+        free_all();
+        GNS_TRY(dalloc(reinterpret_cast<void **>(&buf), tot));
+        cap = tot;
+    }
+    uint8_t *p = buf;
+    for (const StageItem &it : l) {
+        if (!it.bytes) continue;
+        if (it.src) GNS_HIP(hipMemcpyAsync(p, it.src, it.bytes, hipMemcpyHostToDevice, s));
+        *it.patch = p;
+        p += (it.bytes + 15) & ~size_t(15);
+    }
+    return GNS_OK;
+}
+
+void HostStage::free_all() {
+    dfree(buf);
+    buf = nullptr;
+    cap = 0;
+}
+
+void FlowDict::limits() {
+    D.cap = (uint32_t)(dict_slots - dict_slots / 4);
+    max_flows = std::max<uint64_t>(max_flows, dict_slots / 2);
+}
+
+int FlowDict::reclaim(DictIds *ids, int n, uint64_t min_slots, hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t before = claimed, slots0 = dict_slots;
+    uint64_t live = 0;
+    GNS_TRY(dict_rebuild(D, dict_slots, ids, n, nullptr, ids, n, std::min(kDictMaxSlots, std::max(dict_slots, min_slots)),
+                         s, dsc, &live, nullptr, kDictMaxSlots));
+    reclaim_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    n_reclaim++;
+    if (dict_slots != slots0) n_grow++;
+    limits();
+    n_dropped += before > live ? before - live : 0;
+    claimed = live;
+    last_live = live;
+    return GNS_OK;
+}
+
+void FlowDict::free_all() {
+    dfree(D.rec); dfree(dctl); dfree(stats_bak);
+    dsc.free_all();
+}
+
+int stats_save(unsigned long long *bak, const unsigned long long *stats, hipStream_t s) {
+    GNS_HIP(hipMemcpyAsync(bak, stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    return GNS_OK;
+}
+
+int stats_undo(unsigned long long *stats, const unsigned long long *bak, bool clear_full, hipStream_t s) {
+    GNS_HIP(hipMemcpyAsync(stats, bak, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (clear_full) GNS_HIP(hipMemsetAsync(stats + 3, 0, sizeof(unsigned long long), s));
+    return GNS_OK;
+}
+
+int DictRecovery::batch(const InputDesc &d, uint64_t m, bool fresh) const {
+    if (m == 0) return GNS_OK;
+    if (fd.full) {
+        set_error("flow dictionary full (%llu slots, %llu live flows)", (unsigned long long)fd.dict_slots,
+                  (unsigned long long)fd.last_live);
+        return GNS_E_FULL;
+    }
+    if (fd.claimed >= fd.max_flows) {  // proactive: keep the load <= ~1/2
+        GNS_TRY(reclaim(0));
+        fresh = true;
+    }
+    for (;;) {
+        GNS_TRY(stats_save(fd.stats_bak, stats, stream));
+        const int rc = run(d, m);
+        // (full: a piece of a split made by run itself has already failed for good)
+        if (rc != GNS_E_FULL || fd.full) return rc;
+        // not applied: undo its counters, drop its claims and the dead flows
+        GNS_TRY(stats_undo(stats, fd.stats_bak, true, stream));
+        fd.n_retry++;
+        if (!fresh) {  // the flows that died since the last rebuild may be room enough
+            GNS_TRY(reclaim(0));
+            fresh = true;
+            continue;
+        }
+        if (m > chunk) {  // split: each half meets a fresh dictionary
+            GNS_TRY(reclaim(0));
+            break;
+        }
+        if (fd.dict_slots >= kDictMaxSlots) {  // cannot happen below ~ 3/4 * 2^30 live flows
+            GNS_TRY(reclaim(0));
+            fd.full = true;
+            const unsigned long long one = 1;
+            GNS_HIP(hipMemcpy(stats + 3, &one, sizeof(one), hipMemcpyHostToDevice));
+            set_error("flow dictionary full: %llu live flows plus one %s exceed %llu slots",
+                      (unsigned long long)fd.last_live, piece, (unsigned long long)fd.dict_slots);
+            return GNS_E_FULL;
+        }
+        GNS_TRY(reclaim(fd.dict_slots * 2));  // grow, then re-run the piece
+    }
+    const uint64_t h = ((m / 2 + chunk - 1) / chunk) * chunk;
+    GNS_TRY(batch(d, h, true));
+    return batch(advance(d, h), m - h, false);
 }
 
 uint32_t layout_bytes(const gns_layout &l) {
@@ -166,13 +322,7 @@ extern "C" int gns_device_alloc(uint64_t bytes, int device, void **out) {
     if (!out) { gns::set_error("null argument"); return GNS_E_ARG; }
     *out = nullptr;
     (void)hipGetLastError();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        gns::set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (device < 0 || device >= ndev) { gns::set_error("device %d out of range", device); return GNS_E_ARG; }
+    GNS_TRY(gns::check_device(device));
     if (hipSetDevice(device) != hipSuccess) { gns::set_error("hipSetDevice(%d) failed", device); return GNS_E_HIP; }
     return gns::dalloc(out, bytes);
 }

@@ -1,6 +1,7 @@
-// gns_common.hpp -- host-side plumbing shared by the Count-Min and SuperSpread
-// engines: error reporting, device buffers, per-stage HIP-event timing, and
-// staging of host inputs into device memory.
+// gns_common.hpp -- host-side plumbing shared by the engines: error reporting,
+// the device check and set, device buffers, per-stage HIP-event timing, advancing
+// and staging of host inputs into device memory, and the flow dictionary's
+// ownership, reclaim and batch recovery.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -43,6 +45,54 @@ int dalloc_t(T **p, size_t count) {
     return dalloc(reinterpret_cast<void **>(p), count * sizeof(T) + 16);
 }
 void dfree(void *p);
+// Grow-only buffer, to twice the request: heavy-hitter lists grow window by
+// window over a period, and every reallocation (hipFree synchronizes the device)
+// cost more than the whole device-side list build.
+template <typename T>
+int grow_buf(T **p, uint64_t &have, uint64_t need) {
+    if (need <= have && *p) return GNS_OK;
+    dfree(*p);
+    *p = nullptr;
+    have = 0;
+    const uint64_t n = std::max<uint64_t>(2 * need, 1);
+    GNS_TRY(dalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
+    have = n;
+    return GNS_OK;
+}
+
+// A device exists and `device` names one (GNS_E_NODEV / GNS_E_ARG).
+int check_device(int device);
+// Clears a stale error of an earlier runtime call on this thread (e.g. the host
+// framework's: it must not fail this call's launch checks) and sets the device.
+int set_device(int device);
+
+// `in` from record `off` on: every per-record array that is set.
+InputDesc advance(const InputDesc &in, uint64_t off);
+
+// Host batches staged into one grow-only device buffer: each item's bytes are
+// copied on the stream, one after the other at 16-byte boundaries, and *patch is
+// pointed at the copy.  An item without bytes is skipped; one without a source
+// only gets its room (the engine fills it on the stream).
+struct StageItem {
+    const void *src;
+    size_t bytes;
+    const void **patch;
+};
+using StageList = std::vector<StageItem>;
+template <class T>
+void stage_add(StageList &l, const T *src, size_t bytes, const T **patch) {
+    l.push_back({src, bytes, reinterpret_cast<const void **>(patch)});
+}
+// the first m records of host batch d: every per-record array that is set is to
+// be staged (hdr, tuple arrays, keys, keys2, rec16, then sizes) and d pointed at it
+void stage_input(StageList &l, InputDesc &d, uint64_t m);
+struct HostStage {
+    uint8_t *buf = nullptr;
+    size_t cap = 0;
+    static size_t need(const StageList &l);
+    int copy(const StageList &l, hipStream_t s);  // grows the buffer to need(l) first
+    void free_all();
+};
 
 // Flow-key plan from a configured layout (task.go:265-300, :327-338).
 int make_plan(const gns_layout &l, uint32_t key_bytes, KeyPlanN *out);
@@ -129,6 +179,52 @@ int dict_rebuild(DictDev &D, uint64_t &slots, const DictIds *mark, int nmark, co
 // Largest dictionary: flow ids are u32 slots below kDictMarked (0xFFFFFFFE /
 // GNS_ID_NONE are reserved); 2^30 slots keep a 64-byte-record table at 64 GB.
 constexpr uint64_t kDictMaxSlots = 1ull << 30;
+
+// What an engine that recycles flow ids owns of its dictionary (Count-Min,
+// SuperSpread): the table, its limits and the recovery accounting.
+struct FlowDict {
+    DictDev D{};
+    uint64_t dict_slots = 0;
+    uint64_t max_flows = 0;               // proactive reclaim once this many slots are claimed
+    uint64_t claimed = 0;                 // D.ctl[0] as of the last batch
+    bool full = false;                    // live flows + one batch piece exceed the largest table (sticky)
+    uint32_t *dctl = nullptr;             // D.ctl: [0] claimed slots, [1] abort flag
+    DictScratch dsc;                      // rebuild scratch (grow-only)
+    unsigned long long *stats_bak = nullptr;  // [3] counters before the running batch (undone on abort)
+    uint64_t n_reclaim = 0, n_dropped = 0, last_live = 0, n_retry = 0, n_grow = 0;
+    double reclaim_ms = 0.0;
+
+    // claims beyond 3/4 load abort the batch; proactive reclaim at load 1/2
+    void limits();
+    // Rebuild keeping the flows that `ids` name (and remapping them).  The table
+    // doubles while the live flows exceed a quarter of it, and to at least min_slots.
+    int reclaim(DictIds *ids, int n, uint64_t min_slots, hipStream_t s);
+    void free_all();
+};
+
+// Engine counters [0..2] saved before a batch runs and restored when it aborts
+// (clear_full: with the dictionary-full word [3] the abort raised).
+int stats_save(unsigned long long *bak, const unsigned long long *stats, hipStream_t s);
+int stats_undo(unsigned long long *stats, const unsigned long long *bak, bool clear_full, hipStream_t s);
+
+// One device batch (device-resident inputs) with dictionary recovery: a batch
+// whose new flows overflow the dictionary is aborted before it changes the
+// engine's state, its counters are undone and its claims dropped with the dead
+// flows (reclaim); it is re-run as is once, then in halves.  A piece of <= chunk
+// records that does not fit a freshly rebuilt dictionary doubles the table
+// instead, so the engine keeps counting whatever the stream brings: live ids are
+// bounded by the engine's cells, the table by kDictMaxSlots.
+struct DictRecovery {
+    FlowDict &fd;
+    unsigned long long *stats;
+    hipStream_t stream;
+    uint64_t chunk;      // halves are whole chunks
+    const char *piece;   // what the last error message calls a piece that cannot fit
+    std::function<int(const InputDesc &, uint64_t)> run;  // one batch; may itself split through batch()
+    std::function<int(uint64_t)> reclaim;                 // the engine's reclaim (min_slots)
+    // fresh: the dictionary was rebuilt right before this batch
+    int batch(const InputDesc &d, uint64_t m, bool fresh) const;
+};
 
 // gns_frame.cpp: one captured frame -> one 64-byte record for the device
 // parser.  Returns 0 = copied verbatim (device fast-path shape), 1 = decoded

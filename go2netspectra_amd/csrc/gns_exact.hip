@@ -1274,23 +1274,16 @@ struct gns_ex {
     uint32_t *ptotal = nullptr;
     unsigned long long *stats = nullptr;
     uint32_t *h_pin = nullptr;
-    uint8_t *stage = nullptr;
-    size_t stage_bytes = 0;
+    HostStage stage;
     StageTimer timer;
 };
 
 namespace {
 
-int ex_set_dev(gns_ex *ex) {
-    (void)hipGetLastError();  // clear a stale error of an earlier runtime call on this thread
-    GNS_HIP(hipSetDevice(ex->device));
-    return GNS_OK;
-}
-
 void ex_free_all(gns_ex *ex) {
     dfree(ex->D.rec); dfree(ex->f.pkts); dfree(ex->f.bytes); dfree(ex->f.first); dfree(ex->f.last);
     dfree(ex->f.start); dfree(ex->f.end); dfree(ex->pend[0]); dfree(ex->pend[1]);
-    dfree(ex->pcnt[0]); dfree(ex->pcnt[1]); dfree(ex->ptotal); dfree(ex->stats); dfree(ex->stage);
+    dfree(ex->pcnt[0]); dfree(ex->pcnt[1]); dfree(ex->ptotal); dfree(ex->stats); ex->stage.free_all();
     dfree(ex->sk[0]); dfree(ex->sk[1]); dfree(ex->ph); dfree(ex->pgs); dfree(ex->pb);
     dfree(ex->hot_ids); dfree(ex->touch); dfree(ex->hot_tab); dfree(ex->hpart); dfree(ex->hctl); dfree(ex->ccnt);
     dfree(ex->dctl); dfree(ex->stats_bak); ex->dsc.free_all();
@@ -1505,14 +1498,7 @@ int ex_dispatch(gns_ex *ex, const ExIn &x, uint64_t n) {
 // doubles and the batch runs again.
 ExIn ex_advance(const ExIn &x0, uint64_t off) {
     ExIn x = x0;
-    InputDesc &d = x.in;
-    if (d.hdr) d.hdr += off * 16;
-    if (d.src16) d.src16 += off * 16;
-    if (d.dst16) d.dst16 += off * 16;
-    if (d.sport) d.sport += off;
-    if (d.dport) d.dport += off;
-    if (d.proto) d.proto += off;
-    if (d.sizes) d.sizes += off;
+    x.in = advance(x0.in, off);
     if (x.ipver) x.ipver += off;
     x.ts += off;
     return x;
@@ -1527,11 +1513,10 @@ int ex_batch_recover(gns_ex *ex, const ExIn &x, uint64_t m) {
         return GNS_OK;
     }
     for (;;) {
-        GNS_HIP(hipMemcpyAsync(ex->stats_bak, ex->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ex->stream));
+        GNS_TRY(stats_save(ex->stats_bak, ex->stats, ex->stream));
         const int rc = ex_dispatch<KIND>(ex, x, m);
         if (rc != GNS_E_FULL) return rc;
-        GNS_HIP(hipMemcpyAsync(ex->stats, ex->stats_bak, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ex->stream));
-        GNS_HIP(hipMemsetAsync(ex->stats + 3, 0, sizeof(unsigned long long), ex->stream));
+        GNS_TRY(stats_undo(ex->stats, ex->stats_bak, true, ex->stream));
         ex->n_retry++;
         const int g = ex_grow(ex);
         if (g != GNS_OK) {
@@ -1545,50 +1530,20 @@ int ex_batch_recover(gns_ex *ex, const ExIn &x, uint64_t m) {
 
 template <int KIND>
 int ex_insert(gns_ex *ex, const ExIn &x0, uint64_t n, gns_mem where) {
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     for (uint64_t off = 0, m = 0; off < n; off += m) {
         // a batch without designated flows sends every packet through P (the heavy
         // flows serialise in P4's LDS atomics): keep it short, so that designation
         // starts early (as Count-Min's cold start)
         const uint64_t cap = ex->warm ? ex->bmax : std::min<uint64_t>(ex->bmax, std::max<uint64_t>(1ull << 20, ex->bmax / 32));
         m = std::min<uint64_t>(cap, n - off);
-        ExIn x = x0;
-        InputDesc &d = x.in;
-        const InputDesc &in = x0.in;
-        if (where == GNS_MEM_DEVICE) {
-            x = ex_advance(x0, off);
-        } else {
-            const void *src[9] = {in.hdr ? (const void *)(in.hdr + off * 16) : nullptr,
-                                  in.src16 ? (const void *)(in.src16 + off * 16) : nullptr,
-                                  in.dst16 ? (const void *)(in.dst16 + off * 16) : nullptr,
-                                  in.sport ? (const void *)(in.sport + off) : nullptr,
-                                  in.dport ? (const void *)(in.dport + off) : nullptr,
-                                  in.proto ? (const void *)(in.proto + off) : nullptr,
-                                  in.sizes ? (const void *)(in.sizes + off) : nullptr,
-                                  x0.ipver ? (const void *)(x0.ipver + off) : nullptr,
-                                  (const void *)(x0.ts + off)};
-            const size_t bytes[9] = {in.hdr ? m * 64 : 0, in.src16 ? m * 16 : 0, in.dst16 ? m * 16 : 0,
-                                     in.sport ? m * 2 : 0, in.dport ? m * 2 : 0, in.proto ? m : 0,
-                                     in.sizes ? m * 4 : 0, x0.ipver ? m : 0, m * 8};
-            size_t tot = 0;
-            for (int i = 0; i < 9; i++) tot += (bytes[i] + 15) & ~size_t(15);
-            if (ex->stage_bytes < tot) {
-                dfree(ex->stage);
-                ex->stage = nullptr;
-                ex->stage_bytes = 0;
-                GNS_TRY(dalloc(reinterpret_cast<void **>(&ex->stage), tot));
-                ex->stage_bytes = tot;
-            }
-            uint8_t *p = ex->stage;
-            const void **dst[9] = {(const void **)&d.hdr, (const void **)&d.src16, (const void **)&d.dst16,
-                                   (const void **)&d.sport, (const void **)&d.dport, (const void **)&d.proto,
-                                   (const void **)&d.sizes, (const void **)&x.ipver, (const void **)&x.ts};
-            for (int i = 0; i < 9; i++) {
-                if (!bytes[i]) continue;
-                GNS_HIP(hipMemcpyAsync(p, src[i], bytes[i], hipMemcpyHostToDevice, ex->stream));
-                *dst[i] = p;
-                p += (bytes[i] + 15) & ~size_t(15);
-            }
+        ExIn x = ex_advance(x0, off);
+        if (where != GNS_MEM_DEVICE) {  // stage the piece on the device
+            StageList l;
+            stage_input(l, x.in, m);
+            stage_add(l, x.ipver, x.ipver ? m : 0, &x.ipver);
+            stage_add(l, x.ts, m * 8, &x.ts);
+            GNS_TRY(ex->stage.copy(l, ex->stream));
         }
         GNS_TRY(ex_batch_recover<KIND>(ex, x, m));
     }
@@ -1602,18 +1557,12 @@ extern "C" {
 int gns_ex_create(const gns_ex_params *p, gns_ex **out) {
     if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return GNS_E_ARG; }
+    GNS_TRY(check_device(p->device));
     gns_ex *ex = new gns_ex();
     ex->device = p->device;
     int rc = GNS_OK;
     do {
-        if ((rc = ex_set_dev(ex)) != GNS_OK) break;
+        if ((rc = set_device(ex->device)) != GNS_OK) break;
         if (p->key.n_fields == 0) { set_error("exact task needs key_fields"); rc = GNS_E_ARG; break; }
         for (uint32_t i = 0; i < p->key.n_fields; i++)
             if (p->key.fields[i] < GNS_F_SRCIP || p->key.fields[i] > GNS_F_PROTO) {
@@ -1716,7 +1665,7 @@ int gns_ex_insert_headers(gns_ex *ex, const uint8_t *hdr, const uint32_t *wirele
 
 int gns_ex_flush(gns_ex *ex) {
     if (!ex) return GNS_E_ARG;
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     GNS_HIP(hipStreamSynchronize(ex->stream));
     ex->timer.collect();
     return GNS_OK;
@@ -1727,7 +1676,7 @@ static int ex_query_impl(gns_ex *ex, const uint8_t *flows, uint32_t stride, uint
     if (n == 0) return GNS_OK;
     if (stride < ex->K) { set_error("stride < key bytes"); return GNS_E_ARG; }
     if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     uint8_t *dk = nullptr;
     uint64_t *dout = nullptr;
     if (dev) {
@@ -1765,7 +1714,7 @@ int gns_ex_query_device(gns_ex *ex, const uint8_t *flows, uint32_t stride, uint6
 int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_ns, uint64_t *pkts,
                     uint64_t *bytes, uint64_t *n_io) {
     if (!ex || !n_io) { set_error("null argument"); return GNS_E_ARG; }
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     hipStream_t s = ex->stream;
     uint32_t *ids = nullptr, *cnt = nullptr;
     GNS_TRY(dalloc(reinterpret_cast<void **>(&cnt), 16));
@@ -1825,7 +1774,7 @@ int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_
             return GNS_E_ARG;
         }
     if (nf == 0) return GNS_OK;
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     // per filter: the 37 tuple bytes (make_plan's numbering) and which of them are masked;
     // the layout's byte plan carries them to their place in the record's key words
     static const struct { uint32_t base, len; } kSpan[6] = {{0, 0}, {0, 16}, {16, 16}, {32, 2}, {34, 2}, {36, 1}};
@@ -1900,7 +1849,7 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
                          uint64_t *values, uint64_t *n_io) {
     if (!ex || !n_io) { set_error("null argument"); return GNS_E_ARG; }
     if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     hipStream_t s = ex->stream;
     const unsigned grid = (unsigned)std::min<uint64_t>((ex->slots + 255) / 256, 2048);
     uint32_t *dh = nullptr;  // [0..kQBands) band histogram, [kQBands] rows collected
@@ -1963,7 +1912,7 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
 
 int gns_ex_reset(gns_ex *ex) {
     if (!ex) return GNS_E_ARG;
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     GNS_TRY(ex_clear(ex));
     GNS_HIP(hipStreamSynchronize(ex->stream));
     return GNS_OK;
@@ -1971,7 +1920,7 @@ int gns_ex_reset(gns_ex *ex) {
 
 int gns_ex_counters(gns_ex *ex, uint64_t out[8]) {
     if (!ex || !out) return GNS_E_ARG;
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     GNS_HIP(hipStreamSynchronize(ex->stream));
     unsigned long long h[8];
     GNS_HIP(hipMemcpy(h, ex->stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -1998,7 +1947,7 @@ int gns_ex_set_timing(gns_ex *ex, int on) {
 
 int gns_ex_stage_times(gns_ex *ex, double ms[8], uint64_t launches[8], int reset) {
     if (!ex) return GNS_E_ARG;
-    GNS_TRY(ex_set_dev(ex));
+    GNS_TRY(set_device(ex->device));
     ex->timer.collect();
     for (int i = 0; i < 8; i++) {
         if (ms) ms[i] = ex->timer.ms[i];

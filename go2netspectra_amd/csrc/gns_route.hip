@@ -330,13 +330,7 @@ int gns_route_create_keyed(uint32_t nshards, const gns_layout *owner, int device
     for (uint32_t i = 0; i < owner->n_fields; i++)
         for (uint32_t j = 0; j < i; j++)
             if (owner->fields[i] == owner->fields[j]) { set_error("owner key repeats a field"); return GNS_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range", device); return GNS_E_ARG; }
+    GNS_TRY(check_device(device));
     GNS_HIP(hipSetDevice(device));
     gns_route *r = new gns_route();
     r->device = device;

@@ -346,26 +346,18 @@ struct gns_exs {
     uint64_t n_fgrow = 0, n_pgrow = 0;
     double grow_ms = 0.0;
     DictScratch dsc;
-    uint8_t *stage = nullptr;
-    size_t stage_bytes = 0;
+    HostStage stage;
     StageTimer timer;
-    CmScratch *hh = nullptr;
+    HhScratch hh;
 };
 
 namespace {
 
-int exs_set_dev(gns_exs *h) {
-    (void)hipGetLastError();  // clear a stale error of an earlier runtime call on this thread
-    GNS_HIP(hipSetDevice(h->device));
-    return GNS_OK;
-}
-
 void exs_free_all(gns_exs *h) {
     dfree(h->P.rec); dfree(h->F.rec); dfree(h->spread); dfree(h->ident); dfree(h->ctl); dfree(h->ptotal);
-    dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); dfree(h->stage);
+    dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); h->stage.free_all();
     h->dsc.free_all();
-    gns::hh_scratch_free(h->hh);
-    h->hh = nullptr;
+    h->hh.free_all();
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     h->timer.destroy();
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -553,50 +545,16 @@ int exs_batch(gns_exs *h, const InputDesc &d, uint64_t m) {
     }
 }
 
-InputDesc exs_advance(const InputDesc &in, uint64_t off) {
-    InputDesc d = in;
-    if (d.hdr) d.hdr += off * 16;
-    if (d.src16) d.src16 += off * 16;
-    if (d.dst16) d.dst16 += off * 16;
-    if (d.sport) d.sport += off;
-    if (d.dport) d.dport += off;
-    if (d.proto) d.proto += off;
-    if (d.keys) d.keys += off * d.stride;
-    if (d.keys2) d.keys2 += off * d.stride2;
-    if (d.sizes) d.sizes += off;
-    return d;
-}
-
 template <int KIND>
 int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where) {
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     for (uint64_t off = 0; off < n; off += h->bmax) {
         const uint64_t m = std::min<uint64_t>(h->bmax, n - off);
-        InputDesc d = exs_advance(in, off);
+        InputDesc d = advance(in, off);
         if (where != GNS_MEM_DEVICE) {  // stage the piece on the device
-            const void *src[9] = {d.hdr, d.src16, d.dst16, d.sport, d.dport, d.proto, d.keys, d.keys2, d.sizes};
-            const size_t bytes[9] = {d.hdr ? m * 64 : 0, d.src16 ? m * 16 : 0, d.dst16 ? m * 16 : 0,
-                                     d.sport ? m * 2 : 0, d.dport ? m * 2 : 0, d.proto ? m : 0,
-                                     d.keys ? m * d.stride : 0, d.keys2 ? m * d.stride2 : 0, d.sizes ? m * 4 : 0};
-            size_t tot = 0;
-            for (int i = 0; i < 9; i++) tot += (bytes[i] + 15) & ~size_t(15);
-            if (h->stage_bytes < tot) {
-                dfree(h->stage);
-                h->stage = nullptr;
-                h->stage_bytes = 0;
-                GNS_TRY(dalloc(reinterpret_cast<void **>(&h->stage), tot));
-                h->stage_bytes = tot;
-            }
-            uint8_t *p = h->stage;
-            const void **dst[9] = {(const void **)&d.hdr, (const void **)&d.src16, (const void **)&d.dst16,
-                                   (const void **)&d.sport, (const void **)&d.dport, (const void **)&d.proto,
-                                   (const void **)&d.keys, (const void **)&d.keys2, (const void **)&d.sizes};
-            for (int i = 0; i < 9; i++) {
-                if (!bytes[i]) continue;
-                GNS_HIP(hipMemcpyAsync(p, src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-                *dst[i] = p;
-                p += (bytes[i] + 15) & ~size_t(15);
-            }
+            StageList l;
+            stage_input(l, d, m);
+            GNS_TRY(h->stage.copy(l, h->stream));
         }
         GNS_TRY(exs_batch<KIND>(h, d, m));
     }
@@ -631,19 +589,13 @@ int gns_exs_create(const gns_exs_params *p, gns_exs **out) {
         set_error("max_flows > 2^29 or max_pairs > 2^30");
         return GNS_E_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return GNS_E_ARG; }
+    GNS_TRY(check_device(p->device));
     gns_exs *h = new gns_exs();
     h->device = p->device;
     h->kpf = kpf; h->kpm = kpm; h->Kf = kpf.K; h->Km = kpm.K; h->has_layout = has_layout;
     int rc = GNS_OK;
     do {
-        if ((rc = exs_set_dev(h)) != GNS_OK) break;
+        if ((rc = set_device(h->device)) != GNS_OK) break;
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
             set_error("hipStreamCreate failed"); rc = GNS_E_HIP; break;
         }
@@ -727,7 +679,7 @@ int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirel
 
 int gns_exs_flush(gns_exs *h) {
     if (!h) return GNS_E_ARG;
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     GNS_HIP(hipStreamSynchronize(h->stream));
     h->timer.collect();
     return GNS_OK;
@@ -738,7 +690,7 @@ static int exs_query_impl(gns_exs *h, const uint8_t *flows, uint32_t stride, uin
     if (n == 0) return GNS_OK;
     if (stride < h->Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
     if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     uint8_t *dk = nullptr;
     uint64_t *dout = nullptr;
     if (dev) {
@@ -777,9 +729,8 @@ int gns_exs_query_device(gns_exs *h, const uint8_t *flows, uint32_t stride, uint
 // slot.  A list longer than the caller's buffers is reported and not written.
 int gns_exs_heavy_hitters(gns_exs *h, uint32_t threshold, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
     if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     GNS_HIP(hipStreamSynchronize(h->stream));
-    if (!h->hh) h->hh = gns::hh_scratch_new();
     const uint64_t cap = *n_io;
     std::vector<uint8_t> tf(flows ? cap * h->Kf : 0);
     std::vector<uint32_t> tv(spreads ? cap : 0);
@@ -797,7 +748,7 @@ int gns_exs_heavy_hitters(gns_exs *h, uint32_t threshold, uint8_t *flows, uint32
 
 int gns_exs_snapshot(gns_exs *h, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
     if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     hipStream_t s = h->stream;
     GNS_HIP(hipStreamSynchronize(s));
     const uint64_t cap = *n_io, nf = h->fclaimed;  // every claimed flow slot holds a seen flow
@@ -832,7 +783,7 @@ int gns_exs_snapshot(gns_exs *h, uint8_t *flows, uint32_t *spreads, uint64_t *n_
 
 int gns_exs_reset(gns_exs *h) {
     if (!h) return GNS_E_ARG;
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     GNS_TRY(exs_clear(h));
     GNS_HIP(hipStreamSynchronize(h->stream));
     return GNS_OK;
@@ -840,7 +791,7 @@ int gns_exs_reset(gns_exs *h) {
 
 int gns_exs_counters(gns_exs *h, uint64_t out[8]) {
     if (!h || !out) return GNS_E_ARG;
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     GNS_HIP(hipStreamSynchronize(h->stream));
     unsigned long long st[8];
     GNS_HIP(hipMemcpy(st, h->stats, sizeof(st), hipMemcpyDeviceToHost));
@@ -864,7 +815,7 @@ int gns_exs_set_timing(gns_exs *h, int on) {
 
 int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset) {
     if (!h) return GNS_E_ARG;
-    GNS_TRY(exs_set_dev(h));
+    GNS_TRY(set_device(h->device));
     h->timer.collect();
     for (int i = 0; i < 8; i++) {
         if (ms) ms[i] = h->timer.ms[i];

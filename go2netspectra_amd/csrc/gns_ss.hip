@@ -22,7 +22,6 @@
 #include <cstring>
 
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "gns_common.hpp"
@@ -1306,7 +1305,7 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_bins(SpArgs a) {
 // ===========================================================================
 using namespace gns;
 
-struct gns_ss {
+struct gns_ss : FlowDict {
     int device = 0;
     hipStream_t stream = nullptr;
     SsGeom g{};
@@ -1315,16 +1314,6 @@ struct gns_ss {
     uint8_t *regs = nullptr;
     double *pbits = nullptr;
     uint32_t *values = nullptr, *keys = nullptr;
-    DictDev D{};
-    uint64_t dict_slots = 0;
-    uint64_t max_flows = 0;  // dictionary capacity (gns_ss_params.max_flows)
-    uint64_t claimed = 0;    // D.ctl[0] as of the last batch
-    bool full = false;       // live flows + one batch piece exceed the dictionary (sticky)
-    uint32_t *dctl = nullptr;
-    DictScratch dsc;
-    unsigned long long *stats_bak = nullptr;
-    uint64_t n_reclaim = 0, n_dropped = 0, last_live = 0, n_retry = 0, n_grow = 0;
-    double reclaim_ms = 0.0;
     uint32_t epoch = 0;
     uint64_t pkt = 0;     // records inserted since create (RNG packet index)
     bool s1_pipe = true;
@@ -1356,29 +1345,21 @@ struct gns_ss {
     uint32_t *sorder = nullptr;  // [nb] P4 schedule
     unsigned long long *stats = nullptr;
     uint32_t *h_pin = nullptr;
-    uint8_t *stage = nullptr;
-    size_t stage_bytes = 0;
+    HostStage stage;
     StageTimer timer;
-    CmScratch *hh = nullptr;     // HeavyHitters' device list buffers (gns_hh.hpp), made on first use
+    HhScratch hh;                // HeavyHitters' device list buffers (gns_hh.hpp), filled on first use
 };
 
 namespace {
 
-int ss_set_dev(gns_ss *ss) {
-    (void)hipGetLastError();  // clear a stale error of an earlier runtime call on this thread
-    GNS_HIP(hipSetDevice(ss->device));
-    return GNS_OK;
-}
-
 void ss_free_all(gns_ss *ss) {
-    dfree(ss->regs); dfree(ss->pbits); dfree(ss->values); dfree(ss->keys); dfree(ss->D.rec);
+    dfree(ss->regs); dfree(ss->pbits); dfree(ss->values); dfree(ss->keys);
     dfree(ss->pcnt[0]); dfree(ss->pcnt[1]);
     dfree(ss->ptotal); dfree(ss->ckey); dfree(ss->ckey_s); dfree(ss->skey); dfree(ss->skey_s);
     dfree(ss->cval); dfree(ss->sval); dfree(ss->shist); dfree(ss->spart); dfree(ss->sorder);
-    dfree(ss->counts); dfree(ss->heads); dfree(ss->hlen); dfree(ss->sprof); dfree(ss->cblk); dfree(ss->stats); dfree(ss->stage);
-    dfree(ss->dctl); dfree(ss->stats_bak); ss->dsc.free_all();
-    gns::hh_scratch_free(ss->hh);
-    ss->hh = nullptr;
+    dfree(ss->counts); dfree(ss->heads); dfree(ss->hlen); dfree(ss->sprof); dfree(ss->cblk); dfree(ss->stats); ss->stage.free_all();
+    ss->FlowDict::free_all();
+    ss->hh.free_all();
     if (ss->h_pin) (void)hipHostFree(ss->h_pin);
     ss->timer.destroy();
     if (ss->stream) (void)hipStreamDestroy(ss->stream);
@@ -1582,42 +1563,9 @@ int ss_run_batch(gns_ss *ss, const InputDesc &in, uint64_t n) {
 // later comparison, query or heavy hitter; every other dictionary record is
 // dropped.  The table doubles while the live flows exceed a quarter of it (live
 // ids are at most d*w), and to at least min_slots.
-void ss_dict_limits(gns_ss *ss) {
-    ss->D.cap = (uint32_t)(ss->dict_slots - ss->dict_slots / 4);
-    ss->max_flows = std::max<uint64_t>(ss->max_flows, ss->dict_slots / 2);
-}
-
 int ss_reclaim(gns_ss *ss, uint64_t min_slots = 0) {
-    const uint64_t cells = (uint64_t)ss->g.d * ss->g.w;
-    DictIds ids{ss->keys, cells};
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t before = ss->claimed, slots0 = ss->dict_slots;
-    uint64_t live = 0;
-    GNS_TRY(dict_rebuild(ss->D, ss->dict_slots, &ids, 1, nullptr, &ids, 1,
-                         std::min(kDictMaxSlots, std::max(ss->dict_slots, min_slots)), ss->stream, ss->dsc, &live,
-                         nullptr, kDictMaxSlots));
-    ss->reclaim_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ss->n_reclaim++;
-    if (ss->dict_slots != slots0) ss->n_grow++;
-    ss_dict_limits(ss);
-    ss->n_dropped += before > live ? before - live : 0;
-    ss->claimed = live;
-    ss->last_live = live;
-    return GNS_OK;
-}
-
-InputDesc ss_advance(const InputDesc &in, uint64_t off) {
-    InputDesc d = in;
-    if (d.hdr) d.hdr += off * 16;
-    if (d.src16) d.src16 += off * 16;
-    if (d.dst16) d.dst16 += off * 16;
-    if (d.sport) d.sport += off;
-    if (d.dport) d.dport += off;
-    if (d.proto) d.proto += off;
-    if (d.keys) d.keys += off * d.stride;
-    if (d.keys2) d.keys2 += off * d.stride2;
-    if (d.sizes) d.sizes += off;
-    return d;
+    DictIds ids{ss->keys, (uint64_t)ss->g.d * ss->g.w};
+    return ss->reclaim(&ids, 1, min_slots, ss->stream);
 }
 
 template <int KIND>
@@ -1632,115 +1580,40 @@ int ss_batch(gns_ss *ss, const InputDesc &d, uint64_t m) {
 }
 
 // A batch whose encodes overflow the dictionary is aborted in S3b, before any
-// state write: undo its counters, reclaim, re-run it once, then in halves (the
-// declared RNG is indexed by record, so the split does not change any draw); a
-// piece of <= kSsChunk records that does not fit a fresh dictionary doubles the
-// table instead, so every stream is counted (super_spread.go:182-235 has no
-// failure mode).
+// state write, and recovered by DictRecovery (the declared RNG is indexed by
+// record, so a split does not change any draw): every stream is counted
+// (super_spread.go:182-235 has no failure mode).
 template <int KIND>
-int ss_batch_recover(gns_ss *ss, const InputDesc &d, uint64_t m, bool fresh) {
-    if (m == 0) return GNS_OK;
-    if (ss->full) {
-        set_error("flow dictionary full (%llu slots, %llu live flows)", (unsigned long long)ss->dict_slots,
-                  (unsigned long long)ss->last_live);
-        return GNS_E_FULL;
-    }
-    if (ss->claimed >= ss->max_flows) {
-        GNS_TRY(ss_reclaim(ss));
-        fresh = true;
-    }
-    for (;;) {
-        GNS_HIP(hipMemcpyAsync(ss->stats_bak, ss->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                               ss->stream));
-        const int rc = ss_batch<KIND>(ss, d, m);
-        if (rc == GNS_E_RANGE && m > ss->sp_cap) {
-            // P4: a cell got more than kSpCap encodes (S3b aborts before any state write).
-            // Undo S1's counters and split: a cell takes at most one encode per record, so
-            // pieces of <= kSpCap records always fit (the RNG is indexed by record, so the
-            // split changes no draw)
-            GNS_HIP(hipMemcpyAsync(ss->stats, ss->stats_bak, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                                   ss->stream));
-            ss->n_retry++;
-            const uint64_t h = m > 2ull * kSsChunk ? ((m / 2 + kSsChunk - 1) / kSsChunk) * kSsChunk : m / 2;
-            GNS_TRY(ss_batch_recover<KIND>(ss, d, h, false));
-            return ss_batch_recover<KIND>(ss, ss_advance(d, h), m - h, false);
-        }
-        if (rc != GNS_E_FULL) return rc;
-        GNS_HIP(hipMemcpyAsync(ss->stats, ss->stats_bak, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                               ss->stream));
-        GNS_HIP(hipMemsetAsync(ss->stats + 3, 0, sizeof(unsigned long long), ss->stream));
+int ss_batch_recover(gns_ss *ss, const InputDesc &d, uint64_t m) {
+    DictRecovery r{*ss, ss->stats, ss->stream, kSsChunk, "batch piece", nullptr,
+                   [ss](uint64_t min_slots) { return ss_reclaim(ss, min_slots); }};
+    r.run = [ss, &r](const InputDesc &pd, uint64_t pm) {
+        const int rc = ss_batch<KIND>(ss, pd, pm);
+        if (rc != GNS_E_RANGE || pm <= ss->sp_cap) return rc;
+        // P4: a cell got more than kSpCap encodes (S3b aborts before any state write).
+        // Undo S1's counters (saved right before this run) and split: a cell takes at
+        // most one encode per record, so pieces of <= kSpCap records always fit
+        GNS_TRY(stats_undo(ss->stats, ss->stats_bak, false, ss->stream));
         ss->n_retry++;
-        if (!fresh) {
-            GNS_TRY(ss_reclaim(ss));
-            fresh = true;
-            continue;
-        }
-        if (m > kSsChunk) {
-            GNS_TRY(ss_reclaim(ss));
-            break;
-        }
-        if (ss->dict_slots >= kDictMaxSlots) {
-            GNS_TRY(ss_reclaim(ss));
-            ss->full = true;
-            const unsigned long long one = 1;
-            GNS_HIP(hipMemcpy(ss->stats + 3, &one, sizeof(one), hipMemcpyHostToDevice));
-            set_error("flow dictionary full: %llu live flows plus one batch piece exceed %llu slots",
-                      (unsigned long long)ss->last_live, (unsigned long long)ss->dict_slots);
-            return GNS_E_FULL;
-        }
-        GNS_TRY(ss_reclaim(ss, ss->dict_slots * 2));
-    }
-    const uint64_t h = ((m / 2 + kSsChunk - 1) / kSsChunk) * kSsChunk;
-    GNS_TRY(ss_batch_recover<KIND>(ss, d, h, true));
-    return ss_batch_recover<KIND>(ss, ss_advance(d, h), m - h, false);
+        const uint64_t h = pm > 2ull * kSsChunk ? ((pm / 2 + kSsChunk - 1) / kSsChunk) * kSsChunk : pm / 2;
+        GNS_TRY(r.batch(pd, h, false));
+        return r.batch(advance(pd, h), pm - h, false);
+    };
+    return r.batch(d, m, false);
 }
 
 template <int KIND>
 int ss_insert(gns_ss *ss, InputDesc in, uint64_t n, gns_mem where) {
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     for (uint64_t off = 0; off < n; off += ss->bmax) {
         const uint64_t m = std::min<uint64_t>(ss->bmax, n - off);
-        InputDesc d = in;
-        if (where == GNS_MEM_DEVICE) {
-            d = ss_advance(in, off);
-        } else {
-            const void *src[8] = {in.hdr ? (const void *)(in.hdr + off * 16) : nullptr,
-                                  in.src16 ? (const void *)(in.src16 + off * 16) : nullptr,
-                                  in.dst16 ? (const void *)(in.dst16 + off * 16) : nullptr,
-                                  in.sport ? (const void *)(in.sport + off) : nullptr,
-                                  in.dport ? (const void *)(in.dport + off) : nullptr,
-                                  in.proto ? (const void *)(in.proto + off) : nullptr,
-                                  in.keys ? (const void *)(in.keys + off * in.stride) : nullptr,
-                                  in.keys2 ? (const void *)(in.keys2 + off * in.stride2) : nullptr};
-            const size_t bytes[8] = {in.hdr ? m * 64 : 0, in.src16 ? m * 16 : 0, in.dst16 ? m * 16 : 0,
-                                     in.sport ? m * 2 : 0, in.dport ? m * 2 : 0, in.proto ? m : 0,
-                                     in.keys ? m * in.stride : 0, in.keys2 ? m * in.stride2 : 0};
-            size_t tot = 0;
-            for (int i = 0; i < 8; i++) tot += (bytes[i] + 15) & ~size_t(15);
-            tot += (m * 4 + 15) & ~size_t(15);
-            if (ss->stage_bytes < tot) {
-                dfree(ss->stage);
-                ss->stage = nullptr;
-                ss->stage_bytes = 0;
-                GNS_TRY(dalloc(reinterpret_cast<void **>(&ss->stage), tot));
-                ss->stage_bytes = tot;
-            }
-            uint8_t *p = ss->stage;
-            const void **dst[8] = {(const void **)&d.hdr, (const void **)&d.src16, (const void **)&d.dst16,
-                                   (const void **)&d.sport, (const void **)&d.dport, (const void **)&d.proto,
-                                   (const void **)&d.keys, (const void **)&d.keys2};
-            for (int i = 0; i < 8; i++) {
-                if (!bytes[i]) continue;
-                GNS_HIP(hipMemcpyAsync(p, src[i], bytes[i], hipMemcpyHostToDevice, ss->stream));
-                *dst[i] = p;
-                p += (bytes[i] + 15) & ~size_t(15);
-            }
-            if (in.sizes) {
-                GNS_HIP(hipMemcpyAsync(p, in.sizes + off, m * 4, hipMemcpyHostToDevice, ss->stream));
-                d.sizes = reinterpret_cast<const uint32_t *>(p);
-            }
+        InputDesc d = advance(in, off);
+        if (where != GNS_MEM_DEVICE) {  // stage the piece on the device
+            StageList l;
+            stage_input(l, d, m);
+            GNS_TRY(ss->stage.copy(l, ss->stream));
         }
-        GNS_TRY(ss_batch_recover<KIND>(ss, d, m, false));
+        GNS_TRY(ss_batch_recover<KIND>(ss, d, m));
     }
     return GNS_OK;
 }
@@ -1752,18 +1625,12 @@ extern "C" {
 int gns_ss_create(const gns_ss_params *p, gns_ss **out) {
     if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available");
-        return GNS_E_NODEV;
-    }
-    if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return GNS_E_ARG; }
+    GNS_TRY(check_device(p->device));
     gns_ss *ss = new gns_ss();
     ss->device = p->device;
     int rc = GNS_OK;
     do {
-        if ((rc = ss_set_dev(ss)) != GNS_OK) break;
+        if ((rc = set_device(ss->device)) != GNS_OK) break;
         SsGeom &g = ss->g;
         // super_spread.go:12-20,129-149 defaults
         g.w = p->width ? p->width : (1u << 20);
@@ -1862,7 +1729,7 @@ int gns_ss_create(const gns_ss_params *p, gns_ss **out) {
         if ((rc = dalloc_t(&ss->D.rec, slots * ss->D.RW)) != GNS_OK) break;
         if ((rc = dalloc_t(&ss->dctl, 4)) != GNS_OK || (rc = dalloc_t(&ss->stats_bak, 3)) != GNS_OK) break;
         ss->D.ctl = ss->dctl;
-        ss_dict_limits(ss);
+        ss->limits();
         ss->bmax = p->batch_packets ? p->batch_packets : (8ull << 20);
         ss->bmax = std::min<uint64_t>(((ss->bmax + kSsChunk - 1) / kSsChunk) * kSsChunk, 1ull << kSsPktBits);
         ss->nblk_max = (uint32_t)(ss->bmax / kSsChunk);
@@ -1930,7 +1797,7 @@ int gns_ss_insert_headers(gns_ss *ss, const uint8_t *hdr, const uint32_t *wirele
 
 int gns_ss_flush(gns_ss *ss) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_HIP(hipStreamSynchronize(ss->stream));
     ss->timer.collect();
     return GNS_OK;
@@ -1941,7 +1808,7 @@ static int ss_query_impl(gns_ss *ss, const uint8_t *flows, uint32_t stride, uint
     if (n == 0) return GNS_OK;
     if (stride < ss->g.Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
     if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     uint8_t *dk = nullptr;
     uint64_t *dout = nullptr;
     if (dev) {
@@ -2008,9 +1875,8 @@ static int ss_ids_to_bytes(gns_ss *ss, const std::vector<uint32_t> &ids, std::ve
 // them unordered).  Nothing but the list leaves the device.
 int gns_ss_heavy_hitters(gns_ss *ss, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
     if (!ss || !n_io) { set_error("null argument"); return GNS_E_ARG; }
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_HIP(hipStreamSynchronize(ss->stream));
-    if (!ss->hh) ss->hh = gns::hh_scratch_new();
     const uint64_t cells = (uint64_t)ss->g.d * ss->g.w;
     return gns::hh_heavy_list(ss->hh, ss->stream, ss->D, ss->dict_slots, ss->g.Kf, cells, ss->values, ss->keys,
                               ss->thr, flows, spreads, n_io);
@@ -2018,7 +1884,7 @@ int gns_ss_heavy_hitters(gns_ss *ss, uint8_t *flows, uint32_t *spreads, uint64_t
 
 int gns_ss_reset(gns_ss *ss) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_TRY(ss_reset_state(ss, false));
     GNS_HIP(hipStreamSynchronize(ss->stream));
     return GNS_OK;
@@ -2026,7 +1892,7 @@ int gns_ss_reset(gns_ss *ss) {
 
 int gns_ss_export_state(gns_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *regs, double *pbits) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_HIP(hipStreamSynchronize(ss->stream));
     const uint64_t cells = (uint64_t)ss->g.d * ss->g.w;
     if (values) GNS_HIP(hipMemcpy(values, ss->values, cells * 4, hipMemcpyDeviceToHost));
@@ -2044,7 +1910,7 @@ int gns_ss_export_state(gns_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *re
 
 int gns_ss_stats(gns_ss *ss, uint64_t stats[4]) {
     if (!ss || !stats) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_HIP(hipStreamSynchronize(ss->stream));
     unsigned long long h[8];
     GNS_HIP(hipMemcpy(h, ss->stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -2054,7 +1920,7 @@ int gns_ss_stats(gns_ss *ss, uint64_t stats[4]) {
 
 int gns_ss_counters(gns_ss *ss, uint64_t out[8]) {
     if (!ss || !out) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     GNS_HIP(hipStreamSynchronize(ss->stream));
     unsigned long long h[8];
     GNS_HIP(hipMemcpy(h, ss->stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -2065,7 +1931,7 @@ int gns_ss_counters(gns_ss *ss, uint64_t out[8]) {
 
 int gns_ss_reclaim(gns_ss *ss) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     return ss_reclaim(ss);
 }
 
@@ -2085,7 +1951,7 @@ int gns_ss_set_timing(gns_ss *ss, int on) {
 
 int gns_ss_stage_times(gns_ss *ss, double ms[8], uint64_t launches[8], int reset) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(ss_set_dev(ss));
+    GNS_TRY(set_device(ss->device));
     ss->timer.collect();
     for (int i = 0; i < 8; i++) {
         if (ms) ms[i] = ss->timer.ms[i];
