@@ -6,6 +6,7 @@ Count-Min / SuperSpread bucket updates, plus the exact per-flow aggregator
 (internal/engine/impl/exact), executed by hand-written gfx950 HIP kernels
 behind the C ABI in include/gns_sketch.h (libgns_sketch.so).
 """
+from . import checkpoint
 from ._lib import GnsError, build, load
 from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_config
 from .exact import (ExactAggregator, ExactTask, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
@@ -23,5 +24,5 @@ __all__ = [
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
-    "make_filter", "merge_summaries",
+    "make_filter", "merge_summaries", "checkpoint",
 ]

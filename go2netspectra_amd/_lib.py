@@ -212,6 +212,9 @@ def load() -> ct.CDLL:
         "gns_exs_set_timing": ([vp, i32], i32), "gns_exs_stage_times": ([vp, vp, vp, i32], i32),
         "gns_ex_aggregate": ([vp, vp, u32, vp], i32),
         "gns_ex_heavy_hitters": ([vp, i32, u64, u64, vp, vp, vp], i32),
+        "gns_cm_import_state": ([vp, vp, vp, vp, vp, vp], i32),
+        "gns_ss_import_state": ([vp, vp, vp, vp, vp, u64, vp], i32),
+        "gns_ex_merge": ([vp, vp, vp, vp, vp, vp, u64, i32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -4387,6 +4387,82 @@ int gns_cm_reset(gns_cm *cm) {
     return GNS_OK;
 }
 
+// One fingerprint array of an exported state -> the ids of its cells, in pieces
+// staged through the handle's first staging buffer: the live cells' keys are
+// found or claimed in the dictionary (dict_resolve_keys), the empty cells get
+// GNS_ID_NONE.  vals = the cells' values, already on the device.  A piece whose
+// new flows overflow the table doubles it (the ids written so far follow the
+// rebuild) and runs again.
+static int cm_import_fps(gns_cm *cm, KeyResolveScratch &sc, const uint8_t *fp, const uint32_t *vals, uint32_t *ids) {
+    const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
+    hipStream_t s = cm->stream;
+    for (uint64_t off = 0; off < cells; off += kResolvePiece) {
+        const uint64_t m = std::min<uint64_t>(kResolvePiece, cells - off);
+        KeyResolve r{};
+        hipEvent_t t0 = nullptr;
+        cm->timer.begin(0, &t0);
+        {
+            StageList l;
+            stage_add(l, fp + off * cm->K, (size_t)m * cm->K, &r.keys);
+            GNS_TRY(cm->stage[0].copy(l, s));
+        }
+        cm->timer.end(0, t0);
+        r.stride = cm->K; r.n = m; r.live = KEYS_CELL; r.vals = vals + off; r.ids = ids + off;
+        r.rc.d = cm->g.d; r.rc.w = cm->g.w; r.rc.pow2 = cm->g.pow2; r.rc.wmask = cm->g.wmask;
+        for (uint32_t i = 0; i < 8; i++) r.rc.seeds[i] = cm->g.seeds[i];
+        r.full_word = cm->stats + 3;
+        for (;;) {
+            const int rc = dict_resolve_keys(cm->D, cm->epoch, r, sc, s, &cm->claimed, &cm->timer, 1);
+            if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+            if (cm->dict_slots >= kDictMaxSlots) return rc;
+            GNS_HIP(hipMemsetAsync(cm->stats + 3, 0, sizeof(unsigned long long), s));
+            cm->n_retry++;
+            DictIds live[2] = {{cm->Fc, cells}, {cm->Fs, cells}};  // every view is stale: none is kept
+            GNS_TRY(cm->reclaim(live, 2, cm->dict_slots * 2, s));
+        }
+    }
+    return GNS_OK;
+}
+
+int gns_cm_import_state(gns_cm *cm, const uint32_t *C, const uint32_t *S, const uint8_t *FPc, const uint8_t *FPs,
+                        const uint64_t *counters) {
+    if (!cm || !C || !S || !FPc || !FPs) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(cm->device));
+    ViewsQuiesced q(cm);
+    cm->period.fetch_add(1);
+    const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
+    hipStream_t s = cm->stream;
+    KeyResolveScratch sc;
+    unsigned long long h[3] = {0, 0, 0};
+    auto run = [&]() -> int {
+        GNS_TRY(cm_reset_state(cm));
+        GNS_HIP(hipMemsetAsync(cm->stats + 9, 0, sizeof(unsigned long long), s));
+        {
+            ScopedStage st(cm->timer, 0);
+            GNS_HIP(hipMemcpyAsync(cm->C, C, cells * 4, hipMemcpyHostToDevice, s));
+            GNS_HIP(hipMemcpyAsync(cm->S, S, cells * 4, hipMemcpyHostToDevice, s));
+        }
+        GNS_TRY(cm_import_fps(cm, sc, FPc, cm->C, cm->Fc));
+        GNS_TRY(cm_import_fps(cm, sc, FPs, cm->S, cm->Fs));
+        if (counters) {
+            for (int i = 0; i < 3; i++) h[i] = counters[i];
+            GNS_HIP(hipMemcpyAsync(cm->stats, h, sizeof(h), hipMemcpyHostToDevice, s));
+        }
+        GNS_HIP(hipStreamSynchronize(s));
+        return GNS_OK;
+    };
+    const int rc = run();
+    if (rc != GNS_OK) {  // as after gns_cm_reset
+        const std::string msg = gns_last_error();
+        (void)hipStreamSynchronize(s);
+        (void)cm_reset_state(cm);
+        (void)hipStreamSynchronize(s);
+        set_error("%s", msg.c_str());
+    }
+    sc.free_all();
+    return rc;
+}
+
 int gns_cm_stats(gns_cm *cm, uint64_t stats[4]) {
     if (!cm || !stats) return GNS_E_ARG;
     GNS_TRY(set_device(cm->device));

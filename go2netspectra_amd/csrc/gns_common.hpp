@@ -1,7 +1,7 @@
 // gns_common.hpp -- host-side plumbing shared by the engines: error reporting,
 // the device check and set, device buffers, per-stage HIP-event timing, advancing
 // and staging of host inputs into device memory, and the flow dictionary's
-// ownership, reclaim and batch recovery.
+// ownership, reclaim and batch recovery, and its key resolution for the imports.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -176,6 +176,57 @@ struct DictScratch {
 int dict_rebuild(DictDev &D, uint64_t &slots, const DictIds *mark, int nmark, const unsigned long long *keep_nz,
                  DictIds *remap_arrays, int nremap, uint64_t new_slots, hipStream_t s, DictScratch &sc,
                  uint64_t *live_out, uint32_t **old_rec_out, uint64_t grow_max = 0);
+// Keys -> flow ids, claiming the absent ones (gns_dict.hip): the write side of
+// the state interface (gns_cm_import_state, gns_ss_import_state, gns_ex_merge)
+// names flows by key bytes, as the exports do.  ids[i] = the slot of key i, or
+// GNS_ID_NONE for a key that is not live.  The same key may occur any number of
+// times.  The claim protocol is the ingest kernels' (gns_keys.cuh): a key whose
+// slot was claimed in this launch is parked in its block's list and re-probed by
+// the next launch, whose kernel boundary has published the key bytes; nothing is
+// handed from one workgroup to another inside a launch.  The first three rounds
+// are queued without a host round trip; from then on the host reads the parked
+// total before each further round.
+enum KeyLive {
+    KEYS_ALL = 0,    // every key is live
+    KEYS_CELL = 1,   // vals = u32[n]: live when a key byte or the value is nonzero (an exported sketch cell)
+    KEYS_VAL64 = 2,  // vals = u64[n]: live when the value is nonzero (an exact-table row with packets)
+};
+// Count-Min records cache the key's row buckets in words 12.. (dict_record_words_cm); the
+// claimer writes them with the key.  d == 0: no cache.
+struct RowCache {
+    uint32_t d = 0, w = 0, pow2 = 0, wmask = 0;
+    uint32_t seeds[8] = {};
+};
+constexpr uint32_t kResolveChunk = 4096;      // keys per block (one parked list each)
+constexpr uint64_t kResolvePiece = 1u << 20;  // most keys per call: the scratch is bounded by it
+struct KeyResolveScratch {
+    uint64_t *pend[2] = {nullptr, nullptr};  // [kResolvePiece] parked lists, per-block regions of kResolveChunk
+    uint32_t *pcnt[2] = {nullptr, nullptr};  // [blocks] their lengths
+    uint32_t *ptotal = nullptr;              // [2] parked totals of the two lists
+    uint32_t *h_pin = nullptr;               // pinned host mirror of the words a round's check reads
+    int reserve();
+    void free_all();
+};
+struct KeyResolve {
+    const uint8_t *keys;  // device, n * stride bytes
+    uint32_t stride;
+    uint64_t n;           // <= kResolvePiece
+    int live;             // KeyLive
+    const void *vals;     // device; see KeyLive
+    uint32_t *ids;        // device [n]
+    RowCache rc;
+    unsigned long long *full_word;  // the engine's dictionary-full counter (raised with the abort flag)
+};
+// GNS_E_FULL: the claims crossed D.cap (the abort flag D.ctl[1] and *full_word are
+// raised, ids are incomplete): the caller grows the table, clears *full_word and
+
+// GNS_E_FULL: the claims crossed D.cap (the abort flag D.ctl[1] and *full_word are
+// raised, ids are incomplete): the caller grows the table, clears *full_word and
+// re-runs the call.  *claimed = D.ctl[0]; each round is timed as one launch of
+// `stage` when a timer is given.  Synchronizes s.
+int dict_resolve_keys(const DictDev &D, uint32_t &epoch, const KeyResolve &r, KeyResolveScratch &sc, hipStream_t s,
+                      uint64_t *claimed, StageTimer *timer = nullptr, int stage = 0);
+
 // Largest dictionary: flow ids are u32 slots below kDictMarked (0xFFFFFFFE /
 // GNS_ID_NONE are reserved); 2^30 slots keep a 64-byte-record table at 64 GB.
 constexpr uint64_t kDictMaxSlots = 1ull << 30;

@@ -1,4 +1,5 @@
-// gns_dict.hip -- flow-dictionary rebuild: reclaim dead flows, grow the table.
+// gns_dict.hip -- flow-dictionary rebuild: reclaim dead flows, grow the table;
+// and keys -> flow ids for the state imports (dict_resolve_keys, below).
 //
 // The reference sketches are fixed-size: a bucket holds its fingerprint's key
 // bytes (count_min.go:66-81, super_spread.go:163-176), so Go keeps inserting
@@ -94,6 +95,173 @@ __global__ __launch_bounds__(256) void k_dict_remap(uint32_t *ids, uint64_t n, u
             const uint32_t r = remap[id];
             ids[i] = r < kDictMarked ? r : GNS_ID_NONE;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Keys -> flow ids, claiming (dict_resolve_keys, gns_common.hpp)
+// ---------------------------------------------------------------------------
+struct KeyResolveArgs {
+    DictDev D;
+    uint32_t epoch;
+    KeyResolve r;
+    uint32_t aligned;         // keys word-loadable
+    const uint64_t *pend_in;  // later rounds: local index << 32 | slot to resume at
+    const uint32_t *cnt_in;
+    uint64_t *pend_out;
+    uint32_t *cnt_out;
+    uint32_t *total_out;
+};
+
+// One round over block blk's keys [blk * kResolveChunk, ...): all of them (FIRST)
+// or its parked list.  A key found or claimed gets its id; one that meets a slot
+// claimed in this launch is parked again with the slot to resume at.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_keys_resolve(KeyResolveArgs a) {
+    __shared__ uint32_t s_cnt, s_full, s_claim, s_abort;
+    const uint32_t tid = threadIdx.x, blk = blockIdx.x;
+    const uint64_t beg = (uint64_t)blk * kResolveChunk;
+    const uint32_t cnt = FIRST ? (uint32_t)min((uint64_t)kResolveChunk, a.r.n - beg) : a.cnt_in[blk];
+    if (cnt == 0) {  // block-uniform
+        if (tid == 0) a.cnt_out[blk] = 0;
+        return;
+    }
+    if (tid == 0) { s_cnt = 0; s_full = 0; s_claim = 0; s_abort = dict_aborted(a.D); }
+    __syncthreads();
+    if (s_abort) {
+        if (tid == 0) a.cnt_out[blk] = 0;
+        return;
+    }
+    const uint32_t K = a.D.K;
+    for (uint32_t i = tid; i < cnt; i += 256) {
+        uint32_t li = i, slot = 0;
+        if (!FIRST) {
+            const uint64_t v = a.pend_in[beg + i];
+            li = (uint32_t)(v >> 32);
+            slot = (uint32_t)v;
+        }
+        const uint64_t p = beg + li;
+        uint32_t kw[GNS_KWMAX];
+        load_key_bytes<GNS_KWMAX>(a.r.keys + p * a.r.stride, K, a.aligned != 0, kw);
+        if (FIRST) {
+            bool live = true;
+            if (a.r.live == KEYS_CELL) {
+                uint32_t any = static_cast<const uint32_t *>(a.r.vals)[p];
+#pragma unroll
+                for (int j = 0; j < GNS_KWMAX; j++) any |= kw[j];
+                live = any != 0u;
+            } else if (a.r.live == KEYS_VAL64) {
+                live = static_cast<const unsigned long long *>(a.r.vals)[p] != 0ull;
+            }
+            if (!live) {
+                a.r.ids[p] = GNS_ID_NONE;
+                continue;
+            }
+            slot = mm3_n<GNS_KWMAX>(kw, K, a.D.seed) & a.D.mask;
+        }
+        uint32_t out = 0;
+        const int res = dict_find_or_claim(a.D, kw, slot, a.epoch, &out);
+        if (res == DICT_FOUND || res == DICT_CLAIMED) {
+            a.r.ids[p] = out;
+            if (res == DICT_CLAIMED) {
+                atomicAdd(&s_claim, 1u);
+                if (a.D.bw && a.r.rc.d) {  // the bucket cache, published with the key
+                    uint32_t mk[GNS_KWMAX];
+                    mm3_premix<GNS_KWMAX>(kw, K, mk);
+                    uint32_t *tp = a.D.rec + (size_t)out * a.D.RW;
+                    const uint32_t nc = a.D.RW >= 32 ? 8u : 4u;
+                    for (uint32_t rr = 0; rr < nc && rr < a.r.rc.d; rr++) {
+                        const uint32_t h = mm3_chain<GNS_KWMAX>(mk, K, a.r.rc.seeds[rr]);
+                        tp[12 + rr] = a.r.rc.pow2 ? (h & a.r.rc.wmask) : (h % a.r.rc.w);
+                    }
+                }
+            }
+        } else if (res == DICT_PENDING) {
+            a.pend_out[beg + atomicAdd(&s_cnt, 1u)] = (uint64_t)li << 32 | out;
+        } else {
+            a.r.ids[p] = GNS_ID_NONE;
+            atomicAdd(&s_full, 1u);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.cnt_out[blk] = s_cnt;
+        if (s_cnt) atomicAdd(a.total_out, s_cnt);
+        if (s_full) {  // a probe chain beyond GNS_DICT_MAX_PROBE: the table is to grow
+            atomicExch(&a.D.ctl[1], 1u);
+            atomicAdd(a.r.full_word, (unsigned long long)s_full);
+        }
+        dict_flush_claims(a.D, s_claim, a.r.full_word);
+    }
+}
+
+int KeyResolveScratch::reserve() {
+    if (pend[0]) return GNS_OK;
+    const uint64_t nblk = kResolvePiece / kResolveChunk;
+    int rc = GNS_OK;
+    if ((rc = dalloc_t(&pend[0], kResolvePiece)) || (rc = dalloc_t(&pend[1], kResolvePiece)) ||
+        (rc = dalloc_t(&pcnt[0], nblk)) || (rc = dalloc_t(&pcnt[1], nblk)) || (rc = dalloc_t(&ptotal, 2))) {
+        free_all();
+        return rc;
+    }
+    if (hipHostMalloc(reinterpret_cast<void **>(&h_pin), 32, 0) != hipSuccess) {
+        h_pin = nullptr;
+        free_all();
+        set_error("hipHostMalloc failed");
+        return GNS_E_OOM;
+    }
+    return GNS_OK;
+}
+
+void KeyResolveScratch::free_all() {
+    dfree(pend[0]); dfree(pend[1]); dfree(pcnt[0]); dfree(pcnt[1]); dfree(ptotal);
+    if (h_pin) (void)hipHostFree(h_pin);
+    pend[0] = pend[1] = nullptr;
+    pcnt[0] = pcnt[1] = ptotal = h_pin = nullptr;
+}
+
+int dict_resolve_keys(const DictDev &D, uint32_t &epoch, const KeyResolve &r, KeyResolveScratch &sc, hipStream_t s,
+                      uint64_t *claimed, StageTimer *timer, int stage) {
+    if (r.n == 0) return GNS_OK;
+    if (r.n > kResolvePiece) { set_error("dict_resolve_keys: %llu keys in one call", (unsigned long long)r.n); return GNS_E_ARG; }
+    GNS_TRY(sc.reserve());
+    const uint32_t nblk = (uint32_t)((r.n + kResolveChunk - 1) / kResolveChunk);
+    KeyResolveArgs a{};
+    a.D = D; a.r = r;
+    a.aligned = (r.stride % 4 == 0 && (reinterpret_cast<uintptr_t>(r.keys) & 3) == 0 && r.stride >= ((D.K + 3) & ~3u)) ? 1u : 0u;
+    GNS_HIP(hipMemsetAsync(sc.ptotal, 0, 8, s));
+    GNS_HIP(hipMemsetAsync(D.ctl + 1, 0, 4, s));  // this call's abort flag
+    int cur = 0;
+    for (int round = 0;; round++) {
+        if (round > 2) {  // the parked total, the dictionary-full word, the claims and the abort flag
+            GNS_HIP(hipMemcpyAsync(sc.h_pin, sc.ptotal + cur, 4, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipMemcpyAsync(sc.h_pin + 2, r.full_word, 8, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipMemcpyAsync(sc.h_pin + 4, D.ctl, 8, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipStreamSynchronize(s));
+            if (claimed) *claimed = sc.h_pin[4];
+            if (sc.h_pin[2] | sc.h_pin[3] | sc.h_pin[5]) {
+                set_error("flow dictionary full (%llu slots)", (unsigned long long)D.mask + 1);
+                return GNS_E_FULL;
+            }
+            if (sc.h_pin[0] == 0) return GNS_OK;
+        }
+        if (round > 64) { set_error("dictionary resolve did not converge"); return GNS_E_FULL; }
+        if (++epoch == 0) epoch = 1;
+        a.epoch = epoch;
+        hipEvent_t t0 = nullptr;
+        if (timer) timer->begin(stage, &t0);
+        if (round == 0) {
+            a.pend_out = sc.pend[0]; a.cnt_out = sc.pcnt[0]; a.total_out = sc.ptotal;
+            hipLaunchKernelGGL(k_keys_resolve<true>, dim3(nblk), dim3(256), 0, s, a);
+        } else {
+            GNS_HIP(hipMemsetAsync(sc.ptotal + (cur ^ 1), 0, 4, s));
+            a.pend_in = sc.pend[cur]; a.cnt_in = sc.pcnt[cur];
+            a.pend_out = sc.pend[cur ^ 1]; a.cnt_out = sc.pcnt[cur ^ 1]; a.total_out = sc.ptotal + (cur ^ 1);
+            hipLaunchKernelGGL(k_keys_resolve<false>, dim3(nblk), dim3(256), 0, s, a);
+            cur ^= 1;
+        }
+        if (timer) timer->end(stage, t0);
+        GNS_HIP(hipGetLastError());
     }
 }
 

@@ -1235,6 +1235,33 @@ __global__ __launch_bounds__(256) void k_ex_init(FlowState f, uint64_t slots) {
     f.pkts[s] = 0; f.bytes[s] = 0; f.first[s] = ~0ull; f.last[s] = 0; f.start[s] = 0; f.end[s] = 0;
 }
 
+// gns_ex_merge: row i is one pseudo-record at stream position base + i.  Counts add
+// (u64 wrap); first / last keep the stream-order rule among the rows of one call and
+// against the table (an existing flow's first lies below base), and the rows that
+// hold a flow's first / last position give it their timestamps.
+__global__ __launch_bounds__(256) void k_ex_merge_add(const uint32_t *ids, uint64_t n, const unsigned long long *pkts,
+                                                      const unsigned long long *bytes, unsigned long long base,
+                                                      FlowState f) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id == GNS_ID_NONE) return;  // a row without packets
+    atomicAdd(&f.pkts[id], pkts[i]);
+    atomicAdd(&f.bytes[id], bytes[i]);
+    atomicMin(&f.first[id], base + i);
+    atomicMax(&f.last[id], base + i + 1);
+}
+
+__global__ __launch_bounds__(256) void k_ex_merge_times(const uint32_t *ids, uint64_t n, const long long *start,
+                                                        const long long *end, unsigned long long base, FlowState f) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id == GNS_ID_NONE) return;
+    if (f.first[id] == base + i) f.start[id] = start[i];
+    if (f.last[id] == base + i + 1) f.end[id] = end[i];
+}
+
 }  // namespace gns
 
 using namespace gns;
@@ -1256,6 +1283,7 @@ struct gns_ex {
     FlowState f{};
     uint32_t epoch = 0;
     uint64_t pkt = 0, batches = 0;
+    uint64_t merged = 0;                     // rows gns_ex_merge placed in the stream: positions are pkt + merged
     uint64_t bmax = 0;
     uint32_t nblk_max = 0;
     uint64_t *sk[2] = {nullptr, nullptr};    // X1 block regions of tail words; the same partitioned by bin
@@ -1316,6 +1344,7 @@ template <int KIND, int MODE>
 int ex_run_batch(gns_ex *ex, const ExIn &xin, uint64_t n) {
     if (n == 0) return GNS_OK;
     hipStream_t s = ex->stream;
+    const uint64_t pos = ex->pkt + ex->merged;  // stream position of the batch's first record
     const uint32_t nblk = (uint32_t)((n + kXChunk - 1) / kXChunk);
     ScopedStage total_stage(ex->timer, 5);
     GNS_HIP(hipMemsetAsync(ex->ptotal, 0, 8, s));
@@ -1368,10 +1397,10 @@ int ex_run_batch(gns_ex *ex, const ExIn &xin, uint64_t n) {
         ScopedStage st(ex->timer, 4);
         GNS_HIP(hipMemsetAsync(ex->hctl + 515, 0, 4, s));  // touched flows of this batch
         if (touch)
-            hipLaunchKernelGGL(k_ex_hot_reduce<true>, dim3(kExHot), dim3(256), 0, s, ex->hpart, nblk, ex->hot_ids, ex->pkt,
+            hipLaunchKernelGGL(k_ex_hot_reduce<true>, dim3(kExHot), dim3(256), 0, s, ex->hpart, nblk, ex->hot_ids, pos,
                                ex->f, touch, ex->hctl + 515);
         else
-            hipLaunchKernelGGL(k_ex_hot_reduce<false>, dim3(kExHot), dim3(256), 0, s, ex->hpart, nblk, ex->hot_ids, ex->pkt,
+            hipLaunchKernelGGL(k_ex_hot_reduce<false>, dim3(kExHot), dim3(256), 0, s, ex->hpart, nblk, ex->hot_ids, pos,
                                ex->f, touch, ex->hctl + 515);
         GNS_HIP(hipGetLastError());
     }
@@ -1390,17 +1419,17 @@ int ex_run_batch(gns_ex *ex, const ExIn &xin, uint64_t n) {
         ScopedStage st(ex->timer, 3);
         if (touch)
             hipLaunchKernelGGL(k_ex_pagg<true>, dim3(kPBins), dim3(kAggThreads), 0, s, ex->sk[1], ex->pb, ex->sb, ex->ib,
-                           xin.in.sizes, ex->pkt, ex->f, touch, ex->hctl + 515);
+                           xin.in.sizes, pos, ex->f, touch, ex->hctl + 515);
         else
             hipLaunchKernelGGL(k_ex_pagg<false>, dim3(kPBins), dim3(kAggThreads), 0, s, ex->sk[1], ex->pb, ex->sb, ex->ib,
-                           xin.in.sizes, ex->pkt, ex->f, touch, ex->hctl + 515);
+                           xin.in.sizes, pos, ex->f, touch, ex->hctl + 515);
         GNS_HIP(hipGetLastError());
     }
     {   // timestamps of the touched flows; the next batch's designated flows
         ScopedStage st(ex->timer, 4);
         if (touch) {
             const unsigned sg = (unsigned)std::min<uint64_t>((n + kExHot + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_ex_times_list, dim3(sg), dim3(256), 0, s, ex->f, touch, ex->hctl + 515, ex->slots, ex->pkt,
+            hipLaunchKernelGGL(k_ex_times_list, dim3(sg), dim3(256), 0, s, ex->f, touch, ex->hctl + 515, ex->slots, pos,
                                n, xin.ts);
             GNS_HIP(hipMemsetAsync(ex->hctl, 0, 514 * 4, s));
             GNS_HIP(hipMemsetAsync(ex->hot_ids, 0xFF, kExHot * 4, s));
@@ -1411,7 +1440,7 @@ int ex_run_batch(gns_ex *ex, const ExIn &xin, uint64_t n) {
                                ex->slots, ex->hctl + 512, ex->hctl + 513, ex->hot_ids);
         } else {
             const unsigned sg = (unsigned)((ex->slots + 255) / 256);
-            hipLaunchKernelGGL(k_ex_times, dim3(sg), dim3(256), 0, s, ex->f, ex->slots, ex->pkt, n, xin.ts);
+            hipLaunchKernelGGL(k_ex_times, dim3(sg), dim3(256), 0, s, ex->f, ex->slots, pos, n, xin.ts);
             GNS_HIP(hipMemsetAsync(ex->hctl, 0, 514 * 4, s));
             GNS_HIP(hipMemsetAsync(ex->hot_ids, 0xFF, kExHot * 4, s));
             hipLaunchKernelGGL(k_exh_hist, dim3(std::min<unsigned>(sg, 2048)), dim3(256), 0, s, ex->f.pkts, ex->slots,
@@ -1908,6 +1937,65 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
     dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk); dfree(dv);
     if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
     return GNS_OK;
+}
+
+int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
+                 const uint64_t *pkts, const uint64_t *bytes, uint64_t n, gns_mem where) {
+    if (!ex || (n && (!keys || !start_ns || !end_ns || !pkts || !bytes))) { set_error("null argument"); return GNS_E_ARG; }
+    if (n == 0) return GNS_OK;
+    if (where == GNS_MEM_DEVICE && (((uintptr_t)start_ns | (uintptr_t)end_ns | (uintptr_t)pkts | (uintptr_t)bytes) & 7u)) {
+        set_error("merge: device row arrays not 8-byte aligned");
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(ex->device));
+    hipStream_t s = ex->stream;
+    KeyResolveScratch sc;
+    uint32_t *ids = nullptr;
+    GNS_TRY(dalloc_t(&ids, std::min<uint64_t>(n, kResolvePiece)));
+    auto run = [&]() -> int {
+        for (uint64_t off = 0; off < n; off += kResolvePiece) {
+            const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
+            const uint8_t *dk = keys + off * ex->K;
+            const long long *ds = reinterpret_cast<const long long *>(start_ns) + off;
+            const long long *de = reinterpret_cast<const long long *>(end_ns) + off;
+            const unsigned long long *dp = reinterpret_cast<const unsigned long long *>(pkts) + off;
+            const unsigned long long *db = reinterpret_cast<const unsigned long long *>(bytes) + off;
+            if (where != GNS_MEM_DEVICE) {  // stage the piece on the device
+                StageList l;
+                stage_add(l, dk, (size_t)m * ex->K, &dk);
+                stage_add(l, ds, m * 8, &ds);
+                stage_add(l, de, m * 8, &de);
+                stage_add(l, dp, m * 8, &dp);
+                stage_add(l, db, m * 8, &db);
+                GNS_TRY(ex->stage.copy(l, s));
+            }
+            if (ex->claimed >= ex->slots / 2) GNS_TRY(ex_grow(ex));  // keep the load <= ~1/2
+            KeyResolve r{};
+            r.keys = dk; r.stride = ex->K; r.n = m; r.live = KEYS_VAL64; r.vals = dp; r.ids = ids;
+            r.full_word = ex->stats + 3;
+            for (;;) {  // no state is written before every id of the piece is known
+                const int rc = dict_resolve_keys(ex->D, ex->epoch, r, sc, s, &ex->claimed, &ex->timer, 1);
+                if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+                GNS_HIP(hipMemsetAsync(ex->stats + 3, 0, sizeof(unsigned long long), s));
+                ex->n_retry++;
+                GNS_TRY(ex_grow(ex));  // the flow state follows the table; the piece's claims are dropped
+            }
+            const unsigned long long base = ex->pkt + ex->merged;
+            const dim3 grid((unsigned)((m + 255) / 256));
+            hipLaunchKernelGGL(k_ex_merge_add, grid, dim3(256), 0, s, ids, m, dp, db, base, ex->f);
+            hipLaunchKernelGGL(k_ex_merge_times, grid, dim3(256), 0, s, ids, m, ds, de, base, ex->f);
+            GNS_HIP(hipGetLastError());
+            ex->merged += m;
+        }
+        GNS_TRY(ex_hot_clear(ex));  // the next batch re-picks the designated flows
+        GNS_HIP(hipStreamSynchronize(s));
+        return GNS_OK;
+    };
+    const int rc = run();
+    if (rc != GNS_OK) (void)hipStreamSynchronize(s);
+    dfree(ids);
+    sc.free_all();
+    return rc;
 }
 
 int gns_ex_reset(gns_ex *ex) {

@@ -1298,6 +1298,14 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_bins(SpArgs a) {
     }
 }
 
+// gns_ss_import_state: registers above maxv (they would index past the power tables)
+__global__ __launch_bounds__(256) void k_ss_check_regs(const uint8_t *regs, uint64_t n, uint32_t maxv, uint32_t *bad) {
+    uint32_t c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        c += regs[i] > maxv ? 1u : 0u;
+    if (c) atomicAdd(bad, c);
+}
+
 }  // namespace gns
 
 // ===========================================================================
@@ -1906,6 +1914,81 @@ int gns_ss_export_state(gns_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *re
         if (ss->g.Kf) memcpy(keys, kb.data(), cells * ss->g.Kf);
     }
     return GNS_OK;
+}
+
+// Import.  The registers index the power tables (regs <= maxv), so they are
+// checked on the device -- piece by piece through the staging buffer -- before
+// anything of the handle is written.
+int gns_ss_import_state(gns_ss *ss, const uint32_t *values, const uint8_t *keys, const uint8_t *regs,
+                        const double *pbits, uint64_t records, const uint64_t *counters) {
+    if (!ss || !values || !keys || !regs || !pbits) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(ss->device));
+    hipStream_t s = ss->stream;
+    const uint64_t cells = (uint64_t)ss->g.d * ss->g.w, nreg = cells * ss->g.m;
+    GNS_HIP(hipStreamSynchronize(s));
+    {   // ptotal is free between batches: [0] counts the registers out of range
+        GNS_HIP(hipMemsetAsync(ss->ptotal, 0, 4, s));
+        const uint64_t piece = 16ull << 20;
+        for (uint64_t off = 0; off < nreg; off += piece) {
+            const uint64_t m = std::min(piece, nreg - off);
+            StageList l;
+            const uint8_t *dr = nullptr;
+            stage_add(l, regs + off, (size_t)m, &dr);
+            GNS_TRY(ss->stage.copy(l, s));
+            hipLaunchKernelGGL(k_ss_check_regs, dim3((unsigned)std::min<uint64_t>((m + 255) / 256, 4096)), dim3(256), 0, s,
+                               dr, m, ss->g.maxv, ss->ptotal);
+            GNS_HIP(hipGetLastError());
+        }
+        uint32_t bad = 0;
+        GNS_HIP(hipMemcpyAsync(&bad, ss->ptotal, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        if (bad) {
+            set_error("import: %u registers exceed 2^size - 1 = %u", bad, ss->g.maxv);
+            return GNS_E_ARG;
+        }
+    }
+    KeyResolveScratch sc;
+    unsigned long long h[3] = {0, 0, 0};
+    auto run = [&]() -> int {
+        GNS_TRY(ss_reset_state(ss, false));
+        GNS_HIP(hipMemcpyAsync(ss->values, values, cells * 4, hipMemcpyHostToDevice, s));
+        GNS_HIP(hipMemcpyAsync(ss->regs, regs, nreg, hipMemcpyHostToDevice, s));
+        GNS_HIP(hipMemcpyAsync(ss->pbits, pbits, cells * 8, hipMemcpyHostToDevice, s));  // bit patterns
+        for (uint64_t off = 0; off < cells; off += kResolvePiece) {
+            const uint64_t m = std::min<uint64_t>(kResolvePiece, cells - off);
+            KeyResolve r{};
+            StageList l;
+            stage_add(l, keys + off * ss->g.Kf, (size_t)m * ss->g.Kf, &r.keys);
+            GNS_TRY(ss->stage.copy(l, s));
+            r.stride = ss->g.Kf; r.n = m; r.live = KEYS_CELL; r.vals = ss->values + off; r.ids = ss->keys + off;
+            r.full_word = ss->stats + 3;
+            for (;;) {
+                const int rc = dict_resolve_keys(ss->D, ss->epoch, r, sc, s, &ss->claimed, &ss->timer, 1);
+                if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+                if (ss->dict_slots >= kDictMaxSlots) return rc;
+                GNS_HIP(hipMemsetAsync(ss->stats + 3, 0, sizeof(unsigned long long), s));
+                ss->n_retry++;
+                GNS_TRY(ss_reclaim(ss, ss->dict_slots * 2));
+            }
+        }
+        if (counters) {
+            for (int i = 0; i < 3; i++) h[i] = counters[i];
+            GNS_HIP(hipMemcpyAsync(ss->stats, h, sizeof(h), hipMemcpyHostToDevice, s));
+        }
+        GNS_HIP(hipStreamSynchronize(s));
+        ss->pkt = records;
+        return GNS_OK;
+    };
+    const int rc = run();
+    if (rc != GNS_OK) {  // as after gns_ss_reset
+        const std::string msg = gns_last_error();
+        (void)hipStreamSynchronize(s);
+        (void)ss_reset_state(ss, false);
+        (void)hipStreamSynchronize(s);
+        set_error("%s", msg.c_str());
+    }
+    sc.free_all();
+    return rc;
 }
 
 int gns_ss_stats(gns_ss *ss, uint64_t stats[4]) {

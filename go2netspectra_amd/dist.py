@@ -639,6 +639,17 @@ def assemble_slices(states, ranges, width: int, depth: int):
     return C, S, Fc, Fs
 
 
+def load_global(cm, state) -> None:
+    """The exact global mode's last step: import the global state ``assemble_slices`` /
+    ``allgather_slices`` built (host arrays) into ``cm``, a full-range CountMin of the same
+    geometry, key layout and seeds, which then answers queries and heavy hitters for the whole
+    stream on the device (CountMin.import_state)."""
+    if getattr(cm, "bucket_range", None) is not None:
+        raise ValueError("load_global needs a full-range sketch (bucket_range=None)")
+    C, S, Fc, Fs = state
+    cm.import_state(C, S, Fc, Fs)
+
+
 def allgather_slices(state, rank: int, world: int, width: int, depth: int):
     """All-gather of every rank's slice (RCCL on GPU, gloo on CPU) -> the global state."""
     import torch

@@ -281,6 +281,39 @@ class ExactAggregator:
         m = min(m, n2.value)
         return keys[:m, : self.key_bytes], st[:m], en[:m], pk[:m], by[:m]
 
+    def merge(self, keys, start, end, pkts, bytes) -> None:
+        """gns_ex_merge: add the rows of a snapshot_arrays() (this handle's or another shard's) to
+        the table, each row one pseudo-record at the current end of the stream -- a restore when
+        the table is empty, a union otherwise.  numpy arrays, or device tensors (keys uint8
+        [n, key_bytes], the others int64 holding the 64-bit values)."""
+        arrs = (keys, start, end, pkts, bytes)
+        dev = [_is_dev(a) for a in arrs]
+        if all(dev):
+            n = int(start.shape[0])
+            keys = keys.reshape(n, -1) if n else keys
+            if n and (int(keys.shape[1]) != self.key_bytes or keys.element_size() != 1):
+                raise ValueError(f"merge: keys must be uint8 [n, {self.key_bytes}]")
+            if any(a.element_size() != 8 or int(a.shape[0]) != n for a in arrs[1:]):
+                raise ValueError("merge: start / end / pkts / bytes must be 64-bit [n]")
+            arrs = tuple(a.contiguous() for a in (keys,) + arrs[1:])
+            _lib.device_ready(*arrs)
+            where = _lib.MEM_DEVICE
+        elif any(dev):
+            raise ValueError("mix of host and device arrays")
+        else:
+            st, en = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+            pk, by = np.ascontiguousarray(pkts, np.uint64), np.ascontiguousarray(bytes, np.uint64)
+            n = int(st.shape[0])
+            keys = np.ascontiguousarray(keys, np.uint8).reshape(n, -1) if n else np.zeros((0, self.key_bytes), np.uint8)
+            if n and keys.shape[1] != self.key_bytes:
+                raise ValueError(f"merge: keys must be [n, {self.key_bytes}]")
+            if not (en.shape[0] == pk.shape[0] == by.shape[0] == n):
+                raise ValueError("merge: row arrays differ in length")
+            arrs = (keys, st, en, pk, by)
+            where = _lib.MEM_HOST
+        if n:
+            check(self._L.gns_ex_merge(self._h, *[_ptr(a) for a in arrs], n, where))
+
     def aggregate(self, filters) -> List[Summary]:
         """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
         arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
@@ -423,6 +456,16 @@ class ExactTask:
 
     def flush(self) -> None:
         self.agg.flush()
+
+    def save(self, path) -> None:
+        """The flow table as one checkpoint file (checkpoint.save)."""
+        from . import checkpoint
+        checkpoint.save(self.agg, path)
+
+    def restore(self, path) -> None:
+        """Replace the flow table by a checkpoint's (checkpoint.restore)."""
+        from . import checkpoint
+        checkpoint.restore(self.agg, path)
 
     # --- query.Querier (internal/query/querier.go) on the live table ---
     def aggregate_flows_many(self, requests) -> List[TaskSummary]:

@@ -103,6 +103,23 @@ class Manager:
         for t in self.tasks():
             t.reset()
 
+    def checkpoint(self, dir) -> List[str]:
+        """Every task's state into ``dir``, one file per task name (task.save); returns the paths."""
+        import os
+        os.makedirs(dir, exist_ok=True)
+        paths = []
+        for t in self.tasks():
+            paths.append(os.path.join(dir, t.name() + ".npz"))
+            t.save(paths[-1])
+        return paths
+
+    def restore(self, dir) -> None:
+        """Every task's state from the files ``checkpoint`` wrote into ``dir`` (task.restore):
+        the tasks must be configured as the saved ones were."""
+        import os
+        for t in self.tasks():
+            t.restore(os.path.join(dir, t.name() + ".npz"))
+
     def stop(self) -> Dict[str, object]:
         """Drain (flush every stream) and take the final snapshot (manager.go:196-216)."""
         for t in self.tasks():

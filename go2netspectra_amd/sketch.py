@@ -337,6 +337,22 @@ class CountMin:
                                           Fs.ctypes.data))
         return C, S, Fc[:, : self.key_bytes], Fs[:, : self.key_bytes]
 
+    def import_state(self, C, S, FPc, FPs, counters=None) -> None:
+        """Replace the whole state by the arrays export_state() returns (of a sketch of the
+        same geometry, key width and seeds): gns_cm_import_state.  counters: None, or the new
+        (inserted, dropped, unsupported)."""
+        n = self.depth * self.width
+        C, S = _host(C, np.uint32).reshape(-1), _host(S, np.uint32).reshape(-1)
+        FPc, FPs = _host(FPc, np.uint8).reshape(-1), _host(FPs, np.uint8).reshape(-1)
+        if C.size != n or S.size != n or FPc.size != n * self.key_bytes or FPs.size != n * self.key_bytes:
+            raise ValueError(f"import_state: arrays do not match {self.depth} x {self.width} cells of "
+                             f"{self.key_bytes}-byte keys")
+        cnt = None if counters is None else _host(counters, np.uint64).reshape(-1)
+        if cnt is not None and cnt.size < 3:
+            raise ValueError("import_state: counters needs 3 values")
+        check(self._L.gns_cm_import_state(self._h, C.ctypes.data, S.ctypes.data, FPc.ctypes.data, FPs.ctypes.data,
+                                          None if cnt is None else cnt.ctypes.data))
+
     def stats(self) -> dict:
         s = (ct.c_uint64 * 4)()
         check(self._L.gns_cm_stats(self._h, s))
@@ -403,6 +419,9 @@ class SuperSpread:
         self.threshold, self.m = threshold or 4096, m or 128
         self.flow_bytes, self.elem_bytes = fb, eb
         self.device = device
+        # as given (0 = the reference default): compared by checkpoint.restore
+        self.size, self.base, self.b = size, base, b
+        self.hll_master, self.rng_seed = hll_master, rng_seed
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -504,6 +523,25 @@ class SuperSpread:
         check(self._L.gns_ss_export_state(self._h, values.ctypes.data, keys.ctypes.data, regs.ctypes.data,
                                           pbits.ctypes.data))
         return values, keys[:, : self.flow_bytes], regs, pbits
+
+    def import_state(self, values, keys, regs, pbits, records, counters=None) -> None:
+        """Replace the whole state by the arrays export_state() returns (gns_ss_import_state).
+        records = counters()["records"] of the exporting handle: the position of the declared
+        generator, part of the state.  counters: None, or (inserted, dropped, unsupported)."""
+        n = self.depth * self.width
+        values = _host(values, np.uint32).reshape(-1)
+        keys, regs = _host(keys, np.uint8).reshape(-1), _host(regs, np.uint8).reshape(-1)
+        pbits = np.ascontiguousarray(pbits).reshape(-1)
+        if pbits.dtype != np.float64:
+            pbits = pbits.view(np.float64) if pbits.dtype == np.uint64 else pbits.astype(np.float64)
+        if values.size != n or keys.size != n * self.flow_bytes or regs.size != n * self.m or pbits.size != n:
+            raise ValueError(f"import_state: arrays do not match {self.depth} x {self.width} cells "
+                             f"(flow_bytes {self.flow_bytes}, m {self.m})")
+        cnt = None if counters is None else _host(counters, np.uint64).reshape(-1)
+        if cnt is not None and cnt.size < 3:
+            raise ValueError("import_state: counters needs 3 values")
+        check(self._L.gns_ss_import_state(self._h, values.ctypes.data, keys.ctypes.data, regs.ctypes.data,
+                                          pbits.ctypes.data, int(records), None if cnt is None else cnt.ctypes.data))
 
     def stats(self) -> dict:
         s = (ct.c_uint64 * 4)()

@@ -138,6 +138,16 @@ class SketchTask:
     def flush(self) -> None:
         self.sketch.flush()
 
+    def save(self, path) -> None:
+        """The sketch's whole state as one checkpoint file (checkpoint.save)."""
+        from . import checkpoint
+        checkpoint.save(self.sketch, path)
+
+    def restore(self, path) -> None:
+        """Replace the sketch's state by a checkpoint's (checkpoint.restore)."""
+        from . import checkpoint
+        checkpoint.restore(self.sketch, path)
+
     def alerter_msg(self, rules) -> str:
         """AlerterMsg (task.go:187-243); rules: dicts with task_name/metric/operator/threshold/name."""
         snap = self.snapshot()

@@ -187,6 +187,32 @@ int gns_cm_reset(gns_cm *cm);
 /* Full state for parity: C/S [depth*width], FPc/FPs [depth*width*key_bytes]
  * (any pointer may be NULL). */
 int gns_cm_export_state(gns_cm *cm, uint32_t *C, uint32_t *S, uint8_t *FPc, uint8_t *FPs);
+/* Restore: replace the handle's whole state by the arrays gns_cm_export_state
+ * writes (host pointers, all four required; layout as there).  counters: NULL =
+ * leave gns_cm_counters' [0..2] as they are, else their new values.
+ *   - The call equals gns_cm_reset followed by whatever inserts produced the
+ *     arrays: gns_cm_export_state then returns the same bytes, queries and both
+ *     heavy-hitter lists answer as the exporting handle's did, and every later
+ *     insert leaves the state bit-equal to the sequential reference continued from
+ *     that state.  The arrays must come from a sketch of the same geometry, key
+ *     width and row seeds; the call cannot detect any other.
+ *   - A cell is live when its fingerprint bytes are non-zero or its value is
+ *     non-zero.  C == 0 with a live FPc (count_min.go:145-151) and S == 0 with a
+ *     live FPs (:121-125) are legal states and survive the round trip; a zero
+ *     fingerprint with a zero value is the empty cell.
+ *   - Derived structures: the flow dictionary is rebuilt from the distinct
+ *     fingerprints on the device (bucket cache included; the table grows as for
+ *     ingest), the hot-bucket designation is cleared (the next batch re-picks it;
+ *     results do not depend on it), the error words [3], [4] and [9] are cleared.
+ *   - Snapshot views are quiesced and the period is bumped: a view taken before
+ *     the import answers GNS_E_ARG until refreshed, as after gns_cm_reset.
+ *   - GNS_E_ARG (a null pointer) leaves the handle untouched; any later error
+ *     leaves it as after gns_cm_reset.
+ * With gns_cm_set_timing on, stage 0 times the host-to-device staging and stage 1
+ * the resolve rounds (one launch each).  The exact spread aggregator (gns_exs_*)
+ * has no import: its pair set is not exportable, only per-flow counts are. */
+int gns_cm_import_state(gns_cm *cm, const uint32_t *C, const uint32_t *S, const uint8_t *FPc, const uint8_t *FPs,
+                        const uint64_t *counters /* [3] or NULL */);
 /* stats[0]=packets inserted, [1]=records dropped (not IP), [2]=records outside
  * the fast-parse subset, [3]=distinct flows in the dictionary */
 int gns_cm_stats(gns_cm *cm, uint64_t stats[4]);
@@ -275,6 +301,17 @@ int gns_ss_heavy_hitters(gns_ss *ss, uint8_t *flows, uint32_t *spreads, uint64_t
 int gns_ss_reset(gns_ss *ss);
 /* values[d*w], keys[d*w*flow_bytes], regs[d*w*m] (u8), pbits[d*w] */
 int gns_ss_export_state(gns_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *regs, double *pbits);
+/* Restore from the arrays gns_ss_export_state writes (host pointers, all
+ * required), as gns_cm_import_state.  records = the declared generator's
+ * position, gns_ss_counters' [6] (records since create, dropped ones included):
+ * it is part of the state -- without it a restored sketch draws other uniforms.
+ * counters: NULL or the new [0..2].  pbits is taken as bit patterns.  A cell's key
+ * is live when its bytes or its value are non-zero.  A register above 2^size - 1
+ * is GNS_E_ARG: it would index past the power tables; the check runs on the device
+ * before any state is written, and the handle stays untouched (as for a null
+ * pointer).  Any later error leaves the handle as after gns_ss_reset. */
+int gns_ss_import_state(gns_ss *ss, const uint32_t *values, const uint8_t *keys, const uint8_t *regs,
+                        const double *pbits, uint64_t records, const uint64_t *counters /* [3] or NULL */);
 int gns_ss_stats(gns_ss *ss, uint64_t stats[4]);
 /* out[8]: inserted, dropped, unsupported, dictionary full, HLL candidates
  * (lz above the batch-entry register), HLL encodes, records, device batches */
@@ -459,6 +496,19 @@ int gns_ex_query_device(gns_ex *ex, const uint8_t *flows, uint32_t stride, uint6
  * (stream order), pkts/bytes = PacketCount/ByteCount.  Any pointer may be NULL. */
 int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_ns, uint64_t *pkts,
                     uint64_t *bytes, uint64_t *n_io);
+/* Merge n rows of the form gns_ex_snapshot writes (canonical 16-byte-IP keys;
+ * host or device pointers, device ones 8-byte aligned) into the table.  Each row
+ * is one pseudo-record placed at the current end of the stream, row i after row
+ * i-1, so timestamps follow the stream-order rule: a key not in the table is
+ * created with the row's start and end; an existing key keeps its start and takes
+ * the row's end; pkts and bytes add (u64 wrap).  Rows with pkts == 0 are ignored
+ * (a flow exists iff it has packets).  The same key may occur in several rows.
+ * A restore is a merge into an empty table; the union of two shards is a merge of
+ * one's snapshot into the other.  gns_ex_counters changes only in [4] flows; the
+ * table grows as for ingest; gns_ex_aggregate / gns_ex_heavy_hitters see merged
+ * flows exactly as ingested ones. */
+int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
+                 const uint64_t *pkts, const uint64_t *bytes, uint64_t n, gns_mem where);
 int gns_ex_reset(gns_ex *ex);
 /* out[8]: inserted, dropped, unsupported, dictionary full, flows, records, batches, 0 */
 int gns_ex_counters(gns_ex *ex, uint64_t out[8]);

@@ -392,6 +392,29 @@ func (c *CountMin) Reset() {
 }
 
 // Close releases the device sketch.
+// ImportState replaces the sketch's whole state by arrays laid out as gns_cm_export_state
+// writes them (C, S: depth*width counters; FPc, FPs: depth*width*keyBytes fingerprint
+// bytes) -- a checkpoint taken from a sketch of the same geometry, key layout and seeds.
+// counters: nil, or the new (inserted, dropped, unsupported).  Views taken before the call
+// are stale until refreshed, as after Reset (gns_cm_import_state).
+func (c *CountMin) ImportState(cnt, size []uint32, fpc, fps []byte, counters *[3]uint64) error {
+	n := len(cnt)
+	if n == 0 || len(size) != n || len(fpc) != n*c.keyBytes || len(fps) != n*c.keyBytes || c.keyBytes == 0 {
+		return errors.New("sketchgpu: ImportState arrays do not match each other")
+	}
+	var cp *C.uint64_t
+	if counters != nil {
+		cp = (*C.uint64_t)(unsafe.Pointer(&counters[0]))
+	}
+	err := lastErr(C.gns_cm_import_state(c.h, (*C.uint32_t)(unsafe.Pointer(&cnt[0])),
+		(*C.uint32_t)(unsafe.Pointer(&size[0])), (*C.uint8_t)(unsafe.Pointer(&fpc[0])),
+		(*C.uint8_t)(unsafe.Pointer(&fps[0])), cp))
+	if err == nil {
+		c.err = nil
+	}
+	return err
+}
+
 func (c *CountMin) Close() { C.gns_cm_destroy(c.h) }
 
 var _ statistic.Sketch = (*CountMin)(nil)
@@ -565,6 +588,30 @@ func (s *SuperSpread) Reset() {
 }
 
 // Close releases the device sketch.
+// ImportState replaces the sketch's whole state by arrays laid out as gns_ss_export_state
+// writes them (values, keys, regs, pbits) plus records, the declared generator's position
+// (gns_ss_counters [6]) -- without it a restored sketch draws other uniforms.  counters: nil,
+// or the new (inserted, dropped, unsupported).  A register above 2^size - 1 is rejected
+// before anything is written (gns_ss_import_state).
+func (s *SuperSpread) ImportState(values []uint32, keys, regs []byte, pbits []float64, records uint64,
+	counters *[3]uint64) error {
+	n := len(values)
+	if n == 0 || len(pbits) != n || len(keys) != n*s.flowSize || len(regs) == 0 || len(regs)%n != 0 || s.flowSize == 0 {
+		return errors.New("sketchgpu: ImportState arrays do not match each other")
+	}
+	var cp *C.uint64_t
+	if counters != nil {
+		cp = (*C.uint64_t)(unsafe.Pointer(&counters[0]))
+	}
+	err := lastErr(C.gns_ss_import_state(s.h, (*C.uint32_t)(unsafe.Pointer(&values[0])),
+		(*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint8_t)(unsafe.Pointer(&regs[0])),
+		(*C.double)(unsafe.Pointer(&pbits[0])), C.uint64_t(records), cp))
+	if err == nil {
+		s.err = nil
+	}
+	return err
+}
+
 func (s *SuperSpread) Close() { C.gns_ss_destroy(s.h) }
 
 var _ statistic.Sketch = (*SuperSpread)(nil)
@@ -744,6 +791,24 @@ func (e *Exact) HeavyHitters(metric int, threshold, limit uint64) (keys []byte, 
 		err = fmt.Errorf("sketchgpu: heavy-hitter list changed length between calls (%d, %d)", m, int(n))
 	}
 	return keys[:m*e.keyBytes], values, err
+}
+
+// Merge adds rows laid out as Flows returns them to the table (gns_ex_merge): each row is one
+// pseudo-record at the current end of the stream, so a new key takes the row's start and end,
+// an existing key keeps its start and takes the row's end, and the counts add.  Rows without
+// packets are ignored.  A restore is a Merge into an empty table; the union of two shards is a
+// Merge of one's Flows into the other.
+func (e *Exact) Merge(keys []byte, start, end []int64, pkts, bytes []uint64) error {
+	n := len(pkts)
+	if n == 0 {
+		return nil
+	}
+	if len(keys) != n*e.keyBytes || len(start) != n || len(end) != n || len(bytes) != n {
+		return errors.New("sketchgpu: Merge arrays do not match each other")
+	}
+	return lastErr(C.gns_ex_merge(e.h, (*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.int64_t)(unsafe.Pointer(&start[0])),
+		(*C.int64_t)(unsafe.Pointer(&end[0])), (*C.uint64_t)(unsafe.Pointer(&pkts[0])),
+		(*C.uint64_t)(unsafe.Pointer(&bytes[0])), C.uint64_t(n), C.GNS_MEM_HOST))
 }
 
 // Reset is exact.Task.Reset (task.go:194-210).
