@@ -14,12 +14,16 @@
 //                   same launch (rare after the first batch).
 //   K2 k_scan*    : exclusive scan of the histograms -> stable bin offsets.
 //   K3 k_scatter  : stable partition of 8-byte bucket updates into (row, tile)
-//                   bins (LDS-staged so every bin receives contiguous runs).
+//                   bins (k_scatter_st, rows of at most 512 bins: LDS-staged so
+//                   every bin receives contiguous runs).
 //   K4 k_apply    : persistent, one workgroup per CU taking bins from a work
 //                   counter (largest first); the tile's bucket state lives in
 //                   LDS; updates are applied chunk by chunk in stream order:
 //                   order-free aggregate fast path where provably exact,
 //                   sequential replay for the buckets where it is not.
+//                   Wide rows, whose bins span several tiles (super-bins), take
+//                   k_apply_sparse: the same chunk steps over an LDS hash table
+//                   of the buckets a bin's updates touch.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -52,7 +56,6 @@ constexpr uint32_t kMaxTilesPerRow = 1024;
 // sums of K4 (kApChunk = 2^13 updates) stay under 2^32, so the packed
 // own/foreign 32-bit halves of accS never carry.
 constexpr uint32_t kEntShift = 16;
-constexpr uint32_t kLowMask = (1u << kEntShift) - 1u;
 constexpr uint32_t kSizeEsc = 0xFFFFu;
 constexpr uint32_t kOvfFlag = 0x80000000u;
 constexpr uint32_t kOvfCap = 1u << 20;             // initial overflow table (grows per batch as needed)
@@ -174,19 +177,7 @@ struct ExtractArgs {
     const uint32_t *Fc, *Fs;  // batch-entry fingerprints (hot slots' owners)
     HotSum *hsum;             // [d*kHot][nblk]
     unsigned long long *stats;
-    // compact streams (CM kernels): per (block, K1 wave, row) the wave's
-    // cold / hot row-updates in packet order, code = bucket (cold) or hot slot (hot)
-    // << 12 | packet index within the wave's 4096-packet range; counts [blk][wave][row][2]
-    uint32_t *cstr, *hstr, *scnt;
-    uint32_t hoff;  // hstr - cstr (words)
 };
-
-// compact streams: a K1 wave owns kCsWave consecutive packets of its block
-constexpr uint32_t kCsWaves = 4;                     // K1 waves per block (256 threads)
-constexpr uint32_t kCsWave = kChunk / kCsWaves;      // packets per K1 wave = stream capacity
-constexpr uint32_t kCsBits = 12;                     // packet index bits in a code
-static_assert(kCsWave == (1u << kCsBits), "a code holds a 12-bit packet index");
-constexpr uint32_t kCsNone = 0xFFFFFFFFu;
 
 template <int KIND, int MODE>
 __device__ __forceinline__ int packet_key(const InputDesc &in, uint32_t K, const uint8_t *s_src,
@@ -268,23 +259,15 @@ struct K1Lds {
     unsigned long long *s_os, *s_fs;
 };
 
-// Wave-uniform running lengths of the wave's compact streams (CM kernels), per row:
-// cold count in the low 16 bits, hot count in the high 16 (each <= kCsWave).
-template <int RMAX>
-struct CsRun {
-    uint32_t ch[RMAX];
-    uint32_t sb;  // stream base of row 0 (uniform)
-};
-
 // record quads a K1 probe loads: words 0..15, and 16..19 (rows 4..7 of the bucket cache) for deep sketches
 template <int RMAX>
 constexpr int kProbeQuads = RMAX > 4 ? 5 : 4;
 
-template <int RMAX, bool CM>
+template <int RMAX>
 __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S, uint32_t K, uint32_t d, bool bw,
                                            uint64_t p, uint64_t beg, bool ok, const uint32_t (&kw)[GNS_KWMAX],
                                            uint32_t slot0, const uint4 (&r4)[kProbeQuads<RMAX>], uint32_t sz,
-                                           uint32_t &n_ok, CsRun<RMAX> &cs) {
+                                           uint32_t &n_ok) {
     constexpr int NQ = kProbeQuads<RMAX>;
     uint32_t *s_tab = S.s_tab, *s_hist = S.s_hist, *s_hFc = S.s_hFc, *s_hFs = S.s_hFs, *s_nfc = S.s_nfc;
     uint32_t *s_nfs = S.s_nfs, *s_smax = S.s_smax;
@@ -308,22 +291,13 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
         for (int i = 0; i < GNS_KWMAX; i++)
             if ((uint32_t)i < ((K + 3) >> 2)) eq = eq && (rec[1 + i] == kw[i]);
         first = tag == a.epoch ? 1 : (eq ? 0 : (tag == 0 ? 2 : 3));
-#ifdef GNS_K1_ABL_DICT
-        (void)tag;
-        first = 0;  // timing ablation: every packet "found" at its (in-range) probe slot
-        rec[12] = rec[13] = rec[14] = rec[15] = 0;
-#endif
         if (first == 0) { res = CM_FOUND; out = slot0; }
         else if (first == 1) { res = CM_PENDING; out = slot0; }
     }
     // row buckets: from the record's cache (rows 0..3 of a committed flow, 0..7 in a
     // 32-word record), else hashed
     uint32_t bk[RMAX];
-#ifdef GNS_K1_ABL_DICT
-    const bool cached = false;  // buckets hashed: the ablation's record holds no cache
-#else
     const bool cached = bw && ok && first == 0;
-#endif
     const uint32_t nc = (NQ > 4 && a.D.RW >= 32) ? 8u : 4u;  // cached rows
 #pragma unroll
     for (uint32_t rr = 0; rr < RMAX; rr++) bk[rr] = (rr < nc && cached) ? rec[12 + rr] : 0u;
@@ -397,24 +371,8 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
             const uint32_t b = bk[rr];
             h = hs[rr];
             // bin code for K3: bucket, or 1<<31 | hot slot for a designated bucket
-            if constexpr (!CM) a.idx[(uint64_t)rr * a.n + p] = h >= 0 ? (0x80000000u | (uint32_t)h) : b;
+            a.idx[(uint64_t)rr * a.n + p] = h >= 0 ? (0x80000000u | (uint32_t)h) : b;
             binid = h >= 0 ? a.g.nbins + rr * kHot + (uint32_t)h : rr * a.g.ntiles + (b >> a.g.bin_bits);
-        }
-        if constexpr (CM) {
-            // compact streams: this wave's cold and hot row-rr updates, appended in packet
-            // order (the wave's lanes hold consecutive packets), so K3 reads only the
-            // updates it partitions and no per-packet code array exists
-            // (the hot streams follow the cold ones in one buffer: hstr = cstr + a.hoff)
-            const bool cold = ok && h < 0, hot = ok && h >= 0;
-            const uint64_t mc = __ballot(cold), mh = __ballot(hot);
-            const uint32_t run = cs.ch[rr];
-            const uint32_t pc = __builtin_amdgcn_mbcnt_hi((uint32_t)(mc >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mc, 0u));
-            const uint32_t ph = __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u));
-            const uint32_t pos = cold ? (run & 0xFFFFu) + pc : a.hoff + (run >> 16) + ph;
-            // packet index within the wave's range: the wave's range starts at a multiple of kCsWave
-            const uint32_t code = (cold ? bk[rr] : (uint32_t)h) << kCsBits | ((uint32_t)p & (kCsWave - 1u));
-            if (ok) a.cstr[cs.sb + rr * kCsWave + pos] = code;
-            cs.ch[rr] = run + (uint32_t)__popcll(mc) + ((uint32_t)__popcll(mh) << 16);
         }
         // heavy bins: one LDS add for the wave's majority bin
         const uint32_t b0 = __builtin_amdgcn_readfirstlane(binid);
@@ -470,9 +428,6 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
 //     4.46 vs 4.02 here, 2.36 vs 2.22 at d=4; so did size sums as two 32-bit halves,
 //     3.86 vs 3.55 here and 3.28 vs 2.37 at d=4.  The plain loop
 //     at d=4 with five waves per SIMD (GNS_C2_PIPE=0 GNS_EX_MINW=5): 2.49 vs 2.37)
-#ifndef GNS_K1_V4HASH
-#define GNS_K1_V4HASH 1  // A/B: 0 hashes every wave's 5-tuple key generically
-#endif
 #ifndef GNS_C5_THREADS
 #define GNS_C5_THREADS 512
 #endif
@@ -488,20 +443,15 @@ constexpr bool kC2Pipe = GNS_C2_PIPE != 0;  // the two-stage pipeline for d != 8
 // NT = threads per block: 256 (four blocks per CU) when the block's LDS fits four
 // times in a CU, else 1024 (one block of 16 waves: wide or deep sketches, whose
 // histogram and hot-slot tables take more than a quarter of the LDS).
-// CM: compact streams instead of the per-packet code array (256-thread blocks only);
-// then each wave takes a contiguous quarter of the block's packets, 64 at a time.
-template <int KIND, int MODE, int KB, int DD, int NT, bool CM = false>
+// (Compact per-wave update streams in place of the per-packet code array were measured
+// in round 5 and retired: K3 -0.31 ms, K1 +0.51 ms at the bench geometry.)
+template <int KIND, int MODE, int KB, int DD, int NT>
 __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) void k_extract(ExtractArgs a) {
-    static_assert(!CM || NT == 256, "compact streams: four waves per block");
-    constexpr bool WC = CM;  // (the classic outputs with this loop measured the same: 2.38 vs 2.35 ms)
     extern __shared__ __attribute__((aligned(16))) uint8_t xsm[];
     __shared__ uint32_t s_pend, s_drop, s_unsup, s_full, s_ok, s_claim;
     __shared__ uint8_t s_src[80];
-#ifdef GNS_K1_XCD
-    const uint32_t tid = threadIdx.x, blk = xcd_block(blockIdx.x, gridDim.x);  // A/B
-#else
+    // (an XCD-contiguous block order like K3s's measured slower here: 2.34 -> 2.40 ms, retired)
     const uint32_t tid = threadIdx.x, blk = blockIdx.x;
-#endif
     const uint32_t NS = a.g.d * kHot;
     unsigned long long *s_os = reinterpret_cast<unsigned long long *>(xsm);
     unsigned long long *s_fs = s_os + NS;
@@ -529,16 +479,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
     const bool bw = a.D.bw != 0;
     uint32_t n_ok = 0;
     const K1Lds S{s_tab, s_hist, s_hFc, s_hFs, s_nfc, s_nfs, s_smax, &s_pend, &s_full, &s_claim, s_os, s_fs};
-    // lane's packets: classic p = beg + tid, beg + tid + NT, ...; CM: the wave's range
-    // [wbeg, wend), p = wbeg + lane, + 64, ...  (wave-uniform trip counts either way)
-    constexpr uint32_t STEP = WC ? 64u : (uint32_t)NT;
-    const uint64_t wbeg = WC ? beg + (uint64_t)(tid >> 6) * (kChunk / (NT / 64)) : beg;
-    const uint64_t wend = WC ? min(end, wbeg + kChunk / (NT / 64)) : end;
-    const uint32_t loff = WC ? (tid & 63u) : tid;
-    CsRun<RMAX> cs;
-#pragma unroll
-    for (uint32_t rr = 0; rr < RMAX; rr++) cs.ch[rr] = 0;
-    cs.sb = (blk * kCsWaves + (tid >> 6)) * d * kCsWave;
+    // lane's packets: p = beg + tid, beg + tid + NT, ...  (wave-uniform trip counts)
     if constexpr (KIND == IN_HDR && (DD == 8 ? kC5Pipe : kC2Pipe)) {
         // Two-stage software pipeline over the block's packets: iteration k
         // parses packet k+1 and issues its dictionary probe (and the header
@@ -558,12 +499,12 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
         constexpr int NQ = kProbeQuads<RMAX>;
         auto stage_b = [&](uint64_t q, bool &okq, uint32_t (&kwq)[GNS_KWMAX], uint32_t &slotq, uint4 (&r4q)[NQ],
                            uint32_t &szq) {
-            okq = q < wend;
+            okq = q < end;
             uint32_t cw[16];
 #pragma unroll
             for (int i = 0; i < 4; i++) { cw[4 * i] = hv[i].x; cw[4 * i + 1] = hv[i].y; cw[4 * i + 2] = hv[i].z; cw[4 * i + 3] = hv[i].w; }
             szq = hsz;
-            load_hdr(q + STEP);
+            load_hdr(q + NT);
             if (okq) {
                 uint32_t tw[10];
                 const int st = parse_record_fast(cw, szq, true, tw);
@@ -579,7 +520,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
             // (the address slots' upper 12 bytes): when the whole wave is IPv4 they are
             // hashed as constants, which folds their mixing and chain steps (same slot)
             bool v4w = false;
-            if constexpr (GNS_K1_V4HASH && MODE == PLAN_SLICE0 && KB == 37 && GNS_KWMAX >= 10) {
+            if constexpr (MODE == PLAN_SLICE0 && KB == 37 && GNS_KWMAX >= 10) {
                 const bool wide = okq && (kwq[1] | kwq[2] | kwq[3] | kwq[5] | kwq[6] | kwq[7]) != 0;
                 v4w = __ballot(wide) == 0;  // wave-uniform
             }
@@ -594,29 +535,23 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
                 mm3_premix<GNS_KWMAX>(kwq, K, mk);
                 slotq = mm3_chain<GNS_KWMAX>(mk, K, a.D.seed) & a.D.mask;
             }
-#ifdef GNS_K1_ABL_DICT
-            // TIMING ABLATION ONLY (wrong counters; never a product build, tools/r06_k1abl.sh):
-            // the probe reads one of the table's first 4096 records (256 KB, L2-resident), so
-            // K1 keeps its streams, hashing, histogram and summaries but pays no dictionary miss
-            slotq &= 4095u;
-#endif
             if (okq) {
                 const uint4 *rq = reinterpret_cast<const uint4 *>(a.D.rec + (size_t)slotq * a.D.RW);
 #pragma unroll
                 for (int i = 0; i < NQ; i++) r4q[i] = (4u * i < a.D.RW) ? rq[i] : make_uint4(0, 0, 0, 0);
             }
         };
-        load_hdr(wbeg + loff);
+        load_hdr(beg + tid);
         bool okc;
         uint32_t kwc[GNS_KWMAX], slotc, szc;
         uint4 r4c[NQ];
-        stage_b(wbeg + loff, okc, kwc, slotc, r4c, szc);
-        for (uint64_t p0 = wbeg; p0 < wend; p0 += STEP) {  // wave-uniform trip count
+        stage_b(beg + tid, okc, kwc, slotc, r4c, szc);
+        for (uint64_t p0 = beg; p0 < end; p0 += NT) {  // wave-uniform trip count
             bool okn = false;
             uint32_t kwn[GNS_KWMAX], slotn = 0, szn = 0;
             uint4 r4n[NQ];
-            if (p0 + STEP < wend) stage_b(p0 + STEP + loff, okn, kwn, slotn, r4n, szn);
-            k1_consume<RMAX, CM>(a, S, K, d, bw, p0 + loff, beg, okc, kwc, slotc, r4c, szc, n_ok, cs);
+            if (p0 + NT < end) stage_b(p0 + NT + tid, okn, kwn, slotn, r4n, szn);
+            k1_consume<RMAX>(a, S, K, d, bw, p0 + tid, beg, okc, kwc, slotc, r4c, szc, n_ok);
             okc = okn; slotc = slotn; szc = szn;
 #pragma unroll
             for (int i = 0; i < GNS_KWMAX; i++) kwc[i] = kwn[i];
@@ -624,9 +559,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
             for (int i = 0; i < NQ; i++) r4c[i] = r4n[i];
         }
     } else {
-        for (uint64_t p0 = wbeg; p0 < wend; p0 += STEP) {  // wave-uniform trip count
-            const uint64_t p = p0 + loff;
-            bool ok = p < wend;
+        for (uint64_t p0 = beg; p0 < end; p0 += NT) {  // wave-uniform trip count
+            const uint64_t p = p0 + tid;
+            bool ok = p < end;
             uint32_t kw[GNS_KWMAX];
             if (ok) {
                 const int st = packet_key<KIND, MODE>(a.in, K, s_src, p, kw);
@@ -648,15 +583,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? GNS_EX_MINW : (NT == 512 ? 2 : 1)) 
 #pragma unroll
                 for (int i = 0; i < kProbeQuads<RMAX>; i++) r4[i] = (4u * i < a.D.RW) ? q[i] : make_uint4(0, 0, 0, 0);
             }
-            k1_consume<RMAX, CM>(a, S, K, d, bw, p, beg, ok, kw, slot0, r4, ok ? a.in.sizes[p] : 0u, n_ok, cs);
-        }
-    }
-    if constexpr (CM) {  // the wave's stream lengths
-        if ((tid & 63u) == 0) {
-            uint32_t *sc = a.scnt + ((uint64_t)blk * kCsWaves + (tid >> 6)) * d * 2;
-#pragma unroll
-            for (uint32_t rr = 0; rr < RMAX; rr++)
-                if (rr < d) { sc[rr * 2] = cs.ch[rr] & 0xFFFFu; sc[rr * 2 + 1] = cs.ch[rr] >> 16; }
+            k1_consume<RMAX>(a, S, K, d, bw, p, beg, ok, kw, slot0, r4, ok ? a.in.sizes[p] : 0u, n_ok);
         }
     }
     atomicAdd(&s_ok, n_ok);
@@ -764,7 +691,6 @@ __global__ __launch_bounds__(kExThreads) void k_resolve(ResolveArgs a) {
 // ---------------------------------------------------------------------------
 struct ScatterArgs {
     uint64_t n;
-    uint32_t xcd_map;  // K3s: consecutive K1 blocks to workgroups on one XCD (GNS_K3_XCD=0: off)
     CmGeom g;
     const uint32_t *keyid;
     const uint32_t *idx;
@@ -783,8 +709,6 @@ struct ScatterArgs {
     uint32_t hot_mode;
     const uint32_t *hflag2;
     const uint32_t *hany;
-    // compact streams (k_scatter_cs, k_hot_scatter_cs): K1's per-(block, wave, row) codes
-    const uint32_t *cstr, *hstr, *scnt;
 };
 
 // LDS layout of k_scatter (dynamic): s_cnt[2][kScWaves][LB] (double-buffered), s_goff[d][LB],
@@ -1011,50 +935,51 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(4)))
 constexpr uint32_t kStSub = GNS_ST_SUB;               // packets per sub-pass
 static_assert(kChunk % kStSub == 0, "whole sub-passes per K1 block");
 
-// NT threads, rows of at most BINS bins: <1024, 256> (the bench geometry) and
-// <1024, 512, kStSub, PK> (the wide/deep configs[4]/[5] geometry: 16 waves in one 136 KB
-// block per CU; the former <512, 512>, 8 waves, stays behind GNS_K3_STAGED=u:
-// K3s 3.08 -> 3.04 ms at configs[4], profiles/r05_ab_k3pack.txt).
+// 1024 threads, rows of at most BINS bins: <256> (the bench geometry) and <512, PK> (the
+// wide/deep configs[4]/[5] geometry: 16 waves in one 136 KB block per CU).  Retired after
+// their A/Bs: 512-bin rows with 512 threads (8 waves, plain counters), K3s 3.08 ms against
+// this one's 3.04 at configs[4] (profiles/r05_ab_k3pack.txt); 256-bin rows as two
+// 512-thread blocks per CU with 4096-packet sub-passes, 1.47 ms against 1.26 at the bench
+// geometry (profiles/r05_ab_k3half.txt); the unstaged K3 for narrow rows; and the
+// round-robin block order (below).
 // PK: the (wave, bin) counters as 16-bit halves, bins t and t + BINS/2 in one word (a wave
-// counts at most SUB/kWaves updates of a bin per sub-pass), which is what lets 16 waves'
+// counts at most kStSub/kWaves updates of a bin per sub-pass), which is what lets 16 waves'
 // counters fit
-template <int NT, int BINS, int SUB = (int)kStSub, bool PK = false>
+constexpr int kStThreads = 1024;
+template <int BINS, bool PK>
 struct StLds {
-    static constexpr int kWaves = NT / 64;
+    static constexpr int kWaves = kStThreads / 64;
     static constexpr int kCw = PK ? BINS / 2 : BINS;  // counter words per wave
-    uint64_t stage[SUB];
-    uint16_t sbin[SUB];
+    uint64_t stage[kStSub];
+    uint16_t sbin[kStSub];
     uint32_t cnt[2][kWaves][kCw];
     uint32_t lstart[BINS], gpos[BINS];
-    uint32_t goff[8][BINS];
+    uint32_t goff[8][BINS];  // [row]: gns_cm_create rejects a depth above 8
     uint32_t wsum[BINS / 64];
-    uint32_t dummy[NT];  // rank adds of lanes without an update
+    uint32_t dummy[kStThreads];  // rank adds of lanes without an update
 };
 
-template <int NT, int BINS, int SUB = (int)kStSub, bool PK = false>
-__global__ __launch_bounds__(NT) void k_scatter_st(ScatterArgs a) {
-    static_assert(!PK || (SUB / (NT / 64) < 65536 && BINS % 128 == 0), "16-bit counter halves");
-    constexpr uint32_t kCw = StLds<NT, BINS, SUB, PK>::kCw;
-    static_assert(kChunk % SUB == 0, "whole sub-passes per K1 block");
-    constexpr int kStThreads = NT;
-    constexpr int kStWaves = NT / 64;
-    constexpr int kStItems = (uint32_t)SUB / NT;
+template <int BINS, bool PK>
+__global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
+    static_assert(!PK || (kStSub / (kStThreads / 64) < 65536 && BINS % 128 == 0), "16-bit counter halves");
+    constexpr uint32_t kCw = StLds<BINS, PK>::kCw;
+    constexpr int kStWaves = kStThreads / 64;
+    constexpr int kStItems = kStSub / kStThreads;
     constexpr uint32_t kStBins = BINS;
-    static_assert((uint32_t)SUB / kStWaves == kStItems * 64, "a wave owns kStItems x 64 consecutive packets of a sub-pass");
-    static_assert(BINS <= NT && BINS % 64 == 0, "one thread per bin in the bin scan");
-    __shared__ StLds<NT, BINS, SUB, PK> L;
+    static_assert(kStSub / kStWaves == kStItems * 64, "a wave owns kStItems x 64 consecutive packets of a sub-pass");
+    static_assert(BINS <= kStThreads && BINS % 64 == 0, "one thread per bin in the bin scan");
+    __shared__ StLds<BINS, PK> L;
 #ifdef GNS_K3_PROF
     uint64_t k3t[5] = {0, 0, 0, 0, 0}, k3prev = __builtin_amdgcn_s_memtime();
 #endif
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t blk = blockIdx.x;
     const uint32_t d = a.g.d, nt = a.g.ntiles;
     // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH: observed, not promised),
     // so K1 block b and b + 1 -- whose runs of a bin are adjacent in `entries` and share the
     // partial lines at their boundary -- would be written through two different L2s.  Give each
     // XCD a contiguous range of K1 blocks instead: headline K3s 1.37 -> 1.25 ms, configs[4]
     // 3.42 -> 2.67 ms (profiles/r05_ab_k3xcd.txt).  Only the speed depends on the placement.
-    if (a.xcd_map) blk = xcd_block(blk, gridDim.x);
+    const uint32_t blk = xcd_block(blockIdx.x, gridDim.x);
     const uint32_t tmask = (1u << a.g.bin_bits) - 1u;
     const uint64_t beg = (uint64_t)blk * kChunk;
     const uint64_t end = min(a.n, beg + kChunk);
@@ -1064,7 +989,7 @@ __global__ __launch_bounds__(NT) void k_scatter_st(ScatterArgs a) {
     }
     for (uint32_t i = tid; i < 2 * kStWaves * kCw; i += kStThreads) (&L.cnt[0][0][0])[i] = 0;
     // packet of item j in a sub-pass: wave-contiguous, (j, lane) order inside the wave
-    auto pkt = [&](uint64_t sp, int j) { return sp + (uint64_t)wave * ((uint32_t)SUB / kStWaves) + (uint64_t)j * 64 + lane; };
+    auto pkt = [&](uint64_t sp, int j) { return sp + (uint64_t)wave * (kStSub / kStWaves) + (uint64_t)j * 64 + lane; };
     uint32_t ids[kStItems], szs[kStItems], cds[kStItems];
     uint32_t ncd[kStItems], nids[kStItems], nszs[kStItems];
     auto load_ids = [&](uint64_t sp, uint32_t (&di)[kStItems], uint32_t (&ds)[kStItems]) {
@@ -1087,7 +1012,7 @@ __global__ __launch_bounds__(NT) void k_scatter_st(ScatterArgs a) {
     load_codes(beg, 0, cds);
     uint32_t par = 0;
     __syncthreads();
-    for (uint64_t sp = beg; sp < end; sp += (uint32_t)SUB) {
+    for (uint64_t sp = beg; sp < end; sp += kStSub) {
         for (uint32_t r = 0; r < d; r++) {
             uint32_t (&cnt)[kStWaves][kCw] = L.cnt[par];
             K3_MARK(4);  // loop
@@ -1138,7 +1063,7 @@ __global__ __launch_bounds__(NT) void k_scatter_st(ScatterArgs a) {
             }
             // the next step's codes (and ids / sizes at a sub-pass boundary) load during C and D
             const uint32_t r1 = r + 1 < d ? r + 1 : 0u;
-            const uint64_t sp1 = r + 1 < d ? sp : sp + (uint32_t)SUB;
+            const uint64_t sp1 = r + 1 < d ? sp : sp + kStSub;
             if (sp1 < end) {
                 load_codes(sp1, r1, ncd);
                 if (r1 == 0) load_ids(sp1, nids, nszs);
@@ -1234,252 +1159,6 @@ __global__ __launch_bounds__(NT) void k_scatter_st(ScatterArgs a) {
 #endif
 }
 
-// ---------------------------------------------------------------------------
-// K3c: K3s over K1's compact cold streams.  Per (block, row) the stream is the
-// four K1 waves' cold codes of that row in wave order = packet order, so only
-// the updates that move are read (no per-packet codes, no lanes without an
-// update): sub-passes of kStSub updates, the flow id and size of each gathered
-// from the block's keyid / size words (the K1 block's 64 KB of each stays in
-// L2 across its rows).  Ranks, stage and copy-out as K3s; the output is
-// identical to K3s's.
-// ---------------------------------------------------------------------------
-template <int NT, int BINS>
-__global__ __launch_bounds__(NT) void k_scatter_cs(ScatterArgs a) {
-    constexpr int kStThreads = NT;
-    constexpr int kStWaves = NT / 64;
-    constexpr int kStItems = kStSub / NT;
-    constexpr uint32_t kStBins = BINS;
-    static_assert(kStSub / kStWaves == kStItems * 64, "a wave owns kStItems x 64 consecutive updates of a sub-pass");
-    static_assert(BINS <= NT && BINS % 64 == 0, "one thread per bin in the bin scan");
-    __shared__ StLds<NT, BINS> L;
-    __shared__ uint32_t s_pre[8][kCsWaves + 1];  // per row: the K1 waves' stream starts, then the row total
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t blk = blockIdx.x, d = a.g.d, nt = a.g.ntiles;
-    const uint32_t tmask = (1u << a.g.bin_bits) - 1u;
-    const uint64_t beg = (uint64_t)blk * kChunk;
-    for (uint32_t i = tid; i < d * kStBins; i += kStThreads) {
-        const uint32_t r = i / kStBins, t = i % kStBins;
-        L.goff[r][t] = t < nt ? a.offsets[(uint64_t)blk * a.g.nbins_all + r * nt + t] : 0u;
-    }
-    if (tid < d) {
-        uint32_t run = 0;
-        for (uint32_t w = 0; w < kCsWaves; w++) {
-            s_pre[tid][w] = run;
-            run += a.scnt[(((uint64_t)blk * kCsWaves + w) * d + tid) * 2];
-        }
-        s_pre[tid][kCsWaves] = run;
-    }
-    for (uint32_t i = tid; i < 2 * kStWaves * kStBins; i += kStThreads) (&L.cnt[0][0][0])[i] = 0;
-    __syncthreads();
-    // update j of a sub-pass at stream position x: wave-contiguous, (j, lane) order inside the wave
-    auto spos = [&](uint32_t sp, int j) { return sp + wave * (kStSub / kStWaves) + (uint32_t)j * 64 + lane; };
-    // codes of step (r, sp): bucket << 14 | packet offset in the block (the K1 wave's range
-    // start + the code's index), kCsNone past the row's end
-    auto load_codes = [&](uint32_t r, uint32_t sp, uint32_t (&c)[kStItems], uint32_t (&po)[kStItems]) {
-        const uint32_t p1 = s_pre[r][1], p2 = s_pre[r][2], p3 = s_pre[r][3], tot = s_pre[r][4];
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const uint32_t x = spos(sp, j);
-            c[j] = kCsNone;
-            po[j] = 0;
-            if (x < tot) {
-                const uint32_t w = (x >= p1 ? 1u : 0u) + (x >= p2 ? 1u : 0u) + (x >= p3 ? 1u : 0u);
-                const uint32_t x0 = w == 0 ? 0u : (w == 1 ? p1 : (w == 2 ? p2 : p3));
-                c[j] = a.cstr[(((uint64_t)blk * kCsWaves + w) * d + r) * kCsWave + (x - x0)];
-                po[j] = w * kCsWave;
-            }
-        }
-    };
-    auto gather = [&](const uint32_t (&c)[kStItems], const uint32_t (&po)[kStItems], uint32_t (&di)[kStItems],
-                      uint32_t (&ds)[kStItems]) {
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const uint64_t pp = beg + po[j] + (c[j] & (kCsWave - 1u));
-            di[j] = c[j] != kCsNone ? a.keyid[pp] : GNS_ID_NONE;
-            ds[j] = c[j] != kCsNone ? a.sizes[pp] : 0u;
-        }
-    };
-    // steps: rows in order, sub-passes of kStSub updates in each
-    uint32_t r = 0, sp = 0;
-    while (r < d && s_pre[r][kCsWaves] == 0) r++;
-    uint32_t cds[kStItems], pos[kStItems], ids[kStItems], szs[kStItems];
-    uint32_t ncd[kStItems], npo[kStItems];
-    if (r < d) {
-        load_codes(r, 0, cds, pos);
-        gather(cds, pos, ids, szs);
-    }
-    uint32_t par = 0;
-    while (r < d) {  // block-uniform
-        // the next step
-        uint32_t r1 = r, sp1 = sp + kStSub;
-        if (sp1 >= s_pre[r1][kCsWaves]) {
-            r1++;
-            sp1 = 0;
-            while (r1 < d && s_pre[r1][kCsWaves] == 0) r1++;
-        }
-        uint32_t (&cnt)[kStWaves][kStBins] = L.cnt[par];
-        // phase A: entries and stable ranks within (wave, bin)
-        uint64_t ent[kStItems];
-        uint32_t tb[kStItems];  // bin << 16 | rank, 0xFFFF bin = no update
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const bool valid = cds[j] != kCsNone && ids[j] != GNS_ID_NONE;
-            uint32_t t = 0xFFFFu;
-            uint64_t e = 0;
-            if (valid) {
-                const uint32_t b = cds[j] >> kCsBits;
-                t = b >> a.g.bin_bits;
-                const uint32_t low = b & tmask, sz = szs[j];
-                uint32_t lo = ids[j], sf = sz;
-                if (sz >= kSizeEsc) {
-                    const uint32_t q = atomicAdd(a.ovf_cnt, 1u);
-                    if (q < a.ovf_cap) {
-                        a.ovf[q] = (uint64_t)sz << 32 | ids[j];
-                        lo = kOvfFlag | q;
-                    } else {
-                        atomicAdd(&a.stats[4], 1ull);
-                        lo = kOvfFlag | (a.ovf_cap - 1);
-                    }
-                    sf = kSizeEsc;
-                }
-                e = (uint64_t)((sf << kEntShift) | low) << 32 | lo;
-            }
-            ent[j] = e;
-            tb[j] = t << 16;
-        }
-        {
-            uint32_t rks[kStItems];
-#pragma unroll
-            for (int j = 0; j < kStItems; j++) {
-                const uint32_t t = tb[j] >> 16;
-                uint32_t *ad = t != 0xFFFFu ? &cnt[wave][t] : &L.dummy[tid];
-                rks[j] = atomicAdd(ad, t != 0xFFFFu ? 1u : 0u);
-            }
-#pragma unroll
-            for (int j = 0; j < kStItems; j++) tb[j] |= rks[j];
-        }
-        if (r1 < d) load_codes(r1, sp1, ncd, npo);
-        __syncthreads();
-        // phase C: per bin, prefix over the waves and the bin's total; scan of the totals
-        uint32_t total = 0, incl = 0;
-        if (tid < kStBins) {
-            const uint32_t t = tid;
-            uint32_t run = 0;
-            if (t < nt) {
-#pragma unroll
-                for (int w = 0; w < kStWaves; w++) {
-                    const uint32_t x = cnt[w][t];
-                    cnt[w][t] = run;
-                    run += x;
-                }
-            }
-            total = run;
-            incl = wave_incl_scan(total);
-            if (lane == 63) L.wsum[wave] = incl;
-        }
-        __syncthreads();
-        // the next step's flow ids and sizes (its codes have had phase C to arrive)
-        uint32_t nids[kStItems], nszs[kStItems];
-        if (r1 < d) gather(ncd, npo, nids, nszs);
-        if (tid < kStBins) {
-            uint32_t base = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kStBins / 64; w++) base += w < wave ? L.wsum[w] : 0u;
-            const uint32_t t = tid;
-            L.lstart[t] = base + incl - total;
-            L.gpos[t] = L.goff[r][t];
-            L.goff[r][t] += total;
-        }
-        __syncthreads();
-        // phase D: updates into the bin-ordered stage
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const uint32_t t = tb[j] >> 16;
-            if (t != 0xFFFFu) {
-                const uint32_t q = L.lstart[t] + cnt[wave][t] + (tb[j] & 0xFFFFu);
-                L.stage[q] = ent[j];
-                L.sbin[q] = (uint16_t)t;
-            }
-        }
-        __syncthreads();
-        // phase E: the bins out as contiguous runs; clear this step's counters
-        uint32_t ntot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kStBins / 64; w++) ntot += L.wsum[w];
-        for (uint32_t i = tid; i < ntot; i += kStThreads) {
-            const uint32_t t = L.sbin[i];
-            a.entries[L.gpos[t] + (i - L.lstart[t])] = L.stage[i];
-        }
-        for (uint32_t i = tid; i < kStWaves * kStBins; i += kStThreads) (&cnt[0][0])[i] = 0;
-        par ^= 1u;
-        if (r1 < d) {
-#pragma unroll
-            for (int j = 0; j < kStItems; j++) { cds[j] = ncd[j]; pos[j] = npo[j]; ids[j] = nids[j]; szs[j] = nszs[j]; }
-        }
-        r = r1;
-        sp = sp1;
-    }
-}
-
-// The exact entry path for designated buckets over K1's compact hot streams
-// (k_scatter's hot mode, for the slots k_hot_decide / k_hot_blockcheck flagged):
-// one wave per K1 block walks each row's hot stream in order and writes the
-// flagged slots' updates to their hot bins (ranks by ballot multisplit over the
-// slot).  Rare (cold start, ownership changes); the whole grid exits when no
-// slot is flagged.
-__global__ __launch_bounds__(64) void k_hot_scatter_cs(ScatterArgs a) {
-    __shared__ uint32_t s_base[8 * kHot];
-    if (*a.hany == 0) return;
-    const uint32_t lane = threadIdx.x, blk = blockIdx.x, d = a.g.d;
-    const uint64_t beg = (uint64_t)blk * kChunk;
-    const uint64_t lt = lane ? (~0ull >> (64u - lane)) : 0ull;
-    for (uint32_t i = lane; i < d * kHot; i += 64) s_base[i] = a.offsets[(uint64_t)blk * a.g.nbins_all + a.g.nbins + i];
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t r = 0; r < d; r++) {
-        for (uint32_t w = 0; w < kCsWaves; w++) {
-            const uint64_t sb = (((uint64_t)blk * kCsWaves + w) * d + r) * kCsWave;
-            const uint32_t n = a.scnt[(((uint64_t)blk * kCsWaves + w) * d + r) * 2 + 1];
-            for (uint32_t x0 = 0; x0 < n; x0 += 64) {
-                const uint32_t x = x0 + lane;
-                uint32_t slot = 0, code = 0;
-                bool valid = false;
-                if (x < n) {
-                    code = a.hstr[sb + x];
-                    slot = r * kHot + (code >> kCsBits);
-                    valid = (a.hflag2[slot] & 3u) != 0;
-                }
-                uint64_t peers = __ballot(valid);
-#pragma unroll
-                for (uint32_t bit = 0; bit < kHotBits + 3; bit++) {
-                    const uint64_t m = __ballot(valid && ((slot >> bit) & 1u));
-                    peers &= ((slot >> bit) & 1u) ? m : ~m;
-                }
-                if (valid) {
-                    const uint64_t p = beg + w * kCsWave + (code & (kCsWave - 1u));
-                    const uint32_t id = a.keyid[p], sz = a.sizes[p];
-                    uint32_t lo = id, sf = sz;
-                    if (sz >= kSizeEsc) {
-                        const uint32_t q = atomicAdd(a.ovf_cnt, 1u);
-                        if (q < a.ovf_cap) {
-                            a.ovf[q] = (uint64_t)sz << 32 | id;
-                            lo = kOvfFlag | q;
-                        } else {
-                            atomicAdd(&a.stats[4], 1ull);
-                            lo = kOvfFlag | (a.ovf_cap - 1);
-                        }
-                        sf = kSizeEsc;
-                    }
-                    const uint32_t pos = s_base[slot] + (uint32_t)__popcll(peers & lt);
-                    a.entries[pos] = (uint64_t)((sf << kEntShift) | slot) << 32 | lo;
-                }
-                __builtin_amdgcn_wave_barrier();
-                if (valid && __popcll(peers & lt) == 0) s_base[slot] += (uint32_t)__popcll(peers);
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
-}
-
 // Does a returning LDS add serve the same-address lanes of one wave
 // instruction in lane order?  (K3's RANK 1 relies on it; measured on gfx950:
 // tools/lds_order.hip, 0 of 1.3e10 same-address lane pairs out of order.)
@@ -1547,8 +1226,6 @@ __global__ __launch_bounds__(1024) void k_order(const uint32_t *offsets, uint32_
 struct ApplyArgs {
     unsigned long long *stats;  // [5] replayed updates, [6] chunks, [7] chunks with a replay
     const uint64_t *entries;
-    uint64_t *entries2;         // super-bin sub-partition scratch (sub_bits > 0)
-    const uint16_t *rseg;       // [round][16] tile starts inside each k_subpart round, or null
     const uint32_t *offsets;
     uint32_t nblk, nbins;
     const uint32_t *total;
@@ -1567,9 +1244,6 @@ constexpr uint32_t kM14 = (1u << 14) - 1;
 constexpr uint32_t kAccForce = 28;
 static_assert(kApChunk < (1u << 14), "accN field widths");
 static_assert(kScRound <= 65536, "K3 packs ranks in 16 bits");
-#ifndef GNS_REPLAY_LEAD
-#define GNS_REPLAY_LEAD 1  // 0: one LDS round per same-bucket lane (A/B)
-#endif
 #ifndef GNS_REP_CAP
 #define GNS_REP_CAP 1536
 #endif
@@ -1695,7 +1369,6 @@ __device__ __forceinline__ void replay_group(ApplyLds &L, bool pending, uint32_t
         }
         if (mine) pending = false;
     }
-#if GNS_REPLAY_LEAD
     // the rest: the lowest lane of each bucket's lanes (its leader) takes the bucket's
     // state into registers and applies its peers' updates in lane (= stream) order,
     // fetched with cross-lane reads, then writes the state back once
@@ -1730,36 +1403,6 @@ __device__ __forceinline__ void replay_group(ApplyLds &L, bool pending, uint32_t
         }
     }
     if (leader) { L.sCS[b] = cs; L.sF[b] = f; peer[b] = 0; }
-#else
-    uint32_t *own = reinterpret_cast<uint32_t *>(L.accS);
-    while (__ballot(pending)) {
-        if (pending) atomicMax(&own[b], 64u - lane);
-        const bool win = pending && own[b] == 64u - lane;
-        if (win) {
-            // (bucket b belongs to this wave and one lane wins it per round: the
-            // whole pair is read and written back)
-            uint2 cs = L.sCS[b], f = L.sF[b];
-            if (rf & 2u) {  // size half, count_min.go:99-128
-                uint32_t S = cs.y, F = f.y;
-                if (S == 0) { S = s; F = k; }
-                else if (F == k) S = S + s;
-                else if (s > S) { S = s; F = k; }
-                else S = S - s;
-                cs.y = S; f.y = F;
-            }
-            if (rf & 1u) {  // count half, count_min.go:130-155
-                uint32_t C = cs.x, F = f.x;
-                if (C == 0) { C = 1; F = k; }
-                else if (F == k) C = C + 1;
-                else { C = C - 1; if (C == 0) F = k; }
-                cs.x = C; f.x = F;
-            }
-            L.sCS[b] = cs; L.sF[b] = f;
-            own[b] = 0;
-            pending = false;
-        }
-    }
-#endif
 }
 
 // A tile's bucket state in registers (kTileMax / kApThreads buckets per thread):
@@ -1791,36 +1434,14 @@ __device__ __forceinline__ void tile_none(TilePre &pre) {
     for (uint32_t m = 0; m < kTilePer; m++) { pre.c[m] = 0; pre.fc[m] = 0; pre.s[m] = 0; pre.fs[m] = 0; }
 }
 
-// Where K4 reads a tile's updates: one contiguous range of the entry array, or
-// (super-bins) the tile's run in each k_subpart round, in round order.  at(q, h)
-// returns logical update q; h is the caller's running segment hint.
-struct EntFlat {
-    const uint64_t *p;
-    struct Cur {};
-    __device__ __forceinline__ uint64_t at(uint32_t q, Cur &) const { return p[q]; }
-    __device__ __forceinline__ uint64_t at_any(uint32_t q) const { return p[q]; }
-};
-struct SegLds;
-struct EntSegs {
-    const uint64_t *p;
-    const SegLds *G;       // run r holds logical [spre[r], spre[r+1]) at p + sbase[r] (tables in LDS)
-    uint32_t off, nseg;    // this tile's table: entries off .. off + nseg (spre has nseg + 1)
-    // a wave's current run [lo, hi) at base (wave-uniform; the lanes of a wave ask for
-    // consecutive q, and q only grows along apply_tile's loads)
-    struct Cur { uint32_t r = 0, lo = 0, hi = 0, base = 0; };
-    __device__ __forceinline__ uint64_t at(uint32_t q, Cur &c) const;
-    __device__ __forceinline__ uint64_t at_any(uint32_t q) const;
-};
-
-// Updates [beg, end) (stream order; logical indices of src) of one LDS tile:
+// Updates [beg, end) of the entry array (stream order) of one LDS tile:
 // buckets cbase .. cbase+tn-1.
 // pre holds this tile's state if it was prefetched (pre.cbase == cbase); on
 // return it holds the state of the tile at next_cbase (kNoTile: none), loaded
 // after this tile's stores were issued.
-template <class Src>
-__device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, const Src &ent, uint32_t beg,
-                                           uint32_t end, uint64_t cbase, uint32_t tn, uint32_t col0,
-                                           TilePre &pre, uint64_t next_cbase, uint32_t next_tn) {
+__device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, uint32_t beg, uint32_t end,
+                                           uint64_t cbase, uint32_t tn, uint32_t col0, TilePre &pre,
+                                           uint64_t next_cbase, uint32_t next_tn) {
     uint32_t *accN = L.accN;
     unsigned long long *accS = L.accS;
     uint16_t *s_list = L.s_list;
@@ -1850,11 +1471,10 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, cons
 #endif
     const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     uint64_t e[kApItems], en[kApItems];
-    typename Src::Cur hint{};
 #pragma unroll
     for (int j = 0; j < kApItems; j++) {  // first chunk
         const uint32_t q = beg + j * kApThreads + tid;
-        e[j] = q < end ? ent.at(q, hint) : 0ull;
+        e[j] = q < end ? a.entries[q] : 0ull;
     }
     // engine counters in registers (global atomics inside the loop would be
     // drained by the next chunk's load waits)
@@ -1902,7 +1522,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, cons
 #pragma unroll
         for (int j = 0; j < kApItems; j++) {
             const uint32_t q = cb + kApChunk + j * kApThreads + tid;
-            en[j] = q < end ? ent.at(q, hint) : 0ull;
+            en[j] = q < end ? a.entries[q] : 0ull;
         }
         __syncthreads();
         K4_MARK(0);
@@ -2034,7 +1654,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, cons
                 bool pending = false;
                 uint32_t b = 0, k = 0, s = 0, rf = 0;
                 if (i < nlist) {
-                    const uint64_t ee = i < kRepCap ? L.s_rep[i] : ent.at_any(cb + s_list[i]);
+                    const uint64_t ee = i < kRepCap ? L.s_rep[i] : a.entries[cb + s_list[i]];
                     b = (uint32_t)(ee >> 32) & (kTileMax - 1u);
                     pending = b % kApWaves == wave;
                     if (pending) {
@@ -2049,7 +1669,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, cons
             for (uint32_t g0 = 0; g0 < nlist; g0 += 64) {
                 const uint32_t i = g0 + lane;
                 if (i < nlist) {
-                    const uint64_t ee = i < kRepCap ? L.s_rep[i] : ent.at_any(cb + s_list[i]);
+                    const uint64_t ee = i < kRepCap ? L.s_rep[i] : a.entries[cb + s_list[i]];
                     const uint32_t b = (uint32_t)(ee >> 32) & (kTileMax - 1u);
                     if (b % kApWaves == wave) accN[b] = 0;
                 }
@@ -2092,197 +1712,11 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs &a, ApplyLds &L, cons
 #endif
 }
 
-constexpr uint32_t kSubPairs = kApItems * kApWaves;  // (item, wave) groups of a k_subpart round, in stream order
-
-// Super-bin sub-partition as a launch of its own, one workgroup per super-bin and
-// two per CU (16 KB of LDS instead of K4's 156 KB), so that its barrier- and
-// latency-bound rounds overlap across workgroups instead of running inside K4's
-// one-workgroup-per-CU loop.  One pass: every round of kApChunk updates is
-// grouped by tile in place of the round (stable inside each tile), and the
-// round's tile starts go to rseg; K4 reads a tile as its run in each round, in
-// round order, which is the tile's stream order.  (Round 4 counted every tile of
-// the bin first and wrote each tile contiguously: a second read of every update.)
-// Round r of bin b has index beg/kApChunk + r + b: unique
-// and below total/kApChunk + nbins.
-#ifndef GNS_SEG_ALL
-#define GNS_SEG_ALL 416
-#endif
-constexpr uint32_t kSegAll = GNS_SEG_ALL;  // table entries (8 B each; K4's LDS is nearly full)
-template <int NT>
-__global__ __launch_bounds__(NT, NT == 512 ? 4 : 1) void k_subpart(ApplyArgs a, uint16_t *rseg) {
-    constexpr int kW = NT / 64, kI = (int)kApChunk / NT;  // waves; updates per thread and round
-    static_assert(kW * kI == (int)kSubPairs, "(item, wave) groups of a round");
-    __shared__ uint32_t cnt[2][kSubPairs * 16];
-    __shared__ uint32_t ttot[2][16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t bin = blockIdx.x;  // block-uniform exit below
-    const uint32_t sub_bits = a.g.sub_bits, nsub = 1u << sub_bits, tile_bits = a.g.tile_bits;
-    const uint32_t beg = a.offsets[bin];
-    const uint32_t end = (bin + 1 < a.g.nbins_all) ? a.offsets[bin + 1] : *a.total;
-    if (beg >= end) return;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    // a bin too big for K4's tables goes to the second K4 launch, which exits at once without one
-    if (tid == 0 && (end - beg + kApChunk - 1) / kApChunk + 1 > kSegAll) atomicAdd(a.work + 2, 1u);
-    if (tid < 32) (&ttot[0][0])[tid] = 0;
-    uint64_t e[kI], en[kI];
-#pragma unroll
-    for (int j = 0; j < kI; j++) {
-        const uint32_t q = beg + j * NT + tid;
-        e[j] = q < end ? a.entries[q] : 0ull;
-    }
-    __syncthreads();
-    uint32_t par = 0;
-    for (uint32_t rb = beg; rb < end; rb += kApChunk) {
-        uint32_t *cb = cnt[par], *tt = ttot[par];
-        // the next round's updates load while this round is ranked and stored
-#pragma unroll
-        for (int j = 0; j < kI; j++) {
-            const uint32_t q = rb + kApChunk + j * NT + tid;
-            en[j] = q < end ? a.entries[q] : 0ull;
-        }
-        uint32_t sb[kI];  // tile | rank among the wave's earlier updates of the tile << 8
-#pragma unroll
-        for (int j = 0; j < kI; j++) {
-            const uint32_t q = rb + j * NT + tid;
-            const bool valid = q < end;
-            const uint32_t sub = valid ? (((uint32_t)(e[j] >> 32) & kLowMask) >> tile_bits) : 0xFFu;
-            uint64_t peers = __ballot(valid);
-            for (uint32_t bit = 0; bit < sub_bits; bit++) {
-                const uint64_t m = __ballot(valid && ((sub >> bit) & 1u));
-                peers &= ((sub >> bit) & 1u) ? m : ~m;
-            }
-            const uint32_t before = __popcll(peers & lt_mask);
-            sb[j] = sub | before << 8;
-            // this wave's slots of group (j, wave): zeroed, then the first lane of
-            // each tile's peers writes the count (one wave: LDS ops stay in order)
-            if (lane < 16) cb[(j * kW + wave) * 16 + lane] = 0;
-            if (valid && before == 0) {
-                const uint32_t c = (uint32_t)__popcll(peers);
-                cb[(j * kW + wave) * 16 + sub] = c;
-                atomicAdd(&tt[sub], c);
-            }
-        }
-        __syncthreads();
-        if (wave < nsub) {  // (nsub <= kW) wave t: tile t's start in the round + exclusive scan of its group counts
-            constexpr uint32_t GPL = kSubPairs / 64;  // groups per lane (1 or 2)
-            static_assert(GPL * 64 == kSubPairs && GPL <= 2, "one or two groups per lane");
-            const uint32_t t = wave;
-            uint32_t b0 = 0;
-            for (uint32_t u = 0; u < t; u++) b0 += tt[u];
-            const uint32_t x0 = cb[(GPL * lane) * 16 + t], x1 = GPL == 2 ? cb[(GPL * lane + 1) * 16 + t] : 0u;
-            const uint32_t inc = wave_incl_scan(x0 + x1);
-            const uint32_t ex = b0 + inc - (x0 + x1);
-            cb[(GPL * lane) * 16 + t] = ex;
-            if (GPL == 2) cb[(GPL * lane + 1) * 16 + t] = ex + x0;
-            if (lane == 0) rseg[((uint64_t)(rb / kApChunk) + bin) * 16 + t] = (uint16_t)b0;
-        }
-        // the next round's tile totals (last read in the previous round, before this round's first barrier)
-        if (tid >= NT - 16) ttot[par ^ 1u][tid - (NT - 16)] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < kI; j++)
-            if ((sb[j] & 0xFFu) != 0xFFu) a.entries2[rb + cb[(j * kW + wave) * 16 + (sb[j] & 0xFFu)] + (sb[j] >> 8)] = e[j];
-#pragma unroll
-        for (int j = 0; j < kI; j++) e[j] = en[j];
-        par ^= 1u;
-    }
-}
-
-// K4's view of a super-bin's tiles: each tile's run in every k_subpart round, in
-// round order, with the runs' logical starts scanned.  All tiles' tables are built
-// at the bin's start (wave t scans tile t: one barrier per bin) when they fit
-// kSegAll entries (nsub * (rounds + 1): every C5 bin of typical size); otherwise
-// one tile at a time in windows of rounds (a tile spread over several windows is
-// stored and reloaded between them).
-struct SegLds {
-    uint32_t tot[16];             // the super-bin's updates per tile
-    uint32_t sbase[kSegAll];      // physical start of a tile's run in a round
-    uint32_t spre[kSegAll];       // logical start of each run, then the table's total
-};
-
-// The run of the wave's first lane comes from the cursor, advanced (wave-uniform
-// reads, bisection) only when that lane has left it: about once per 16 wave loads
-// at the bench geometry.  Lanes past the run's end step forward on their own.
-__device__ __forceinline__ uint64_t EntSegs::at(uint32_t q, Cur &c) const {
-    const uint32_t *spre = G->spre + off, *sbase = G->sbase + off;
-    const uint32_t qf = __builtin_amdgcn_readfirstlane(q);
-    if (qf >= c.hi) {  // wave-uniform
-        uint32_t lo = c.r, hi = nseg;  // largest r with spre[r] <= qf (empty runs skipped)
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (spre[mid] <= qf) lo = mid; else hi = mid;
-        }
-        c.r = __builtin_amdgcn_readfirstlane(lo);
-        c.lo = __builtin_amdgcn_readfirstlane(spre[c.r]);
-        c.hi = __builtin_amdgcn_readfirstlane(spre[c.r + 1]);
-        c.base = __builtin_amdgcn_readfirstlane(sbase[c.r]);
-    }
-    uint32_t idx = c.base + (q - c.lo);
-    if (q >= c.hi) {
-        uint32_t r2 = c.r + 1;
-        while (spre[r2 + 1] <= q) r2++;  // spre[nseg] = the total > q
-        idx = sbase[r2] + (q - spre[r2]);
-    }
-    return p[idx];
-}
-
-__device__ __forceinline__ uint64_t EntSegs::at_any(uint32_t q) const {
-    const uint32_t *spre = G->spre + off, *sbase = G->sbase + off;
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (spre[mid] <= q) lo = mid; else hi = mid;
-    }
-    return p[sbase[lo] + (q - spre[lo])];
-}
-
-// One wave: tile st's runs of rounds [w0, w0 + nr) into the table at off (nr + 1 entries).
-__device__ __forceinline__ uint32_t seg_scan_wave(const ApplyArgs &a, SegLds &G, uint32_t beg, uint32_t end,
-                                                  uint64_t ridx0, uint32_t nsub, uint32_t st, uint32_t w0,
-                                                  uint32_t nr, uint32_t off) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t carry = 0;
-    for (uint32_t i0 = 0; i0 < nr; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        uint32_t len = 0;
-        if (i < nr) {
-            const uint32_t r = w0 + i;
-            const uint32_t rb = beg + r * kApChunk, rl = min(kApChunk, end - rb);
-            const uint16_t *rs = a.rseg + (ridx0 + r) * 16;
-            const uint32_t s0 = rs[st], e0 = st + 1 < nsub ? rs[st + 1] : rl;
-            G.sbase[off + i] = rb + s0;
-            len = e0 - s0;
-        }
-        const uint32_t inc = wave_incl_scan(len);
-        if (i < nr) G.spre[off + i] = carry + inc - len;
-        carry += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) G.spre[off + nr] = carry;
-    return carry;
-}
-
-__device__ __forceinline__ void seg_totals(const ApplyArgs &a, SegLds &G, uint32_t beg, uint32_t end,
-                                           uint64_t ridx0, uint32_t nsub) {
-    const uint32_t tid = threadIdx.x;
-    if (tid < 16) G.tot[tid] = 0;
-    __syncthreads();
-    const uint32_t R = (end - beg + kApChunk - 1) / kApChunk;
-    for (uint32_t i = tid; i < R * nsub; i += kApThreads) {
-        const uint32_t r = i / nsub, t = i % nsub;
-        const uint32_t rl = min(kApChunk, end - (beg + r * kApChunk));
-        const uint16_t *rs = a.rseg + (ridx0 + r) * 16;
-        const uint32_t e = t + 1 < nsub ? rs[t + 1] : rl;
-        if (e > rs[t]) atomicAdd(&G.tot[t], e - rs[t]);
-    }
-    __syncthreads();
-}
-
 // Persistent: each workgroup takes bins from the size-ordered schedule through
 // a work counter, one bin ahead, so the next tile's state can be loaded while
 // the current tile is stored.
 struct ApplyTile {
-    uint32_t bin;
-    uint32_t beg, end;  // update range in the bin (super-bin: sub-partitioned later)
+    uint32_t beg, end;  // update range of the bin
     uint32_t r, bbase;  // row, first bucket of the bin
     bool valid;
 };
@@ -2292,7 +1726,6 @@ __device__ __forceinline__ ApplyTile apply_bin(const ApplyArgs &a, uint32_t k) {
     t.valid = false;
     if (k >= a.g.nbins) return t;
     const uint32_t bin = a.order ? a.order[k] : k;
-    t.bin = bin;
     t.beg = a.offsets[bin];
     t.end = (bin + 1 < a.g.nbins_all) ? a.offsets[bin + 1] : *a.total;
     t.r = bin / a.g.ntiles;
@@ -2301,111 +1734,35 @@ __device__ __forceinline__ ApplyTile apply_bin(const ApplyArgs &a, uint32_t k) {
     return t;
 }
 
-// MODE 0: rows of single tiles (bins = tiles); 1: super-bins read through k_subpart's
-// rounds (3: the super-bins too big for MODE 1's tables, a second launch).  One
-// variant per launch, so each inlines only its own tile loop (and stays within 128
-// VGPRs).
-template <int MODE>
+// Rows of single tiles (bins = tiles); rows of super-bins go to k_apply_sparse.
 __global__ __launch_bounds__(kApThreads) void k_apply(ApplyArgs a) {
     __shared__ ApplyLds L;
-    __shared__ SegLds G;
     __shared__ uint32_t s_k;
     const CmGeom &g = a.g;
     const uint32_t tid = threadIdx.x;
     const uint32_t tw = 1u << g.tile_bits;
     TilePre pre;
     tile_none(pre);
-    if constexpr (MODE == 3) {
-        if (a.work[2] == 0) return;  // no bin needs windows (k_subpart counts them): the common case
-    }
-    unsigned int *work = a.work + (MODE == 3 ? 1 : 0);
-    if (tid == 0) s_k = atomicAdd(work, 1u);
+    if (tid == 0) s_k = atomicAdd(a.work, 1u);
     __syncthreads();
     uint32_t k = s_k;
     __syncthreads();
     while (k < g.nbins) {
-        if (tid == 0) s_k = atomicAdd(work, 1u);  // the bin after this one
+        if (tid == 0) s_k = atomicAdd(a.work, 1u);  // the bin after this one
         const ApplyTile cur = apply_bin(a, k);
         __syncthreads();
         const uint32_t kn = s_k;
         const ApplyTile nxt = apply_bin(a, kn);
-        // first tile of the next bin (its state is prefetched; a super-bin's first
-        // tile may turn out empty, which only wastes that prefetch)
+        // the next bin's tile (its state is prefetched)
         uint64_t nb_cbase = kNoTile;
         uint32_t nb_tn = 0;
-        if (MODE != 3 && nxt.valid && nxt.beg < nxt.end && nxt.bbase < g.w) {
+        if (nxt.valid && nxt.beg < nxt.end && nxt.bbase < g.w) {
             nb_cbase = (uint64_t)nxt.r * g.w + nxt.bbase;
             nb_tn = min(tw, g.w - nxt.bbase);
         }
-        if (cur.beg < cur.end) {
-            if constexpr (MODE == 0) {
-                apply_tile(a, L, EntFlat{a.entries}, cur.beg, cur.end, (uint64_t)cur.r * g.w + cur.bbase,
-                           min(tw, g.w - cur.bbase), cur.bbase, pre, nb_cbase, nb_tn);
-            } else {
-                const uint32_t nsub = 1u << g.sub_bits;
-                {  // MODE 1 / 3: rounds grouped by tile (k_subpart)
-                    const uint64_t ridx0 = (uint64_t)(cur.beg / kApChunk) + cur.bin;
-                    const uint32_t R = (cur.end - cur.beg + kApChunk - 1) / kApChunk;
-                    // MODE 1: bins whose tables fit kSegAll, all tiles' at once or (bigger bins)
-                    // one tile's at a time; MODE 3 (a second launch): the rest
-                    const bool all = nsub * (R + 1) <= kSegAll;  // block-uniform
-                    const bool fits = R + 1 <= kSegAll;
-                    if ((MODE == 1) == fits) {
-                        if (MODE == 1 && all) {
-                            for (uint32_t t = tid >> 6; t < nsub; t += kApWaves) {  // wave t (mod waves): tile t
-                                const uint32_t tot = seg_scan_wave(a, G, cur.beg, cur.end, ridx0, nsub, t, 0, R, t * (R + 1));
-                                if ((tid & 63u) == 0) G.tot[t] = tot;
-                            }
-                            __syncthreads();
-                        } else {
-                            seg_totals(a, G, cur.beg, cur.end, ridx0, nsub);
-                        }
-                        for (uint32_t st = 0; st < nsub; st++) {
-                            const uint32_t tbase = cur.bbase + (st << g.tile_bits);
-                            if (tbase >= g.w || G.tot[st] == 0) continue;
-                            uint64_t ncb = nb_cbase;
-                            uint32_t ntn = nb_tn;
-                            for (uint32_t s2 = st + 1; s2 < nsub; s2++) {
-                                const uint32_t tb2 = cur.bbase + (s2 << g.tile_bits);
-                                if (tb2 < g.w && G.tot[s2]) {
-                                    ncb = (uint64_t)cur.r * g.w + tb2;
-                                    ntn = min(tw, g.w - tb2);
-                                    break;
-                                }
-                            }
-                            const uint64_t cbase = (uint64_t)cur.r * g.w + tbase;
-                            const uint32_t tn = min(tw, g.w - tbase);
-                            if constexpr (MODE == 1) {
-                                uint32_t off = st * (R + 1);
-                                if (!all) {
-                                    if (tid < 64) seg_scan_wave(a, G, cur.beg, cur.end, ridx0, nsub, st, 0, R, 0);
-                                    __syncthreads();
-                                    off = 0;
-                                }
-                                apply_tile(a, L, EntSegs{a.entries2, &G, off, R}, 0u, G.tot[st], cbase, tn, tbase, pre,
-                                           ncb, ntn);
-                                __syncthreads();
-                            } else {
-                                // windows of rounds; a tile spread over several is stored and
-                                // reloaded between them (no prefetch of itself)
-                                constexpr uint32_t kWin = kSegAll - 1;
-                                for (uint32_t w0 = 0; w0 < R; w0 += kWin) {
-                                    const uint32_t nr = min(kWin, R - w0);
-                                    if (tid < 64) seg_scan_wave(a, G, cur.beg, cur.end, ridx0, nsub, st, w0, nr, 0);
-                                    __syncthreads();
-                                    const uint32_t n = G.spre[nr];
-                                    const bool last = w0 + kWin >= R;
-                                    if (n)
-                                        apply_tile(a, L, EntSegs{a.entries2, &G, 0u, nr}, 0u, n, cbase, tn, tbase, pre,
-                                                   last ? ncb : kNoTile, last ? ntn : 0u);
-                                    __syncthreads();
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        if (cur.beg < cur.end)
+            apply_tile(a, L, cur.beg, cur.end, (uint64_t)cur.r * g.w + cur.bbase, min(tw, g.w - cur.bbase), cur.bbase,
+                       pre, nb_cbase, nb_tn);
         __syncthreads();
         k = kn;
     }
@@ -2416,8 +1773,9 @@ __global__ __launch_bounds__(kApThreads) void k_apply(ApplyArgs a) {
 // bins K3s can count, configs[4]: d=8 w=2^24, 512 super-bins of 8 tiles per
 // row).  A 100M-packet batch gives a cold update to only ~6% of the 2^27
 // buckets, so loading and storing every tile's 64 KB of state (2 GB per batch
-// each way) and sub-partitioning every super-bin by tile first (k_subpart: a
-// second read and write of all updates) cost more than the updates themselves.
+// each way) and sub-partitioning every super-bin by tile first (a second read
+// and write of all updates) cost more than the updates themselves: that tile
+// path, round 5's, is retired (the A/B: DESIGN.md §4).
 // Here a workgroup takes a super-bin's updates in K3s's stream order and keeps
 // only the buckets they touch, in an LDS hash table whose slots ARE the tile
 // state slots of apply_tile: an update's bucket field is rewritten to its slot,
@@ -2861,7 +2219,6 @@ struct HotArgs {
     uint32_t chk_cap;
     const uint32_t *keyid, *idx, *sizes;
     uint64_t n;
-    const uint32_t *hstr, *scnt;  // compact hot streams (CM kernels), or null: per-packet codes in idx
 };
 
 __device__ __forceinline__ void hot_bin_range(const HotArgs &a, uint32_t hb, uint32_t &beg, uint32_t &end) {
@@ -3125,34 +2482,17 @@ __global__ __launch_bounds__(256) void k_hot_blockcheck(HotArgs a) {
     long long run = (long long)((unsigned long long)c.z | (unsigned long long)c.w << 32);
     const uint64_t beg = (uint64_t)blk * kChunk, end = min(a.n, beg + kChunk);
     const uint32_t *idxr = a.idx + (uint64_t)r * a.n;
-    // compact streams: walk the block's row-r hot stream (its K1 waves in order = packet
-    // order) instead of every packet's code
-    uint32_t spre[kCsWaves + 1] = {0, 0, 0, 0, 0};
-    if (a.hstr) {
-        for (uint32_t w = 0; w < kCsWaves; w++)
-            spre[w + 1] = spre[w] + a.scnt[(((uint64_t)blk * kCsWaves + w) * a.g.d + r) * 2 + 1];
-    }
-    const uint64_t lim = a.hstr ? (uint64_t)spre[kCsWaves] : end - beg;
+    const uint64_t lim = end - beg;
     bool ev = false;
-    for (uint64_t q0 = 0; q0 < lim; q0 += 1024) {  // 4 consecutive packets (stream entries) per thread
+    for (uint64_t q0 = 0; q0 < lim; q0 += 1024) {  // 4 consecutive packets per thread
         long long dl[4], tl = 0;
         bool fo[4];
         uint32_t sv[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint64_t x = q0 + tid * 4 + i;
-            uint64_t p = beg + x;
-            bool hit = false;
-            if (x < lim) {
-                if (a.hstr) {
-                    const uint32_t w = (x >= spre[1] ? 1u : 0u) + (x >= spre[2] ? 1u : 0u) + (x >= spre[3] ? 1u : 0u);
-                    const uint32_t cc = a.hstr[(((uint64_t)blk * kCsWaves + w) * a.g.d + r) * kCsWave + (x - spre[w])];
-                    p = beg + w * kCsWave + (cc & (kCsWave - 1u));
-                    hit = (cc >> kCsBits) == slot % kHot;
-                } else {
-                    hit = idxr[p] == code;
-                }
-            }
+            const uint64_t p = beg + x;
+            const bool hit = x < lim && idxr[p] == code;
             dl[i] = 0; fo[i] = false; sv[i] = 0;
             if (hit && a.keyid[p] != GNS_ID_NONE) {
                 const uint32_t s = a.sizes[p];
@@ -3431,10 +2771,7 @@ struct gns_cm : FlowDict {
     uint32_t *pcnt[2] = {nullptr, nullptr};
     uint32_t *ptotal = nullptr;        // [2]
     uint32_t *hist = nullptr, *part = nullptr, *total = nullptr, *order = nullptr;
-    uint64_t *entries = nullptr, *entries2 = nullptr;
-    uint16_t *rseg = nullptr;          // [round][16] k_subpart round tile starts (sub_bits > 0)
-    int subpart_nt = 0;                // GNS_SUBPART_NT (A/B)
-    bool k4_sparse = true;             // super-bins through k_apply_sparse (GNS_K4_SPARSE=0: k_subpart + tiles)
+    uint64_t *entries = nullptr;
     uint32_t *rec_sizes = nullptr;     // 16-byte compact records from device memory: a batch's sizes
     uint64_t *ovf = nullptr;
     uint32_t *ovf_cnt = nullptr;
@@ -3453,15 +2790,6 @@ struct gns_cm : FlowDict {
     uint4 *chk = nullptr;                 // [kChkCap]
     bool warm = false;                    // a batch has run since create/reset
     bool lds_ordered = false;             // k_lds_order_probe passed: K3 ranks by LDS adds
-    bool k3_half = false, k3_pack = false;
-    uint32_t k3_xcd = 0;
-    bool k3_staged = true;                // K3s (LDS-staged runs) where the geometry allows; GNS_K3_STAGED=0: K3
-    // compact streams (K1 -> K3c): off by default (K3 -0.31 ms, K1 +0.51 ms
-    // at the bench geometry); GNS_CMODE=1 turns them on where the geometry allows
-    // (256-thread K1, K3s rows, buckets < 2^20)
-    bool cmode = false;
-    uint32_t *hstr = nullptr;             // [nblk][4][d][4096] hot codes (cold codes live in idx)
-    uint32_t *scnt = nullptr;             // [nblk][4][d][2] stream lengths
     uint32_t *h_pin = nullptr;            // pinned host mirror of small counters
     // staging for host inputs: two device buffers; batch i+1's H2D copies run on
     // cstream while batch i computes on `stream` (events order the reuse)
@@ -3499,10 +2827,10 @@ namespace {
 
 int cm_free_all(gns_cm *cm) {
     dfree(cm->C); dfree(cm->S); dfree(cm->Fc); dfree(cm->Fs); cm->rd.free_all();
-    dfree(cm->keyid); dfree(cm->idx); dfree(cm->scnt);  // hstr lives in idx
+    dfree(cm->keyid); dfree(cm->idx);
     dfree(cm->pend[0]); dfree(cm->pend[1]); dfree(cm->pcnt[0]); dfree(cm->pcnt[1]);
     dfree(cm->ptotal); dfree(cm->hist); dfree(cm->part); dfree(cm->total); dfree(cm->order);
-    dfree(cm->entries); dfree(cm->entries2); dfree(cm->rseg); dfree(cm->rec_sizes); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
+    dfree(cm->entries); dfree(cm->rec_sizes); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
     cm->stage[0].free_all(); cm->stage[1].free_all(); dfree(cm->side_dev);
     for (int i = 0; i < 2; i++) {
         if (cm->ev_copied[i]) (void)hipEventDestroy(cm->ev_copied[i]);
@@ -3574,7 +2902,7 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
         z.add(cm->hflag2, ((size_t)g.d * kHot + 2) * 4);
         z.add(cm->stats + 8, 8);
         z.add(cm->ovf_cnt, 4);  // K3's oversize list (both K3 modes append)
-        z.add(cm->work, 12);    // K4's work counters
+        z.add(cm->work, 4);     // K4's work counter
         z.add(cm->hflag, (size_t)g.d * kHot * 4);
         GNS_HIP(ctl_zero(z, s));
     }
@@ -3586,22 +2914,13 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
         a.pend_total = cm->ptotal; a.hist = cm->hist; a.nblk = nblk; a.hot_ids = cm->hot_ids;
         a.Fc = cm->Fc; a.Fs = cm->Fs; a.hsum = cm->hsum; a.hot_tab = cm->hot_tab;
         a.stats = cm->stats;
-        a.cstr = cm->idx; a.hstr = cm->hstr; a.scnt = cm->scnt; a.hoff = (uint32_t)(cm->hstr - cm->idx);
         ScopedStage st(cm->timer, 0);
         const size_t lds = extract_lds_bytes(g.nbins_all, g.d);
-        // 256-thread K1: with compact streams when the handle uses them
-#define GNS_K1_256(KB_, DD_)                                                                                   \
-    do {                                                                                                       \
-        if (cm->cmode)                                                                                         \
-            hipLaunchKernelGGL((k_extract<KIND, MODE, KB_, DD_, 256, true>), dim3(nblk), dim3(256), lds, s, a); \
-        else                                                                                                   \
-            hipLaunchKernelGGL((k_extract<KIND, MODE, KB_, DD_, 256>), dim3(nblk), dim3(kExThreads), lds, s, a); \
-    } while (0)
         if constexpr (KIND == IN_REC16) {  // PCIe-bound host path: runtime key width and depth
             if (lds > kExLdsSmall)
                 hipLaunchKernelGGL((k_extract<KIND, MODE, 0, 0, 1024>), dim3(nblk), dim3(1024), lds, s, a);
             else
-                GNS_K1_256(0, 0);
+                hipLaunchKernelGGL((k_extract<KIND, MODE, 0, 0, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         } else if (lds > kExLdsSmall) {  // deep / wide sketch: one large block per CU
             // configs[4] (d=8, 5-tuple): the plain loop, two 512-thread blocks per CU
             // (see kC5Threads)
@@ -3614,16 +2933,15 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
             else
                 hipLaunchKernelGGL((k_extract<KIND, MODE, 0, 0, 1024>), dim3(nblk), dim3(1024), lds, s, a);
         } else if (cm->K == 37 && g.d == 4)
-            GNS_K1_256(37, 4);
+            hipLaunchKernelGGL((k_extract<KIND, MODE, 37, 4, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         else if (cm->K == 37)
-            GNS_K1_256(37, 0);
+            hipLaunchKernelGGL((k_extract<KIND, MODE, 37, 0, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         else if (cm->K == 16 && g.d == 4)
-            GNS_K1_256(16, 4);
+            hipLaunchKernelGGL((k_extract<KIND, MODE, 16, 4, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         else if (cm->K == 16)
-            GNS_K1_256(16, 0);
+            hipLaunchKernelGGL((k_extract<KIND, MODE, 16, 0, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         else
-            GNS_K1_256(0, 0);
-#undef GNS_K1_256
+            hipLaunchKernelGGL((k_extract<KIND, MODE, 0, 0, 256>), dim3(nblk), dim3(kExThreads), lds, s, a);
         GNS_HIP(hipGetLastError());
     }
     // K1b: resolve parked packets until none remain.  The first two rounds are queued
@@ -3690,22 +3008,14 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
     {
         ScatterArgs a{};
         a.n = n; a.g = g; a.keyid = cm->keyid; a.idx = cm->idx; a.sizes = in.sizes;
-        a.xcd_map = cm->k3_xcd;
         a.offsets = cm->hist; a.nblk = nblk; a.entries = cm->entries; a.ovf = cm->ovf;
         a.ovf_cnt = cm->ovf_cnt; a.ovf_cap = (uint32_t)cm->ovf_cap; a.hot_ids = cm->hot_ids; a.stats = cm->stats;
         a.hot_mode = 0; a.hflag2 = cm->hflag2; a.hany = cm->hflag2 + g.d * kHot;
-        a.cstr = cm->idx; a.hstr = cm->hstr; a.scnt = cm->scnt;
         ScopedStage st(cm->timer, 3);
-        if (cm->cmode)
-            hipLaunchKernelGGL((k_scatter_cs<1024, 256>), dim3(nblk), dim3(1024), 0, s, a);
-        else if (cm->lds_ordered && cm->k3_staged && g.ntiles <= 256 && g.d <= 8 && cm->k3_half)
-            hipLaunchKernelGGL((k_scatter_st<512, 256, 4096>), dim3(nblk), dim3(512), 0, s, a);
-        else if (cm->lds_ordered && cm->k3_staged && g.ntiles <= 256 && g.d <= 8)
-            hipLaunchKernelGGL((k_scatter_st<1024, 256>), dim3(nblk), dim3(1024), 0, s, a);
-        else if (cm->lds_ordered && cm->k3_staged && g.ntiles <= 512 && g.d <= 8 && cm->k3_pack)
-            hipLaunchKernelGGL((k_scatter_st<1024, 512, (int)kStSub, true>), dim3(nblk), dim3(1024), 0, s, a);
-        else if (cm->lds_ordered && cm->k3_staged && g.ntiles <= 512 && g.d <= 8)
-            hipLaunchKernelGGL((k_scatter_st<512, 512>), dim3(nblk), dim3(512), 0, s, a);
+        if (cm->lds_ordered && g.ntiles <= 256)
+            hipLaunchKernelGGL((k_scatter_st<256, false>), dim3(nblk), dim3(kStThreads), 0, s, a);
+        else if (cm->lds_ordered && g.ntiles <= 512)
+            hipLaunchKernelGGL((k_scatter_st<512, true>), dim3(nblk), dim3(kStThreads), 0, s, a);
         else if (cm->lds_ordered)
             hipLaunchKernelGGL(k_scatter<1>, dim3(nblk), dim3(kScThreads), scatter_lds_bytes(g.ntiles + kHot, g.d), s, a);
         else
@@ -3720,36 +3030,18 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
                                cm->total, cm->order);
         ApplyArgs a{};
         a.stats = cm->stats;
-        a.entries = cm->entries; a.entries2 = cm->entries2; a.offsets = cm->hist; a.nblk = nblk; a.nbins = g.nbins;
+        a.entries = cm->entries; a.offsets = cm->hist; a.nblk = nblk; a.nbins = g.nbins;
         a.total = cm->total; a.order = ordered ? cm->order : nullptr; a.ovf = cm->ovf; a.g = g;
         a.C = cm->C; a.Fc = cm->Fc; a.S = cm->S; a.Fs = cm->Fs; a.work = cm->work;
         ScopedStage st(cm->timer, 4);
-        if (g.sub_bits && cm->k4_sparse) {
-            // super-bins in stream order, touched buckets only (k_apply_sparse): no
-            // sub-partition pass and no tile sweep; GNS_K4_SPARSE=0 restores the tile path
+        // persistent: one workgroup per CU (the LDS state fills a CU), bins from the schedule counter
+        if (g.sub_bits) {
+            // super-bins in stream order, touched buckets only: no sub-partition pass and no tile sweep
             const dim3 apg(std::min(g.nbins, cm->ncu));
             hipLaunchKernelGGL(k_apply_sparse, apg, dim3(kApThreads), 0, s, a);
-        } else if (g.sub_bits) {
-            // 512-thread workgroups (16 updates per thread and round, two per CU) when a
-            // wave per tile fits; GNS_SUBPART_NT=1024 for the A/B
-            if ((1u << g.sub_bits) <= 8 && cm->subpart_nt != 1024)
-                hipLaunchKernelGGL(k_subpart<512>, dim3(g.nbins), dim3(512), 0, s, a, cm->rseg);
-            else
-                hipLaunchKernelGGL(k_subpart<1024>, dim3(g.nbins), dim3(1024), 0, s, a, cm->rseg);
-            GNS_HIP(hipGetLastError());
-            a.rseg = cm->rseg;
-        }
-        // persistent: one workgroup per CU (the tile LDS fills a CU), bins from the schedule counter
-        const dim3 apg(std::min(g.nbins, cm->ncu * (kApThreads <= 512 ? 2u : 1u)));  // workgroups the LDS fits per CU
-        if (g.sub_bits && cm->k4_sparse) {
-            // (launched above)
-        } else if (!g.sub_bits) {
-            hipLaunchKernelGGL(k_apply<0>, apg, dim3(kApThreads), 0, s, a);
         } else {
-            hipLaunchKernelGGL(k_apply<1>, apg, dim3(kApThreads), 0, s, a);
-            GNS_HIP(hipGetLastError());
-            // super-bins too big for K4's LDS tables (none at the bench geometry): windows of rounds
-            hipLaunchKernelGGL(k_apply<3>, apg, dim3(kApThreads), 0, s, a);
+            const dim3 apg(std::min(g.nbins, cm->ncu * (kApThreads <= 512 ? 2u : 1u)));  // workgroups the LDS fits per CU
+            hipLaunchKernelGGL(k_apply, apg, dim3(kApThreads), 0, s, a);
         }
         GNS_HIP(hipGetLastError());
     }
@@ -3762,7 +3054,6 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
         h.hsum = cm->hsum; h.hflag2 = cm->hflag2; h.hany = cm->hflag2 + g.d * kHot; h.nchk = h.hany + 1;
         h.hres = cm->hres; h.chk = cm->chk; h.chk_cap = kChkCap;
         h.keyid = cm->keyid; h.idx = cm->idx; h.sizes = in.sizes; h.n = n;
-        h.hstr = cm->cmode ? cm->hstr : nullptr; h.scnt = cm->scnt;
         ScopedStage st(cm->timer, 6);
         // summary path: decide, exact block checks, commit
         hipLaunchKernelGGL(k_hot_decide, dim3(g.d * kHot), dim3(256), 0, s, h);
@@ -3775,10 +3066,7 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
             a.offsets = cm->hist; a.nblk = nblk; a.entries = cm->entries; a.ovf = cm->ovf;
             a.ovf_cnt = cm->ovf_cnt; a.ovf_cap = (uint32_t)cm->ovf_cap; a.hot_ids = cm->hot_ids; a.stats = cm->stats;
             a.hot_mode = 1; a.hflag2 = cm->hflag2; a.hany = h.hany;
-            a.cstr = cm->idx; a.hstr = cm->hstr; a.scnt = cm->scnt;
-            if (cm->cmode)
-                hipLaunchKernelGGL(k_hot_scatter_cs, dim3(nblk), dim3(64), 0, s, a);
-            else if (cm->lds_ordered)
+            if (cm->lds_ordered)
                 hipLaunchKernelGGL(k_scatter<1>, dim3(nblk), dim3(kScThreads), scatter_lds_bytes(g.ntiles + kHot, g.d), s, a);
             else
                 hipLaunchKernelGGL(k_scatter<0>, dim3(nblk), dim3(kScThreads), scatter_lds_bytes(g.ntiles + kHot, g.d), s, a);
@@ -4021,10 +3309,8 @@ int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
             (rc = dalloc_t(&cm->ptotal, 2)) || (rc = dalloc_t(&cm->hist, (uint64_t)g.nbins_all * cm->nblk_max)) ||
             (rc = dalloc_t(&cm->part, nscan)) || (rc = dalloc_t(&cm->total, 1)) ||
             (rc = dalloc_t(&cm->order, g.nbins)) || (rc = dalloc_t(&cm->entries, cm->bmax * g.d)) ||
-            (g.sub_bits && (rc = dalloc_t(&cm->entries2, cm->bmax * g.d))) ||
-            (g.sub_bits && (rc = dalloc_t(&cm->rseg, (cm->bmax * g.d / kApChunk + g.nbins + 2) * 16))) ||
             (rc = dalloc_t(&cm->ovf, kOvfCap)) || (rc = dalloc_t(&cm->ovf_cnt, 1)) ||
-            (rc = dalloc_t(&cm->stats, kStatsProf + 16)) || (rc = dalloc_t(&cm->work, 4)) || (rc = dalloc_t(&cm->hot_ids, g.d * kHot)) ||
+            (rc = dalloc_t(&cm->stats, kStatsProf + 16)) || (rc = dalloc_t(&cm->work, 1)) || (rc = dalloc_t(&cm->hot_ids, g.d * kHot)) ||
             (rc = dalloc_t(&cm->segtot, (size_t)g.d * kHot * kHotSegs * 2)) || (rc = dalloc_t(&cm->hflag, g.d * kHot)) ||
             (rc = dalloc_t(&cm->hhist, g.d * kHotKeys)) || (rc = dalloc_t(&cm->hthr, 8)) || (rc = dalloc_t(&cm->hcnt, 8)) ||
             (rc = dalloc_t(&cm->hcand, (size_t)g.d * kHotCand)) || (rc = dalloc_t(&cm->hcn, 16)) ||
@@ -4055,26 +3341,6 @@ int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
             dfree(viol);
             if (e != hipSuccess) { set_error("lds order probe: %s", hipGetErrorString(e)); rc = GNS_E_HIP; break; }
             cm->lds_ordered = hv == 0 && !(env && env[0] == '0');
-            const char *es = getenv("GNS_K3_STAGED");
-            cm->k3_staged = !(es && es[0] == '0');
-            cm->k3_half = es && es[0] == 'h';
-            const char *ex = getenv("GNS_K3_XCD");
-            cm->k3_xcd = ex && ex[0] == '0' ? 0u : 1u;
-            cm->k3_pack = !(es && es[0] == 'u');  // 512-bin rows: 1024-thread K3s, 16-bit counters (u: 512 threads)  // A/B: 512-thread K3s, 4096-packet sub-passes, two per CU
-            const char *en = getenv("GNS_SUBPART_NT");
-            cm->subpart_nt = en ? atoi(en) : 0;
-            const char *esp = getenv("GNS_K4_SPARSE");  // super-bins: touched buckets only (0: tile path)
-            cm->k4_sparse = !(esp && esp[0] == '0');
-            const char *ec = getenv("GNS_CMODE");
-            cm->cmode = ec && ec[0] == '1' && cm->lds_ordered && cm->k3_staged && g.ntiles <= 256 && g.d <= 8 &&
-                        extract_lds_bytes(g.nbins_all, g.d) <= kExLdsSmall && g.w <= (1u << (32 - kCsBits));
-            if (cm->cmode) {  // the hot streams after the cold ones (K1 addresses both from one base)
-                dfree(cm->idx);
-                cm->idx = nullptr;
-                if ((rc = dalloc_t(&cm->idx, 2 * cm->bmax * g.d)) != GNS_OK) break;
-                cm->hstr = cm->idx + cm->bmax * g.d;
-                if ((rc = dalloc_t(&cm->scnt, (uint64_t)cm->nblk_max * kCsWaves * g.d * 2)) != GNS_OK) break;
-            }
         }
         // the read side's heavy-hitter buffers (a window's first call allocates nothing)
         if ((rc = hh_reserve(cm->rd.hh, (uint64_t)cm->g.d * cm->g.w, cm->dict_slots, cm->K, cm->stream)) != GNS_OK) break;
@@ -4501,8 +3767,7 @@ int gns_cm_counters(gns_cm *cm, uint64_t out[8]) {
     for (int i = 5; i < 8; i++) out[i] = h[i];
     return GNS_OK;
 #endif
-#ifdef GNS_K4_PROF  // profiling build: K4 phase cycles (classify, decide, compact, replay, tile load,
-                    // tile store, sub-partition), chunks
+#ifdef GNS_K4_PROF  // profiling build: K4 phase cycles
     // phases (classify, decide, compact, replay barrier + loop top, replay gather, tile load +
     // store, replay groups), then the slowest wave's and the summed per-wave replay cycles
     for (int i = 0; i < 4; i++) out[i] = h[kStatsProf + i];

@@ -303,15 +303,14 @@ def test_large_sizes_mixed_owner(gpu, oracle):
     (1 << 24, 8, 4, 1 << 16, 2_000_000),   # C5 geometry: bins of 16 LDS tiles
     (1 << 22, 8, 8, 1 << 15, 1_000_000),   # d * tiles > 4096: bins of 2 tiles
     (5_000_000, 3, 13, 50_000, 1_000_000),  # non power-of-two wide row
-    (20_000_000, 8, 4, 1 << 15, 1_000_000),  # bins of 16 tiles (k_subpart's 1024-thread variant)
+    (20_000_000, 8, 4, 1 << 15, 1_000_000),  # bins of 16 tiles, non power-of-two
+], ids=[  # the ids these cases had while a second K4 path was parametrised in front (its cases are gone)
+    "1-16777216-8-4-65536-2000000", "1-4194304-8-8-32768-1000000",
+    "1-5000000-3-13-50000-1000000", "1-20000000-8-4-32768-1000000",
 ])
-@pytest.mark.parametrize("sparse", ["1", "0"])
-def test_wide_rows_parity(gpu, oracle, monkeypatch, w, d, K, nflows, n, sparse):
+def test_wide_rows_parity(gpu, oracle, w, d, K, nflows, n):
     """Widths beyond 1024 LDS tiles per row: K3 bins hold 2^sub_bits tiles.  K4 takes a
-    bin in stream order with only its touched buckets in LDS (k_apply_sparse, the
-    default), or (GNS_K4_SPARSE=0) partitions each bin by tile before the in-order
-    tile pass (k_subpart + k_apply)."""
-    monkeypatch.setenv("GNS_K4_SPARSE", sparse)
+    bin in stream order with only its touched buckets in LDS (k_apply_sparse)."""
     rng = np.random.default_rng(w % 1000 + d)
     cm, orc = make_pair(oracle, w, d, K, st=1 << 16, ct=100, max_flows=1 << 20)
     keys, flows, _ = zipf_keys(rng, n, nflows, K)
@@ -574,10 +573,11 @@ def test_heavy_hitters_beyond_2p26_candidates(gpu):
     (1000, 3, 13, 5000, 200_000, 70_000),
     (1 << 20, 4, 37, 1 << 18, 2_000_000, 0),
 ])
-def test_compact_streams_parity(gpu, oracle, monkeypatch, w, d, K, nflows, n, batch):
-    """K1's compact cold / hot streams and K3c (GNS_CMODE=1, the measured A/B variant of
-    DESIGN §10): the same bit-exact state as the per-packet code array."""
-    monkeypatch.setenv("GNS_CMODE", "1")
+def test_compact_streams_parity(gpu, oracle, w, d, K, nflows, n, batch):
+    """1% of the packets carry large sizes (the overflow side table and its exact replay), over
+    four geometries: 256 staged bins, a row of one tile, a non power-of-two row fed in several
+    batches, and the bench geometry.  (The name is from the retired compact-streams variant of
+    K1 / K3 these inputs were written for; they now run the one remaining path.)"""
     rng = np.random.default_rng(w + 11 * d)
     cm, orc = make_pair(oracle, w, d, K, batch_packets=batch)
     keys, _, _ = zipf_keys(rng, n, nflows, K)
@@ -591,10 +591,11 @@ def test_compact_streams_parity(gpu, oracle, monkeypatch, w, d, K, nflows, n, ba
 
 
 @pytest.mark.parametrize("w", [16, 4096])
-def test_compact_streams_hot_fallbacks(gpu, oracle, monkeypatch, w):
-    """Ownership changes of designated buckets with compact streams: the block checks and
-    the exact entry path read K1's hot streams (k_hot_blockcheck, k_hot_scatter_cs)."""
-    monkeypatch.setenv("GNS_CMODE", "1")
+def test_hot_ownership_changes_with_huge_sizes(gpu, oracle, w):
+    """Five phases, each with another flow holding 70% of the packets, so the designated buckets
+    change owners from phase to phase; phase 3 adds sizes of 2^21 .. 2^31.  The summary path's
+    block checks (k_hot_blockcheck) and the exact entry path behind them must keep the state
+    bit-exact after every phase."""
     rng = np.random.default_rng(100 + w)
     cm, orc = make_pair(oracle, w, 2, 8, st=1 << 20, ct=100)
     flows = rng.integers(0, 256, (40, 8), dtype=np.uint8)
@@ -665,9 +666,8 @@ def _mm3_words(words, seed):
 @pytest.mark.parametrize("n2", [2_500_000, 4_000_000])
 def test_superbin_many_rounds(gpu, oracle, n2):
     """One super-bin (w=2^23: bins of two 4096-bucket tiles) takes millions of cold updates of
-    one batch: k_subpart groups ~300 / ~460 rounds by tile; K4 reads each tile through its
-    runs from a per-tile table (2.5M) or, past one table, in windows of rounds in the second
-    launch (4M: state stored and reloaded between windows)."""
+    one batch: one workgroup of k_apply_sparse walks ~300 / ~460 chunks of it in stream order,
+    its hash table holding the at most 3000 buckets they touch across all of them."""
     rng = np.random.default_rng(2323)
     w, d, K = 1 << 23, 2, 4
     cm, orc = make_pair(oracle, w, d, K, st=1 << 30, ct=1 << 30, batch_packets=1 << 23, max_flows=1 << 16)
@@ -709,14 +709,12 @@ def test_tiny_sizes_drain_size_counters(gpu, oracle, w, d, nflows):
     assert_same_state(cm, orc)
 
 
-@pytest.mark.parametrize("sparse", ["1", "0"])
-def test_contested_superbins_parity(gpu, oracle, monkeypatch, sparse):
+def test_contested_superbins_parity(gpu, oracle):
     """Super-bin geometry (w = 2^22, d = 8: bins of two tiles) under heavy contention:
     1.5M flows over 4M buckets per row, so buckets change owners all the time, most
     chunks replay, and a chunk's replay list can outgrow the LDS copy (the fallback that
-    re-reads updates and, in k_apply_sparse, maps them to their slots again).  One device
+    re-reads updates and maps them to their slots again).  One device
     batch of 3M packets with sizes that take the overflow table, then a second batch."""
-    monkeypatch.setenv("GNS_K4_SPARSE", sparse)
     rng = np.random.default_rng(4404)
     n = 3_000_000
     cm, orc = make_pair(oracle, 1 << 22, 8, 8, st=1 << 12, ct=3, max_flows=1 << 22, batch_packets=n)
