@@ -9,7 +9,8 @@
 //
 // Pipeline per device batch:
 //   K1 k_extract  : packet -> flow key (registers) -> flow id (exact dictionary)
-//                   -> d row indices; per-block (row, tile) histograms.
+//                   -> d row indices; per-block (row, tile) histograms; one mask
+//                   bit per packet: inserted, with a row that K3s must scatter.
 //   K1b k_resolve : re-probe packets whose dictionary slot was claimed in the
 //                   same launch (rare after the first batch).
 //   K2 k_scan*    : exclusive scan of the histograms -> stable bin offsets.
@@ -30,6 +31,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gns_coldmask.cuh"
 #include "gns_common.hpp"
 #include "gns_ctl.cuh"
 #include "gns_hh.hpp"
@@ -167,6 +169,7 @@ struct ExtractArgs {
     uint32_t epoch;
     uint32_t *keyid;
     uint32_t *idx;       // [d][n]
+    uint64_t *cold;      // [ceil(n / 64)] bit p & 63 of word p >> 6: packet p is inserted and has a cold row
     uint64_t *pend;      // per-block regions of kChunk
     uint32_t *pend_cnt;  // [nblk]
     uint32_t *pend_total;
@@ -351,6 +354,10 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
             kid = out;
         }
     }
+    // cold-packet mask for K3s: inserted (parked counts) with a row that is not designated,
+    // gathered in the rows loop.  The whole wave is here and its 64 packets are one aligned
+    // group (block starts and block sizes are multiples of 64)
+    uint64_t cmask = 0;
 
     if (bw && res == CM_CLAIMED) {  // publish the bucket cache with the key (visible next launch)
         uint32_t *tp = a.D.rec + (size_t)out * a.D.RW;
@@ -374,6 +381,7 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
             a.idx[(uint64_t)rr * a.n + p] = h >= 0 ? (0x80000000u | (uint32_t)h) : b;
             binid = h >= 0 ? a.g.nbins + rr * kHot + (uint32_t)h : rr * a.g.ntiles + (b >> a.g.bin_bits);
         }
+        cmask |= __ballot(ok && h < 0);
         // heavy bins: one LDS add for the wave's majority bin
         const uint32_t b0 = __builtin_amdgcn_readfirstlane(binid);
         const uint64_t mm = __ballot(binid == b0 && b0 != 0xFFFFFFFFu);
@@ -404,6 +412,7 @@ __device__ __forceinline__ void k1_consume(const ExtractArgs &a, const K1Lds &S,
             atomicAdd(&s_os[binid - a.g.nbins], (unsigned long long)ownv);
         }
     }
+    if ((threadIdx.x & 63u) == 0 && p < a.n) a.cold[p >> 6] = cmask;
 }
 
 // K1: parse/encode, dictionary, row buckets, block histogram, hot summaries.
@@ -694,6 +703,7 @@ struct ScatterArgs {
     CmGeom g;
     const uint32_t *keyid;
     const uint32_t *idx;
+    const uint64_t *cold;     // K1's cold-packet mask (k_scatter_st)
     const uint32_t *sizes;
     const uint32_t *offsets;  // scanned hist
     uint32_t nblk;
@@ -920,20 +930,25 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(4)))
 }
 
 // ---------------------------------------------------------------------------
-// K3s: the same stable partition, staged.  A 1024-thread block takes its K1
-// block (16384 packets) in sub-passes of 8192 packets and, per row, ranks the
+// K3s: the same stable partition, staged.  A 1024-thread block takes the cold
+// packets of its K1 block (16384 packets) -- those K1's mask marks as inserted
+// with a row that is not designated; a heavy flow's packets have every row
+// designated and are skipped whole -- in sub-passes of 8192 and, per row, ranks the
 // cold updates like K3 (returning LDS adds per (wave, bin), waves owning
-// contiguous packet ranges), lays them out bin by bin in LDS, and copies the
-// bins out as contiguous runs (~15 updates per bin and sub-pass at the bench
-// geometry).  Scattered 8-byte stores cost 2-3x the time of runs of >= 16
+// contiguous rank ranges of the packet-ordered cold list), lays them out bin by
+// bin in LDS, and copies the bins out as contiguous runs.  At the bench stream
+// about 7400 of a block's packets are cold, so a block is one sub-pass with
+// ~29 updates per bin.  Scattered 8-byte stores cost 2-3x the time of runs of >= 16
 // (tools/membench3.hip); the output is identical to K3's.  Rows of at most
 // 512 bins (the bench geometry has 256, configs[5] 512); wider rows use K3.
 // ---------------------------------------------------------------------------
 #ifndef GNS_ST_SUB
 #define GNS_ST_SUB 8192
 #endif
-constexpr uint32_t kStSub = GNS_ST_SUB;               // packets per sub-pass
+constexpr uint32_t kStSub = GNS_ST_SUB;               // (cold) packets per sub-pass
 static_assert(kChunk % kStSub == 0, "whole sub-passes per K1 block");
+constexpr uint32_t kStMaskW = kChunk / 64;            // mask words per K1 block
+static_assert(kStSub <= kColdNone && kChunk <= kColdNone, "16-bit packet offsets, kColdNone = none");
 
 // 1024 threads, rows of at most BINS bins: <256> (the bench geometry) and <512, PK> (the
 // wide/deep configs[4]/[5] geometry: 16 waves in one 136 KB block per CU).  Retired after
@@ -957,6 +972,10 @@ struct StLds {
     uint32_t goff[8][BINS];  // [row]: gns_cm_create rejects a depth above 8
     uint32_t wsum[BINS / 64];
     uint32_t dummy[kStThreads];  // rank adds of lanes without an update
+    uint64_t cmask[kStMaskW];    // the K1 block's cold-packet mask
+    uint32_t cpre[kStMaskW];     // cold packets before each mask word
+    uint32_t cws[kStMaskW / 64];
+    uint16_t clist[kStSub];      // packet offsets of one sub-pass's cold packets
 };
 
 template <int BINS, bool PK>
@@ -972,7 +991,8 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
 #ifdef GNS_K3_PROF
     uint64_t k3t[5] = {0, 0, 0, 0, 0}, k3prev = __builtin_amdgcn_s_memtime();
 #endif
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in a scalar register
     const uint32_t d = a.g.d, nt = a.g.ntiles;
     // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH: observed, not promised),
     // so K1 block b and b + 1 -- whose runs of a bin are adjacent in `entries` and share the
@@ -983,36 +1003,81 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
     const uint32_t tmask = (1u << a.g.bin_bits) - 1u;
     const uint64_t beg = (uint64_t)blk * kChunk;
     const uint64_t end = min(a.n, beg + kChunk);
+    // the block's cold-packet mask and the cold packets before each word (the first loads
+    // depend on them: the bin offsets and the counters are set up behind those loads, below)
+    static_assert(kStMaskW <= kStThreads && kStMaskW % 64 == 0, "whole waves scan the mask words");
+    {
+        uint32_t pc = 0, incl = 0;
+        if (tid < kStMaskW) {
+            const uint32_t nw = (uint32_t)((end - beg + 63) >> 6);  // K1 wrote the words of [beg, end)
+            const uint64_t m = tid < nw ? a.cold[(beg >> 6) + tid] : 0ull;
+            L.cmask[tid] = m;
+            pc = (uint32_t)__popcll(m);
+            incl = wave_incl_scan(pc);
+            if (lane == 63) L.cws[wave] = incl;
+        }
+        __syncthreads();
+        if (tid < kStMaskW) {
+            uint32_t base = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kStMaskW / 64; w++) base += w < wave ? L.cws[w] : 0u;
+            L.cpre[tid] = base + incl - pc;
+        }
+    }
+    uint32_t ncold = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kStMaskW / 64; w++) ncold += L.cws[w];
+    const uint32_t nsub = (ncold + kStSub - 1) / kStSub;  // block-uniform; 0: nothing to scatter
+    // Sub-pass k takes cold ranks [k kStSub, (k + 1) kStSub).  Item j of a lane is rank
+    // wave * (kStSub / kStWaves) + 64 j + lane of the sub-pass: wave-contiguous, (j, lane)
+    // order inside the wave, packet order throughout.  Each wave expands its share of the
+    // mask words into L.clist, which holds sub-pass k's packet offsets while its rows load
+    // (read again at every step: the registers are all spoken for) and sub-pass k + 1's
+    // from the step before k's last row on.
+    auto expand = [&](uint32_t k) {
+        cold_expand_lane(L.cmask, L.cpre, wave * (kStMaskW / kStWaves), (wave + 1) * (kStMaskW / kStWaves), lane,
+                         k * kStSub, kStSub, L.clist);
+    };
+    static_assert(kStMaskW % kStWaves == 0, "whole mask words per wave");
+    uint32_t ids[kStItems], szs[kStItems], cds[kStItems];
+    uint32_t ncd[kStItems], nids[kStItems], nszs[kStItems];
+    // row r's codes of sub-pass k (L.clist holds its offsets), and with r = 0 the ids and
+    // sizes; a rank past the block's cold packets is an empty item.  Block-uniform bases
+    // and 32-bit offsets: one address register per gathered load
+    const uint32_t *kbase = a.keyid + beg, *sbase = a.sizes + beg;
+    auto load_step = [&](uint32_t k, uint32_t r, uint32_t (&c)[kStItems], uint32_t (&di)[kStItems],
+                         uint32_t (&ds)[kStItems]) {
+        const uint32_t *cbase = a.idx + ((uint64_t)r * a.n + beg);
+#pragma unroll
+        for (int j = 0; j < kStItems; j++) {
+            const uint32_t rk = wave * (kStSub / kStWaves) + (uint32_t)j * 64u + lane;
+            const bool has = k * kStSub + rk < ncold;
+            const uint32_t o = has ? (uint32_t)L.clist[rk] : 0u;  // (beg < end: a block has packets)
+            c[j] = cbase[o];
+            if (r == 0) {
+                di[j] = has ? kbase[o] : GNS_ID_NONE;
+                ds[j] = sbase[o];
+            }
+        }
+    };
+    __syncthreads();
+    if (nsub) {
+        expand(0);
+        __syncthreads();
+        load_step(0, 0, cds, ids, szs);
+    }
     for (uint32_t i = tid; i < d * kStBins; i += kStThreads) {
         const uint32_t r = i / kStBins, t = i % kStBins;
         L.goff[r][t] = t < nt ? a.offsets[(uint64_t)blk * a.g.nbins_all + r * nt + t] : 0u;
     }
     for (uint32_t i = tid; i < 2 * kStWaves * kCw; i += kStThreads) (&L.cnt[0][0][0])[i] = 0;
-    // packet of item j in a sub-pass: wave-contiguous, (j, lane) order inside the wave
-    auto pkt = [&](uint64_t sp, int j) { return sp + (uint64_t)wave * (kStSub / kStWaves) + (uint64_t)j * 64 + lane; };
-    uint32_t ids[kStItems], szs[kStItems], cds[kStItems];
-    uint32_t ncd[kStItems], nids[kStItems], nszs[kStItems];
-    auto load_ids = [&](uint64_t sp, uint32_t (&di)[kStItems], uint32_t (&ds)[kStItems]) {
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const uint64_t p = pkt(sp, j);
-            const uint64_t pc = p < end ? p : end - 1;
-            di[j] = p < end ? a.keyid[pc] : GNS_ID_NONE;
-            ds[j] = a.sizes[pc];
-        }
-    };
-    auto load_codes = [&](uint64_t sp, uint32_t r, uint32_t (&c)[kStItems]) {
-#pragma unroll
-        for (int j = 0; j < kStItems; j++) {
-            const uint64_t p = pkt(sp, j);
-            c[j] = a.idx[(uint64_t)r * a.n + (p < end ? p : end - 1)];
-        }
-    };
-    load_ids(beg, ids, szs);
-    load_codes(beg, 0, cds);
+    if (d == 1 && nsub > 1) {  // the first step is sub-pass 0's last row
+        __syncthreads();
+        expand(1);
+    }
     uint32_t par = 0;
     __syncthreads();
-    for (uint64_t sp = beg; sp < end; sp += kStSub) {
+    for (uint32_t k = 0; k < nsub; k++) {
         for (uint32_t r = 0; r < d; r++) {
             uint32_t (&cnt)[kStWaves][kCw] = L.cnt[par];
             K3_MARK(4);  // loop
@@ -1063,11 +1128,9 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
             }
             // the next step's codes (and ids / sizes at a sub-pass boundary) load during C and D
             const uint32_t r1 = r + 1 < d ? r + 1 : 0u;
-            const uint64_t sp1 = r + 1 < d ? sp : sp + kStSub;
-            if (sp1 < end) {
-                load_codes(sp1, r1, ncd);
-                if (r1 == 0) load_ids(sp1, nids, nszs);
-            }
+            const uint32_t k1 = r1 ? k : k + 1;
+            const bool more = k1 < nsub;  // block-uniform
+            if (more) load_step(k1, r1, ncd, nids, nszs);
             __syncthreads();
             K3_MARK(0);
             // phase C: per bin, prefix over the waves and the bin's total; scan of the totals
@@ -1118,6 +1181,10 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
             }
             __syncthreads();
             K3_MARK(1);
+            // When the next step is a sub-pass's last row, it loads the sub-pass after that
+            // one: its offsets replace the list here, between the barrier after this step's
+            // loads and the one before the next step's
+            if (more && r1 + 1 == d && k1 + 1 < nsub) expand(k1 + 1);
             // phase D: updates into the bin-ordered stage
 #pragma unroll
             for (int j = 0; j < kStItems; j++) {
@@ -1134,7 +1201,7 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
             // phase E: take the next step's inputs first (the wait for them lands here,
             // before this step's stores are issued, not after them), then the bins out
             // as contiguous runs; clear this step's counters
-            if (sp1 < end) {
+            if (more) {
 #pragma unroll
                 for (int j = 0; j < kStItems; j++) cds[j] = ncd[j];
                 if (r1 == 0) {
@@ -1155,7 +1222,13 @@ __global__ __launch_bounds__(kStThreads) void k_scatter_st(ScatterArgs a) {
         }
     }
 #ifdef GNS_K3_PROF
-    if (threadIdx.x == 0) for (int i = 0; i < 5; i++) atomicAdd(&a.stats[kStatsProf + i], (unsigned long long)k3t[i]);
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < 5; i++) atomicAdd(&a.stats[kStatsProf + i], (unsigned long long)k3t[i]);
+        // cold packets per K1 block: sum, maximum, blocks needing more than one sub-pass
+        atomicAdd(&a.stats[kStatsProf + 5], (unsigned long long)ncold);
+        atomicMax(&a.stats[kStatsProf + 6], (unsigned long long)ncold);
+        if (nsub > 1) atomicAdd(&a.stats[kStatsProf + 7], 1ull);
+    }
 #endif
 }
 
@@ -2767,6 +2840,7 @@ struct gns_cm : FlowDict {
     uint64_t bmax = 0;
     uint32_t nblk_max = 0;
     uint32_t *keyid = nullptr, *idx = nullptr;
+    uint64_t *cold = nullptr;          // [bmax / 64] K1's cold-packet mask
     uint64_t *pend[2] = {nullptr, nullptr};
     uint32_t *pcnt[2] = {nullptr, nullptr};
     uint32_t *ptotal = nullptr;        // [2]
@@ -2827,7 +2901,7 @@ namespace {
 
 int cm_free_all(gns_cm *cm) {
     dfree(cm->C); dfree(cm->S); dfree(cm->Fc); dfree(cm->Fs); cm->rd.free_all();
-    dfree(cm->keyid); dfree(cm->idx);
+    dfree(cm->keyid); dfree(cm->idx); dfree(cm->cold);
     dfree(cm->pend[0]); dfree(cm->pend[1]); dfree(cm->pcnt[0]); dfree(cm->pcnt[1]);
     dfree(cm->ptotal); dfree(cm->hist); dfree(cm->part); dfree(cm->total); dfree(cm->order);
     dfree(cm->entries); dfree(cm->rec_sizes); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
@@ -2910,7 +2984,7 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
     {
         ExtractArgs a{};
         a.in = in; a.n = n; a.kp = cm->kp; a.g = g; a.D = cm->D; a.epoch = cm->epoch;
-        a.keyid = cm->keyid; a.idx = cm->idx; a.pend = cm->pend[0]; a.pend_cnt = cm->pcnt[0];
+        a.keyid = cm->keyid; a.idx = cm->idx; a.cold = cm->cold; a.pend = cm->pend[0]; a.pend_cnt = cm->pcnt[0];
         a.pend_total = cm->ptotal; a.hist = cm->hist; a.nblk = nblk; a.hot_ids = cm->hot_ids;
         a.Fc = cm->Fc; a.Fs = cm->Fs; a.hsum = cm->hsum; a.hot_tab = cm->hot_tab;
         a.stats = cm->stats;
@@ -3008,7 +3082,7 @@ int cm_run_batch(gns_cm *cm, const InputDesc &in, uint64_t n) {
     {
         ScatterArgs a{};
         a.n = n; a.g = g; a.keyid = cm->keyid; a.idx = cm->idx; a.sizes = in.sizes;
-        a.offsets = cm->hist; a.nblk = nblk; a.entries = cm->entries; a.ovf = cm->ovf;
+        a.offsets = cm->hist; a.nblk = nblk; a.entries = cm->entries; a.ovf = cm->ovf; a.cold = cm->cold;
         a.ovf_cnt = cm->ovf_cnt; a.ovf_cap = (uint32_t)cm->ovf_cap; a.hot_ids = cm->hot_ids; a.stats = cm->stats;
         a.hot_mode = 0; a.hflag2 = cm->hflag2; a.hany = cm->hflag2 + g.d * kHot;
         ScopedStage st(cm->timer, 3);
@@ -3304,6 +3378,7 @@ int gns_cm_create(const gns_cm_params *p, gns_cm **out) {
         // K2 scratch: group sums [ngrp][nbins_all] + bin totals [nbins_all]
         const uint64_t nscan = ((uint64_t)(cm->nblk_max + kTGrp - 1) / kTGrp + 2) * g.nbins_all;
         if ((rc = dalloc_t(&cm->keyid, cm->bmax)) || (rc = dalloc_t(&cm->idx, cm->bmax * g.d)) ||
+            (rc = dalloc_t(&cm->cold, cm->bmax / 64)) ||
             (rc = dalloc_t(&cm->pend[0], cm->bmax)) || (rc = dalloc_t(&cm->pend[1], cm->bmax)) ||
             (rc = dalloc_t(&cm->pcnt[0], cm->nblk_max)) || (rc = dalloc_t(&cm->pcnt[1], cm->nblk_max)) ||
             (rc = dalloc_t(&cm->ptotal, 2)) || (rc = dalloc_t(&cm->hist, (uint64_t)g.nbins_all * cm->nblk_max)) ||
@@ -3762,9 +3837,9 @@ int gns_cm_counters(gns_cm *cm, uint64_t out[8]) {
     out[7] = h[6];
     return GNS_OK;
 #endif
-#ifdef GNS_K3_PROF  // profiling build: K3 phase cycles (loads, rank, scan, stage, write)
-    for (int i = 0; i < 5; i++) out[i] = h[kStatsProf + i];
-    for (int i = 5; i < 8; i++) out[i] = h[i];
+#ifdef GNS_K3_PROF  // profiling build: K3 phase cycles (loads, rank, scan, stage, write), then K3s's
+    // cold packets per K1 block: sum, maximum, blocks taking more than one sub-pass
+    for (int i = 0; i < 8; i++) out[i] = h[kStatsProf + i];
     return GNS_OK;
 #endif
 #ifdef GNS_K4_PROF  // profiling build: K4 phase cycles
