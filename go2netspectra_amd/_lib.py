@@ -47,6 +47,8 @@ EXPORTED = [
     "gns_exs_flush", "gns_exs_query", "gns_exs_query_device", "gns_exs_heavy_hitters", "gns_exs_snapshot",
     "gns_exs_reset", "gns_exs_counters", "gns_exs_dict_stats", "gns_exs_set_timing", "gns_exs_stage_times",
     "gns_ex_aggregate", "gns_ex_heavy_hitters",
+    "gns_ex_view_create", "gns_ex_view_destroy", "gns_ex_view_refresh", "gns_ex_view_snapshot",
+    "gns_ex_view_aggregate", "gns_ex_view_heavy_hitters",
 ]
 
 
@@ -215,6 +217,11 @@ def load() -> ct.CDLL:
         "gns_cm_import_state": ([vp, vp, vp, vp, vp, vp], i32),
         "gns_ss_import_state": ([vp, vp, vp, vp, vp, u64, vp], i32),
         "gns_ex_merge": ([vp, vp, vp, vp, vp, vp, u64, i32], i32),
+        "gns_ex_view_create": ([vp, vp], i32), "gns_ex_view_destroy": ([vp], i32),
+        "gns_ex_view_refresh": ([vp, u64, vp], i32),
+        "gns_ex_view_snapshot": ([vp, vp, vp, vp, vp, vp, vp], i32),
+        "gns_ex_view_aggregate": ([vp, vp, u32, vp], i32),
+        "gns_ex_view_heavy_hitters": ([vp, i32, u64, u64, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -42,11 +42,14 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <mutex>
+#include <optional>
 #include <vector>
 
 #include <rocprim/device/device_merge_sort.hpp>
 
 #include "gns_common.hpp"
+#include "gns_scan.cuh"
 #include "gns_xcd.cuh"
 
 namespace gns {
@@ -453,7 +456,7 @@ extern "C" __device__ unsigned long long __ockl_wfred_add_u64(unsigned long long
 extern "C" __device__ unsigned __ockl_wfred_min_u32(unsigned);
 extern "C" __device__ unsigned __ockl_wfred_max_u32(unsigned);
 extern "C" __device__ unsigned __ockl_wfred_add_u32(unsigned);
-extern "C" __device__ unsigned __ockl_wfscan_add_u32(unsigned, bool);
+// (__ockl_wfscan_add_u32: declared by gns_scan.cuh)
 
 // H: the per-block partials of each designated flow -> its flow state (one
 // workgroup per hot slot; the only writer of these flows until P4, which merges
@@ -972,16 +975,71 @@ __global__ __launch_bounds__(256) void k_ex_list(DictDev D, uint64_t slots, cons
     if (occ) ids[base + __popcll(m & ((1ull << lane) - 1))] = (uint32_t)s;
 }
 
+// ids == NULL: row p is record p (a snapshot view's dense rows); start == NULL: key bytes only
+// (a view's state arrays are dense already)
 __global__ __launch_bounds__(256) void k_ex_gather(const uint32_t *ids, uint64_t n, DictDev D, FlowState f,
                                                    uint8_t *keys, long long *start, long long *end,
                                                    unsigned long long *pkts, unsigned long long *bytes) {
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const uint32_t id = ids[p];
+    const uint32_t id = ids ? ids[p] : (uint32_t)p;
     uint32_t r[12];
     load_record(D, id, r);
     for (uint32_t j = 0; j < D.K; j++) keys[p * D.K + j] = (uint8_t)(r[1 + (j >> 2)] >> (8 * (j & 3)));
-    start[p] = f.start[id]; end[p] = f.end[id]; pkts[p] = f.pkts[id]; bytes[p] = f.bytes[id];
+    if (start) { start[p] = f.start[id]; end[p] = f.end[id]; pkts[p] = f.pkts[id]; bytes[p] = f.bytes[id]; }
+}
+
+// ---------------------------------------------------------------------------
+// Snapshot view (gns_ex_view_refresh): the selected flows -- occupied as k_ex_list
+// has it, and touched after stream position `since` -- compacted in slot order into
+// a dense table of the same layout (records at stride RW, one state array per
+// field), so the query kernels below run on a view as on the live table.
+//   V1 k_exv_count  per block of 256 slots: the number selected (wave ballots)
+//   V2 k_tscan_*    exclusive offsets of the blocks, the total (gns_scan.cuh)
+//   V3 k_exv_write  selected slot -> row = block offset + rank within the block
+// The scan of gns_scan.cuh orders (bin, block) pairs bin-major; slot block i is
+// given bin i / nb and block i % nb of kVBins bins, so that order is slot order
+// and the scan's threads each own one bin.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kVBins = 256;
+__device__ __forceinline__ uint64_t exv_cell(uint32_t i, uint32_t nb) { return (uint64_t)(i % nb) * kVBins + i / nb; }
+__device__ __forceinline__ bool exv_selected(const DictDev &D, const FlowState &f, uint64_t s, uint64_t slots,
+                                             unsigned long long since) {
+    return s < slots && D.rec[s * D.RW] != 0u && f.pkts[s] != 0ull && f.last[s] > since;
+}
+// grid = nb * kVBins blocks (>= the slot blocks; the cells past them count 0)
+__global__ __launch_bounds__(256) void k_exv_count(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
+                                                   uint32_t nb, uint32_t *cnt) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x;
+    const bool sel = exv_selected(D, f, (uint64_t)blockIdx.x * 256 + tid, slots, since);
+    const uint64_t m = __ballot(sel);
+    if ((tid & 63u) == 0) s_w[tid >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (tid == 0) cnt[exv_cell(blockIdx.x, nb)] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+// V: the view's tables (cap rows each); a row past cap is not written (cap >= the claimed slots >= the rows)
+__global__ __launch_bounds__(256) void k_exv_write(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
+                                                   uint32_t nb, const uint32_t *off, DictDev V, FlowState vf,
+                                                   uint64_t cap) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + tid;
+    const bool sel = exv_selected(D, f, s, slots, since);
+    const uint64_t m = __ballot(sel);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!sel) return;
+    uint64_t r = off[exv_cell(blockIdx.x, nb)] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; w++) r += s_w[w];
+    if (r >= cap) return;
+    const uint4 *q = reinterpret_cast<const uint4 *>(D.rec + s * D.RW);
+    uint4 *o = reinterpret_cast<uint4 *>(V.rec + r * D.RW);
+    // {tag, key words} fill at most 11 words: the last quarter of a 16-word record holds nothing
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (4u * i < D.RW) o[i] = i < 3 ? q[i] : make_uint4(0, 0, 0, 0);
+    vf.pkts[r] = f.pkts[s]; vf.bytes[r] = f.bytes[s]; vf.start[r] = f.start[s]; vf.end[r] = f.end[s];
 }
 
 // ---------------------------------------------------------------------------
@@ -1266,6 +1324,96 @@ __global__ __launch_bounds__(256) void k_ex_merge_times(const uint32_t *ids, uin
 
 using namespace gns;
 
+// Scratch of the read side (gns_ex_aggregate, gns_ex_heavy_hitters, a view's snapshot).
+// The handle's own calls take one per call, sized exactly, copy straight to the caller's
+// memory and free it on return, as they always have.  A snapshot view keeps one (keep):
+// its buffers only grow, to twice the request, and every host copy goes through pinned
+// staging -- hipFree synchronizes the device and a copy to pageable memory blocks in the
+// runtime, and neither may happen under a reader while the handle ingests.
+constexpr size_t kPinChunk = 4u << 20;
+struct ExRead {
+    bool keep = false;
+    ExQFilter *df = nullptr;
+    unsigned long long *da = nullptr, *dv = nullptr;
+    uint32_t *dh = nullptr;
+    ExHhRow *rows[2] = {nullptr, nullptr};
+    uint8_t *tmp = nullptr, *dk = nullptr;
+    uint64_t df_n = 0, da_n = 0, dv_n = 0, dh_n = 0, rows_n[2] = {0, 0}, tmp_n = 0, dk_n = 0;
+    uint8_t *pin = nullptr;  // keep: pinned host staging, two chunks
+    size_t pin_n = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // keep: a chunk's copy has landed
+
+    template <class T>
+    int buf(T **p, uint64_t &have, uint64_t need) {
+        if (need <= have && *p) return GNS_OK;
+        dfree(*p);
+        *p = nullptr;
+        have = 0;
+        const uint64_t n = std::max<uint64_t>(keep ? 2 * need : need, 1);
+        GNS_TRY(dalloc_t(p, n));
+        have = n;
+        return GNS_OK;
+    }
+    int reserve_pin(size_t bytes) {
+        if (bytes <= pin_n && pin) return GNS_OK;
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr;
+        pin_n = 0;
+        if (hipHostMalloc(reinterpret_cast<void **>(&pin), bytes, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipHostMalloc(%zu bytes) failed", bytes);
+            return GNS_E_OOM;
+        }
+        pin_n = bytes;
+        return GNS_OK;
+    }
+    int init_keep() {
+        keep = true;
+        for (int i = 0; i < 2; i++)
+            if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
+                set_error("view event");
+                return GNS_E_HIP;
+            }
+        return reserve_pin(2 * kPinChunk);
+    }
+    void free_all() {
+        dfree(df); dfree(da); dfree(dv); dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk);
+        df = nullptr; da = dv = nullptr; dh = nullptr; rows[0] = rows[1] = nullptr; tmp = dk = nullptr;
+        df_n = da_n = dv_n = dh_n = rows_n[0] = rows_n[1] = tmp_n = dk_n = 0;
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr;
+        pin_n = 0;
+        for (int i = 0; i < 2; i++) {
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+            ev[i] = nullptr;
+        }
+    }
+    // Device bytes -> the caller's host memory.  !keep: straight out (the caller synchronizes
+    // the stream).  keep: through the pinned buffer, one half in flight while the other is
+    // copied out; complete on return.
+    int copy_out(void *dst, const void *src, size_t bytes, hipStream_t s) {
+        if (!keep) {
+            GNS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+            return GNS_OK;
+        }
+        const size_t half = pin_n / 2, nchunk = (bytes + half - 1) / half;
+        for (size_t j = 0; j <= nchunk; j++) {
+            if (j < nchunk) {
+                const size_t off = j * half;
+                GNS_HIP(hipMemcpyAsync(pin + (j & 1) * half, static_cast<const uint8_t *>(src) + off,
+                                       std::min(half, bytes - off), hipMemcpyDeviceToHost, s));
+                GNS_HIP(hipEventRecord(ev[j & 1], s));
+            }
+            if (j > 0) {
+                const size_t i = j - 1, off = i * half;
+                GNS_HIP(hipEventSynchronize(ev[i & 1]));
+                memcpy(static_cast<uint8_t *>(dst) + off, pin + (i & 1) * half, std::min(half, bytes - off));
+            }
+        }
+        return GNS_OK;
+    }
+};
+
 struct gns_ex {
     int device = 0;
     bool force_list = false;  // GNS_EX_LIST=1: T/D over the touched list at any table size (tests)
@@ -1304,6 +1452,26 @@ struct gns_ex {
     uint32_t *h_pin = nullptr;
     HostStage stage;
     StageTimer timer;
+};
+
+// A dense copy of the flows one refresh selected: records at stride RW and the four
+// exported state arrays, `cap` rows of room, the row count on the device (*total) until a
+// reader fetches it.  Nothing in it points into the handle's table.
+struct gns_ex_view {
+    gns_ex *ex = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ready = nullptr;
+    std::mutex mu;         // refresh vs readers: a refresh waits for the reader call in progress
+    bool fresh = false;    // refreshed at least once
+    bool counted = false;  // n holds this refresh's row count
+    uint64_t n = 0;
+    DictDev D{};
+    FlowState f{};         // (first / last stay NULL: no query reads them)
+    uint64_t cap = 0;
+    uint32_t *scan = nullptr;  // V1's block counts / offsets, then the scan's group sums and bin totals
+    uint64_t scan_n = 0;
+    uint32_t *total = nullptr;
+    ExRead rd;
 };
 
 namespace {
@@ -1579,6 +1747,236 @@ int ex_insert(gns_ex *ex, const ExIn &x0, uint64_t n, gns_mem where) {
     return GNS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Read side: the query plane as functions of (table, rows, stream, scratch): the same
+// code answers for the live table on the handle's stream and for a view's dense rows on
+// the view's own stream.
+// ---------------------------------------------------------------------------
+// One table the query kernels scan: the live table (rows = slots) or a view's rows.
+struct ExTable {
+    DictDev D;
+    FlowState f;
+    uint64_t rows;
+};
+
+int ex_filters_check(const gns_ex_filter *filters, uint32_t nf) {
+    constexpr uint32_t kFieldBits = (1u << GNS_F_SRCIP) | (1u << GNS_F_DSTIP) | (1u << GNS_F_SRCPORT) |
+                                    (1u << GNS_F_DSTPORT) | (1u << GNS_F_PROTO);
+    for (uint32_t i = 0; i < nf; i++)
+        if (filters[i].mask & ~kFieldBits) {
+            set_error("filter %u: mask 0x%x has bits outside the five key fields", i, filters[i].mask);
+            return GNS_E_ARG;
+        }
+    return GNS_OK;
+}
+
+// gns_ex_aggregate over table T (the argument checks are the caller's; nf != 0)
+int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer,
+                    const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
+    // per filter: the 37 tuple bytes (make_plan's numbering) and which of them are masked;
+    // the layout's byte plan carries them to their place in the record's key words
+    static const struct { uint32_t base, len; } kSpan[6] = {{0, 0}, {0, 16}, {16, 16}, {32, 2}, {34, 2}, {36, 1}};
+    const size_t acc_bytes = (size_t)nf * kQAcc * 8, flt_bytes = (size_t)nf * sizeof(ExQFilter);
+    std::vector<ExQFilter> vf;
+    std::vector<unsigned long long> va;
+    ExQFilter *hf;
+    unsigned long long *ha;
+    if (rd.keep) {  // staged in the view's pinned buffer: accumulators, then filters
+        GNS_TRY(rd.reserve_pin(acc_bytes + flt_bytes));
+        ha = reinterpret_cast<unsigned long long *>(rd.pin);
+        hf = reinterpret_cast<ExQFilter *>(rd.pin + acc_bytes);
+    } else {
+        vf.resize(nf);
+        va.resize((size_t)nf * kQAcc);
+        hf = vf.data();
+        ha = va.data();
+    }
+    for (uint32_t i = 0; i < nf; i++) {
+        const gns_ex_filter &q = filters[i];
+        uint8_t tb[40] = {0}, tm[40] = {0};
+        memcpy(tb, q.src16, 16);
+        memcpy(tb + 16, q.dst16, 16);
+        tb[32] = (uint8_t)(q.sport >> 8); tb[33] = (uint8_t)q.sport;
+        tb[34] = (uint8_t)(q.dport >> 8); tb[35] = (uint8_t)q.dport;
+        tb[36] = q.proto;
+        for (uint32_t fld = GNS_F_SRCIP; fld <= GNS_F_PROTO; fld++)
+            if (q.mask >> fld & 1u) memset(tm + kSpan[fld].base, 0xFF, kSpan[fld].len);
+        ExQFilter &w = hf[i];
+        memset(&w, 0, sizeof(w));
+        uint8_t seen[40] = {0};
+        for (uint32_t j = 0; j < ex->K; j++) {
+            const uint32_t t = ex->kp.src[j];
+            if (t >= 37 || !tm[t]) continue;
+            seen[t] = 1;
+            w.m[j >> 2] |= 0xFFu << (8 * (j & 3));
+            w.v[j >> 2] |= (uint32_t)tb[t] << (8 * (j & 3));
+        }
+        // a masked field outside the key is a NULL column (writer_clickhouse.go:142-148):
+        // `NULL = ?` selects nothing -> a pair no word satisfies
+        for (uint32_t t = 0; t < 37; t++)
+            if (tm[t] && !seen[t]) { w.m[0] = 0u; w.v[0] = 1u; break; }
+        for (uint32_t j = 0; j < kQAcc; j++) ha[(size_t)i * kQAcc + j] = exq_acc_init(j);
+    }
+    if (T.rows != 0) {  // (a view without rows: every answer is the initial one)
+        GNS_TRY(rd.buf(&rd.df, rd.df_n, nf));
+        GNS_TRY(rd.buf(&rd.da, rd.da_n, (uint64_t)nf * kQAcc));
+        ExQFilter *df = rd.df;
+        unsigned long long *da = rd.da;
+        hipError_t e = hipMemcpyAsync(df, hf, flt_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(da, ha, acc_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            std::optional<ScopedStage> stg;
+            if (timer) stg.emplace(*timer, 6);
+            const unsigned grid = (unsigned)std::min<uint64_t>((T.rows + 255) / 256, 2048);
+            for (uint32_t p0 = 0; p0 < nf; p0 += kQBatch) {
+                const uint32_t nb = std::min(kQBatch, nf - p0);
+                if (nb > kQNarrow)
+                    hipLaunchKernelGGL(k_exq_aggregate<true>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, df + p0,
+                                       nb, da + (size_t)p0 * kQAcc);
+                else
+                    hipLaunchKernelGGL(k_exq_aggregate<false>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, df + p0,
+                                       nb, da + (size_t)p0 * kQAcc);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(ha, da, acc_bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("exact aggregate: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    }
+    for (uint32_t i = 0; i < nf; i++) {
+        const unsigned long long *a = &ha[(size_t)i * kQAcc];
+        gns_ex_summary &o = out[i];
+        memset(&o, 0, sizeof(o));
+        if (a[0] == 0) continue;
+        o.flows = a[0]; o.packets = a[1]; o.bytes = a[2];
+        o.first_ns = (int64_t)(a[3] ^ kQSign); o.last_ns = (int64_t)(a[4] ^ kQSign);
+        o.max_packets = a[5]; o.max_bytes = a[6];
+    }
+    return GNS_OK;
+}
+
+// gns_ex_heavy_hitters over table T (the argument checks are the caller's)
+int ex_heavy_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer, int metric,
+                uint64_t threshold, uint64_t limit, uint8_t *keys, uint64_t *values, uint64_t *n_io) {
+    if (T.rows == 0) {  // a view without rows
+        *n_io = 0;
+        return GNS_OK;
+    }
+    const unsigned grid = (unsigned)std::min<uint64_t>((T.rows + 255) / 256, 2048);
+    GNS_TRY(rd.buf(&rd.dh, rd.dh_n, kQBands + 1));  // [0..kQBands) band histogram, [kQBands] rows collected
+    uint32_t *dh = rd.dh;
+    std::vector<uint32_t> vh;
+    uint32_t *hist;
+    if (rd.keep) {
+        hist = reinterpret_cast<uint32_t *>(rd.pin);  // (two chunks of room: never smaller than the histogram)
+    } else {
+        vh.resize(kQBands);
+        hist = vh.data();
+    }
+    hipError_t e = hipMemsetAsync(dh, 0, (kQBands + 1) * 4, s);
+    if (e == hipSuccess) {
+        std::optional<ScopedStage> stg;
+        if (timer) stg.emplace(*timer, 6);
+        hipLaunchKernelGGL(k_exq_hh_hist, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                           (unsigned long long)threshold, dh);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, dh, kQBands * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < kQBands; b++) total += hist[b];
+    const uint64_t cap = *n_io, len = limit ? std::min<uint64_t>(limit, total) : total;
+    *n_io = len;
+    if (len == 0 || len > cap || (!keys && !values)) return GNS_OK;
+    // the lowest band the first `len` rows can reach, and the rows from it up
+    uint32_t band = kQBands - 1;
+    uint64_t nrows = hist[band];
+    while (band > 0 && nrows < len) nrows += hist[--band];
+    size_t tmp_bytes = 0;
+    ExHhRow *none = nullptr;
+    if (rocprim::merge_sort(nullptr, tmp_bytes, none, none, (size_t)nrows, ExHhLess(), s) != hipSuccess) {
+        set_error("exact heavy hitters: merge sort sizing");
+        return GNS_E_HIP;
+    }
+    GNS_TRY(rd.buf(&rd.rows[0], rd.rows_n[0], nrows));
+    GNS_TRY(rd.buf(&rd.rows[1], rd.rows_n[1], nrows));
+    GNS_TRY(rd.buf(&rd.tmp, rd.tmp_n, tmp_bytes));
+    GNS_TRY(rd.buf(&rd.dk, rd.dk_n, len * std::max<uint32_t>(ex->K, 1)));
+    GNS_TRY(rd.buf(&rd.dv, rd.dv_n, len));
+    {
+        std::optional<ScopedStage> stg;
+        if (timer) stg.emplace(*timer, 6);
+        hipLaunchKernelGGL(k_exq_hh_collect, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                           (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = rocprim::merge_sort(rd.tmp, tmp_bytes, rd.rows[0], rd.rows[1], (size_t)nrows, ExHhLess(), s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_exq_hh_out, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, rd.rows[1], len,
+                               ex->K, rd.dk, rd.dv);
+            e = hipGetLastError();
+        }
+    }
+    if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    if (keys) GNS_TRY(rd.copy_out(keys, rd.dk, len * ex->K, s));
+    if (values) GNS_TRY(rd.copy_out(values, rd.dv, len * 8, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+// --- snapshot view ---
+void exv_free_rows(DictDev &D, FlowState &f) {
+    dfree(D.rec); dfree(f.pkts); dfree(f.bytes); dfree(f.start); dfree(f.end);
+    D.rec = nullptr;
+    f.pkts = f.bytes = nullptr;
+    f.start = f.end = nullptr;
+}
+
+void exv_free(gns_ex_view *v) {
+    exv_free_rows(v->D, v->f);
+    dfree(v->scan); dfree(v->total);
+    v->rd.free_all();
+    if (v->ready) (void)hipEventDestroy(v->ready);
+    if (v->stream) (void)hipStreamDestroy(v->stream);
+}
+
+// Room for `need` rows.  Growing is an ingest-side matter: new tables first (a failure
+// leaves the view as it was), then the old ones are freed, which waits for whatever of an
+// earlier refresh is still running on the handle's stream.
+int exv_reserve(gns_ex_view *v, uint64_t need) {
+    if (need <= v->cap) return GNS_OK;
+    const gns_ex *ex = v->ex;
+    const uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(2 * need, ex->slots), need);
+    DictDev D = v->D;
+    FlowState f{};
+    D.rec = nullptr;
+    int rc;
+    if ((rc = dalloc_t(&D.rec, cap * D.RW)) || (rc = dalloc_t(&f.pkts, cap)) || (rc = dalloc_t(&f.bytes, cap)) ||
+        (rc = dalloc_t(&f.start, cap)) || (rc = dalloc_t(&f.end, cap))) {
+        exv_free_rows(D, f);
+        return rc;
+    }
+    exv_free_rows(v->D, v->f);
+    v->D = D;
+    v->f = f;
+    v->cap = cap;
+    return GNS_OK;
+}
+
+// reader side, under v->mu: the view has rows to answer from; v->n = their number
+int exv_rows(gns_ex_view *v) {
+    if (!v->fresh) { set_error("view never refreshed"); return GNS_E_ARG; }
+    if (!v->counted) {
+        uint32_t *h = reinterpret_cast<uint32_t *>(v->rd.pin);
+        GNS_HIP(hipMemcpyAsync(h, v->total, 4, hipMemcpyDeviceToHost, v->stream));
+        GNS_HIP(hipStreamSynchronize(v->stream));
+        v->n = std::min<uint64_t>(*h, v->cap);
+        v->counted = true;
+    }
+    return GNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1795,83 +2193,13 @@ int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_n
 
 int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
     if (!ex || (nf && (!filters || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    constexpr uint32_t kFieldBits = (1u << GNS_F_SRCIP) | (1u << GNS_F_DSTIP) | (1u << GNS_F_SRCPORT) |
-                                    (1u << GNS_F_DSTPORT) | (1u << GNS_F_PROTO);
-    for (uint32_t i = 0; i < nf; i++)
-        if (filters[i].mask & ~kFieldBits) {
-            set_error("filter %u: mask 0x%x has bits outside the five key fields", i, filters[i].mask);
-            return GNS_E_ARG;
-        }
+    GNS_TRY(ex_filters_check(filters, nf));
     if (nf == 0) return GNS_OK;
     GNS_TRY(set_device(ex->device));
-    // per filter: the 37 tuple bytes (make_plan's numbering) and which of them are masked;
-    // the layout's byte plan carries them to their place in the record's key words
-    static const struct { uint32_t base, len; } kSpan[6] = {{0, 0}, {0, 16}, {16, 16}, {32, 2}, {34, 2}, {36, 1}};
-    std::vector<ExQFilter> hf(nf);
-    std::vector<unsigned long long> ha((size_t)nf * kQAcc);
-    for (uint32_t i = 0; i < nf; i++) {
-        const gns_ex_filter &q = filters[i];
-        uint8_t tb[40] = {0}, tm[40] = {0};
-        memcpy(tb, q.src16, 16);
-        memcpy(tb + 16, q.dst16, 16);
-        tb[32] = (uint8_t)(q.sport >> 8); tb[33] = (uint8_t)q.sport;
-        tb[34] = (uint8_t)(q.dport >> 8); tb[35] = (uint8_t)q.dport;
-        tb[36] = q.proto;
-        for (uint32_t fld = GNS_F_SRCIP; fld <= GNS_F_PROTO; fld++)
-            if (q.mask >> fld & 1u) memset(tm + kSpan[fld].base, 0xFF, kSpan[fld].len);
-        ExQFilter &w = hf[i];
-        memset(&w, 0, sizeof(w));
-        uint8_t seen[40] = {0};
-        for (uint32_t j = 0; j < ex->K; j++) {
-            const uint32_t t = ex->kp.src[j];
-            if (t >= 37 || !tm[t]) continue;
-            seen[t] = 1;
-            w.m[j >> 2] |= 0xFFu << (8 * (j & 3));
-            w.v[j >> 2] |= (uint32_t)tb[t] << (8 * (j & 3));
-        }
-        // a masked field outside the key is a NULL column (writer_clickhouse.go:142-148):
-        // `NULL = ?` selects nothing -> a pair no word satisfies
-        for (uint32_t t = 0; t < 37; t++)
-            if (tm[t] && !seen[t]) { w.m[0] = 0u; w.v[0] = 1u; break; }
-        for (uint32_t j = 0; j < kQAcc; j++) ha[(size_t)i * kQAcc + j] = exq_acc_init(j);
-    }
-    hipStream_t s = ex->stream;
-    ExQFilter *df = nullptr;
-    unsigned long long *da = nullptr;
-    GNS_TRY(dalloc_t(&df, nf));
-    int rc = dalloc_t(&da, (size_t)nf * kQAcc);
-    if (rc) { dfree(df); return rc; }
-    hipError_t e = hipMemcpyAsync(df, hf.data(), (size_t)nf * sizeof(ExQFilter), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(da, ha.data(), ha.size() * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        ScopedStage stg(ex->timer, 6);
-        const unsigned grid = (unsigned)std::min<uint64_t>((ex->slots + 255) / 256, 2048);
-        for (uint32_t p0 = 0; p0 < nf; p0 += kQBatch) {
-            const uint32_t nb = std::min(kQBatch, nf - p0);
-            if (nb > kQNarrow)
-                hipLaunchKernelGGL(k_exq_aggregate<true>, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, df + p0,
-                                   nb, da + (size_t)p0 * kQAcc);
-            else
-                hipLaunchKernelGGL(k_exq_aggregate<false>, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, df + p0,
-                                   nb, da + (size_t)p0 * kQAcc);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(ha.data(), da, ha.size() * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dfree(df);
-    dfree(da);
-    if (e != hipSuccess) { set_error("exact aggregate: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    for (uint32_t i = 0; i < nf; i++) {
-        const unsigned long long *a = &ha[(size_t)i * kQAcc];
-        gns_ex_summary &o = out[i];
-        memset(&o, 0, sizeof(o));
-        if (a[0] == 0) continue;
-        o.flows = a[0]; o.packets = a[1]; o.bytes = a[2];
-        o.first_ns = (int64_t)(a[3] ^ kQSign); o.last_ns = (int64_t)(a[4] ^ kQSign);
-        o.max_packets = a[5]; o.max_bytes = a[6];
-    }
-    return GNS_OK;
+    ExRead rd;
+    const int rc = ex_aggregate_on(ex, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, filters, nf, out);
+    rd.free_all();
+    return rc;
 }
 
 int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit, uint8_t *keys,
@@ -1879,64 +2207,145 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
     if (!ex || !n_io) { set_error("null argument"); return GNS_E_ARG; }
     if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
     GNS_TRY(set_device(ex->device));
-    hipStream_t s = ex->stream;
-    const unsigned grid = (unsigned)std::min<uint64_t>((ex->slots + 255) / 256, 2048);
-    uint32_t *dh = nullptr;  // [0..kQBands) band histogram, [kQBands] rows collected
-    GNS_TRY(dalloc_t(&dh, kQBands + 1));
-    std::vector<uint32_t> hist(kQBands);
-    hipError_t e = hipMemsetAsync(dh, 0, (kQBands + 1) * 4, s);
-    if (e == hipSuccess) {
-        ScopedStage stg(ex->timer, 6);
-        hipLaunchKernelGGL(k_exq_hh_hist, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, metric,
-                           (unsigned long long)threshold, dh);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), dh, kQBands * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { dfree(dh); set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    uint64_t total = 0;
-    for (uint32_t b = 0; b < kQBands; b++) total += hist[b];
-    const uint64_t cap = *n_io, len = limit ? std::min<uint64_t>(limit, total) : total;
-    *n_io = len;
-    if (len == 0 || len > cap || (!keys && !values)) { dfree(dh); return GNS_OK; }
-    // the lowest band the first `len` rows can reach, and the rows from it up
-    uint32_t band = kQBands - 1;
-    uint64_t nrows = hist[band];
-    while (band > 0 && nrows < len) nrows += hist[--band];
-    ExHhRow *rows[2] = {nullptr, nullptr};
-    void *tmp = nullptr;
-    uint8_t *dk = nullptr;
-    unsigned long long *dv = nullptr;
-    size_t tmp_bytes = 0;
+    ExRead rd;
+    const int rc = ex_heavy_on(ex, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, metric, threshold,
+                               limit, keys, values, n_io);
+    rd.free_all();
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Snapshot views: the table, or the flows touched since a cursor, exported and
+// queried on another thread while the handle ingests (the reference's snapshotter
+// hands every flow to the writer while the workers insert, manager.go:139-159,
+// exact/task.go:154-194).
+// ---------------------------------------------------------------------------
+int gns_ex_view_create(gns_ex *ex, gns_ex_view **out) {
+    if (!ex || !out) { set_error("null argument"); return GNS_E_ARG; }
+    *out = nullptr;
+    GNS_TRY(set_device(ex->device));
+    gns_ex_view *v = new gns_ex_view();
+    v->ex = ex;
+    v->D = ex->D;  // RW, K: the record layout; the rest names nothing of the handle's
+    v->D.rec = nullptr; v->D.ctl = nullptr; v->D.mask = 0; v->D.cap = 0;
     int rc = GNS_OK;
-    ExHhRow *sorted = nullptr;
-    if (rocprim::merge_sort(nullptr, tmp_bytes, rows[0], rows[1], (size_t)nrows, ExHhLess(), s) != hipSuccess) e = hipErrorUnknown;
-    if (e == hipSuccess && ((rc = dalloc_t(&rows[0], nrows)) || (rc = dalloc_t(&rows[1], nrows)) ||
-                            (rc = dalloc(&tmp, tmp_bytes)) ||
-                            (rc = dalloc(reinterpret_cast<void **>(&dk), len * std::max<uint32_t>(ex->K, 1))) ||
-                            (rc = dalloc_t(&dv, len)))) {
-        dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk); dfree(dv);
-        return rc;
-    }
-    if (e == hipSuccess) {
-        ScopedStage stg(ex->timer, 6);
-        hipLaunchKernelGGL(k_exq_hh_collect, dim3(grid), dim3(256), 0, s, ex->D, ex->slots, ex->f, metric,
-                           (unsigned long long)threshold, band, rows[0], dh + kQBands, (uint32_t)nrows);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = rocprim::merge_sort(tmp, tmp_bytes, rows[0], rows[1], (size_t)nrows, ExHhLess(), s);
-        sorted = rows[1];
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_exq_hh_out, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, sorted, len, ex->K,
-                               dk, dv);
-            e = hipGetLastError();
+    do {
+        // the device's highest priority, as a Count-Min view's stream: a reader's small
+        // launches are dispatched ahead of the ingest pipeline's queued workgroups
+        int lo_pri = 0, hi_pri = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
+        if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
+            hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess) {
+            set_error("view stream/event"); rc = GNS_E_HIP; break;
         }
-    }
-    if (e == hipSuccess && keys) e = hipMemcpyAsync(keys, dk, len * ex->K, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && values) e = hipMemcpyAsync(values, dv, len * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk); dfree(dv);
-    if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+        if ((rc = v->rd.init_keep()) != GNS_OK || (rc = dalloc_t(&v->total, 4)) != GNS_OK) break;
+    } while (0);
+    if (rc) { exv_free(v); delete v; return rc; }
+    *out = v;
     return GNS_OK;
+}
+
+int gns_ex_view_destroy(gns_ex_view *v) {
+    if (!v) return GNS_OK;
+    (void)hipSetDevice(v->ex->device);
+    {   // wait for a reader call in progress; the mutex is released before the delete
+        std::lock_guard<std::mutex> lk(v->mu);
+        if (v->stream) (void)hipStreamSynchronize(v->stream);
+        // (freeing the tables waits for a refresh still running on the handle's stream)
+    }
+    exv_free(v);
+    delete v;
+    return GNS_OK;
+}
+
+int gns_ex_view_refresh(gns_ex_view *v, uint64_t since, uint64_t *cursor) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    gns_ex *ex = v->ex;
+    const uint64_t pos = ex->pkt + ex->merged;  // the next stream position (ex_run_batch, gns_ex_merge)
+    if (since > pos) {
+        set_error("view refresh: since %llu is beyond the stream position %llu", (unsigned long long)since,
+                  (unsigned long long)pos);
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(ex->device));
+    std::lock_guard<std::mutex> lk(v->mu);  // no reader is using the rows
+    GNS_TRY(exv_reserve(v, std::max<uint64_t>(ex->claimed, 1)));  // rows <= flows with packets <= claimed slots
+    const uint32_t nblk = (uint32_t)((ex->slots + 255) / 256);
+    const uint32_t nb = (nblk + kVBins - 1) / kVBins, ngrp = (nb + kTGrp - 1) / kTGrp;
+    const uint64_t words = (uint64_t)nb * kVBins + (uint64_t)ngrp * kVBins + kVBins;
+    if (words > v->scan_n) GNS_TRY(grow_buf(&v->scan, v->scan_n, words));
+    uint32_t *cnt = v->scan, *part = cnt + (uint64_t)nb * kVBins, *tot = part + (uint64_t)ngrp * kVBins;
+    hipStream_t s = ex->stream;
+    v->fresh = false;
+    {
+        ScopedStage st(ex->timer, 7);
+        hipLaunchKernelGGL(k_exv_count, dim3(nb * kVBins), dim3(256), 0, s, ex->D, ex->slots, ex->f,
+                           (unsigned long long)since, nb, cnt);
+        hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part);
+        hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, s, part, ngrp, kVBins, tot);
+        hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, s, tot, kVBins, v->total);
+        hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part, tot);
+        hipLaunchKernelGGL(k_exv_write, dim3(nblk), dim3(256), 0, s, ex->D, ex->slots, ex->f,
+                           (unsigned long long)since, nb, cnt, v->D, v->f, v->cap);
+        GNS_HIP(hipGetLastError());
+    }
+    // the rows are the state after every insert and merge issued so far and before any
+    // later one; the view's stream waits for them
+    GNS_HIP(hipEventRecord(v->ready, s));
+    GNS_HIP(hipStreamWaitEvent(v->stream, v->ready, 0));
+    v->fresh = true;
+    v->counted = false;
+    if (cursor) *cursor = pos;
+    return GNS_OK;
+}
+
+int gns_ex_view_snapshot(gns_ex_view *v, uint8_t *keys, int64_t *start_ns, int64_t *end_ns, uint64_t *pkts,
+                         uint64_t *bytes, uint64_t *n_io) {
+    if (!v || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(v->ex->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(exv_rows(v));
+    const uint64_t m = std::min<uint64_t>(*n_io, v->n);
+    *n_io = v->n;
+    if (m == 0) return GNS_OK;
+    hipStream_t s = v->stream;
+    ExRead &rd = v->rd;
+    const uint32_t K = v->ex->K;
+    if (keys) {
+        GNS_TRY(rd.buf(&rd.dk, rd.dk_n, m * K));
+        hipLaunchKernelGGL(k_ex_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)nullptr, m,
+                           v->D, v->f, rd.dk, (long long *)nullptr, (long long *)nullptr,
+                           (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+        GNS_HIP(hipGetLastError());
+        GNS_TRY(rd.copy_out(keys, rd.dk, m * K, s));
+    }
+    if (start_ns) GNS_TRY(rd.copy_out(start_ns, v->f.start, m * 8, s));
+    if (end_ns) GNS_TRY(rd.copy_out(end_ns, v->f.end, m * 8, s));
+    if (pkts) GNS_TRY(rd.copy_out(pkts, v->f.pkts, m * 8, s));
+    if (bytes) GNS_TRY(rd.copy_out(bytes, v->f.bytes, m * 8, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+int gns_ex_view_aggregate(gns_ex_view *v, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
+    if (!v || (nf && (!filters || !out))) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(ex_filters_check(filters, nf));
+    GNS_TRY(set_device(v->ex->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(exv_rows(v));
+    if (nf == 0) return GNS_OK;
+    return ex_aggregate_on(v->ex, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, filters, nf, out);
+}
+
+int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, uint64_t limit, uint8_t *keys,
+                              uint64_t *values, uint64_t *n_io) {
+    if (!v || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
+    GNS_TRY(set_device(v->ex->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(exv_rows(v));
+    return ex_heavy_on(v->ex, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, metric, threshold, limit, keys,
+                       values, n_io);
 }
 
 int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,

@@ -196,6 +196,115 @@ def _is_dev(a) -> bool:
     return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
 
 
+def _snapshot_arrays(fn, h, key_bytes: int):
+    """The two calls of a snapshot export (length, then rows) through gns_ex_snapshot or
+    gns_ex_view_snapshot."""
+    n = ct.c_uint64(0)
+    check(fn(h, None, None, None, None, None, ct.byref(n)))
+    m = n.value
+    K = max(key_bytes, 1)
+    keys = np.zeros((max(m, 1), K), np.uint8)
+    st, en = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+    pk, by = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+    n2 = ct.c_uint64(m)
+    check(fn(h, keys.ctypes.data, st.ctypes.data, en.ctypes.data, pk.ctypes.data, by.ctypes.data, ct.byref(n2)))
+    m = min(m, n2.value)
+    return keys[:m, :key_bytes], st[:m], en[:m], pk[:m], by[:m]
+
+
+def _aggregate(fn, h, filters) -> List[Summary]:
+    flt = [f if isinstance(f, _lib.ExFilter) else make_filter(**f) for f in filters]
+    for f in flt:
+        check_filter(f)
+    n = len(flt)
+    if n == 0:
+        return []
+    arr = (_lib.ExFilter * n)(*flt)
+    out = (_lib.ExSummary * n)()
+    check(fn(h, arr, n, out))
+    return [Summary(int(o.flows), int(o.packets), int(o.bytes), int(o.first_ns), int(o.last_ns),
+                    int(o.max_packets), int(o.max_bytes)) for o in out]
+
+
+def _heavy_hitters(fn, h, key_bytes: int, metric: int, threshold: int, limit: int):
+    if metric not in (0, 1):
+        raise ValueError(f"metric {metric}: 0 (PacketCount) or 1 (ByteCount)")
+    if threshold < 0 or limit < 0:
+        raise ValueError("threshold and limit are unsigned")
+    n = ct.c_uint64(limit if 0 < limit <= 1 << 16 else 0)
+    if n.value == 0:  # the list's length first
+        check(fn(h, metric, threshold, limit, None, None, ct.byref(n)))
+    cap = n.value
+    K = max(key_bytes, 1)
+    keys, vals = np.zeros((max(cap, 1), K), np.uint8), np.zeros(max(cap, 1), np.uint64)
+    if cap:
+        check(fn(h, metric, threshold, limit, keys.ctypes.data, vals.ctypes.data, ct.byref(n)))
+    m = min(cap, n.value)
+    return keys[:m, :key_bytes], vals[:m]
+
+
+def apply_delta(state: dict, arrays) -> dict:
+    """The consumer's rule for delta exports: fold the rows of one ``snapshot_arrays()`` (of a
+    full or a delta view) into a map key bytes -> (start, end, packets, bytes) and return the
+    new map.  Rows carry cumulative state, so a later row of a key replaces the earlier one
+    (the store's argMax(..., Timestamp), querier.go:191-248); an empty delta changes nothing."""
+    keys, st, en, pk, by = arrays
+    out = dict(state)
+    for i in range(len(pk)):
+        out[bytes(keys[i])] = (int(st[i]), int(en[i]), int(pk[i]), int(by[i]))
+    return out
+
+
+class ExactView:
+    """Snapshot view of an ExactAggregator (gns_ex_view_*): a dense copy of the table, or of
+    the flows touched since a cursor, taken at a point of the insert stream (``refresh``) and
+    exported or queried from any thread while the aggregator keeps ingesting.  The rows stay
+    what they were at the refresh whatever the aggregator does afterwards, reset included."""
+
+    def __init__(self, agg: "ExactAggregator"):
+        self._L = agg._L
+        self._agg = agg  # the handle outlives its views
+        self.key_fields = list(agg.key_fields)
+        self.key_bytes = agg.key_bytes
+        h = ct.c_void_p()
+        check(self._L.gns_ex_view_create(agg._h, ct.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.gns_ex_view_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def refresh(self, since: int = 0) -> int:
+        """Ingest side, asynchronous: select the flows touched after ``since`` (0: every flow;
+        else a cursor an earlier refresh returned) as of every insert and merge issued so far.
+        Returns the cursor of this point."""
+        if since < 0:
+            raise ValueError("since is a stream position (unsigned)")
+        cur = ct.c_uint64(0)
+        check(self._L.gns_ex_view_refresh(self._h, since, ct.byref(cur)))
+        return int(cur.value)
+
+    def snapshot_arrays(self):
+        """(keys [n,K] canonical bytes, start, end, packets, bytes) of the view's rows, dictionary
+        slot order: after refresh(0), what ExactAggregator.snapshot_arrays() gave at that point."""
+        return _snapshot_arrays(self._L.gns_ex_view_snapshot, self._h, self.key_bytes)
+
+    def aggregate(self, filters) -> List[Summary]:
+        """ExactAggregator.aggregate over the view's rows."""
+        return _aggregate(self._L.gns_ex_view_aggregate, self._h, filters)
+
+    def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0):
+        """ExactAggregator.heavy_hitters over the view's rows."""
+        return _heavy_hitters(self._L.gns_ex_view_heavy_hitters, self._h, self.key_bytes, metric, threshold, limit)
+
+
 class ExactAggregator:
     """One exact task's device state (gns_ex handle)."""
 
@@ -212,6 +321,8 @@ class ExactAggregator:
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            for v in list(getattr(self, "_views", ())):  # a view is destroyed before its handle
+                v.close()
             self._L.gns_ex_destroy(self._h)
             self._h = None
 
@@ -268,18 +379,16 @@ class ExactAggregator:
 
     def snapshot_arrays(self):
         """(keys [n,K] canonical bytes, start, end, packets, bytes), dictionary slot order."""
-        n = ct.c_uint64(0)
-        check(self._L.gns_ex_snapshot(self._h, None, None, None, None, None, ct.byref(n)))
-        m = n.value
-        K = max(self.key_bytes, 1)
-        keys = np.zeros((max(m, 1), K), np.uint8)
-        st, en = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
-        pk, by = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
-        n2 = ct.c_uint64(m)
-        check(self._L.gns_ex_snapshot(self._h, keys.ctypes.data, st.ctypes.data, en.ctypes.data, pk.ctypes.data,
-                                      by.ctypes.data, ct.byref(n2)))
-        m = min(m, n2.value)
-        return keys[:m, : self.key_bytes], st[:m], en[:m], pk[:m], by[:m]
+        return _snapshot_arrays(self._L.gns_ex_snapshot, self._h, self.key_bytes)
+
+    def view(self) -> ExactView:
+        """A snapshot view of this aggregator (closed with it at the latest)."""
+        import weakref
+        v = ExactView(self)
+        if not hasattr(self, "_views"):
+            self._views = weakref.WeakSet()
+        self._views.add(v)
+        return v
 
     def merge(self, keys, start, end, pkts, bytes) -> None:
         """gns_ex_merge: add the rows of a snapshot_arrays() (this handle's or another shard's) to
@@ -317,37 +426,13 @@ class ExactAggregator:
     def aggregate(self, filters) -> List[Summary]:
         """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
         arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
-        flt = [f if isinstance(f, _lib.ExFilter) else make_filter(**f) for f in filters]
-        for f in flt:
-            check_filter(f)
-        n = len(flt)
-        if n == 0:
-            return []
-        arr = (_lib.ExFilter * n)(*flt)
-        out = (_lib.ExSummary * n)()
-        check(self._L.gns_ex_aggregate(self._h, arr, n, out))
-        return [Summary(int(o.flows), int(o.packets), int(o.bytes), int(o.first_ns), int(o.last_ns),
-                        int(o.max_packets), int(o.max_bytes)) for o in out]
+        return _aggregate(self._L.gns_ex_aggregate, self._h, filters)
 
     def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0):
         """gns_ex_heavy_hitters: (keys [n, K] canonical bytes, values uint64 [n]) of the flows
         with PacketCount (metric 0) / ByteCount (metric 1) >= threshold, value descending, ties
         by key bytes ascending, cut to ``limit`` rows when limit != 0."""
-        if metric not in (0, 1):
-            raise ValueError(f"metric {metric}: 0 (PacketCount) or 1 (ByteCount)")
-        if threshold < 0 or limit < 0:
-            raise ValueError("threshold and limit are unsigned")
-        n = ct.c_uint64(limit if 0 < limit <= 1 << 16 else 0)
-        if n.value == 0:  # the list's length first
-            check(self._L.gns_ex_heavy_hitters(self._h, metric, threshold, limit, None, None, ct.byref(n)))
-        cap = n.value
-        K = max(self.key_bytes, 1)
-        keys, vals = np.zeros((max(cap, 1), K), np.uint8), np.zeros(max(cap, 1), np.uint64)
-        if cap:
-            check(self._L.gns_ex_heavy_hitters(self._h, metric, threshold, limit, keys.ctypes.data, vals.ctypes.data,
-                                               ct.byref(n)))
-        m = min(cap, n.value)
-        return keys[:m, : self.key_bytes], vals[:m]
+        return _heavy_hitters(self._L.gns_ex_heavy_hitters, self._h, self.key_bytes, metric, threshold, limit)
 
     def reset(self) -> None:
         check(self._L.gns_ex_reset(self._h))
@@ -367,7 +452,7 @@ class ExactAggregator:
     def set_timing(self, on: bool = True, stages=None) -> None:
         check(self._L.gns_ex_set_timing(self._h, _lib.timing_arg(on, stages, self.STAGES)))
 
-    STAGES = ["extract", "resolve", "partition", "aggregate", "hot", "total", "query"]
+    STAGES = ["extract", "resolve", "partition", "aggregate", "hot", "total", "query", "view"]
 
     def stage_times(self, reset: bool = False) -> dict:
         ms = (ct.c_double * 8)()
@@ -434,22 +519,33 @@ class ExactTask:
             return 0
         return int(self.agg.query_many(np.frombuffer(bytes(flow), np.uint8).reshape(1, -1))[0])
 
-    def flows(self) -> List[Flow]:
-        keys, st, en, pk, by = self.agg.snapshot_arrays()
+    def flows(self, arrays=None) -> List[Flow]:
+        keys, st, en, pk, by = self.agg.snapshot_arrays() if arrays is None else arrays
         out = []
         for i in range(len(pk)):
             k, vals = key_string(bytes(keys[i]), self.key_fields)
             out.append(Flow(k, vals, int(st[i]), int(en[i]), int(by[i]), int(pk[i])))
         return out
 
-    def snapshot(self) -> SnapshotData:
+    def snapshot(self, arrays=None) -> SnapshotData:
         """Snapshot (task.go:153-191).  The reference spreads flows over shards by a
         randomly seeded maphash; here by a fixed hash of the key string."""
         import zlib
         shards = [Shard() for _ in range(self.shard_count)]
-        for f in self.flows():
+        for f in self.flows(arrays):
             shards[zlib.crc32(f.Key.encode()) % self.shard_count].Flows[f.Key] = f
         return SnapshotData(self.name_, shards)
+
+    def view(self) -> ExactView:
+        """A snapshot view of the task's table: refresh it on the ingest thread at the interval's
+        end, then hand it to the snapshotter / alerter thread (snapshot_from, view.aggregate)."""
+        return self.agg.view()
+
+    def snapshot_from(self, view: ExactView) -> SnapshotData:
+        """Snapshot built from a view's rows instead of the live table: the whole table after
+        view.refresh(), the interval's changed flows after view.refresh(cursor).  May run on
+        another thread while the task keeps ingesting."""
+        return self.snapshot(view.snapshot_arrays())
 
     def reset(self) -> None:
         self.agg.reset()

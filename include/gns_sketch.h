@@ -517,7 +517,8 @@ int gns_ex_counters(gns_ex *ex, uint64_t out[8]);
 int gns_ex_dict_stats(gns_ex *ex, uint64_t out[8]);
 int gns_ex_set_timing(gns_ex *ex, int on);
 /* stages: 0 extract, 1 resolve, 2 partition, 3 aggregate, 4 hot flows + timestamps, 5 total
- * (of an insert batch), 6 query (the device work of gns_ex_aggregate / gns_ex_heavy_hitters) */
+ * (of an insert batch), 6 query (the device work of gns_ex_aggregate / gns_ex_heavy_hitters),
+ * 7 view (the device work of gns_ex_view_refresh) */
 int gns_ex_stage_times(gns_ex *ex, double ms[8], uint64_t launches[8], int reset);
 
 /* Query plane: the three questions of query.Querier (internal/query/querier.go)
@@ -557,6 +558,51 @@ int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_
  * gns_ex_snapshot, values 64-bit.  threshold 0 lists every flow.  keys / values may be NULL. */
 int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit,
                          uint8_t *keys, uint64_t *values, uint64_t *n_io);
+
+/* Snapshot view: the table, or the flows touched since a cursor, exported and queried
+ * CONCURRENTLY with ingest.  The reference's snapshotter hands every flow of every exact
+ * task to a writer each interval while the workers keep inserting (manager.go:139-159,
+ * exact/task.go:154-194), and the alerter reads the totals (exact/task.go:224-233).  A view
+ * holds a dense copy of the selected flows, key bytes included, so it stays valid
+ * whatever the handle does afterwards: insert, merge, table growth, reset.
+ *   - Refresh point.  gns_ex_view_refresh is an ingest-side call (serialised with the
+ *     handle's other calls) and asynchronous on the handle's stream.  The view then answers
+ *     for the state after every insert or merge issued before that refresh, whatever
+ *     follows on the handle.  A reset does not stale it (unlike a Count-Min view): nothing
+ *     is resolved through the live dictionary.
+ *   - since == 0 selects every flow gns_ex_snapshot would list at that point.  since == a
+ *     cursor an earlier refresh of this handle returned selects only the flows that took a
+ *     packet or a merged row after that point.  since beyond the current position:
+ *     GNS_E_ARG, the view is untouched.
+ *   - Cursor.  *cursor = the next stream position the handle will assign (records inserted
+ *     + rows merged so far; positions never restart): feed it to the next refresh.  A
+ *     cursor taken before gns_ex_reset selects every flow of the new period, since the
+ *     table was emptied after it.  cursor may be NULL.
+ *   - Rows carry cumulative state (start, end, pkts, bytes as of the refresh), not
+ *     increments, in dictionary-slot order: gns_ex_view_snapshot after a refresh with
+ *     since == 0 returns arrays bit-equal to gns_ex_snapshot called at that point.  The
+ *     reference's store keeps the latest row per flow (argMax(..., Timestamp),
+ *     querier.go:191-248), so a writer that stores only each interval's delta answers
+ *     every query as one that stores the whole table each time.
+ *   - gns_ex_view_snapshot / _aggregate / _heavy_hitters take the arguments of
+ *     gns_ex_snapshot / gns_ex_aggregate / gns_ex_heavy_hitters and answer over the view's
+ *     rows.  They may run on any thread while the handle ingests, on the view's own
+ *     stream, and allocate and free nothing once warm.  There is no point query: a filter
+ *     on every key field through gns_ex_view_aggregate is one (TraceFlow).
+ *   - A view that was never refreshed answers GNS_E_ARG.  A refresh waits for a reader
+ *     call in progress on the same view.  Null-argument checks run before any device
+ *     call.  Destroy a view before its handle.
+ * Memory: a record plus 32 bytes per row, for the flows the handle held at the refresh
+ * (the buffers only grow), and 8 MB of pinned host staging. */
+typedef struct gns_ex_view gns_ex_view;
+int gns_ex_view_create(gns_ex *ex, gns_ex_view **out);
+int gns_ex_view_destroy(gns_ex_view *v);
+int gns_ex_view_refresh(gns_ex_view *v, uint64_t since, uint64_t *cursor);
+int gns_ex_view_snapshot(gns_ex_view *v, uint8_t *keys, int64_t *start_ns, int64_t *end_ns,
+                         uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
+int gns_ex_view_aggregate(gns_ex_view *v, const gns_ex_filter *f, uint32_t nf, gns_ex_summary *out);
+int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, uint64_t limit,
+                              uint8_t *keys, uint64_t *values, uint64_t *n_io);
 
 /* ------------------------------------------------------------------ */
 /* Exact spread: the device ground truth of SuperSpread                */

@@ -726,14 +726,9 @@ func exactFilterIP(dst *[16]C.uint8_t, ip net.IP) error {
 	return nil
 }
 
-// Aggregate answers every filter from one device scan per 64 filters (gns_ex_aggregate):
-// AggregateFlows and TraceFlow on the live table, without a snapshot leaving the GPU.
-func (e *Exact) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
-	n := len(filters)
-	if n == 0 {
-		return nil, nil
-	}
-	cf := make([]C.gns_ex_filter, n)
+// exactFilters lays the filters out as gns_ex_filter.
+func exactFilters(filters []ExactFilter) ([]C.gns_ex_filter, error) {
+	cf := make([]C.gns_ex_filter, len(filters))
 	for i, f := range filters {
 		if f.SrcIP != nil {
 			if err := exactFilterIP(&cf[i].src16, f.SrcIP); err != nil {
@@ -760,17 +755,35 @@ func (e *Exact) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
 			cf[i].mask |= 1 << C.GNS_F_PROTO
 		}
 	}
-	cs := make([]C.gns_ex_summary, n)
-	if err := lastErr(C.gns_ex_aggregate(e.h, &cf[0], C.uint32_t(n), &cs[0])); err != nil {
-		return nil, err
-	}
-	out := make([]ExactSummary, n)
+	return cf, nil
+}
+
+func exactSummaries(cs []C.gns_ex_summary) []ExactSummary {
+	out := make([]ExactSummary, len(cs))
 	for i, s := range cs {
 		out[i] = ExactSummary{Flows: uint64(s.flows), Packets: uint64(s.packets), Bytes: uint64(s.bytes),
 			FirstNs: int64(s.first_ns), LastNs: int64(s.last_ns),
 			MaxPackets: uint64(s.max_packets), MaxBytes: uint64(s.max_bytes)}
 	}
-	return out, nil
+	return out
+}
+
+// Aggregate answers every filter from one device scan per 64 filters (gns_ex_aggregate):
+// AggregateFlows and TraceFlow on the live table, without a snapshot leaving the GPU.
+func (e *Exact) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cf, err := exactFilters(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_aggregate(e.h, &cf[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
 }
 
 // HeavyHitters is QueryHeavyHitters (querier.go:191-248) on the live table (gns_ex_heavy_hitters):
@@ -816,6 +829,88 @@ func (e *Exact) Reset() { C.gns_ex_reset(e.h) }
 
 // Close releases the device state.
 func (e *Exact) Close() { C.gns_ex_destroy(e.h) }
+
+// ExactView is a snapshot view of an Exact (gns_ex_view_*) for the snapshotter and alerter
+// goroutines (manager.go:139-159, exact/task.go:154-194, :224-233): a dense copy of the
+// table, or of the flows touched since a cursor, taken by Refresh on the ingest goroutine
+// and read by Flows / Aggregate / HeavyHitters on any other goroutine while the task keeps
+// inserting.  It stays what it was at the Refresh whatever the Exact does afterwards, Reset
+// included.  Close it before its Exact.
+type ExactView struct {
+	v        *C.gns_ex_view
+	keyBytes int
+}
+
+// NewView allocates an empty view; its tables are sized by the first Refresh.
+func (e *Exact) NewView() (*ExactView, error) {
+	var v *C.gns_ex_view
+	if err := lastErr(C.gns_ex_view_create(e.h, &v)); err != nil {
+		return nil, err
+	}
+	return &ExactView{v: v, keyBytes: e.keyBytes}, nil
+}
+
+// Refresh selects, as of every InsertTuples and Merge issued so far, the flows touched after
+// the cursor since (0: every flow) and returns the cursor of this point for the next call.
+// Rows are cumulative, and the store keeps the latest row per flow, so a writer may store
+// only each interval's delta.  Ingest side: call it where the Exact's other calls are made.
+func (w *ExactView) Refresh(since uint64) (cursor uint64, err error) {
+	var c C.uint64_t
+	err = lastErr(C.gns_ex_view_refresh(w.v, C.uint64_t(since), &c))
+	return uint64(c), err
+}
+
+// Flows returns the view's rows in the layout of Exact.Flows (after Refresh(0): the arrays
+// Exact.Flows returned at that point).
+func (w *ExactView) Flows() (keys []byte, start, end []int64, pkts, bytes []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_view_snapshot(w.v, nil, nil, nil, nil, nil, &n)); err != nil {
+		return
+	}
+	m := int(n)
+	keys = make([]byte, m*w.keyBytes+1)
+	start, end = make([]int64, m+1), make([]int64, m+1)
+	pkts, bytes = make([]uint64, m+1), make([]uint64, m+1)
+	err = lastErr(C.gns_ex_view_snapshot(w.v, (*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.int64_t)(unsafe.Pointer(&start[0])),
+		(*C.int64_t)(unsafe.Pointer(&end[0])), (*C.uint64_t)(unsafe.Pointer(&pkts[0])),
+		(*C.uint64_t)(unsafe.Pointer(&bytes[0])), &n))
+	m = int(n)
+	return keys[:m*w.keyBytes], start[:m], end[:m], pkts[:m], bytes[:m], err
+}
+
+// Aggregate is Exact.Aggregate over the view's rows (the alerter's totals: one open filter).
+func (w *ExactView) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cf, err := exactFilters(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_view_aggregate(w.v, &cf[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
+}
+
+// HeavyHitters is Exact.HeavyHitters over the view's rows.
+func (w *ExactView) HeavyHitters(metric int, threshold, limit uint64) (keys []byte, values []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_view_heavy_hitters(w.v, C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		nil, nil, &n)); err != nil || n == 0 {
+		return nil, nil, err
+	}
+	m := int(n)
+	keys, values = make([]byte, m*w.keyBytes+1), make([]uint64, m)
+	err = lastErr(C.gns_ex_view_heavy_hitters(w.v, C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		(*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint64_t)(unsafe.Pointer(&values[0])), &n))
+	return keys[:m*w.keyBytes], values, err
+}
+
+// Close releases the view.
+func (w *ExactView) Close() { C.gns_ex_view_destroy(w.v) }
 
 // ThriftDecoder holds the device buffers one batch of NATS messages decodes into
 // (ns-engine's live path: stream_aggregator.go:85 decodes one PacketInfo message
