@@ -49,6 +49,7 @@ EXPORTED = [
     "gns_ex_aggregate", "gns_ex_heavy_hitters",
     "gns_ex_view_create", "gns_ex_view_destroy", "gns_ex_view_refresh", "gns_ex_view_snapshot",
     "gns_ex_view_aggregate", "gns_ex_view_heavy_hitters",
+    "gns_pairs_export", "gns_pairs_merge", "gns_pairs_merge_from",
 ]
 
 
@@ -222,6 +223,9 @@ def load() -> ct.CDLL:
         "gns_ex_view_snapshot": ([vp, vp, vp, vp, vp, vp, vp], i32),
         "gns_ex_view_aggregate": ([vp, vp, u32, vp], i32),
         "gns_ex_view_heavy_hitters": ([vp, i32, u64, u64, vp, vp, vp], i32),
+        "gns_pairs_export": ([vp, u64, vp, vp, vp, vp, i32], i32),
+        "gns_pairs_merge": ([vp, vp, u32, vp, u32, u64, i32], i32),
+        "gns_pairs_merge_from": ([vp, vp, u64, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

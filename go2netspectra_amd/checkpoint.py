@@ -3,8 +3,9 @@
 The reference keeps a measurement period's state in process memory only (SURVEY
 §5 "Checkpoint/resume: no"); here it lives in HBM.  ``save`` exports it through
 the engines' read side (gns_cm_export_state, gns_ss_export_state,
-gns_ex_snapshot), ``restore`` puts it back through the write side
-(gns_cm_import_state, gns_ss_import_state, gns_ex_merge into an emptied table).
+gns_ex_snapshot, gns_pairs_export), ``restore`` puts it back through the write
+side (gns_cm_import_state, gns_ss_import_state, gns_ex_merge / gns_pairs_merge
+into an emptied table).
 
 A file holds the state arrays plus one metadata record (JSON): the class and
 the parameters a state depends on -- geometry, key layout, thresholds, row seeds
@@ -34,12 +35,14 @@ PARAMS = {
     "SuperSpread": ["width", "depth", "flow_bytes", "elem_bytes", "flow_fields", "elem_fields", "threshold", "seeds",
                     "m", "size", "base", "b", "hll_master", "rng_seed"],
     "ExactAggregator": ["key_fields", "key_bytes"],
+    "ExactSpread": ["flow_fields", "elem_fields", "flow_bytes", "elem_bytes"],
 }
 # the arrays a file of each class holds
 ARRAYS = {
     "CountMin": ["C", "S", "FPc", "FPs"],
     "SuperSpread": ["values", "keys", "regs", "pbits"],
     "ExactAggregator": ["keys", "start", "end", "pkts", "bytes"],
+    "ExactSpread": ["flows", "elems"],
 }
 
 
@@ -79,7 +82,7 @@ def _plain(v):
 
 
 def describe(obj) -> dict:
-    """The metadata record of a live CountMin / SuperSpread / ExactAggregator (no state)."""
+    """The metadata record of a live CountMin / SuperSpread / ExactAggregator / ExactSpread (no state)."""
     cls = type(obj).__name__
     if cls not in PARAMS:
         raise TypeError(f"no checkpoint format for {cls}")
@@ -115,6 +118,9 @@ def save(obj, path) -> None:
         c = obj.counters()
         meta["counters"] = [int(c["inserted"]), int(c["dropped"]), int(c["unsupported"])]
         meta["records"] = int(c["records"])
+    elif cls == "ExactSpread":  # the pair set is the whole state; counters are not part of the file
+        f, e, _ = obj.export_pairs()
+        arrays = {"flows": np.ascontiguousarray(f), "elems": np.ascontiguousarray(e)}
     else:
         k, st, en, pk, by = obj.snapshot_arrays()
         arrays = {"keys": np.ascontiguousarray(k), "start": st, "end": en, "pkts": pk, "bytes": by}
@@ -136,6 +142,9 @@ def restore(obj, path) -> None:
     elif cls == "SuperSpread":
         obj.import_state(arrays["values"], arrays["keys"], arrays["regs"], arrays["pbits"].view(np.float64),
                          meta["records"], counters=np.array(meta["counters"], np.uint64))
+    elif cls == "ExactSpread":
+        obj.reset()
+        obj.merge_pairs(arrays["flows"], arrays["elems"])
     else:
         obj.reset()
         obj.merge(arrays["keys"], arrays["start"], arrays["end"], arrays["pkts"], arrays["bytes"])

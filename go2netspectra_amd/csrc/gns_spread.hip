@@ -38,10 +38,19 @@
 // No batch can overflow a table, so none is aborted or re-run and nothing can be
 // counted twice (DESIGN.md §4e states why this replaces the abort-and-retry of
 // the sketches).
+//
+// State interface (gns_pairs_*, DESIGN.md §4e "Pair set export and union"): the
+// pair set is the state.  k_exs_export compacts the live records -- all, or those
+// whose tag (the claim epoch) is newer than a cursor -- into dense flow / element
+// rows; a merge feeds such rows through k_exs_pass in a mode that counts no
+// traffic; merge_from does both between two handles on the device.  Cursors are
+// generation << 32 | epoch; a reset and the epoch's wrap (k_exs_retag) start a
+// new generation.
 #include <cstdlib>
 #include <cstring>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <vector>
 
@@ -127,6 +136,7 @@ struct ExsArgs {
     uint64_t *pend_out;
     uint32_t *cnt_out, *total_out;
     unsigned long long *stats;   // 0 inserted, 1 dropped, 2 unsupported, 3 probe overflow (cannot), 4 new pairs
+    uint32_t merge;              // the rows are a pair set being united (gns_pairs_merge), not traffic: stats[0] stays
 };
 
 // flow key (kwf) and pair key flow ‖ elem (kwm) of packet p: the bytes SuperSpread
@@ -233,7 +243,7 @@ __global__ __launch_bounds__(kExsThreads) void k_exs_pass(ExsArgs a) {
             atomicAdd(&a.stats[4], (unsigned long long)s_new);
         }
         if (s_full) atomicAdd(&a.stats[3], (unsigned long long)s_full);
-        if (s_ok) atomicAdd(&a.stats[0], (unsigned long long)s_ok);
+        if (s_ok && !a.merge) atomicAdd(&a.stats[0], (unsigned long long)s_ok);
         if (s_drop) atomicAdd(&a.stats[1], (unsigned long long)s_drop);
         if (s_unsup) atomicAdd(&a.stats[2], (unsigned long long)s_unsup);
     }
@@ -264,6 +274,95 @@ __global__ __launch_bounds__(256) void k_exs_rehash(PairDev O, uint64_t old_slot
         slot = (slot + 1u) & N.mask;
     }
     atomicAdd(fail, 1u);
+}
+
+// one exported row: the record's key words split at Kf into flows[j * Kf] and elems[j * (K - Kf)].
+// WORDS: both key sizes are multiples of 4 and both buffers word-aligned.
+template <int NW, int LW, bool WORDS>
+__device__ __forceinline__ void pair_store_row(const PairDev &P, const uint32_t (&r)[4 * LW], uint32_t Kf, uint64_t j,
+                                               uint8_t *flows, uint8_t *elems) {
+    const uint32_t Ke = P.K - Kf;
+    if constexpr (WORDS) {
+        uint32_t *fo = reinterpret_cast<uint32_t *>(flows + j * Kf);
+        uint32_t *eo = reinterpret_cast<uint32_t *>(elems + j * Ke);
+        const uint32_t fw = Kf >> 2, nw = P.K >> 2;
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            if (1 + i >= 4 * LW) continue;
+            if ((uint32_t)i < fw) fo[i] = r[1 + i];
+            else if ((uint32_t)i < nw) eo[i - fw] = r[1 + i];
+        }
+    } else {
+        uint8_t *fo = flows + j * Kf, *eo = elems + j * Ke;
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            if (1 + i >= 4 * LW) continue;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const uint32_t k = 4 * i + b;
+                const uint8_t v = (uint8_t)(r[1 + i] >> (8 * b));
+                if (k < Kf) fo[k] = v;
+                else if (k < P.K) eo[k - Kf] = v;
+            }
+        }
+    }
+}
+
+// Pair set export: the live records of slots [beg, end) -- tag non-zero and newer
+// than `since` (0: every record) -- as dense rows.  A workgroup takes kExsExportIt
+// runs of 256 slots, one lane per slot and run; a ballot per wave and run ranks the
+// live lanes, and ONE atomic per workgroup reserves its rows (a table of 2^27 slots
+// is 2^17 adds on the count word, not 2^21).  Rows at or past cap are counted and
+// not written.  The records are committed (an export runs between batches), so
+// their key words are visible.
+constexpr int kExsExportIt = 4;
+template <int NW, bool WORDS>
+__global__ __launch_bounds__(256) void k_exs_export(PairDev P, uint64_t beg, uint64_t end, uint32_t since, uint32_t Kf,
+                                                    uint8_t *flows, uint8_t *elems, uint64_t cap, uint32_t *count) {
+    constexpr int LW = NW <= 8 ? 3 : 5, IT = kExsExportIt;
+    __shared__ uint32_t s_cnt[IT * 4], s_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t s0 = beg + (uint64_t)blockIdx.x * (256 * IT) + tid;
+    uint32_t r[IT][4 * LW];
+    uint64_t m[IT];
+    bool live[IT];
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        const uint64_t s = s0 + (uint64_t)it * 256;
+        live[it] = false;
+        if (s < end) {
+            pair_load<LW>(P, (uint32_t)s, r[it]);
+            live[it] = r[it][0] > since;
+        }
+        m[it] = __ballot(live[it]);
+        if (lane == 0) s_cnt[it * 4 + wave] = (uint32_t)__popcll(m[it]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (int k = 0; k < IT * 4; k++) tot += s_cnt[k];
+        s_base = tot ? atomicAdd(count, tot) : 0u;
+    }
+    __syncthreads();
+    uint64_t run = s_base;  // rows of the workgroup's (run, wave) cells before this lane's
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        uint64_t j = run + (uint32_t)__popcll(m[it] & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint32_t c = s_cnt[it * 4 + w];
+            if ((uint32_t)w < wave) j += c;
+            run += c;
+        }
+        if (live[it] && j < cap) pair_store_row<NW, LW, WORDS>(P, r[it], Kf, j, flows, elems);
+    }
+}
+
+// epoch wrap: every live tag of a table becomes 1, older than every epoch the new generation hands out
+__global__ __launch_bounds__(256) void k_exs_retag(uint32_t *rec, uint64_t slots, uint32_t RW) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s < slots && rec[s * RW] != 0u) rec[s * RW] = 1u;
 }
 
 // flow-table growth: spread[] follows each record to its new slot (gns_dict.hip remap)
@@ -341,7 +440,9 @@ struct gns_exs {
     uint32_t *pcnt[2] = {nullptr, nullptr};
     unsigned long long *stats = nullptr;
     uint32_t *h_pin = nullptr;
-    uint32_t epoch = 0;
+    uint32_t epoch = 0;          // of the last launch; record tags are claim epochs
+    uint32_t gen = 1;            // cursor generation: a reset or an epoch wrap starts a new one
+    uint8_t *xbuf = nullptr;     // export / merge_from staging: kExsStageRows rows of flow and element bytes
     uint64_t bmax = 0, pkt = 0, n_batches = 0;
     uint64_t n_fgrow = 0, n_pgrow = 0;
     double grow_ms = 0.0;
@@ -356,6 +457,7 @@ namespace {
 void exs_free_all(gns_exs *h) {
     dfree(h->P.rec); dfree(h->F.rec); dfree(h->spread); dfree(h->ident); dfree(h->ctl); dfree(h->ptotal);
     dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); h->stage.free_all();
+    dfree(h->xbuf);
     h->dsc.free_all();
     h->hh.free_all();
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -375,6 +477,17 @@ int exs_clear(gns_exs *h) {
 }
 
 unsigned exs_grid(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+// The pair table's hash seed, another for every handle and after every reset.  An
+// export walks a table in slot order, that is in the order of its hash: rows
+// merged into a table under the SAME seed would arrive sorted by home slot, each
+// launch would fill one dense window, and most lanes would meet a slot claimed in
+// their own launch and park, one probe step per resolve round.  Under another seed
+// the exported rows are as scattered as traffic is.
+uint32_t exs_fresh_seed() {
+    static std::atomic<uint32_t> k{0};
+    return 0x9E3779B9u + 0x632BE5ABu * k.fetch_add(1, std::memory_order_relaxed);
+}
 
 int exs_alloc_flow_side(uint64_t slots, hipStream_t s, uint32_t **spread, uint32_t **ident) {
     *spread = *ident = nullptr;
@@ -478,19 +591,36 @@ int exs_reserve(gns_exs *h, uint64_t m) {
     return GNS_OK;
 }
 
+// The epoch of the next launch.  Tags are compared with cursors (newer than) and
+// with the live epoch (claimed in this launch), so the 32-bit epoch must never come
+// round to tags still in the tables: before it would wrap, every live tag is
+// rewritten to 1, the epoch restarts at 2 and a new cursor generation begins.
+int exs_next_epoch(gns_exs *h, uint32_t *out) {
+    if (h->epoch == 0xFFFFFFFFu) {
+        hipLaunchKernelGGL(k_exs_retag, dim3(exs_grid(h->pslots)), dim3(256), 0, h->stream, h->P.rec, h->pslots, h->P.RW);
+        hipLaunchKernelGGL(k_exs_retag, dim3(exs_grid(h->fslots)), dim3(256), 0, h->stream, h->F.rec, h->fslots, h->F.RW);
+        GNS_HIP(hipGetLastError());
+        h->epoch = 1;
+        h->gen++;
+    }
+    *out = ++h->epoch;
+    return GNS_OK;
+}
+
+// merge: the rows are a pair set (gns_pairs_merge): the traffic counters stay
 template <int KIND, int MF, int MM, int NW>
-int exs_run_batch(gns_exs *h, const InputDesc &in, uint64_t n) {
+int exs_run_batch(gns_exs *h, const InputDesc &in, uint64_t n, bool merge) {
     hipStream_t s = h->stream;
     ScopedStage total_stage(h->timer, 5);
     const uint32_t nch = (uint32_t)((n + kExsChunk - 1) / kExsChunk);
     ExsArgs a{};
     a.in = in; a.n = n; a.kpf = h->kpf; a.kpm = h->kpm; a.Kf = h->Kf; a.Km = h->Km;
     a.P = h->P; a.F = h->F; a.spread = h->spread; a.nclaim = h->ctl + 4; a.stats = h->stats;
+    a.merge = merge ? 1u : 0u;
     GNS_HIP(hipMemsetAsync(h->ptotal, 0, 8, s));
     int cur = 0;  // the parked list the next round reads
     for (int round = 0;; round++) {
-        if (++h->epoch == 0) h->epoch = 1;
-        a.epoch = h->epoch;
+        GNS_TRY(exs_next_epoch(h, &a.epoch));
         if (round == 0) {
             ScopedStage st(h->timer, 0);
             a.pend_out = h->pend[0]; a.cnt_out = h->pcnt[0]; a.total_out = h->ptotal;
@@ -523,30 +653,32 @@ int exs_run_batch(gns_exs *h, const InputDesc &in, uint64_t n) {
         if (round > 65536) { set_error("spread resolve did not converge"); return GNS_E_HIP; }
         GNS_HIP(hipMemsetAsync(h->ptotal + (cur ^ 1), 0, 4, s));
     }
-    h->pkt += n;
-    h->n_batches++;
+    if (!merge) {
+        h->pkt += n;
+        h->n_batches++;
+    }
     return GNS_OK;
 }
 
 template <int KIND>
-int exs_batch(gns_exs *h, const InputDesc &d, uint64_t m) {
+int exs_batch(gns_exs *h, const InputDesc &d, uint64_t m, bool merge = false) {
     if (m == 0) return GNS_OK;
     GNS_TRY(exs_reserve(h, m));
     const bool narrow = h->Km <= 32;
     if constexpr (KIND == IN_KEYS) {
-        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m)
-                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m);
+        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m, merge)
+                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m, merge);
     } else if (plan_mode(h->kpf) == PLAN_SLICE0 && plan_mode(h->kpm) == PLAN_SLICE0) {
-        return narrow ? exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 8>(h, d, m)
-                      : exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 20>(h, d, m);
+        return narrow ? exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 8>(h, d, m, merge)
+                      : exs_run_batch<KIND, PLAN_SLICE0, PLAN_SLICE0, 20>(h, d, m, merge);
     } else {
-        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m)
-                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m);
+        return narrow ? exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 8>(h, d, m, merge)
+                      : exs_run_batch<KIND, PLAN_GENERIC, PLAN_GENERIC, 20>(h, d, m, merge);
     }
 }
 
 template <int KIND>
-int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where) {
+int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where, bool merge = false) {
     GNS_TRY(set_device(h->device));
     for (uint64_t off = 0; off < n; off += h->bmax) {
         const uint64_t m = std::min<uint64_t>(h->bmax, n - off);
@@ -556,8 +688,62 @@ int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where) {
             stage_input(l, d, m);
             GNS_TRY(h->stage.copy(l, h->stream));
         }
-        GNS_TRY(exs_batch<KIND>(h, d, m));
+        GNS_TRY(exs_batch<KIND>(h, d, m, merge));
     }
+    return GNS_OK;
+}
+
+// --- pair set export and union ---------------------------------------------
+constexpr uint64_t kExsPiece = 1ull << 20;  // slots per staged piece: the scratch does not grow with the table
+
+uint64_t exs_cursor(const gns_exs *h) { return (uint64_t)h->gen << 32 | h->epoch; }
+
+// `since` names a point of this handle's stream in its current generation (0: the beginning)
+int exs_check_since(const gns_exs *h, uint64_t since) {
+    if (since == 0) return GNS_OK;
+    if ((uint32_t)(since >> 32) != h->gen || (uint32_t)since > h->epoch) {
+        set_error("cursor %llx is not of this handle's generation %u (reset, epoch wrap or another handle): take a full "
+                  "export (since = 0)", (unsigned long long)since, h->gen);
+        return GNS_E_ARG;
+    }
+    return GNS_OK;
+}
+
+constexpr uint64_t kExsStageRows = 2 * kExsPiece;  // merge_from gathers pieces until more than one piece's worth is staged
+
+// the staging buffer laid out for `rows` (<= kExsStageRows) rows: flow bytes, then (16-byte aligned) element bytes
+int exs_stage_rows(gns_exs *h, uint64_t rows, uint8_t **f, uint8_t **e) {
+    if (!h->xbuf) GNS_TRY(dalloc(reinterpret_cast<void **>(&h->xbuf), kExsStageRows * h->Km + 64));
+    *f = h->xbuf;
+    *e = h->xbuf + ((rows * h->Kf + 15) & ~15ull);
+    return GNS_OK;
+}
+
+// src's live records of slots [beg, end) newer than `since`, compacted on stream s into
+// rows at flows / elems (at most cap are written).  *count is zeroed first, or with `append`
+// goes on from the rows already there: the new rows follow them.
+int exs_export_range(const gns_exs *src, uint64_t beg, uint64_t end, uint32_t since, uint8_t *flows, uint8_t *elems,
+                     uint64_t cap, uint32_t *count, hipStream_t s, bool append = false) {
+    if (!append) GNS_HIP(hipMemsetAsync(count, 0, 4, s));
+    const uint32_t Ke = src->Km - src->Kf;
+    const bool words = src->Kf % 4 == 0 && Ke % 4 == 0 && (((uintptr_t)flows | (uintptr_t)elems) & 3u) == 0;
+    const dim3 g((unsigned)((end - beg + 256 * kExsExportIt - 1) / (256 * kExsExportIt))), b(256);
+    if (src->Km <= 32) {
+        if (words) hipLaunchKernelGGL((k_exs_export<8, true>), g, b, 0, s, src->P, beg, end, since, src->Kf, flows, elems, cap, count);
+        else hipLaunchKernelGGL((k_exs_export<8, false>), g, b, 0, s, src->P, beg, end, since, src->Kf, flows, elems, cap, count);
+    } else {
+        if (words) hipLaunchKernelGGL((k_exs_export<20, true>), g, b, 0, s, src->P, beg, end, since, src->Kf, flows, elems, cap, count);
+        else hipLaunchKernelGGL((k_exs_export<20, false>), g, b, 0, s, src->P, beg, end, since, src->Kf, flows, elems, cap, count);
+    }
+    GNS_HIP(hipGetLastError());
+    return GNS_OK;
+}
+
+// the count word of the last exs_export_range on h's stream (synchronizes)
+int exs_read_count(gns_exs *h, uint64_t *out) {
+    GNS_HIP(hipMemcpyAsync(h->h_pin + 8, h->ctl + 6, 4, hipMemcpyDeviceToHost, h->stream));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    *out = h->h_pin[8];
     return GNS_OK;
 }
 
@@ -607,11 +793,13 @@ int gns_exs_create(const gns_exs_params *p, gns_exs **out) {
         while (h->pslots < 2 * mp) h->pslots <<= 1;
         h->bmax = p->batch_packets ? p->batch_packets : (4ull << 20);
         h->bmax = std::min<uint64_t>(h->bmax, 1ull << 26);
+        // tests: a starting epoch a few launches short of 2^32 makes the wrap reachable
+        if (const char *ee = getenv("GNS_EXS_TEST_EPOCH")) h->epoch = (uint32_t)strtoull(ee, nullptr, 0);
         const uint64_t nch = (h->bmax + kExsChunk - 1) / kExsChunk;
         const uint32_t nkw = (h->Km + 3) / 4;
         h->P.RW = 1 + nkw <= 16 ? 16u : 32u;
         h->P.mask = (uint32_t)(h->pslots - 1);
-        h->P.seed = 0x9E3779B9u;
+        h->P.seed = exs_fresh_seed();
         h->P.K = h->Km;
         h->F.mask = (uint32_t)(h->fslots - 1);
         h->F.K = h->Kf;
@@ -785,7 +973,95 @@ int gns_exs_reset(gns_exs *h) {
     if (!h) return GNS_E_ARG;
     GNS_TRY(set_device(h->device));
     GNS_TRY(exs_clear(h));
+    h->gen++;  // cursors taken before name pairs that are gone
+    h->P.seed = exs_fresh_seed();  // restoring this handle's own export must not arrive in its hash order
     GNS_HIP(hipStreamSynchronize(h->stream));
+    return GNS_OK;
+}
+
+int gns_pairs_export(gns_exs *h, uint64_t since, uint8_t *flows, uint8_t *elems, uint64_t *n, uint64_t *cursor,
+                     gns_mem where) {
+    if (!h || !n) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(exs_check_since(h, since));
+    GNS_TRY(set_device(h->device));
+    hipStream_t s = h->stream;
+    const bool rows = flows && elems;
+    const uint64_t cap = rows ? *n : 0, cap_in = *n;
+    const uint32_t se = (uint32_t)since, Ke = h->Km - h->Kf;
+    uint64_t total = 0;
+    if (!rows && since == 0) {
+        GNS_HIP(hipStreamSynchronize(s));
+        total = h->pclaimed;  // every claimed slot holds a pair; the host knows the count as of the last batch
+    } else if (!rows || where == GNS_MEM_DEVICE) {
+        GNS_TRY(exs_export_range(h, 0, h->pslots, se, flows, elems, cap, h->ctl + 6, s));
+        GNS_TRY(exs_read_count(h, &total));
+    } else {
+        for (uint64_t beg = 0; beg < h->pslots; beg += kExsPiece) {
+            const uint64_t end = std::min(h->pslots, beg + kExsPiece);
+            uint8_t *df, *de;
+            GNS_TRY(exs_stage_rows(h, kExsPiece, &df, &de));
+            GNS_TRY(exs_export_range(h, beg, end, se, df, de, kExsPiece, h->ctl + 6, s));
+            uint64_t c = 0;
+            GNS_TRY(exs_read_count(h, &c));
+            const uint64_t w = total < cap ? std::min(c, cap - total) : 0;
+            if (w) {
+                GNS_HIP(hipMemcpy(flows + total * h->Kf, df, w * h->Kf, hipMemcpyDeviceToHost));
+                GNS_HIP(hipMemcpy(elems + total * Ke, de, w * Ke, hipMemcpyDeviceToHost));
+            }
+            total += c;
+        }
+    }
+    *n = total;
+    if (cursor && total <= cap_in && (rows || total == 0)) *cursor = exs_cursor(h);
+    return GNS_OK;
+}
+
+int gns_pairs_merge(gns_exs *h, const uint8_t *flows, uint32_t fstride, const uint8_t *elems, uint32_t estride,
+                    uint64_t n, gns_mem where) {
+    if (!h || (n && (!flows || !elems))) { set_error("null argument"); return GNS_E_ARG; }
+    if (fstride < h->Kf || estride < h->Km - h->Kf) { set_error("stride smaller than key"); return GNS_E_ARG; }
+    InputDesc in{};
+    in.keys = flows; in.stride = fstride; in.keys2 = elems; in.stride2 = estride;
+    return exs_insert<IN_KEYS>(h, in, n, where, true);
+}
+
+int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *cursor) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    if (dst == src) { set_error("merge_from: source and destination are the same handle"); return GNS_E_ARG; }
+    if (dst->Kf != src->Kf || dst->Km != src->Km) {
+        set_error("merge_from: key sizes differ (%u + %u bytes into %u + %u)", src->Kf, src->Km - src->Kf, dst->Kf,
+                  dst->Km - dst->Kf);
+        return GNS_E_ARG;
+    }
+    if (dst->device != src->device) { set_error("merge_from: handles on devices %d and %d", src->device, dst->device); return GNS_E_ARG; }
+    GNS_TRY(exs_check_since(src, since));
+    GNS_TRY(set_device(dst->device));
+    // src is read at this point of its own stream, by kernels on dst's stream
+    hipEvent_t ev;
+    GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, src->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
+    (void)hipEventDestroy(ev);
+    if (e != hipSuccess) { set_error("merge_from: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    const uint64_t at = exs_cursor(src);
+    // Pieces of src's table are compacted one behind the other into the staging rows; once more
+    // than one piece's worth is staged (the next piece might not fit) they are merged, in device
+    // batches of dst.  A sparse table thus still merges batches of 2^20 rows or more.
+    uint8_t *df, *de;
+    GNS_TRY(exs_stage_rows(dst, kExsStageRows, &df, &de));
+    uint64_t staged = 0;
+    for (uint64_t beg = 0; beg < src->pslots; beg += kExsPiece) {
+        const uint64_t end = std::min(src->pslots, beg + kExsPiece);
+        GNS_TRY(exs_export_range(src, beg, end, (uint32_t)since, df, de, kExsStageRows, dst->ctl + 6, dst->stream, staged != 0));
+        GNS_TRY(exs_read_count(dst, &staged));
+        if (staged <= kExsPiece && end < src->pslots) continue;
+        InputDesc in{};
+        in.keys = df; in.stride = dst->Kf; in.keys2 = de; in.stride2 = dst->Km - dst->Kf;
+        for (uint64_t off = 0; off < staged; off += dst->bmax)
+            GNS_TRY(exs_batch<IN_KEYS>(dst, advance(in, off), std::min(dst->bmax, staged - off), true));
+        staged = 0;
+    }
+    if (cursor) *cursor = at;
     return GNS_OK;
 }
 

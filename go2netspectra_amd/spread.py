@@ -66,8 +66,8 @@ class ExactSpread:
                 raise ValueError(f"tensor on cuda:{a.device.index}, handle on cuda:{self.device}")
 
     # --- batched inserts ---
-    def insert_keys(self, flows, elems) -> None:
-        """flows [n, >= flow_bytes], elems [n, >= elem_bytes] uint8 (the leading bytes are the keys)."""
+    def _rows(self, flows, elems):
+        """(flows, elems, flow stride, elem stride, n, where) of key rows, host or device."""
         self._on_device(flows, elems)
         where = _where(flows, elems)
         if where == _lib.MEM_HOST:
@@ -82,6 +82,11 @@ class ExactSpread:
             raise ValueError("flows and elems lengths differ")
         fs = int(flows.shape[1]) if n else self.flow_bytes
         es = int(elems.shape[1]) if n else self.elem_bytes
+        return flows, elems, fs, es, n, where
+
+    def insert_keys(self, flows, elems) -> None:
+        """flows [n, >= flow_bytes], elems [n, >= elem_bytes] uint8 (the leading bytes are the keys)."""
+        flows, elems, fs, es, n, where = self._rows(flows, elems)
         check(self._L.gns_exs_insert_keys(self._h, _ptr(flows), fs, _ptr(elems), es, n, where))
 
     def insert_tuples(self, batch) -> None:
@@ -169,7 +174,58 @@ class ExactSpread:
         return f[:m], v[:m]
 
     def reset(self) -> None:
+        """Empties the tables; cursors taken before are refused afterwards."""
         check(self._L.gns_exs_reset(self._h))
+
+    # --- the pair set: export, delta export, union (gns_pairs_*) ---
+    def export_pairs(self, since: int = 0, device: bool = False):
+        """(flows [n, flow_bytes], elems [n, elem_bytes], cursor): every distinct pair held, or
+        with ``since`` (a cursor this handle returned) only the pairs first inserted or merged
+        after that point.  numpy arrays, or with ``device`` torch tensors on the handle's GPU.
+        Unspecified order, no row twice.  ``cursor`` names the point the export was taken at."""
+        n = ct.c_uint64(0)
+        check(self._L.gns_pairs_export(self._h, since, None, None, ct.byref(n), None, _lib.MEM_HOST))
+        while True:
+            cap = n.value
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                f = torch.empty((max(cap, 1), self.flow_bytes), dtype=torch.uint8, device=dev)
+                e = torch.empty((max(cap, 1), self.elem_bytes), dtype=torch.uint8, device=dev)
+                _lib.device_ready(f, e)
+                where = _lib.MEM_DEVICE
+            else:
+                f = np.zeros((max(cap, 1), self.flow_bytes), np.uint8)
+                e = np.zeros((max(cap, 1), self.elem_bytes), np.uint8)
+                where = _lib.MEM_HOST
+            n = ct.c_uint64(cap)
+            cur = ct.c_uint64(0)
+            check(self._L.gns_pairs_export(self._h, since, _ptr(f), _ptr(e), ct.byref(n), ct.byref(cur), where))
+            if n.value <= cap:  # only another thread's insert between the two calls makes it larger
+                return f[: n.value], e[: n.value], int(cur.value)
+
+    def merge_pairs(self, flows, elems) -> None:
+        """Union with the given pairs (rows as insert_keys takes them, host or device): not
+        traffic, so inserted / records / batches stay; new_pairs rises by the pairs added."""
+        flows, elems, fs, es, n, where = self._rows(flows, elems)
+        check(self._L.gns_pairs_merge(self._h, _ptr(flows), fs, _ptr(elems), es, n, where))
+
+    def merge_from(self, other: "ExactSpread", since: int = 0) -> int:
+        """Union with ``other``'s pairs (those after ``since``, a cursor of ``other``) on the
+        device; ``other`` is not modified.  Returns ``other``'s cursor for the next delta."""
+        cur = ct.c_uint64(0)
+        check(self._L.gns_pairs_merge_from(self._h, other._h, since, ct.byref(cur)))
+        return int(cur.value)
+
+    def save(self, path) -> None:
+        """The whole pair set into one checkpoint file (checkpoint.save)."""
+        from . import checkpoint
+        checkpoint.save(self, path)
+
+    def restore(self, path) -> None:
+        """Replace the pair set by a file's (checkpoint.restore); the key layout must be equal."""
+        from . import checkpoint
+        checkpoint.restore(self, path)
 
     Insert = insert
     Query = query

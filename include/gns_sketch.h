@@ -672,6 +672,50 @@ int gns_exs_set_timing(gns_exs *h, int on);
 /* stages: 0 insert (first pass), 1 resolve rounds, 2 table growth, 5 total */
 int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset);
 
+/* Pair set export and union: the exact spread engine's state interface.  A spread
+ * count can neither be restored (later inserts need the pairs to tell a duplicate
+ * from a new element) nor combined (the overlap is unknown); the set of distinct
+ * (flow, element) pairs can: the union of two pair sets is exactly the pair set of
+ * the concatenated streams, in any order and however the stream was split.
+ *   - Export is a point in the stream: it runs on the handle's stream after
+ *     everything issued so far; the exported rows grouped by flow are what the
+ *     snapshot call of the handle returns, and a full export has dict_stats [5] rows.
+ *   - Capacity: a count above *n on entry is reported with GNS_OK; rows at or past
+ *     the capacity are not written (rows below it may be) and *cursor is not
+ *     written.  Advance a cursor only on a written export and no pair is lost.
+ *   - Delta: `since` is a cursor an earlier export or merge_from of the SAME handle
+ *     returned; the result is exactly the pairs first inserted (or merged in) after
+ *     that point.  Merged pairs count as inserted at the merge, so a collector that
+ *     chains deltas passes them on.
+ *   - Cursors are opaque and belong to a generation of the handle.  The reset call
+ *     starts a new generation, and so does the wrap of the engine's 32-bit launch
+ *     counter (every live record is then re-stamped as older than any new cursor).
+ *     A cursor of another generation, or one the handle has not reached, is
+ *     GNS_E_ARG: take a full export (since = 0).  GNS_EXS_TEST_EPOCH (environment,
+ *     read at create, tests only) sets the starting launch counter.
+ *   - Merge is a union, not traffic: counters [0], [1], [2], [6] and [7] do not move,
+ *     [4] rises by the pairs actually added, [5] follows the flow table.  The tables
+ *     grow before each piece as they do before a batch.
+ *   - merge_from: dst == src, other key sizes or another device is GNS_E_ARG with
+ *     dst untouched; src is read at a point of its own stream and not modified.
+ *   - A null handle or a null n is GNS_E_ARG without a device. */
+/* Every distinct (flow, element) pair the handle holds (since == 0), or only those first
+ * inserted after the point `since` names: rows i of flows[*n * flow_bytes] and
+ * elems[*n * elem_bytes], dense, unspecified order, host or device memory of the handle's GPU.
+ * *n: capacity in rows on entry, the number of such pairs on return; NULL buffers ask for
+ * the count only.  *cursor (may be NULL) names the point of the insert stream the export
+ * was taken at: every insert and merge issued before the call is in, none after. */
+int gns_pairs_export(gns_exs *h, uint64_t since, uint8_t *flows, uint8_t *elems, uint64_t *n,
+                     uint64_t *cursor, gns_mem where);
+/* Union: afterwards the handle holds its pairs and these.  Rows as the keys insert takes
+ * them (strides >= the key sizes); duplicates inside the call and pairs already held count once. */
+int gns_pairs_merge(gns_exs *h, const uint8_t *flows, uint32_t fstride, const uint8_t *elems,
+                    uint32_t estride, uint64_t n, gns_mem where);
+/* The export of src since `since`, merged into dst without the pairs leaving the device and
+ * without a dense copy of the whole set (staged in pieces of 2^20 table slots).  *cursor
+ * (may be NULL): src's point, for the next delta. */
+int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *cursor);
+
 /* Device buffers for callers without a device allocator of their own (the cgo
  * binding's ThriftDecoder: gns_thrift_decode writes device records that
  * gns_*_insert_headers then reads with GNS_MEM_DEVICE). */
