@@ -12,7 +12,7 @@ from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_conf
 from .exact import (ExactAggregator, ExactTask, ExactView, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
                     TaskSummary, apply_delta, make_filter, merge_summaries)
 from .factory import Manager, TaskGroup, create, register_aggregator
-from .packets import (HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
+from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
 from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread
 from .spread import ExactSpread
@@ -24,5 +24,5 @@ __all__ = [
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
-    "make_filter", "merge_summaries", "checkpoint", "ExactView", "apply_delta",
+    "make_filter", "merge_summaries", "checkpoint", "ExactView", "apply_delta", "CompactBatch",
 ]

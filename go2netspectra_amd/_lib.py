@@ -50,6 +50,7 @@ EXPORTED = [
     "gns_ex_view_create", "gns_ex_view_destroy", "gns_ex_view_refresh", "gns_ex_view_snapshot",
     "gns_ex_view_aggregate", "gns_ex_view_heavy_hitters",
     "gns_pairs_export", "gns_pairs_merge", "gns_pairs_merge_from",
+    "gns_ss_insert_compact", "gns_spread_insert_compact", "gns_ex_insert_compact", "gns_pack_pcap_compact_ts",
 ]
 
 
@@ -226,6 +227,10 @@ def load() -> ct.CDLL:
         "gns_pairs_export": ([vp, u64, vp, vp, vp, vp, i32], i32),
         "gns_pairs_merge": ([vp, vp, u32, vp, u32, u64, i32], i32),
         "gns_pairs_merge_from": ([vp, vp, u64, vp], i32),
+        "gns_ss_insert_compact": ([vp, vp, vp, u64, vp, u64, i32], i32),
+        "gns_spread_insert_compact": ([vp, vp, vp, u64, vp, u64, i32], i32),
+        "gns_ex_insert_compact": ([vp, vp, vp, vp, u64, vp, u64, i32], i32),
+        "gns_pack_pcap_compact_ts": ([ct.c_char_p, vp, vp, vp, u64, vp, u64, vp, vp], ct.c_int64),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -94,6 +94,26 @@ struct HostStage {
     void free_all();
 };
 
+// What an engine keeps for compact records (IN_REC16; gns_records.hip): the side
+// records of a host call, staged once (escapes index the side array of the whole
+// call, so it is never advanced with the batches), and the size array of a batch of
+// the 16-byte form (the escapes' parse and the engines read sizes[p]).
+struct CompactInput {
+    uint32_t *side_dev = nullptr;
+    uint64_t side_n = 0;
+    uint32_t *sizes = nullptr;
+    uint64_t sizes_n = 0;
+    // in.side -> a device copy of the host side array.  Waits for stream s first:
+    // the batches of the previous call may still read the buffer.
+    int stage_side(InputDesc &in, hipStream_t s);
+    // 16-byte form: the wire lengths of d's first m records (device memory) unpacked
+    // on stream s, d.sizes pointed at them.  The 20-byte form is left as it is.
+    int unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s);
+    void free_all();
+};
+// The descriptor of a gns_*_insert_compact call (wirelen == NULL: the 16-byte form).
+InputDesc compact_desc(const uint8_t *rec16, const uint32_t *wirelen, const uint8_t *side64, uint64_t n_side);
+
 // Flow-key plan from a configured layout (task.go:265-300, :327-338).
 int make_plan(const gns_layout &l, uint32_t key_bytes, KeyPlanN *out);
 // plan for the concatenation a ‖ b (SuperSpread merged key, super_spread.go:183-190)

@@ -108,7 +108,7 @@ template <int KIND, int MODE>
 __device__ __forceinline__ int ex_key_tw(const ExIn &x, uint32_t K, const uint8_t *s_src, uint64_t p,
                                          uint32_t (&tw)[10], uint32_t (&kw)[GNS_KWMAX]) {
     uint32_t sv, dv;
-    if constexpr (KIND == IN_HDR) { sv = tw[9] >> 24; dv = (tw[9] >> 16) & 0xFFu; }
+    if constexpr (KIND == IN_HDR || KIND == IN_REC16) { sv = tw[9] >> 24; dv = (tw[9] >> 16) & 0xFFu; }
     else { sv = dv = x.ipver ? x.ipver[p] : 4u; }
     // a net.IP of neither 4 nor 16 bytes prints as "?<hex>" / "<nil>" (net/ip.go):
     // outside the canonical form, counted as unsupported
@@ -1451,6 +1451,7 @@ struct gns_ex {
     unsigned long long *stats = nullptr;
     uint32_t *h_pin = nullptr;
     HostStage stage;
+    CompactInput compact;  // compact records: the staged side array, the 16-byte form's sizes
     StageTimer timer;
 };
 
@@ -1480,6 +1481,7 @@ void ex_free_all(gns_ex *ex) {
     dfree(ex->D.rec); dfree(ex->f.pkts); dfree(ex->f.bytes); dfree(ex->f.first); dfree(ex->f.last);
     dfree(ex->f.start); dfree(ex->f.end); dfree(ex->pend[0]); dfree(ex->pend[1]);
     dfree(ex->pcnt[0]); dfree(ex->pcnt[1]); dfree(ex->ptotal); dfree(ex->stats); ex->stage.free_all();
+    ex->compact.free_all();
     dfree(ex->sk[0]); dfree(ex->sk[1]); dfree(ex->ph); dfree(ex->pgs); dfree(ex->pb);
     dfree(ex->hot_ids); dfree(ex->touch); dfree(ex->hot_tab); dfree(ex->hpart); dfree(ex->hctl); dfree(ex->ccnt);
     dfree(ex->dctl); dfree(ex->stats_bak); ex->dsc.free_all();
@@ -1742,6 +1744,7 @@ int ex_insert(gns_ex *ex, const ExIn &x0, uint64_t n, gns_mem where) {
             stage_add(l, x.ts, m * 8, &x.ts);
             GNS_TRY(ex->stage.copy(l, ex->stream));
         }
+        if constexpr (KIND == IN_REC16) GNS_TRY(ex->compact.unpack_sizes(x.in, m, ex->stream));
         GNS_TRY(ex_batch_recover<KIND>(ex, x, m));
     }
     return GNS_OK;
@@ -2088,6 +2091,19 @@ int gns_ex_insert_headers(gns_ex *ex, const uint8_t *hdr, const uint32_t *wirele
     x.in.sizes = wirelen;
     x.ts = ts_ns;
     return ex_insert<IN_HDR>(ex, x, n, where);
+}
+
+int gns_ex_insert_compact(gns_ex *ex, const uint8_t *rec16, const uint32_t *wirelen, const int64_t *ts_ns,
+                          uint64_t n, const uint8_t *side64, uint64_t n_side, gns_mem where) {
+    if (!ex || !ts_ns || (n && !rec16) || (n_side && !side64)) { set_error("null argument"); return GNS_E_ARG; }
+    ExIn x{};
+    x.in = compact_desc(rec16, wirelen, side64, n_side);
+    x.ts = ts_ns;
+    if (where != GNS_MEM_DEVICE) {  // the resolve rounds re-read the side records: one device copy for the whole call
+        GNS_TRY(set_device(ex->device));
+        GNS_TRY(ex->compact.stage_side(x.in, ex->stream));
+    }
+    return ex_insert<IN_REC16>(ex, x, n, where);
 }
 
 int gns_ex_flush(gns_ex *ex) {

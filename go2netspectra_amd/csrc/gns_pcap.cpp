@@ -491,30 +491,14 @@ extern "C" int64_t gns_pack_pcap_ts(const char *path, uint8_t *hdr, uint32_t *wi
 
 // compact records (IN_REC16) for the PCIe-bound host path: 16 bytes + the wire
 // length per packet, the frames whose tuple is not an IPv4 one as 64-byte side
-// records (GNS_E_RANGE when side_cap is too small: *n_side = the number needed)
-extern "C" int64_t gns_pack_pcap_compact(const char *path, uint8_t *rec16, uint32_t *wirelen, uint64_t cap,
-                                         uint8_t *side64, uint64_t side_cap, uint64_t *n_side, uint64_t *total) {
-    Sink o{nullptr, wirelen, nullptr, cap};
+// records (GNS_E_RANGE when side_cap is too small: *n_side = the number needed).
+// rec_len: the 16-byte form, the wire length rides in each record (GNS_E_RANGE
+// when a frame's wire length exceeds 65535).
+static int64_t pack_compact(const char *path, uint8_t *rec16, uint32_t *wirelen, int64_t *ts_ns, bool rec_len,
+                            uint64_t cap, uint8_t *side64, uint64_t side_cap, uint64_t *n_side, uint64_t *total) {
+    Sink o{nullptr, wirelen, ts_ns, cap};
     o.rec16 = rec16;
-    o.side64 = side64;
-    o.side_cap = side_cap;
-    const int64_t r = pack(path, o, total);
-    if (n_side) *n_side = o.side_need;
-    if (r >= 0 && o.side_need > side_cap) {
-        gns::set_error("%s: %llu side records needed, room for %llu", path, (unsigned long long)o.side_need,
-                       (unsigned long long)side_cap);
-        return GNS_E_RANGE;
-    }
-    return r;
-}
-
-// the 16-byte form (gns_cm_insert_compact with no wirelen array): the wire length rides in
-// each record; GNS_E_RANGE when a frame's wire length exceeds 65535
-extern "C" int64_t gns_pack_pcap_compact16(const char *path, uint8_t *rec16, uint64_t cap, uint8_t *side64,
-                                           uint64_t side_cap, uint64_t *n_side, uint64_t *total) {
-    Sink o{nullptr, nullptr, nullptr, cap};
-    o.rec16 = rec16;
-    o.rec_len = true;
+    o.rec_len = rec_len;
     o.side64 = side64;
     o.side_cap = side_cap;
     const int64_t r = pack(path, o, total);
@@ -530,6 +514,23 @@ extern "C" int64_t gns_pack_pcap_compact16(const char *path, uint8_t *rec16, uin
         return GNS_E_RANGE;
     }
     return r;
+}
+
+extern "C" int64_t gns_pack_pcap_compact(const char *path, uint8_t *rec16, uint32_t *wirelen, uint64_t cap,
+                                         uint8_t *side64, uint64_t side_cap, uint64_t *n_side, uint64_t *total) {
+    return pack_compact(path, rec16, wirelen, nullptr, false, cap, side64, side_cap, n_side, total);
+}
+
+extern "C" int64_t gns_pack_pcap_compact16(const char *path, uint8_t *rec16, uint64_t cap, uint8_t *side64,
+                                           uint64_t side_cap, uint64_t *n_side, uint64_t *total) {
+    return pack_compact(path, rec16, nullptr, nullptr, true, cap, side64, side_cap, n_side, total);
+}
+
+// either form (wirelen == NULL: the 16-byte one) with the capture timestamps of gns_pack_pcap_ts
+extern "C" int64_t gns_pack_pcap_compact_ts(const char *path, uint8_t *rec16, uint32_t *wirelen, int64_t *ts_ns,
+                                            uint64_t cap, uint8_t *side64, uint64_t side_cap, uint64_t *n_side,
+                                            uint64_t *total) {
+    return pack_compact(path, rec16, wirelen, ts_ns, wirelen == nullptr, cap, side64, side_cap, n_side, total);
 }
 
 extern "C" int64_t gns_pack_pcap(const char *path, uint8_t *hdr, uint32_t *wirelen, uint64_t cap,

@@ -72,6 +72,59 @@ __global__ __launch_bounds__(256) void k_compact(const uint32_t *hdr, const uint
     }
 }
 
+// 16-byte form: the wire lengths (word 3 bits 16..31) as a batch's size array
+__global__ __launch_bounds__(256) void k_unpack_sizes(const uint32_t *rec16, uint64_t n, uint32_t *sizes) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) sizes[i] = rec16[i * 4 + 3] >> 16;
+}
+
+int CompactInput::stage_side(InputDesc &in, hipStream_t s) {
+    if (!in.n_side) return GNS_OK;
+    GNS_HIP(hipStreamSynchronize(s));
+    if (side_n < in.n_side) {
+        dfree(side_dev);
+        side_dev = nullptr;
+        side_n = 0;
+        GNS_TRY(dalloc_t(&side_dev, in.n_side * 16));
+        side_n = in.n_side;
+    }
+    GNS_HIP(hipMemcpy(side_dev, in.side, in.n_side * 64, hipMemcpyHostToDevice));
+    in.side = side_dev;
+    return GNS_OK;
+}
+
+int CompactInput::unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s) {
+    if (!d.rec_len || m == 0) return GNS_OK;
+    if (sizes_n < m) {
+        GNS_HIP(hipStreamSynchronize(s));  // an earlier batch may still read the array
+        dfree(sizes);
+        sizes = nullptr;
+        sizes_n = 0;
+        GNS_TRY(dalloc_t(&sizes, m));
+        sizes_n = m;
+    }
+    hipLaunchKernelGGL(k_unpack_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d.rec16, m, sizes);
+    GNS_HIP(hipGetLastError());
+    d.sizes = sizes;
+    return GNS_OK;
+}
+
+void CompactInput::free_all() {
+    dfree(side_dev); dfree(sizes);
+    side_dev = nullptr; sizes = nullptr;
+    side_n = sizes_n = 0;
+}
+
+InputDesc compact_desc(const uint8_t *rec16, const uint32_t *wirelen, const uint8_t *side64, uint64_t n_side) {
+    InputDesc in{};
+    in.rec16 = reinterpret_cast<const uint32_t *>(rec16);
+    in.sizes = wirelen;
+    in.rec_len = wirelen ? 0u : 1u;
+    in.side = reinterpret_cast<const uint32_t *>(side64);
+    in.n_side = side64 ? n_side : 0;
+    return in;
+}
+
 }  // namespace gns
 
 using namespace gns;

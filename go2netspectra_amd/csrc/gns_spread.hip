@@ -448,6 +448,7 @@ struct gns_exs {
     double grow_ms = 0.0;
     DictScratch dsc;
     HostStage stage;
+    CompactInput compact;        // compact records: the staged side array, the 16-byte form's sizes
     StageTimer timer;
     HhScratch hh;
 };
@@ -457,6 +458,7 @@ namespace {
 void exs_free_all(gns_exs *h) {
     dfree(h->P.rec); dfree(h->F.rec); dfree(h->spread); dfree(h->ident); dfree(h->ctl); dfree(h->ptotal);
     dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); h->stage.free_all();
+    h->compact.free_all();
     dfree(h->xbuf);
     h->dsc.free_all();
     h->hh.free_all();
@@ -688,6 +690,7 @@ int exs_insert(gns_exs *h, InputDesc in, uint64_t n, gns_mem where, bool merge =
             stage_input(l, d, m);
             GNS_TRY(h->stage.copy(l, h->stream));
         }
+        if constexpr (KIND == IN_REC16) GNS_TRY(h->compact.unpack_sizes(d, m, h->stream));
         GNS_TRY(exs_batch<KIND>(h, d, m, merge));
     }
     return GNS_OK;
@@ -863,6 +866,18 @@ int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirel
     in.hdr = reinterpret_cast<const uint32_t *>(hdr);
     in.sizes = wirelen;
     return exs_insert<IN_HDR>(h, in, n, where);
+}
+
+int gns_spread_insert_compact(gns_exs *h, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
+                           const uint8_t *side64, uint64_t n_side, gns_mem where) {
+    if (!h || (n && !rec16) || (n_side && !side64)) { set_error("null argument"); return GNS_E_ARG; }
+    if (!h->has_layout) { set_error("handle created without field layouts: keys input only"); return GNS_E_ARG; }
+    InputDesc in = compact_desc(rec16, wirelen, side64, n_side);
+    if (where != GNS_MEM_DEVICE) {  // the resolve rounds re-read the side records: one device copy for the whole call
+        GNS_TRY(set_device(h->device));
+        GNS_TRY(h->compact.stage_side(in, h->stream));
+    }
+    return exs_insert<IN_REC16>(h, in, n, where);
 }
 
 int gns_exs_flush(gns_exs *h) {

@@ -303,6 +303,135 @@ __global__ __launch_bounds__(kSsThreads, GNS_SS_MINW) void k_ss_extract_hdr(SsEx
     }
 }
 
+// S1 for compact records (IN_REC16) of the default task (SrcIP / SrcIP|DstIP, d=DD):
+// k_ss_extract_hdr's two-stage pipeline without the parse.  One 16-byte load per
+// packet, the record of packet k+2 in flight behind the register reads of packet
+// k+1.  A tuple record holds the two IPv4 slots' first words and nothing else of
+// the keys, in either form, so the zero-word hash folding applies unless a lane's
+// escape parsed to a wider address (wave-uniform test); an escape parses its side
+// record in a divergent branch, as load_tuple<IN_REC16> does.  The escape's wire
+// length comes from the record in the 16-byte form.  Same candidates as
+// k_ss_extract<IN_REC16, ...>, which stays the default for compact records (GNS_SS_PIPE=1 selects
+// this kernel: DESIGN.md §10 has the A/B).
+template <int DD>
+__global__ __launch_bounds__(kSsThreads, GNS_SS_MINW) void k_ss_extract_rec(SsExtractArgs a) {
+    constexpr uint32_t KF = 16, KM = 32;
+    const uint32_t mmask = a.g.m - 1u;
+    const bool mpow2 = (a.g.m & mmask) == 0;
+    __shared__ uint32_t s_drop, s_unsup, s_ok, s_cc;
+    const uint32_t tid = threadIdx.x, blk = blockIdx.x;
+    if (tid == 0) { s_drop = 0; s_unsup = 0; s_ok = 0; s_cc = 0; }
+    __syncthreads();
+    const uint64_t beg = (uint64_t)blk * kSsChunk;
+    const uint64_t end = min(a.n, beg + kSsChunk);
+    uint64_t *rkey = a.ckey + beg * a.g.d;
+    uint32_t *rval = a.cval + beg * a.g.d;
+    uint32_t n_ok = 0;
+    uint4 rv;
+    auto load_rec = [&](uint64_t q) {
+        rv = *reinterpret_cast<const uint4 *>(a.in.rec16 + min(q, end - 1) * 4);
+    };
+    // stage B of packet q: class, keys, row cells, register reads
+    auto stage_b = [&](uint64_t q, bool &okq, uint64_t (&segq)[DD], uint32_t (&lzq)[DD], uint32_t (&regq)[DD]) {
+        okq = q < end;
+        const uint4 r = rv;
+        load_rec(q + kSsThreads);
+        const uint32_t cls = (r.w >> 8) & 0xFFu;
+        uint32_t s0w = r.x, d0w = r.y;          // tuple words 0 and 4
+        uint32_t zw[6] = {0, 0, 0, 0, 0, 0};    // tuple words 1..3 and 5..7
+        bool wide = false;
+        if (okq && cls != kRecTuple) {
+            int st = cls == kRecDrop ? PARSE_DROP : PARSE_UNSUPPORTED;
+            if (cls == kRecSide && (uint64_t)r.x < a.in.n_side) {  // a short or missing side array: never read
+                uint32_t w[16], tw[10];
+                const uint4 *sq = reinterpret_cast<const uint4 *>(a.in.side + (uint64_t)r.x * 16);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint4 v = sq[i];
+                    w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+                }
+                st = parse_record(w, a.in.rec_len ? r.w >> 16 : a.in.sizes[q], tw);
+                s0w = tw[0]; d0w = tw[4];
+                zw[0] = tw[1]; zw[1] = tw[2]; zw[2] = tw[3]; zw[3] = tw[5]; zw[4] = tw[6]; zw[5] = tw[7];
+            }
+            if (st != PARSE_OK) {
+                atomicAdd(st == PARSE_DROP ? &s_drop : &s_unsup, 1u);
+                okq = false;
+            } else {
+                wide = (zw[0] | zw[1] | zw[2] | zw[3] | zw[4] | zw[5]) != 0;
+            }
+        }
+        auto rows = [&](const uint32_t (&mkf)[GNS_KWMAX], const uint32_t (&mkm)[kSsNW]) {
+#pragma unroll
+            for (int rr = 0; rr < DD; rr++) {
+                const uint32_t j = ss_row_index(a.g, mm3_chain<GNS_KWMAX>(mkf, KF, a.g.seeds[rr]));
+                const uint64_t cell = (uint64_t)rr * a.g.w + j;
+                uint32_t s0, s1;
+                ss_hll_seeds(a.g.hll_master, cell, s0, s1);
+                const uint32_t h0 = mm3_chain<kSsNW>(mkm, KM, s0);  // geometricHash :66-70
+                uint32_t lz = (h0 ? (uint32_t)__clz(h0) : 32u) + 1u;
+                lzq[rr] = lz > a.g.maxv ? a.g.maxv : lz;
+                const uint32_t h1 = mm3_chain<kSsNW>(mkm, KM, s1);
+                const uint32_t idx = mpow2 ? (h1 & mmask) : h1 % a.g.m;  // :87-88
+                segq[rr] = cell * a.g.m + idx;
+                regq[rr] = okq ? (uint32_t)a.regs[segq[rr]] : 0xFFu;
+            }
+        };
+        uint32_t kwf[GNS_KWMAX], kwm[kSsNW], mkf[GNS_KWMAX], mkm[kSsNW];
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++) kwf[i] = 0;
+#pragma unroll
+        for (int i = 0; i < kSsNW; i++) kwm[i] = 0;
+        kwf[0] = s0w; kwm[0] = s0w; kwm[4] = d0w;
+        if (__ballot(wide) != 0) {  // wave-uniform: some lane's escape holds an IPv6 address
+            kwf[1] = zw[0]; kwf[2] = zw[1]; kwf[3] = zw[2];
+            kwm[1] = zw[0]; kwm[2] = zw[1]; kwm[3] = zw[2];
+            kwm[5] = zw[3]; kwm[6] = zw[4]; kwm[7] = zw[5];
+            mm3_premix<GNS_KWMAX>(kwf, KF, mkf);
+            mm3_premix<kSsNW>(kwm, KM, mkm);
+            rows(mkf, mkm);
+        } else {  // 12 of the 16 key words are constant zeros: their mixing and chain steps fold away
+            mm3_premix<GNS_KWMAX>(kwf, KF, mkf);
+            mm3_premix<kSsNW>(kwm, KM, mkm);
+            rows(mkf, mkm);
+        }
+    };
+    load_rec(beg + tid);
+    bool okc;
+    uint32_t lzc[DD], regc[DD];
+    uint64_t segc[DD];
+    stage_b(beg + tid, okc, segc, lzc, regc);
+    for (uint64_t p0 = beg; p0 < end; p0 += kSsThreads) {  // wave-uniform trip count
+        bool okn = false;
+        uint32_t lzn[DD], regn[DD];
+        uint64_t segn[DD];
+        if (p0 + kSsThreads < end) stage_b(p0 + kSsThreads + tid, okn, segn, lzn, regn);
+        const uint64_t p = p0 + tid;
+        if (okc) n_ok++;
+#pragma unroll
+        for (int rr = 0; rr < DD; rr++) {
+            const bool want = okc && lzc[rr] > regc[rr];  // can encode only if above the batch-entry register
+            const uint32_t q = wave_alloc(&s_cc, want);
+            if (want) {
+                rkey[q] = segc[rr] << kSsPktBits | (p & ((1ull << kSsPktBits) - 1));
+                rval[q] = lzc[rr];
+            }
+        }
+        okc = okn;
+#pragma unroll
+        for (int rr = 0; rr < DD; rr++) { segc[rr] = segn[rr]; lzc[rr] = lzn[rr]; regc[rr] = regn[rr]; }
+    }
+    atomicAdd(&s_ok, n_ok);
+    __syncthreads();
+    if (tid == 0) {
+        a.cblk[blk] = s_cc;
+        if (s_cc) atomicAdd(&a.stats[4], (unsigned long long)s_cc);
+        if (s_ok) atomicAdd(&a.stats[0], (unsigned long long)s_ok);
+        if (s_drop) atomicAdd(&a.stats[1], (unsigned long long)s_drop);
+        if (s_unsup) atomicAdd(&a.stats[2], (unsigned long long)s_unsup);
+    }
+}
+
 // S3b: flow ids for the successful encodes only (the MV loop's owner test and
 // the cell keys are the only consumers of flow identity, and only encodes
 // reach them).  Encode q's packet index is in skey[q]; its flow key is
@@ -1325,7 +1454,10 @@ struct gns_ss : FlowDict {
     uint32_t epoch = 0;
     uint64_t pkt = 0;     // records inserted since create (RNG packet index)
     bool s1_pipe = true;
-    bool s1_nodict = false;  // pipelined S1 for header records (GNS_SS_PIPE=0: the plain loop)
+    // compact records: the pipelined S1 only on request (GNS_SS_PIPE=1).  Measured against the generic
+    // instantiation it is within the run-to-run spread, so the generic one is the default
+    bool s1_pipe_rec = false;
+    bool s1_nodict = false;  // pipelined S1 for header and compact records (GNS_SS_PIPE=0: the plain loop)
     uint64_t n_encodes = 0, n_batches = 0;
     uint64_t bmax = 0;
     uint32_t nblk_max = 0;
@@ -1354,6 +1486,7 @@ struct gns_ss : FlowDict {
     unsigned long long *stats = nullptr;
     uint32_t *h_pin = nullptr;
     HostStage stage;
+    CompactInput compact;        // compact records: the staged side array, the 16-byte form's sizes
     StageTimer timer;
     HhScratch hh;                // HeavyHitters' device list buffers (gns_hh.hpp), filled on first use
 };
@@ -1366,6 +1499,7 @@ void ss_free_all(gns_ss *ss) {
     dfree(ss->ptotal); dfree(ss->ckey); dfree(ss->ckey_s); dfree(ss->skey); dfree(ss->skey_s);
     dfree(ss->cval); dfree(ss->sval); dfree(ss->shist); dfree(ss->spart); dfree(ss->sorder);
     dfree(ss->counts); dfree(ss->heads); dfree(ss->hlen); dfree(ss->sprof); dfree(ss->cblk); dfree(ss->stats); ss->stage.free_all();
+    ss->compact.free_all();
     ss->FlowDict::free_all();
     ss->hh.free_all();
     if (ss->h_pin) (void)hipHostFree(ss->h_pin);
@@ -1482,6 +1616,12 @@ int ss_run_batch(gns_ss *ss, const InputDesc &in, uint64_t n) {
         if constexpr (KIND == IN_HDR && MF == PLAN_SLICE0 && MM == PLAN_SLICE0) {
             if (ss->s1_pipe && ss->g.Kf == 16 && ss->g.Km == 32 && ss->g.d == 2) {
                 hipLaunchKernelGGL((k_ss_extract_hdr<MF, MM, 16, 32, 2>), dim3(nblk), dim3(kSsThreads), 0, s, x);
+                piped = true;
+            }
+        }
+        if constexpr (KIND == IN_REC16 && MF == PLAN_SLICE0 && MM == PLAN_SLICE0) {
+            if (ss->s1_pipe_rec && ss->g.Kf == 16 && ss->g.Km == 32 && ss->g.d == 2) {
+                hipLaunchKernelGGL((k_ss_extract_rec<2>), dim3(nblk), dim3(kSsThreads), 0, s, x);
                 piped = true;
             }
         }
@@ -1621,6 +1761,7 @@ int ss_insert(gns_ss *ss, InputDesc in, uint64_t n, gns_mem where) {
             stage_input(l, d, m);
             GNS_TRY(ss->stage.copy(l, ss->stream));
         }
+        if constexpr (KIND == IN_REC16) GNS_TRY(ss->compact.unpack_sizes(d, m, ss->stream));
         GNS_TRY(ss_batch_recover<KIND>(ss, d, m));
     }
     return GNS_OK;
@@ -1733,6 +1874,7 @@ int gns_ss_create(const gns_ss_params *p, gns_ss **out) {
         {
             const char *env = getenv("GNS_SS_PIPE");
             ss->s1_pipe = !(env && env[0] == '0');
+            ss->s1_pipe_rec = env && env[0] == '1';
         }
         if ((rc = dalloc_t(&ss->D.rec, slots * ss->D.RW)) != GNS_OK) break;
         if ((rc = dalloc_t(&ss->dctl, 4)) != GNS_OK || (rc = dalloc_t(&ss->stats_bak, 3)) != GNS_OK) break;
@@ -1801,6 +1943,17 @@ int gns_ss_insert_headers(gns_ss *ss, const uint8_t *hdr, const uint32_t *wirele
     in.hdr = reinterpret_cast<const uint32_t *>(hdr);
     in.sizes = wirelen;
     return ss_insert<IN_HDR>(ss, in, n, where);
+}
+
+int gns_ss_insert_compact(gns_ss *ss, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
+                          const uint8_t *side64, uint64_t n_side, gns_mem where) {
+    if (!ss || (n && !rec16) || (n_side && !side64)) { set_error("null argument"); return GNS_E_ARG; }
+    InputDesc in = compact_desc(rec16, wirelen, side64, n_side);
+    if (where != GNS_MEM_DEVICE) {  // S3b re-reads the side records: one device copy for the whole call
+        GNS_TRY(set_device(ss->device));
+        GNS_TRY(ss->compact.stage_side(in, ss->stream));
+    }
+    return ss_insert<IN_REC16>(ss, in, n, where);
 }
 
 int gns_ss_flush(gns_ss *ss) {

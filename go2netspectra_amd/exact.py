@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .packets import HeaderBatch, PacketBatch
+from .packets import CompactBatch, HeaderBatch, PacketBatch
 from .task import _check, go_ip_string
 
 DEFAULT_SHARDS = 256  # exact/task.go:72
@@ -362,6 +362,18 @@ class ExactAggregator:
         check(self._L.gns_ex_insert_headers(self._h, _ptr(hdr), _ptr(wirelen), _ptr(ts), int(wirelen.shape[0]),
                                             where))
 
+    def insert_compact(self, rec16, wirelen, ts, side=None) -> None:
+        """Compact records (packets.compact_headers / read_pcap_compact) + timestamps: the
+        same stream as insert_headers of the 64-byte records they were made from.
+        wirelen None: the 16-byte form (24 bytes per packet with the timestamps)."""
+        from .sketch import _compact_args
+        if ts is None:
+            raise ValueError("the exact aggregator needs timestamps")
+        (rec, wl, sd, tp), n, ns, where, keep = _compact_args(rec16, wirelen, side, ts)
+        if n == 0:
+            return
+        check(self._L.gns_ex_insert_compact(self._h, rec, wl, tp, n, sd, ns, where))
+
     def flush(self) -> None:
         check(self._L.gns_ex_flush(self._h))
 
@@ -506,6 +518,14 @@ class ExactTask:
         if isinstance(batch, HeaderBatch):
             ts = batch.ts if batch.ts is not None else np.zeros(len(batch), np.int64)
             self.agg.insert_headers(batch.hdr, batch.wirelen, ts)
+        elif isinstance(batch, CompactBatch):
+            ts = batch.ts
+            if ts is None and batch.is_device():
+                import torch
+                ts = torch.zeros(len(batch), dtype=torch.int64, device=batch.rec16.device)
+            elif ts is None:
+                ts = np.zeros(len(batch), np.int64)
+            self.agg.insert_compact(batch.rec16, batch.wirelen, ts, batch.side)
         else:
             self.agg.insert_tuples(batch)
 

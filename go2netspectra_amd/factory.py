@@ -75,6 +75,7 @@ class Manager:
 
     def __init__(self, cfg: Config, **task_kw):
         self.groups = create(cfg, **task_kw)
+        self.device = int(task_kw.get("device", 0))
         self.started = False
 
     def tasks(self) -> List[SketchTask]:
@@ -91,7 +92,13 @@ class Manager:
         return owner_fields([key_fields(t) for t in self.tasks()])
 
     def process(self, batch) -> None:
-        """processPacket (manager.go:232-244) for a whole batch: fan out to every task."""
+        """processPacket (manager.go:232-244) for a whole batch: fan out to every task.
+        A host CompactBatch is uploaded once and every task reads the device copy
+        (each task would otherwise stage its own)."""
+        from .packets import CompactBatch
+        if isinstance(batch, CompactBatch) and not batch.is_device() and len(self.tasks()) > 1 and len(batch):
+            import torch
+            batch = batch.to(torch.device("cuda", self.device))
         for t in self.tasks():
             t.process_packets(batch)
 

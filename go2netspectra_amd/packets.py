@@ -126,6 +126,44 @@ class HeaderBatch:
     def __len__(self) -> int:
         return int(self.wirelen.shape[0])
 
+    def compact(self, rec_len: bool = False) -> "CompactBatch":
+        """The compact form of a device-resident batch (compact_headers), ts carried
+        along.  rec_len: the 16-byte form."""
+        if not (_lib.is_device(self.hdr) and _lib.is_device(self.wirelen)):
+            raise ValueError("HeaderBatch.compact converts device-resident batches (read_pcap_compact packs a "
+                             "capture on the host)")
+        rec, side = compact_headers(self.hdr, self.wirelen, rec_len=rec_len)
+        return CompactBatch(rec, None if rec_len else self.wirelen, side, self.ts)
+
+
+@dataclass
+class CompactBatch:
+    """Compact records (include/gns_sketch.h gns_cm_insert_compact): what the engines'
+    insert_compact consume, host numpy or device torch arrays."""
+    rec16: "np.ndarray"               # [n,16] uint8
+    wirelen: Optional["np.ndarray"]   # [n] uint32, or None: the 16-byte form
+    side: Optional["np.ndarray"]      # [n_side,64] uint8 records the escapes name
+    ts: Optional["np.ndarray"] = None  # [n] int64 capture timestamps (ns)
+
+    def __len__(self) -> int:
+        return int(self.rec16.shape[0])
+
+    def is_device(self) -> bool:
+        return _lib.is_device(self.rec16)
+
+    def to(self, device) -> "CompactBatch":
+        """Copy to a torch device: one upload that any number of engines then read."""
+        import torch
+
+        def f(a, view=None):
+            if a is None:
+                return None
+            if _lib.is_device(a):
+                return a.to(device)
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if view is None else a.view(view)).to(device)
+        return CompactBatch(f(self.rec16), f(self.wirelen, np.int32), f(self.side), f(self.ts))
+
 
 def read_pcap(path: str, limit: Optional[int] = None) -> HeaderBatch:
     """pcap or pcapng -> 64-byte records (C++ packer, one pass, no per-packet objects)."""
@@ -149,10 +187,11 @@ def read_pcap(path: str, limit: Optional[int] = None) -> HeaderBatch:
         cap = total.value
 
 
-def read_pcap_compact(path: str, limit: Optional[int] = None, rec_len: bool = False):
+def read_pcap_compact(path: str, limit: Optional[int] = None, rec_len: bool = False, with_ts: bool = False):
     """pcap or pcapng -> compact records (rec16 [n, 16], wirelen [n], side [n_side, 64]);
     see include/gns_sketch.h gns_cm_insert_compact.  rec_len: the 16-byte form, the wire
-    lengths inside the records (wirelen is then None; GNS_E_RANGE above 65535)."""
+    lengths inside the records (wirelen is then None; GNS_E_RANGE above 65535).
+    with_ts: a CompactBatch with the capture timestamps instead of the tuple."""
     L = _lib.load()
     total, nside = ct.c_uint64(0), ct.c_uint64(0)
     cap = limit if limit is not None else max(1, (os.path.getsize(path) - 24) // 76 + 1)
@@ -161,7 +200,12 @@ def read_pcap_compact(path: str, limit: Optional[int] = None, rec_len: bool = Fa
         rec = np.empty((cap, 16), np.uint8)
         wl = None if rec_len else np.empty(cap, np.uint32)
         side = np.empty((side_cap, 64), np.uint8)
-        if rec_len:
+        ts = np.empty(cap, np.int64) if with_ts else None
+        if with_ts:
+            r = L.gns_pack_pcap_compact_ts(os.fsencode(path), rec.ctypes.data, None if wl is None else wl.ctypes.data,
+                                           ts.ctypes.data, cap, side.ctypes.data, side_cap, ct.byref(nside),
+                                           ct.byref(total))
+        elif rec_len:
             r = L.gns_pack_pcap_compact16(os.fsencode(path), rec.ctypes.data, cap, side.ctypes.data, side_cap,
                                           ct.byref(nside), ct.byref(total))
         else:
@@ -173,6 +217,8 @@ def read_pcap_compact(path: str, limit: Optional[int] = None, rec_len: bool = Fa
         if r < 0:
             check(int(r))
         if limit is not None or total.value <= cap:
+            if with_ts:
+                return CompactBatch(rec[:r], None if wl is None else wl[:r], side[:nside.value], ts[:r])
             return rec[:r], (None if wl is None else wl[:r]), side[:nside.value]
         cap = total.value
 

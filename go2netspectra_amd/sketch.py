@@ -72,6 +72,27 @@ def _where(*arrays) -> int:
     return _lib.MEM_HOST
 
 
+def _compact_args(rec16, wirelen, side, ts=None):
+    """The arguments of a gns_*_insert_compact call: (pointers of rec16, wirelen, side,
+    ts; n; n_side; where), after the host / device check and the length checks.  The
+    arrays the pointers name are returned too (they must outlive the call)."""
+    where = _where(*[a for a in (rec16, wirelen, side, ts) if a is not None])
+    if where == _lib.MEM_HOST:
+        rec16 = _host(rec16, np.uint8)
+        wirelen = _host(wirelen, np.uint32) if wirelen is not None else None
+        side = _host(side, np.uint8) if side is not None else None
+        ts = _host(ts, np.int64) if ts is not None else None
+    n = int(rec16.shape[0])
+    if wirelen is not None and int(wirelen.shape[0]) != n:
+        raise ValueError("rec16 and wirelen lengths differ")
+    if ts is not None and int(ts.shape[0]) != n:
+        raise ValueError("rec16 and ts lengths differ")
+    ns = int(side.shape[0]) if side is not None else 0
+    ptrs = (_ptr(rec16), _ptr(wirelen) if wirelen is not None else None, _ptr(side) if ns else None,
+            _ptr(ts) if ts is not None else None)
+    return ptrs, n, ns, where, (rec16, wirelen, side, ts)
+
+
 def _seeds_arg(seeds, depth):
     if seeds is None:
         return None, None
@@ -459,6 +480,13 @@ class SuperSpread:
             hdr = _host(hdr, np.uint8)
             wirelen = _host(wirelen, np.uint32)
         check(self._L.gns_ss_insert_headers(self._h, _ptr(hdr), _ptr(wirelen), int(wirelen.shape[0]), where))
+
+    def insert_compact(self, rec16, wirelen, side=None) -> None:
+        """Compact records, as CountMin.insert_compact takes them: the same stream as
+        insert_headers of the 64-byte records they were made from.  wirelen None: the
+        16-byte form."""
+        (rec, wl, sd, _), n, ns, where, keep = _compact_args(rec16, wirelen, side)
+        check(self._L.gns_ss_insert_compact(self._h, rec, wl, n, sd, ns, where))
 
     def flush(self) -> None:
         check(self._L.gns_ss_flush(self._h))

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .sketch import HeavyCount, HeavyRecord, _host, _is_device, _ptr, _where
+from .sketch import HeavyCount, HeavyRecord, _compact_args, _host, _is_device, _ptr, _where
 
 
 class ExactSpread:
@@ -105,6 +105,14 @@ class ExactSpread:
             hdr = _host(hdr, np.uint8)
             wirelen = _host(wirelen, np.uint32)
         check(self._L.gns_exs_insert_headers(self._h, _ptr(hdr), _ptr(wirelen), int(wirelen.shape[0]), where))
+
+    def insert_compact(self, rec16, wirelen, side=None) -> None:
+        """Compact records, as CountMin.insert_compact takes them: the same stream as
+        insert_headers of the 64-byte records they were made from.  wirelen None: the
+        16-byte form."""
+        self._on_device(rec16, wirelen, side)
+        (rec, wl, sd, _), n, ns, where, keep = _compact_args(rec16, wirelen, side)
+        check(self._L.gns_spread_insert_compact(self._h, rec, wl, n, sd, ns, where))
 
     def flush(self) -> None:
         check(self._L.gns_exs_flush(self._h))

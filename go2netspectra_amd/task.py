@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .config import SketchTaskDef
-from .packets import HeaderBatch, PacketBatch
+from .packets import CompactBatch, HeaderBatch, PacketBatch
 from .sketch import CountMin, HeavyRecord, SuperSpread
 
 log = logging.getLogger("go2netspectra_amd")
@@ -116,9 +116,11 @@ class SketchTask:
         return self.decode_flow
 
     def process_packets(self, batch) -> None:
-        """Batched ProcessPacket: PacketBatch or HeaderBatch (or device equivalents)."""
+        """Batched ProcessPacket: PacketBatch, HeaderBatch or CompactBatch (or device equivalents)."""
         if isinstance(batch, HeaderBatch):
             self.sketch.insert_headers(batch.hdr, batch.wirelen)
+        elif isinstance(batch, CompactBatch):
+            self.sketch.insert_compact(batch.rec16, batch.wirelen, batch.side)
         else:
             self.sketch.insert_tuples(batch)
 

@@ -293,6 +293,18 @@ int gns_ss_insert_keys(gns_ss *ss, const uint8_t *flows, uint32_t fstride, const
 int gns_ss_insert_tuples(gns_ss *ss, const gns_tuples *t, uint64_t n, gns_mem where);
 int gns_ss_insert_headers(gns_ss *ss, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n,
                           gns_mem where);
+/* Compact records, by the contract of gns_cm_insert_compact: the insert equals
+ * gns_ss_insert_headers of the 64-byte records the compact form was made from
+ * (state, counters [0..2], the declared generator's record index).  wirelen ==
+ * NULL: the 16-byte form.  Class 1 records are dropped and counted in [1]; an
+ * escape whose index is at or past n_side is counted unsupported in [2] and its
+ * side record never read; escapes index the side array of the whole call; every
+ * array of a call lives in `where`.  GNS_E_ARG before any device call for a null
+ * handle, a null rec16 with n > 0, and n_side > 0 with a null side64.  Device
+ * arrays must stay valid until the call returns (the flow ids of the batch's
+ * encodes are derived from them after the sort). */
+int gns_ss_insert_compact(gns_ss *ss, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
+                          const uint8_t *side64, uint64_t n_side, gns_mem where);
 int gns_ss_flush(gns_ss *ss);
 int gns_ss_query(gns_ss *ss, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
 /* device keys / answers, as gns_cm_query_device */
@@ -368,6 +380,12 @@ int64_t gns_pack_pcap_compact16(const char *path, uint8_t *rec16, uint64_t cap, 
                                 uint64_t side_cap, uint64_t *n_side, uint64_t *total);
 int gns_compact_headers16(const uint8_t *hdr, const uint32_t *wirelen, uint64_t n, uint8_t *rec16,
                           uint8_t *side64, uint64_t side_cap, uint64_t *n_side, int device);
+/* gns_pack_pcap_compact (wirelen == NULL: gns_pack_pcap_compact16) with the capture
+ * timestamps gns_pack_pcap_ts writes: records, side array, counts and gns_pack_counts
+ * are those of the call without timestamps (the exact aggregator's compact input) */
+int64_t gns_pack_pcap_compact_ts(const char *path, uint8_t *rec16, uint32_t *wirelen, int64_t *ts_ns,
+                                 uint64_t cap, uint8_t *side64, uint64_t side_cap, uint64_t *n_side,
+                                 uint64_t *total);
 
 /* [0] frames copied verbatim, [1] frames decoded on the host into 0x88B5
  * records, [2] frames without an IP layer, of the calling thread's last
@@ -485,6 +503,13 @@ int gns_ex_insert_tuples(gns_ex *ex, const gns_tuples *t, const uint8_t *ipver, 
 /* fused parse of 64-byte records (as gns_cm_insert_headers) + timestamps */
 int gns_ex_insert_headers(gns_ex *ex, const uint8_t *hdr, const uint32_t *wirelen, const int64_t *ts_ns,
                           uint64_t n, gns_mem where);
+/* Compact records + timestamps, by the contract of gns_cm_insert_compact (see
+ * gns_ss_insert_compact): equals gns_ex_insert_headers of the 64-byte records the
+ * compact form was made from.  The IP versions of a tuple record are those of its
+ * word 3 (IPv4 both ways in the 16-byte form), the ByteCount increment is the wire
+ * length: 24 B/packet in the 16-byte form.  GNS_E_ARG also for a null ts_ns. */
+int gns_ex_insert_compact(gns_ex *ex, const uint8_t *rec16, const uint32_t *wirelen, const int64_t *ts_ns,
+                          uint64_t n, const uint8_t *side64, uint64_t n_side, gns_mem where);
 int gns_ex_flush(gns_ex *ex);
 /* out[i] = PacketCount << 32 | ByteCount (task.go:323); IP fields of the
  * encoded flow are read as 16-byte net.IPs, as the reference does; 0 if absent */
@@ -646,6 +671,12 @@ int gns_exs_insert_keys(gns_exs *h, const uint8_t *flows, uint32_t fstride, cons
 int gns_exs_insert_tuples(gns_exs *h, const gns_tuples *t, uint64_t n, gns_mem where);
 int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n,
                            gns_mem where);
+/* Compact records, by the contract of gns_cm_insert_compact (see
+ * gns_ss_insert_compact): equals gns_exs_insert_headers of the 64-byte records
+ * the compact form was made from.  (Named outside the gns_exs_ family, whose symbol
+ * list is pinned, as the gns_pairs_ calls are.) */
+int gns_spread_insert_compact(gns_exs *h, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
+                           const uint8_t *side64, uint64_t n_side, gns_mem where);
 int gns_exs_flush(gns_exs *h);
 /* out[i] = spread of flow i (0 if never seen) */
 int gns_exs_query(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
