@@ -14,7 +14,7 @@ from .exact import (ExactAggregator, ExactTask, ExactView, FlowLifecycle, HeavyH
 from .factory import Manager, TaskGroup, create, register_aggregator
 from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
-from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread
+from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread, SuperSpreadView
 from .spread import ExactSpread
 from .task import New, SketchTask, decode_flow
 
@@ -25,4 +25,5 @@ __all__ = [
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "apply_delta", "CompactBatch",
+    "SuperSpreadView",
 ]

@@ -51,6 +51,8 @@ EXPORTED = [
     "gns_ex_view_aggregate", "gns_ex_view_heavy_hitters",
     "gns_pairs_export", "gns_pairs_merge", "gns_pairs_merge_from",
     "gns_ss_insert_compact", "gns_spread_insert_compact", "gns_ex_insert_compact", "gns_pack_pcap_compact_ts",
+    "gns_ss_view_create", "gns_ss_view_destroy", "gns_ss_view_refresh", "gns_ss_view_query",
+    "gns_ss_view_query_device", "gns_ss_view_heavy_hitters", "gns_ss_view_heavy_rows", "gns_ss_view_export_state",
 ]
 
 
@@ -231,6 +233,11 @@ def load() -> ct.CDLL:
         "gns_spread_insert_compact": ([vp, vp, vp, u64, vp, u64, i32], i32),
         "gns_ex_insert_compact": ([vp, vp, vp, vp, u64, vp, u64, i32], i32),
         "gns_pack_pcap_compact_ts": ([ct.c_char_p, vp, vp, vp, u64, vp, u64, vp, vp], ct.c_int64),
+        "gns_ss_view_create": ([vp, vp], i32), "gns_ss_view_destroy": ([vp], i32),
+        "gns_ss_view_refresh": ([vp, u32], i32), "gns_ss_view_query": ([vp, vp, u32, u64, vp], i32),
+        "gns_ss_view_query_device": ([vp, vp, u32, u64, vp], i32),
+        "gns_ss_view_heavy_hitters": ([vp, vp, vp, vp], i32), "gns_ss_view_heavy_rows": ([vp, vp, vp], i32),
+        "gns_ss_view_export_state": ([vp, vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -286,6 +293,7 @@ def dict_stats(fn, h) -> dict:
 
 
 GNS_TIMING_MASK = 0x100
+GNS_SS_VIEW_STATE = 1  # gns_ss_view_refresh: also capture registers, pbits, counters, generator position
 
 
 def timing_arg(on, stages, names) -> int:

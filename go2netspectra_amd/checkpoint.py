@@ -2,8 +2,8 @@
 
 The reference keeps a measurement period's state in process memory only (SURVEY
 §5 "Checkpoint/resume: no"); here it lives in HBM.  ``save`` exports it through
-the engines' read side (gns_cm_export_state, gns_ss_export_state,
-gns_ex_snapshot, gns_pairs_export), ``restore`` puts it back through the write
+the engines' read side (gns_cm_export_state, gns_ss_export_state or a
+SuperSpread view's gns_ss_view_export_state, gns_ex_snapshot, gns_pairs_export), ``restore`` puts it back through the write
 side (gns_cm_import_state, gns_ss_import_state, gns_ex_merge / gns_pairs_merge
 into an emptied table).
 
@@ -104,7 +104,17 @@ def check_meta(saved: dict, live: dict) -> None:
 
 
 def save(obj, path) -> None:
-    """Export ``obj``'s state (after its pending inserts) into one file."""
+    """Export ``obj``'s state (after its pending inserts) into one file.  A SuperSpreadView
+    refreshed with state=True writes the file its SuperSpread would have written at the
+    refresh -- from any thread, while the sketch keeps ingesting."""
+    if type(obj).__name__ == "SuperSpreadView":
+        meta = describe(obj.parent)
+        v, k, r, p = obj.export_state()
+        c = obj.counters()
+        meta["counters"] = [c["inserted"], c["dropped"], c["unsupported"]]
+        meta["records"] = c["records"]
+        write(path, meta, {"values": v, "keys": np.ascontiguousarray(k), "regs": r, "pbits": p.view(np.uint64)})
+        return
     meta = describe(obj)
     cls = meta["class"]
     if cls == "CountMin":

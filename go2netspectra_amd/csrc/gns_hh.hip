@@ -540,6 +540,19 @@ int hh_heavy_list(HhScratch &sc, hipStream_t st, const DictDev &D, uint64_t dict
     return GNS_OK;
 }
 
+// gns_hh_order_rows' order for a caller that owns its scratch and its stream: nothing is
+// copied to the host and the stream is left running (the caller synchronizes it).  Keys
+// longer than four bytes cost one small read-back inside the order (the tie flag).
+int hh_order_rows_dev(HhScratch &sc, hipStream_t st, const uint8_t *rows, uint32_t K, uint32_t n, uint8_t *out_rows) {
+    if (n == 0) return GNS_OK;
+    const HhSrc src{nullptr, rows, K, K + 4};
+    uint32_t *perm = nullptr;
+    GNS_TRY(hh_sort(sc, st, src, n, &perm));
+    hipLaunchKernelGGL(k_hh_gather, dim3((n + 255) / 256), dim3(256), 0, st, perm, src, n, nullptr, nullptr, out_rows);
+    GNS_HIP(hipGetLastError());
+    return GNS_OK;
+}
+
 }  // namespace gns
 
 using namespace gns;

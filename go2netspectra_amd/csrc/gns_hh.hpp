@@ -61,4 +61,9 @@ int hh_heavy_list(HhScratch &sc, hipStream_t st, const DictDev &D, uint64_t dict
 // flow ids -> key bytes in host memory (GNS_ID_NONE -> zero bytes, the reference's reset FP)
 int hh_ids_to_host_bytes(HhScratch &sc, hipStream_t st, const DictDev &D, const uint32_t *d_ids, uint64_t n,
                          uint8_t *host);
+// The canonical order (value desc, flow bytes asc) of n packed device rows [flow (K) | u32
+// value] -> out_rows (device, not `rows`), with the caller's scratch on stream st: enqueued,
+// no copy to the host, the stream is not synchronized at the end (gns_hh_order_rows is this
+// on the null stream with a per-thread scratch).
+int hh_order_rows_dev(HhScratch &sc, hipStream_t st, const uint8_t *rows, uint32_t K, uint32_t n, uint8_t *out_rows);
 }  // namespace gns

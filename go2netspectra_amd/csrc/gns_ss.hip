@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "gns_common.hpp"
@@ -1435,6 +1436,130 @@ __global__ __launch_bounds__(256) void k_ss_check_regs(const uint8_t *regs, uint
     if (c) atomicAdd(bad, c);
 }
 
+// ---------------------------------------------------------------------------
+// Snapshot view (gns_ss_view_*): dense per-cell arrays vals[d*w] and kw[d*w][Kw]
+// (the owner's key as the zero-padded little-endian words of its dictionary
+// record, Kw = ceil(flow_bytes / 4)), resolved at the refresh.  Nothing in them
+// names a dictionary slot, so the three kernels below read no handle state.
+// ---------------------------------------------------------------------------
+struct SsViewDev {
+    SsGeom g;
+    uint32_t Kw;             // key words per cell (>= 1: a zero-byte key keeps one zero word)
+    const uint32_t *vals;
+    const uint32_t *kw;
+};
+
+__device__ __forceinline__ bool ssv_key_eq(const SsViewDev &V, uint64_t c, const uint32_t (&kw)[GNS_KWMAX]) {
+    const uint32_t *q = V.kw + c * V.Kw;
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < GNS_KWMAX; j++)
+        if ((uint32_t)j < V.Kw) eq = eq && q[j] == kw[j];
+    return eq;
+}
+
+// Refresh: one lane per cell.  The owner's record was committed by the kernel
+// boundary behind the insert that claimed it.  An id that is no slot
+// of the dictionary is not dereferenced: it raises *bad, which the next reader
+// call reports (k_hh_best's convention).
+__global__ __launch_bounds__(256) void k_ssv_snap(const uint32_t *values, const uint32_t *keys, DictDev D,
+                                                  uint64_t slots, uint64_t cells, uint32_t Kw, uint32_t *vals,
+                                                  uint32_t *kw, uint32_t *bad) {
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= cells) return;
+    const uint32_t id = keys[c];
+    uint32_t r[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) r[i] = 0;
+    if (id != GNS_ID_NONE) {
+        if (id < slots) load_record(D, id, r);
+        else atomicOr(bad, 1u);
+    }
+    vals[c] = values[c];
+    if ((Kw & 3u) == 0) {  // 16 or 32 bytes per cell: whole 16-byte stores (the arrays are 256-byte aligned)
+        uint4 *o = reinterpret_cast<uint4 *>(kw + c * Kw);
+        o[0] = make_uint4(r[1], r[2], r[3], r[4]);
+        if (Kw == 8) o[1] = make_uint4(r[5], r[6], r[7], r[8]);
+    } else {
+        uint32_t *o = kw + c * Kw;
+#pragma unroll
+        for (int j = 0; j < GNS_KWMAX; j++)
+            if ((uint32_t)j < Kw) o[j] = r[1 + j];
+    }
+}
+
+// Query (super_spread.go:238-249) on a view: k_ss_query with the cell's key words
+// in place of the dictionary lookup and the id compare.  An empty cell holds zero
+// words and the value 0, so matching it changes no answer.
+__global__ __launch_bounds__(256) void k_ssv_query(const uint8_t *flows, uint32_t stride, uint64_t n, SsViewDev V,
+                                                   uint64_t *out) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    uint32_t kw[GNS_KWMAX];
+    load_key_bytes<GNS_KWMAX>(flows + p * stride, V.g.Kf, false, kw);
+    uint32_t est = 0;
+    for (uint32_t r = 0; r < V.g.d; r++) {
+        const uint64_t c = (uint64_t)r * V.g.w + ss_row_index(V.g, mm3_n<GNS_KWMAX>(kw, V.g.Kf, V.g.seeds[r]));
+        if (ssv_key_eq(V, c, kw)) est = max(est, V.vals[c]);
+    }
+    out[p] = est > 1 ? est : 1;
+}
+
+// HeavyHitters (super_spread.go:254-294) on a view, without ids or per-flow words:
+// a lane whose cell reaches the threshold takes the cell's key, walks the flow's
+// cell in every row (the loop of :266-276) and keeps the estimate and the lowest
+// row that holds it.  The lane emits [flow bytes | u32 est] iff that cell is its
+// own: exactly one emit per flow with est >= thr, whatever the order.  Rows are
+// appended with one global add per workgroup (ballot ranks + an LDS count); a row
+// at or past cap is counted and not written.  grid = (ceil(w / 256), d).
+__global__ __launch_bounds__(256) void k_ssv_heavy(SsViewDev V, uint32_t thr, uint8_t *rows, uint32_t *count,
+                                                   uint32_t cap) {
+    __shared__ uint32_t s_n, s_base;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
+    const uint32_t K = V.g.Kf;
+    uint32_t kw[GNS_KWMAX];
+    uint32_t est = 0;
+    bool emit = false;
+    if (i < V.g.w) {
+        const uint64_t c = (uint64_t)row * V.g.w + i;
+        const uint32_t v = V.vals[c];
+        if (v > 0 && v >= thr) {
+            const uint32_t *q = V.kw + c * V.Kw;
+#pragma unroll
+            for (int j = 0; j < GNS_KWMAX; j++) kw[j] = (uint32_t)j < V.Kw ? q[j] : 0u;
+            uint64_t best = ~0ull;
+            for (uint32_t r = 0; r < V.g.d; r++) {
+                const uint64_t cr = (uint64_t)r * V.g.w + ss_row_index(V.g, mm3_n<GNS_KWMAX>(kw, K, V.g.seeds[r]));
+                if (!ssv_key_eq(V, cr, kw)) continue;
+                const uint32_t vr = V.vals[cr];
+                if (vr > est) { est = vr; best = cr; }  // strictly greater: the lowest row among ties
+            }
+            emit = best == c;
+        }
+    }
+    const uint64_t peers = __ballot(emit);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t rank = (uint32_t)__popcll(peers & (lane ? (~0ull >> (64u - lane)) : 0ull));
+    uint32_t wbase = 0;
+    if (lane == 0 && peers) wbase = atomicAdd(&s_n, (uint32_t)__popcll(peers));
+    wbase = __shfl(wbase, 0);
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_n ? atomicAdd(count, s_n) : 0u;
+    __syncthreads();
+    if (!emit) return;
+    const uint32_t pos = s_base + wbase + rank;
+    if (pos >= cap) return;
+    uint8_t *o = rows + (uint64_t)pos * (K + 4);
+#pragma unroll
+    for (int j = 0; j < GNS_KWMAX; j++)
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+            if ((uint32_t)(4 * j + b) < K) o[4 * j + b] = (uint8_t)(kw[j] >> (8 * b));
+    o[K] = (uint8_t)est; o[K + 1] = (uint8_t)(est >> 8); o[K + 2] = (uint8_t)(est >> 16); o[K + 3] = (uint8_t)(est >> 24);
+}
+
 }  // namespace gns
 
 // ===========================================================================
@@ -2194,6 +2319,353 @@ int gns_ss_stage_times(gns_ss *ss, double ms[8], uint64_t launches[8], int reset
         if (launches) launches[i] = ss->timer.launches[i];
     }
     if (reset) for (int i = 0; i < 8; i++) { ss->timer.ms[i] = 0; ss->timer.launches[i] = 0; }
+    return GNS_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Snapshot views (gns_ss_view_*): the list, queries and the whole state read on
+// another thread while the handle ingests (the reference's snapshotter and
+// alerter call Task.Snapshot while the workers insert, manager.go:139-159,
+// sketch/task.go:177,187-243).  A view is the exact view's shape:
+// self-contained rows, so reset, reclaim, growth and import leave it readable.
+// ===========================================================================
+constexpr size_t kSsvPinChunk = 4u << 20;
+
+struct gns_ss_view {
+    gns_ss *ss = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ready = nullptr;
+    std::mutex mu;            // refresh vs readers: a refresh waits for the reader call in progress
+    bool fresh = false;       // refreshed at least once
+    bool state = false;       // the last refresh carried GNS_SS_VIEW_STATE
+    SsGeom g{};
+    uint32_t thr = 0, Kw = 1;
+    uint64_t cells = 0;
+    uint32_t *vals = nullptr, *kw = nullptr;   // [cells], [cells][Kw]
+    uint8_t *regs = nullptr;                   // [cells][m]   (first refresh with state)
+    double *pbits = nullptr;                   // [cells]
+    unsigned long long *ctr = nullptr;         // [3] inserted, dropped, unsupported
+    uint64_t records = 0;                      // the generator position at the refresh
+    uint32_t *words = nullptr;                 // [0] refresh: an id named no slot; [1] the list's length
+    // readers' grow-only scratch
+    uint8_t *qk = nullptr;
+    uint64_t *qo = nullptr;
+    uint64_t qk_n = 0, qo_n = 0;
+    uint8_t *rows = nullptr, *orows = nullptr;  // the list as emitted / in canonical order
+    uint64_t rows_n = 0, orows_n = 0, rows_cap = 0;  // bytes, bytes, rows
+    HhScratch hh;                               // the order's scratch
+    uint8_t *pin = nullptr;                     // pinned staging: two chunks (exports), or one piece (lists, queries)
+    size_t pin_n = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint32_t *hsm = nullptr;                    // pinned: [0] bad flag, [1] list length, [2..7] counters
+};
+
+namespace {
+
+void ssv_free(gns_ss_view *v) {
+    dfree(v->vals); dfree(v->kw); dfree(v->regs); dfree(v->pbits); dfree(v->ctr); dfree(v->words);
+    dfree(v->qk); dfree(v->qo); dfree(v->rows); dfree(v->orows);
+    v->hh.free_all();
+    if (v->pin) (void)hipHostFree(v->pin);
+    if (v->hsm) (void)hipHostFree(v->hsm);
+    for (int i = 0; i < 2; i++)
+        if (v->ev[i]) (void)hipEventDestroy(v->ev[i]);
+    if (v->ready) (void)hipEventDestroy(v->ready);
+    if (v->stream) (void)hipStreamDestroy(v->stream);
+}
+
+// pinned staging of at least `bytes` (grow-only, to twice the request)
+int ssv_pin(gns_ss_view *v, size_t bytes) {
+    if (bytes <= v->pin_n && v->pin) return GNS_OK;
+    if (v->pin) (void)hipHostFree(v->pin);
+    v->pin = nullptr;
+    v->pin_n = 0;
+    const size_t want = std::max<size_t>(2 * bytes, 2 * kSsvPinChunk);
+    if (hipHostMalloc(reinterpret_cast<void **>(&v->pin), want, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hipHostMalloc(%zu bytes) failed", want);
+        return GNS_E_OOM;
+    }
+    v->pin_n = want;
+    return GNS_OK;
+}
+
+// Device bytes -> the caller's host memory through the two pinned chunks, one in flight
+// while the other is copied out (gns_ex_view_snapshot's scheme); complete on return.
+// sw != 0: the source is rows of sw bytes of which the first dw go out (key words -> key bytes).
+int ssv_copy_out(gns_ss_view *v, void *dst, const void *src, size_t bytes, size_t sw = 0, size_t dw = 0) {
+    size_t half = kSsvPinChunk;
+    if (sw) half -= half % sw;
+    const size_t nchunk = (bytes + half - 1) / half;
+    uint8_t *d = static_cast<uint8_t *>(dst);
+    for (size_t j = 0; j <= nchunk; j++) {
+        if (j < nchunk) {
+            const size_t off = j * half;
+            GNS_HIP(hipMemcpyAsync(v->pin + (j & 1) * kSsvPinChunk, static_cast<const uint8_t *>(src) + off,
+                                   std::min(half, bytes - off), hipMemcpyDeviceToHost, v->stream));
+            GNS_HIP(hipEventRecord(v->ev[j & 1], v->stream));
+        }
+        if (j > 0) {
+            const size_t i = j - 1, off = i * half, m = std::min(half, bytes - off);
+            GNS_HIP(hipEventSynchronize(v->ev[i & 1]));
+            const uint8_t *p = v->pin + (i & 1) * kSsvPinChunk;
+            if (!sw || sw == dw) {
+                memcpy(d + (sw ? off / sw * dw : off), p, m);
+            } else {
+                uint8_t *o = d + off / sw * dw;
+                for (size_t r = 0; r < m / sw; r++) memcpy(o + r * dw, p + r * sw, dw);
+            }
+        }
+    }
+    return GNS_OK;
+}
+
+SsViewDev ssv_dev(const gns_ss_view *v) { return SsViewDev{v->g, v->Kw, v->vals, v->kw}; }
+
+// reader side, under v->mu
+int ssv_ready(gns_ss_view *v) {
+    if (!v->fresh) { set_error("view never refreshed"); return GNS_E_ARG; }
+    return GNS_OK;
+}
+
+int ssv_bad_id() {
+    set_error("view refresh: a cell's key id named no dictionary slot (corrupt state)");
+    return GNS_E_HIP;
+}
+
+int ssv_query_impl(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
+    if (!v || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
+    if (n && stride < v->g.Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
+    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
+    GNS_TRY(set_device(v->ss->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(ssv_ready(v));
+    if (n == 0) return GNS_OK;
+    hipStream_t s = v->stream;
+    const uint8_t *dk = flows;
+    uint64_t *dout = out;
+    const size_t kb = (size_t)n * stride, ob = (size_t)n * 8, koff = (ob + 15) & ~(size_t)15;
+    if (!dev) {
+        GNS_TRY(grow_buf(&v->qk, v->qk_n, (uint64_t)kb));
+        GNS_TRY(grow_buf(&v->qo, v->qo_n, n));
+        GNS_TRY(ssv_pin(v, koff + kb));
+        memcpy(v->pin + koff, flows, kb);
+        GNS_HIP(hipMemcpyAsync(v->qk, v->pin + koff, kb, hipMemcpyHostToDevice, s));
+        dk = v->qk;
+        dout = v->qo;
+    }
+    hipLaunchKernelGGL(k_ssv_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dk, stride, n, ssv_dev(v), dout);
+    GNS_HIP(hipGetLastError());
+    if (!dev) GNS_HIP(hipMemcpyAsync(v->pin, v->qo, ob, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 4, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    if (v->hsm[0]) return ssv_bad_id();
+    if (!dev) memcpy(out, v->pin, ob);
+    return GNS_OK;
+}
+
+// The view's list in canonical order on the device: *n_out = the full length.  Under v->mu.
+// to_host: ordered into v->orows, and the first min(n, cap) rows copied into the pinned
+// staging.  Else into rows_dev (cap rows; null only asks for the length): a list longer than
+// it is reported and not written.  The stream is synchronized on return.
+int ssv_list(gns_ss_view *v, uint64_t cap, uint8_t *rows_dev, bool to_host, uint64_t *n_out) {
+    hipStream_t s = v->stream;
+    const uint32_t K = v->g.Kf, W = K + 4;
+    uint32_t n = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        GNS_HIP(hipMemsetAsync(v->words + 1, 0, 4, s));
+        hipLaunchKernelGGL(k_ssv_heavy, dim3((v->g.w + 255) / 256, v->g.d), dim3(256), 0, s, ssv_dev(v), v->thr, v->rows,
+                           v->words + 1, (uint32_t)v->rows_cap);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 8, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        if (v->hsm[0]) return ssv_bad_id();
+        n = v->hsm[1];
+        if (n <= v->rows_cap) break;
+        // a list longer than the buffer: grow to the count and run again
+        const uint64_t want = std::min<uint64_t>(v->cells, (uint64_t)n + n / 8);
+        GNS_TRY(grow_buf(&v->rows, v->rows_n, want * W));
+        v->rows_cap = v->rows_n / W;
+    }
+    *n_out = n;
+    if (n == 0) return GNS_OK;
+    if (!to_host && (!rows_dev || n > cap)) return GNS_OK;  // reported, not written
+    uint8_t *dst = rows_dev;
+    if (to_host) {
+        GNS_TRY(grow_buf(&v->orows, v->orows_n, (uint64_t)n * W));
+        dst = v->orows;
+    }
+    GNS_TRY(gns::hh_order_rows_dev(v->hh, s, v->rows, K, n, dst));
+    if (to_host) {
+        const size_t b = (size_t)std::min<uint64_t>(n, cap) * W;
+        if (b) {
+            GNS_TRY(ssv_pin(v, b));
+            GNS_HIP(hipMemcpyAsync(v->pin, dst, b, hipMemcpyDeviceToHost, s));
+        }
+    }
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gns_ss_view_create(gns_ss *ss, gns_ss_view **out) {
+    if (!ss || !out) { set_error("null argument"); return GNS_E_ARG; }
+    *out = nullptr;
+    GNS_TRY(set_device(ss->device));
+    gns_ss_view *v = new gns_ss_view();
+    v->ss = ss;
+    v->g = ss->g;
+    v->thr = ss->thr;
+    v->Kw = std::max<uint32_t>((ss->g.Kf + 3) / 4, 1);
+    v->cells = (uint64_t)ss->g.d * ss->g.w;
+    int rc = GNS_OK;
+    do {
+        // the device's highest priority, as the other views' streams: a reader's small
+        // launches are dispatched ahead of the ingest pipeline's queued workgroups
+        int lo_pri = 0, hi_pri = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
+        if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
+            hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&v->ev[0], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&v->ev[1], hipEventDisableTiming) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void **>(&v->hsm), 64, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("view stream/event"); rc = GNS_E_HIP; break;
+        }
+        if ((rc = dalloc_t(&v->vals, v->cells)) != GNS_OK || (rc = dalloc_t(&v->kw, v->cells * v->Kw)) != GNS_OK ||
+            (rc = dalloc_t(&v->words, 4)) != GNS_OK || (rc = ssv_pin(v, 2 * kSsvPinChunk)) != GNS_OK) break;
+        // the list's rows and the order's scratch for 64K flows up front; longer lists grow them
+        const uint32_t W = ss->g.Kf + 4;
+        const uint64_t nr = std::min<uint64_t>(v->cells, 1u << 16);
+        if ((rc = grow_buf(&v->rows, v->rows_n, nr * W)) != GNS_OK ||
+            (rc = grow_buf(&v->orows, v->orows_n, nr * W)) != GNS_OK ||
+            (rc = grow_buf(&v->hh.u32c, v->hh.u32c_n, nr)) != GNS_OK ||
+            (rc = grow_buf(&v->hh.rsh, v->hh.rsh_n, 16 * 256)) != GNS_OK) break;
+        v->rows_cap = v->rows_n / W;
+        if (hipMemsetAsync(v->words, 0, 16, v->stream) != hipSuccess || hipStreamSynchronize(v->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("view words"); rc = GNS_E_HIP; break;
+        }
+    } while (0);
+    if (rc) { ssv_free(v); delete v; return rc; }
+    *out = v;
+    return GNS_OK;
+}
+
+int gns_ss_view_destroy(gns_ss_view *v) {
+    if (!v) return GNS_OK;
+    (void)hipSetDevice(v->ss->device);
+    {   // wait for a reader call in progress; the mutex is released before the delete
+        std::lock_guard<std::mutex> lk(v->mu);
+        if (v->stream) (void)hipStreamSynchronize(v->stream);
+        // (freeing the arrays waits for a refresh still running on the handle's stream)
+    }
+    ssv_free(v);
+    delete v;
+    return GNS_OK;
+}
+
+int gns_ss_view_refresh(gns_ss_view *v, uint32_t flags) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    if (flags & ~GNS_SS_VIEW_STATE) { set_error("view refresh: unknown flags 0x%x", flags); return GNS_E_ARG; }
+    gns_ss *ss = v->ss;
+    GNS_TRY(set_device(ss->device));
+    std::lock_guard<std::mutex> lk(v->mu);  // no reader is using the arrays
+    const bool st = (flags & GNS_SS_VIEW_STATE) != 0;
+    if (st && !v->regs) {  // the first refresh with state
+        GNS_TRY(dalloc_t(&v->regs, v->cells * ss->g.m));
+        GNS_TRY(dalloc_t(&v->pbits, v->cells));
+        GNS_TRY(dalloc_t(&v->ctr, 3));
+    }
+    hipStream_t s = ss->stream;
+    v->fresh = false;
+    {
+        ScopedStage t(ss->timer, 6);
+        GNS_HIP(hipMemsetAsync(v->words, 0, 4, s));
+        hipLaunchKernelGGL(k_ssv_snap, dim3((unsigned)((v->cells + 255) / 256)), dim3(256), 0, s, ss->values, ss->keys,
+                           ss->D, ss->dict_slots, v->cells, v->Kw, v->vals, v->kw, v->words);
+        GNS_HIP(hipGetLastError());
+        if (st) {
+            GNS_HIP(hipMemcpyAsync(v->regs, ss->regs, v->cells * ss->g.m, hipMemcpyDeviceToDevice, s));
+            GNS_HIP(hipMemcpyAsync(v->pbits, ss->pbits, v->cells * 8, hipMemcpyDeviceToDevice, s));
+            GNS_HIP(hipMemcpyAsync(v->ctr, ss->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    // the arrays are the state after every insert issued so far and before any later
+    // one; the view's stream waits for them
+    GNS_HIP(hipEventRecord(v->ready, s));
+    GNS_HIP(hipStreamWaitEvent(v->stream, v->ready, 0));
+    v->records = ss->pkt;
+    v->state = st;
+    v->fresh = true;
+    return GNS_OK;
+}
+
+int gns_ss_view_query(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
+    return ssv_query_impl(v, flows, stride, n, out, false);
+}
+
+int gns_ss_view_query_device(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
+    return ssv_query_impl(v, flows, stride, n, out, true);
+}
+
+int gns_ss_view_heavy_hitters(gns_ss_view *v, uint8_t *flows, uint32_t *spreads, uint64_t *n_io) {
+    if (!v || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(v->ss->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(ssv_ready(v));
+    const uint64_t cap = *n_io;
+    uint64_t n = 0;
+    GNS_TRY(ssv_list(v, cap, nullptr, true, &n));
+    *n_io = n;
+    const uint64_t m = std::min(n, cap);
+    const uint32_t K = v->g.Kf, W = K + 4;
+    for (uint64_t i = 0; i < m; i++) {
+        const uint8_t *r = v->pin + i * W;
+        if (flows && K) memcpy(flows + i * K, r, K);
+        if (spreads) memcpy(spreads + i, r + K, 4);
+    }
+    return GNS_OK;
+}
+
+int gns_ss_view_heavy_rows(gns_ss_view *v, uint8_t *rows_dev, uint64_t *n_io) {
+    if (!v || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(v->ss->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(ssv_ready(v));
+    uint64_t n = 0;
+    GNS_TRY(ssv_list(v, *n_io, rows_dev, false, &n));
+    *n_io = n;
+    return GNS_OK;
+}
+
+int gns_ss_view_export_state(gns_ss_view *v, uint32_t *values, uint8_t *keys, uint8_t *regs, double *pbits,
+                             uint64_t *records, uint64_t *counters) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(ssv_ready(v));
+    if ((regs || pbits || records || counters) && !v->state) {
+        set_error("view export: the last refresh did not carry GNS_SS_VIEW_STATE");
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(v->ss->device));
+    hipStream_t s = v->stream;
+    const uint64_t cells = v->cells;
+    GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 4, hipMemcpyDeviceToHost, s));
+    if (counters) GNS_HIP(hipMemcpyAsync(v->hsm + 2, v->ctr, 24, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    if (v->hsm[0]) return ssv_bad_id();
+    if (counters) memcpy(counters, v->hsm + 2, 24);
+    if (records) *records = v->records;
+    if (values) GNS_TRY(ssv_copy_out(v, values, v->vals, cells * 4));
+    if (keys && v->g.Kf) GNS_TRY(ssv_copy_out(v, keys, v->kw, cells * v->Kw * 4, (size_t)v->Kw * 4, v->g.Kf));
+    if (regs) GNS_TRY(ssv_copy_out(v, regs, v->regs, cells * v->g.m));
+    if (pbits) GNS_TRY(ssv_copy_out(v, pbits, v->pbits, cells * 8));
     return GNS_OK;
 }
 

@@ -106,6 +106,26 @@ class Manager:
         """takeSnapshotForWriter without writers: name -> HeavyRecord (sketch) / SnapshotData (exact)."""
         return {t.name(): t.snapshot() for t in self.tasks()}
 
+    def views(self) -> List[object]:
+        """One snapshot view per task, in tasks() order (CountMinView, SuperSpreadView,
+        ExactView): the read side of the snapshotter / alerter thread."""
+        return [t.view() for t in self.tasks()]
+
+    def refresh_views(self, views, state: bool = False) -> None:
+        """Ingest side: refresh every view at this point of the stream (asynchronous).
+        state=True: the SuperSpread views also capture what a checkpoint needs."""
+        from .sketch import SuperSpreadView
+        for v in views:
+            if isinstance(v, SuperSpreadView):
+                v.refresh(state=state)
+            else:
+                v.refresh()
+
+    def snapshot_from_views(self, views) -> Dict[str, object]:
+        """snapshot() as of the views' last refresh; may run on another thread while
+        process() keeps feeding the tasks."""
+        return {t.name(): t.snapshot_from(v) for t, v in zip(self.tasks(), views)}
+
     def reset_all(self) -> None:  # resetAllTasks, manager.go:179-193
         for t in self.tasks():
             t.reset()

@@ -411,6 +411,123 @@ class CountMin:
         return int(self._L.gns_cm_stream(self._h) or 0)
 
 
+def _ss_heavy_arrays(fn, h, flow_bytes, owner):
+    """gns_ss_heavy_hitters / gns_ss_view_heavy_hitters into buffers sized from ``owner``'s
+    previous list (``_hh_cap``); a longer list is fetched again with the length reported."""
+    K = max(flow_bytes, 1)
+    hint = getattr(owner, "_hh_cap", 0)
+    while True:
+        cap = max(hint, 1)
+        f = np.empty((cap, K), np.uint8)
+        v = np.empty(cap, np.uint32)
+        n = ct.c_uint64(cap)
+        check(fn(h, f.ctypes.data, v.ctypes.data, ct.byref(n)))
+        if n.value <= cap:
+            owner._hh_cap = 2 * n.value + 64
+            return f[: n.value, : flow_bytes], v[: n.value]
+        hint = n.value
+
+
+class SuperSpreadView:
+    """Snapshot of a SuperSpread taken at a point of its insert stream (``refresh``) and read
+    from any thread while the handle keeps inserting (gns_ss_view_*): the list, queries and --
+    after ``refresh(state=True)`` -- the whole state, i.e. a checkpoint (checkpoint.save(view,
+    path)).  Every answer is what the handle's call would have given at the refresh.  The
+    view holds key bytes, not flow ids: it stays readable after the handle's reset(),
+    reclaim(), dictionary growth and import_state() until its next refresh."""
+
+    def __init__(self, ss: "SuperSpread"):
+        self._L = ss._L
+        self._ss = ss  # the handle outlives its views
+        self.flow_bytes, self.width, self.depth, self.m = ss.flow_bytes, ss.width, ss.depth, ss.m
+        self.device = ss.device
+        h = ct.c_void_p()
+        check(self._L.gns_ss_view_create(ss._h, ct.byref(h)))
+        self._h = h
+
+    @property
+    def parent(self) -> "SuperSpread":
+        return self._ss
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.gns_ss_view_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def refresh(self, state: bool = False) -> None:
+        """Ingest side, asynchronous: snapshot the cells after every insert issued so far;
+        state=True also captures registers, pbits, counters and the generator position."""
+        check(self._L.gns_ss_view_refresh(self._h, _lib.GNS_SS_VIEW_STATE if state else 0))
+
+    def query_many(self, flows):
+        """SuperSpread.query_many at the refresh (numpy in -> numpy out, device tensor in ->
+        device int64 tensor out)."""
+        if _lib.is_device(flows):
+            return _lib.query_device(self._L.gns_ss_view_query_device, self._h, flows)
+        flows = _host(flows, np.uint8)
+        n = flows.shape[0]
+        out = np.zeros(n, dtype=np.uint64)
+        if n:
+            flows = flows.reshape(n, -1)
+            check(self._L.gns_ss_view_query(self._h, flows.ctypes.data, flows.shape[1], n, out.ctypes.data))
+        return out
+
+    def query(self, flow: bytes) -> int:
+        if len(flow) != self.flow_bytes:
+            return 1
+        return int(self.query_many(np.frombuffer(bytes(flow), np.uint8).reshape(1, -1))[0])
+
+    def heavy_hitters_arrays(self):
+        return _ss_heavy_arrays(self._L.gns_ss_view_heavy_hitters, self._h, self.flow_bytes, self)
+
+    def heavy_hitters(self) -> "HeavyRecord":
+        f, v = self.heavy_hitters_arrays()
+        return HeavyRecord(Size=None, Count=[HeavyCount(bytes(f[i]), int(v[i])) for i in range(len(v))])
+
+    def heavy_hitters_rows_device(self):
+        """The list as one DEVICE tensor of packed rows [flow | u32 spread] (uint8
+        [n, flow_bytes + 4]) in canonical order, as CountMin.heavy_hitters_rows_device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        W = self.flow_bytes + 4
+        n = ct.c_uint64(0)
+        check(self._L.gns_ss_view_heavy_rows(self._h, None, ct.byref(n)))
+        while True:
+            rows = torch.empty((max(n.value, 1), W), dtype=torch.uint8, device=dev)
+            n2 = ct.c_uint64(rows.shape[0])
+            check(self._L.gns_ss_view_heavy_rows(self._h, rows.data_ptr(), ct.byref(n2)))
+            if n2.value <= rows.shape[0]:
+                return rows[: n2.value]
+            n = n2  # (a refresh between the two calls)
+
+    def export_state(self, state: bool = True):
+        """(values, keys, regs, pbits) as SuperSpread.export_state at the refresh; the last
+        refresh must have been refresh(state=True).  state=False: (values, keys) only, which
+        any refresh carries."""
+        n = self.depth * self.width
+        values = np.empty(n, np.uint32)
+        keys = np.empty((n, max(self.flow_bytes, 1)), np.uint8)
+        regs = np.empty((n, self.m), np.uint8) if state else None
+        pbits = np.empty(n, np.float64) if state else None
+        check(self._L.gns_ss_view_export_state(
+            self._h, values.ctypes.data, keys.ctypes.data, regs.ctypes.data if state else None,
+            pbits.ctypes.data if state else None, None, None))
+        keys = keys[:, : self.flow_bytes]
+        return (values, keys, regs, pbits) if state else (values, keys)
+
+    def counters(self) -> dict:
+        """inserted / dropped / unsupported / records at the refresh (refresh(state=True))."""
+        rec, cnt = ct.c_uint64(0), (ct.c_uint64 * 3)()
+        check(self._L.gns_ss_view_export_state(self._h, None, None, None, None, ct.byref(rec), cnt))
+        return {"inserted": int(cnt[0]), "dropped": int(cnt[1]), "unsupported": int(cnt[2]), "records": int(rec.value)}
+
+
 class SuperSpread:
     """SuperSpread of super_spread.go on one GPU (declared RNG, injected HLL seeds)."""
 
@@ -446,6 +563,8 @@ class SuperSpread:
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            for v in list(getattr(self, "_views", ())):  # a view is destroyed before its handle
+                v.close()
             self._L.gns_ss_destroy(self._h)
             self._h = None
 
@@ -516,23 +635,22 @@ class SuperSpread:
     def heavy_hitters_arrays(self):
         """HeavyHitters as arrays (flows [n, flow_bytes], spreads): one device call into
         buffers sized from the previous list (a longer list is fetched again)."""
-        K = max(self.flow_bytes, 1)
-        hint = getattr(self, "_hh_cap", 0)
-        while True:
-            cap = max(hint, 1)
-            f = np.empty((cap, K), np.uint8)
-            v = np.empty(cap, np.uint32)
-            n = ct.c_uint64(cap)
-            check(self._L.gns_ss_heavy_hitters(self._h, f.ctypes.data, v.ctypes.data, ct.byref(n)))
-            if n.value <= cap:
-                self._hh_cap = 2 * n.value + 64
-                return f[: n.value, : self.flow_bytes], v[: n.value]
-            hint = n.value
+        return _ss_heavy_arrays(self._L.gns_ss_heavy_hitters, self._h, self.flow_bytes, self)
 
     def heavy_hitters(self) -> HeavyRecord:
         """HeavyHitters (super_spread.go:254-294): Count = (flow, spread estimate), Size = None."""
         f, v = self.heavy_hitters_arrays()
         return HeavyRecord(Size=None, Count=[HeavyCount(bytes(f[i]), int(v[i])) for i in range(len(v))])
+
+    def view(self) -> SuperSpreadView:
+        """A snapshot view of this sketch (closed with it at the latest): refresh() it on the
+        ingest thread, read it on any other (gns_ss_view_*)."""
+        import weakref
+        v = SuperSpreadView(self)
+        if not hasattr(self, "_views"):
+            self._views = weakref.WeakSet()
+        self._views.add(v)
+        return v
 
     def reset(self) -> None:
         check(self._L.gns_ss_reset(self._h))
@@ -592,7 +710,7 @@ class SuperSpread:
     def set_timing(self, on: bool = True, stages=None) -> None:
         check(self._L.gns_ss_set_timing(self._h, _lib.timing_arg(on, stages, self.STAGES)))
 
-    STAGES = ["extract", "resolve", "encode", "apply", "unused", "total"]
+    STAGES = ["extract", "resolve", "encode", "apply", "unused", "total", "view"]
 
     def stage_times(self, reset: bool = False) -> dict:
         ms = (ct.c_double * 8)()

@@ -150,9 +150,27 @@ class SketchTask:
         from . import checkpoint
         checkpoint.restore(self.sketch, path)
 
-    def alerter_msg(self, rules) -> str:
-        """AlerterMsg (task.go:187-243); rules: dicts with task_name/metric/operator/threshold/name."""
-        snap = self.snapshot()
+    def view(self):
+        """A snapshot view of the sketch (CountMinView / SuperSpreadView): refresh it on the
+        ingest thread, then hand it to the snapshotter / alerter thread (snapshot_from,
+        alerter_msg(rules, view=...), save_from)."""
+        return self.sketch.view()
+
+    def snapshot_from(self, view) -> HeavyRecord:
+        """Snapshot from a view instead of the live sketch: what snapshot() gave at the view's
+        refresh.  May run on another thread while the task keeps ingesting."""
+        return view.heavy_hitters()
+
+    def save_from(self, view, path) -> None:
+        """save() from a SuperSpreadView refreshed with state=True: the checkpoint of the
+        refresh point, written while the task keeps ingesting."""
+        from . import checkpoint
+        checkpoint.save(view, path)
+
+    def alerter_msg(self, rules, view=None) -> str:
+        """AlerterMsg (task.go:187-243); rules: dicts with task_name/metric/operator/threshold/name.
+        view: evaluate the rules on that view's snapshot instead of the live sketch's."""
+        snap = self.snapshot() if view is None else self.snapshot_from(view)
         msgs = []
         for rule in rules:
             if rule.get("task_name") != self.name_:

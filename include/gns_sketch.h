@@ -333,6 +333,64 @@ int gns_ss_reclaim(gns_ss *ss);
 int gns_ss_set_timing(gns_ss *ss, int on);
 int gns_ss_stage_times(gns_ss *ss, double ms[8], uint64_t launches[8], int reset);
 
+/* Snapshot view: the list, queries and the whole state (a checkpoint) read
+ * CONCURRENTLY with ingest, at a defined point of the stream (the reference's
+ * snapshotter and alerter call Task.Snapshot while the workers insert,
+ * manager.go:139-159, sketch/task.go:177,187-243).  A view holds, per cell, the
+ * value and the owner's key bytes resolved at the refresh; nothing in it points
+ * into the handle.
+ *   - Refresh.  gns_ss_view_refresh is an ingest-side call, serialized by the
+ *     caller with the handle's other calls.  Everything is enqueued on the
+ *     handle's stream: the snapshot is exactly the state after every insert
+ *     issued so far and before any later one.  An event behind it is what the
+ *     view's stream waits for.  It makes no host synchronization; after the first
+ *     refresh of each kind (with / without GNS_SS_VIEW_STATE) it allocates nothing.
+ *     It takes the view's mutex, so it waits for a reader call in progress.  With
+ *     gns_ss_set_timing on, stage 6 of gns_ss_stage_times is its device time.
+ *   - Readers (every other call but create / destroy) may run on any thread while
+ *     the handle inserts.  They run on the view's own stream, created at the
+ *     device's highest priority, with the view's own grow-only scratch and pinned
+ *     staging: once warm, no hipFree and no copy to or from pageable memory.
+ *   - Results.  Every answer is what the handle's call would have answered at the
+ *     refresh: gns_ss_view_query[_device] = gns_ss_query[_device] (max(1, .) for
+ *     an absent flow included); gns_ss_view_heavy_hitters = gns_ss_heavy_hitters,
+ *     the same list in the same canonical order (estimate desc, flow bytes asc)
+ *     with the same capacity rule (*n: capacity in, full length out, no row at or
+ *     past the capacity is written); gns_ss_view_heavy_rows = that list as packed
+ *     DEVICE rows [flow | u32], as gns_cm_heavy_rows (a list longer than *n is
+ *     reported and not written; rows_dev NULL asks for the length);
+ *     gns_ss_view_export_state = gns_ss_export_state plus gns_ss_counters' [6]
+ *     (records) and [0..2] (counters).  This holds for every state reachable by
+ *     inserts and by importing an exported state.
+ *   - Lifetime.  A view that was never refreshed answers GNS_E_ARG.  A view is NOT
+ *     staled by gns_ss_reset, gns_ss_reclaim, dictionary growth or
+ *     gns_ss_import_state: it answers the refresh-point state until the next
+ *     refresh.  Several views of one handle are independent.  Destroy views
+ *     before their handle.
+ *   - State capture.  regs, pbits, records or counters asked of a view whose last
+ *     refresh did not carry GNS_SS_VIEW_STATE is GNS_E_ARG, before any device call.
+ *     values and keys are always available.  Null output pointers are skipped.
+ *   - Errors.  A null view, a null out (n > 0), a null n and stride < flow_bytes
+ *     are GNS_E_ARG before any device call.  A cell whose key id named no
+ *     dictionary slot at the refresh (corrupt state) is not dereferenced; the next
+ *     reader call answers GNS_E_HIP.
+ *   - A list call synchronizes the view's stream twice (the length, then the
+ *     ordered rows) -- once more when the list outgrew its buffer, and once inside
+ *     the order for keys longer than four bytes (its tie flag).
+ * Memory: 4 + 4*ceil(flow_bytes/4) bytes per cell (depth*width); with state
+ * another m + 8 bytes per cell, allocated at the first refresh that asks for it. */
+typedef struct gns_ss_view gns_ss_view;
+#define GNS_SS_VIEW_STATE 1u   /* refresh flag: also capture registers, pbits, counters, generator position */
+int gns_ss_view_create(gns_ss *ss, gns_ss_view **out);
+int gns_ss_view_destroy(gns_ss_view *v);
+int gns_ss_view_refresh(gns_ss_view *v, uint32_t flags);
+int gns_ss_view_query(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
+int gns_ss_view_query_device(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out);
+int gns_ss_view_heavy_hitters(gns_ss_view *v, uint8_t *flows, uint32_t *spreads, uint64_t *n);
+int gns_ss_view_heavy_rows(gns_ss_view *v, uint8_t *rows_dev, uint64_t *n);
+int gns_ss_view_export_state(gns_ss_view *v, uint32_t *values, uint8_t *keys, uint8_t *regs, double *pbits,
+                             uint64_t *records, uint64_t *counters /* [3] */);
+
 /* ------------------------------------------------------------------ */
 /* Inputs: synthetic traffic and the pcap packer           */
 /* ------------------------------------------------------------------ */

@@ -616,6 +616,106 @@ func (s *SuperSpread) Close() { C.gns_ss_destroy(s.h) }
 
 var _ statistic.Sketch = (*SuperSpread)(nil)
 
+// SuperSpreadView is a snapshot view of a SuperSpread (gns_ss_view_*) for the snapshotter and
+// alerter goroutines (manager.go:139-159): Refresh on the goroutine that inserts, at the
+// interval's end; Query, HeavyHitters and ExportState on any other while the inserts go on.
+// Every answer is the sketch's at the Refresh.  The view holds key bytes, so it stays readable
+// after the sketch's Reset (the resetter is independent of the snapshotter).  Close views
+// before their sketch.
+type SuperSpreadView struct {
+	v        *C.gns_ss_view
+	flowSize int
+	cells    int
+	m        int
+}
+
+// NewView creates a view of s; cells = depth*width and m as given to NewSuperSpread (their
+// defaults resolved) size ExportState's arrays.
+func (s *SuperSpread) NewView(cells, m int) (*SuperSpreadView, error) {
+	var v *C.gns_ss_view
+	if err := lastErr(C.gns_ss_view_create(s.h, &v)); err != nil {
+		return nil, err
+	}
+	return &SuperSpreadView{v: v, flowSize: s.flowSize, cells: cells, m: m}, nil
+}
+
+// Refresh snapshots the cells after every insert issued so far (asynchronous, insert side).
+// state: also registers, pbits, counters and the generator position, for ExportState.
+func (w *SuperSpreadView) Refresh(state bool) error {
+	var flags C.uint32_t
+	if state {
+		flags = C.GNS_SS_VIEW_STATE
+	}
+	return lastErr(C.gns_ss_view_refresh(w.v, flags))
+}
+
+// Query is SuperSpread.Query at the Refresh.
+func (w *SuperSpreadView) Query(flow []byte) uint64 {
+	if len(flow) != w.flowSize || len(flow) == 0 {
+		return 1
+	}
+	var out C.uint64_t
+	if C.gns_ss_view_query(w.v, (*C.uint8_t)(unsafe.Pointer(&flow[0])), C.uint32_t(len(flow)), 1, &out) != C.GNS_OK {
+		return 1
+	}
+	return uint64(out)
+}
+
+// QueryDevice answers n device-resident keys into device memory (gns_ss_view_query_device).
+func (w *SuperSpreadView) QueryDevice(keys unsafe.Pointer, stride uint32, n uint64, out unsafe.Pointer) error {
+	return lastErr(C.gns_ss_view_query_device(w.v, (*C.uint8_t)(keys), C.uint32_t(stride), C.uint64_t(n),
+		(*C.uint64_t)(out)))
+}
+
+// HeavyHitters is SuperSpread.HeavyHitters at the Refresh: Size is nil.
+func (w *SuperSpreadView) HeavyHitters() (statistic.HeavyRecord, error) {
+	K := w.flowSize
+	capN := 64
+	for {
+		fl := make([]byte, capN*K+1)
+		v := make([]uint32, capN+1)
+		n := C.uint64_t(capN)
+		if err := lastErr(C.gns_ss_view_heavy_hitters(w.v, (*C.uint8_t)(unsafe.Pointer(&fl[0])),
+			(*C.uint32_t)(unsafe.Pointer(&v[0])), &n)); err != nil {
+			return statistic.HeavyRecord{Count: []statistic.HeavyCount{}}, err
+		}
+		if int(n) > capN { // longer than the buffers: grow and call again
+			capN = 2 * int(n)
+			continue
+		}
+		rec := statistic.HeavyRecord{Count: make([]statistic.HeavyCount, 0, int(n))}
+		for i := 0; i < int(n); i++ {
+			rec.Count = append(rec.Count, statistic.HeavyCount{Flow: append([]byte(nil), fl[i*K:(i+1)*K]...), Count: v[i]})
+		}
+		return rec, nil
+	}
+}
+
+// HeavyRows writes the list as packed device rows [flow | u32] (capacity capRows); it
+// returns the full length, and writes nothing when that exceeds the capacity.
+func (w *SuperSpreadView) HeavyRows(rowsDev unsafe.Pointer, capRows uint64) (uint64, error) {
+	n := C.uint64_t(capRows)
+	err := lastErr(C.gns_ss_view_heavy_rows(w.v, (*C.uint8_t)(rowsDev), &n))
+	return uint64(n), err
+}
+
+// ExportState returns the arrays SuperSpread.ImportState takes, as of the last Refresh(true).
+func (w *SuperSpreadView) ExportState() (values []uint32, keys, regs []byte, pbits []float64, records uint64,
+	counters [3]uint64, err error) {
+	values = make([]uint32, w.cells+1)
+	keys = make([]byte, w.cells*w.flowSize+1)
+	regs = make([]byte, w.cells*w.m+1)
+	pbits = make([]float64, w.cells+1)
+	var rec C.uint64_t
+	err = lastErr(C.gns_ss_view_export_state(w.v, (*C.uint32_t)(unsafe.Pointer(&values[0])),
+		(*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint8_t)(unsafe.Pointer(&regs[0])),
+		(*C.double)(unsafe.Pointer(&pbits[0])), &rec, (*C.uint64_t)(unsafe.Pointer(&counters[0]))))
+	return values[:w.cells], keys[:w.cells*w.flowSize], regs[:w.cells*w.m], pbits[:w.cells], uint64(rec), counters, err
+}
+
+// Close releases the view.
+func (w *SuperSpreadView) Close() { C.gns_ss_view_destroy(w.v) }
+
 // Exact is the device state of one exact task (internal/engine/impl/exact/task.go).
 type Exact struct {
 	h        *C.gns_ex
