@@ -2813,15 +2813,10 @@ using namespace gns;
 // while the handle ingests.
 struct CmRead {
     HhScratch hh;
-    uint8_t *qkeys = nullptr;
-    uint64_t qkeys_n = 0;
-    uint64_t *qout = nullptr;
-    uint64_t qout_n = 0;
+    QueryStage q;
     void free_all() {
         hh.free_all();
-        dfree(qkeys); dfree(qout);
-        qkeys = nullptr; qout = nullptr;
-        qkeys_n = qout_n = 0;
+        q.free_all();
     }
 };
 
@@ -2846,7 +2841,6 @@ struct gns_cm : FlowDict {
     uint32_t *ptotal = nullptr;        // [2]
     uint32_t *hist = nullptr, *part = nullptr, *total = nullptr, *order = nullptr;
     uint64_t *entries = nullptr;
-    uint32_t *rec_sizes = nullptr;     // 16-byte compact records from device memory: a batch's sizes
     uint64_t *ovf = nullptr;
     uint32_t *ovf_cnt = nullptr;
     uint64_t ovf_cap = 0;                 // entries of ovf
@@ -2868,20 +2862,16 @@ struct gns_cm : FlowDict {
     // staging for host inputs: two device buffers; batch i+1's H2D copies run on
     // cstream while batch i computes on `stream` (events order the reuse)
     HostStage stage[2];
-    uint32_t *side_dev = nullptr;         // staged side records of a compact host insert
-    uint64_t side_n = 0;
+    CompactInput compact;                 // compact records: the staged side array, a device batch's sizes
     hipStream_t cstream = nullptr;
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
     StageTimer timer;
 };
 
-struct gns_cm_view {
+struct gns_cm_view : ViewCore {
     gns_cm *cm = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;
     uint32_t *C = nullptr, *S = nullptr, *Fc = nullptr, *Fs = nullptr;
     CmRead rd;
-    std::mutex mu;          // refresh vs queries: a refresh waits for the query in progress
     uint32_t period = ~0u;  // handle period of the snapshot (~0: never refreshed)
 };
 
@@ -2904,8 +2894,8 @@ int cm_free_all(gns_cm *cm) {
     dfree(cm->keyid); dfree(cm->idx); dfree(cm->cold);
     dfree(cm->pend[0]); dfree(cm->pend[1]); dfree(cm->pcnt[0]); dfree(cm->pcnt[1]);
     dfree(cm->ptotal); dfree(cm->hist); dfree(cm->part); dfree(cm->total); dfree(cm->order);
-    dfree(cm->entries); dfree(cm->rec_sizes); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
-    cm->stage[0].free_all(); cm->stage[1].free_all(); dfree(cm->side_dev);
+    dfree(cm->entries); dfree(cm->ovf); dfree(cm->ovf_cnt); dfree(cm->stats);
+    cm->stage[0].free_all(); cm->stage[1].free_all(); cm->compact.free_all();
     for (int i = 0; i < 2; i++) {
         if (cm->ev_copied[i]) (void)hipEventDestroy(cm->ev_copied[i]);
         if (cm->ev_used[i]) (void)hipEventDestroy(cm->ev_used[i]);
@@ -3195,12 +3185,6 @@ int cm_batch_recover(gns_cm *cm, const InputDesc &d, uint64_t m) {
     return r.batch(d, m, false);
 }
 
-// 16-byte compact records: the wire lengths (word 3 bits 16..31) as the batch's size array
-__global__ __launch_bounds__(256) void k_rec_sizes(const uint32_t *rec16, uint64_t n, uint32_t *sizes) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) sizes[i] = rec16[i * 4 + 3] >> 16;
-}
-
 // Host input: stage batch [off, off+m) into device buffer b on the copy stream,
 // after the batch that last read b has finished; d points into the buffer.
 int stage_host_batch(gns_cm *cm, int b, const InputDesc &in, uint64_t off, uint64_t m, InputDesc &d) {
@@ -3219,11 +3203,7 @@ int stage_host_batch(gns_cm *cm, int b, const InputDesc &in, uint64_t off, uint6
     if (sg.cap < HostStage::need(l)) GNS_HIP(hipEventSynchronize(cm->ev_used[b]));  // the batch that read it is done
     GNS_HIP(hipStreamWaitEvent(cm->cstream, cm->ev_used[b], 0));
     GNS_TRY(sg.copy(l, cm->cstream));
-    if (in.rec_len) {
-        hipLaunchKernelGGL(k_rec_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, cm->cstream, d.rec16, m,
-                           const_cast<uint32_t *>(d.sizes));
-        GNS_HIP(hipGetLastError());
-    }
+    if (in.rec_len) GNS_TRY(CompactInput::unpack_sizes_into(d.rec16, m, const_cast<uint32_t *>(d.sizes), cm->cstream));
     if (d.keys) d.aligned = (d.stride % 4 == 0 && d.stride >= ((cm->K + 3) & ~3u)) ? 1u : 0u;
     GNS_HIP(hipEventRecord(cm->ev_copied[b], cm->cstream));
     return GNS_OK;
@@ -3241,13 +3221,9 @@ int cm_insert(gns_cm *cm, InputDesc in, uint64_t n, gns_mem where) {
         for (uint64_t off = 0, m = 0; off < n; off += m) {
             m = batch_len(off, cm->warm);
             InputDesc d = advance(in, off);
-            if (in.rec_len) {  // 16-byte compact records: the batch's sizes unpacked on the stream
-                if (!cm->rec_sizes) GNS_TRY(dalloc_t(&cm->rec_sizes, cm->bmax));
-                hipLaunchKernelGGL(k_rec_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, cm->stream, d.rec16, m,
-                                   cm->rec_sizes);
-                GNS_HIP(hipGetLastError());
-                d.sizes = cm->rec_sizes;
-            }
+            // 16-byte compact records: the batch's sizes unpacked on the stream (room for the
+            // largest batch from the start: the small cold first one must not cost the second a sync)
+            GNS_TRY(cm->compact.unpack_sizes(d, m, cm->stream, cm->bmax));
             GNS_TRY(cm_batch_recover<KIND>(cm, d, m));
         }
         return GNS_OK;
@@ -3455,44 +3431,22 @@ int gns_cm_insert_tuples(gns_cm *cm, const gns_tuples *t, uint64_t n, gns_mem wh
     if (n && (!t->src16 || !t->dst16 || !t->sport || !t->dport || !t->proto || !t->length)) {
         set_error("null tuple array"); return GNS_E_ARG;
     }
-    InputDesc in{};
-    in.src16 = t->src16; in.dst16 = t->dst16; in.sport = t->sport; in.dport = t->dport;
-    in.proto = t->proto; in.sizes = t->length;
-    return cm_insert<IN_TUPLE>(cm, in, n, where);
+    return cm_insert<IN_TUPLE>(cm, tuples_desc(*t, true), n, where);
 }
 
 int gns_cm_insert_headers(gns_cm *cm, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n,
                           gns_mem where) {
     if (!cm || (n && (!hdr || !wirelen))) { set_error("null argument"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.hdr = reinterpret_cast<const uint32_t *>(hdr);
-    in.sizes = wirelen;
-    return cm_insert<IN_HDR>(cm, in, n, where);
+    return cm_insert<IN_HDR>(cm, headers_desc(hdr, wirelen), n, where);
 }
 
 int gns_cm_insert_compact(gns_cm *cm, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
                           const uint8_t *side64, uint64_t n_side, gns_mem where) {
     if (!cm || (n && !rec16) || (n_side && !side64)) { set_error("null argument"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.rec16 = reinterpret_cast<const uint32_t *>(rec16);
-    in.sizes = wirelen;
-    in.rec_len = wirelen ? 0u : 1u;  // no wirelen array: the 16-byte form
-    in.side = reinterpret_cast<const uint32_t *>(side64);
-    in.n_side = side64 ? n_side : 0;
-    if (where == GNS_MEM_HOST && n_side) {
-        // the side records of the whole call, staged once (escapes index them globally);
-        // the batches of the previous call may still read the buffer
+    InputDesc in = compact_desc(rec16, wirelen, side64, n_side);
+    if (where == GNS_MEM_HOST) {  // the side records of the whole call, staged once (escapes index them globally)
         GNS_TRY(set_device(cm->device));
-        GNS_HIP(hipStreamSynchronize(cm->stream));
-        if (cm->side_n < n_side) {
-            dfree(cm->side_dev);
-            cm->side_dev = nullptr;
-            cm->side_n = 0;
-            GNS_TRY(dalloc_t(&cm->side_dev, n_side * 16));
-            cm->side_n = n_side;
-        }
-        GNS_HIP(hipMemcpy(cm->side_dev, side64, n_side * 64, hipMemcpyHostToDevice));
-        in.side = cm->side_dev;
+        GNS_TRY(cm->compact.stage_side(in, cm->stream));
     }
     return cm_insert<IN_REC16>(cm, in, n, where);
 }
@@ -3520,49 +3474,41 @@ int gns_cm_flush(gns_cm *cm) {
 
 }  // extern "C"
 
-// Query (count_min.go:160-174) of n keys against state (C, Fc, S, Fs) on stream st:
-// host keys / answers (staged through the grow-only scratch), or device keys /
-// answers (dev: no copies; the call returns once the answers are written).
+// a view can answer (under v->mu)
+static int view_check(gns_cm_view *v) {
+    if (v->period == ~0u) { set_error("view never refreshed"); return GNS_E_ARG; }
+    if (v->period != v->cm->period.load()) { set_error("view is stale: the handle was reset; refresh it"); return GNS_E_ARG; }
+    return GNS_OK;
+}
+
+// Query (count_min.go:160-174) of n keys against state (C, Fc, S, Fs) on stream st
+// (query_keys).  v: the view holding that state, checked once the arguments are.
 static int cm_query_impl(gns_cm *cm, hipStream_t st, CmRead &sc, const uint32_t *C, const uint32_t *Fc,
                          const uint32_t *S, const uint32_t *Fs, const uint8_t *keys, uint32_t stride, uint64_t n,
-                         uint64_t *out, bool dev = false) {
-    if (!dev) {
-        GNS_TRY(grow_buf(&sc.qkeys, sc.qkeys_n, n * stride));
-        GNS_TRY(grow_buf(&sc.qout, sc.qout_n, n));
-    }
-    QueryArgs a{};
-    a.keys = dev ? keys : sc.qkeys;
-    a.stride = stride;
-    a.aligned = (stride % 4 == 0 && stride >= ((cm->K + 3) & ~3u) && ((uintptr_t)a.keys & 3u) == 0);
-    a.n = n; a.K = cm->K; a.g = cm->g; a.D = cm->D;
-    a.C = C; a.Fc = Fc; a.S = S; a.Fs = Fs; a.out = dev ? out : sc.qout;
-    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(sc.qkeys, keys, n * stride, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+                         uint64_t *out, bool dev, gns_cm_view *v = nullptr) {
+    const auto launch = [&](const uint8_t *dk, uint64_t *dout) -> int {
+        if (v) GNS_TRY(view_check(v));
+        QueryArgs a{};
+        a.keys = dk;
+        a.stride = stride;
+        a.aligned = (stride % 4 == 0 && stride >= ((cm->K + 3) & ~3u) && ((uintptr_t)dk & 3u) == 0);
+        a.n = n; a.K = cm->K; a.g = cm->g; a.D = cm->D;
+        a.C = C; a.Fc = Fc; a.S = S; a.Fs = Fs; a.out = dout;
         hipLaunchKernelGGL(k_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(out, sc.qout, n * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("query: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
+        return GNS_OK;
+    };
+    return query_keys(cm->device, st, sc.q, "cm", keys, stride, cm->K, n, out, dev, launch);
 }
 
 extern "C" {
 
 int gns_cm_query(gns_cm *cm, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out) {
-    if (!cm || (n && (!keys || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
-    GNS_TRY(set_device(cm->device));
-    return cm_query_impl(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->S, cm->Fs, keys, stride, n, out);
+    if (!cm) { set_error("null argument"); return GNS_E_ARG; }
+    return cm_query_impl(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->S, cm->Fs, keys, stride, n, out, false);
 }
 
 int gns_cm_query_device(gns_cm *cm, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out) {
-    if (!cm || (n && (!keys || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
-    if (((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_device(cm->device));
+    if (!cm) { set_error("null argument"); return GNS_E_ARG; }
     return cm_query_impl(cm, cm->stream, cm->rd, cm->C, cm->Fc, cm->S, cm->Fs, keys, stride, n, out, true);
 }
 
@@ -3616,8 +3562,7 @@ int gns_cm_heavy_rows(gns_cm *cm, uint8_t *count_rows, uint64_t *n_count, uint8_
 static void view_free(gns_cm_view *v) {
     dfree(v->C); dfree(v->S); dfree(v->Fc); dfree(v->Fs);
     v->rd.free_all();
-    if (v->ready) (void)hipEventDestroy(v->ready);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
+    v->destroy();
 }
 
 int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
@@ -3632,14 +3577,7 @@ int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
         if ((rc = dalloc_t(&v->C, cells)) || (rc = dalloc_t(&v->S, cells)) || (rc = dalloc_t(&v->Fc, cells)) ||
             (rc = dalloc_t(&v->Fs, cells)))
             break;
-        // high priority: the read side's small launches are dispatched ahead of the
-        // ingest pipeline's queued workgroups (query latency under load)
-        int lo_pri = 0, hi_pri = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
-        if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess) {
-            set_error("view stream/event"); rc = GNS_E_HIP; break;
-        }
+        if ((rc = v->init()) != GNS_OK) break;
         if ((rc = hh_reserve(v->rd.hh, cells, cm->dict_slots, cm->K, v->stream)) != GNS_OK) break;
         if (hipStreamSynchronize(v->stream) != hipSuccess) { set_error("view sync"); rc = GNS_E_HIP; break; }
     } while (0);
@@ -3660,10 +3598,7 @@ int gns_cm_view_destroy(gns_cm_view *v) {
         std::lock_guard<std::mutex> reg(cm->views_mu);
         cm->views.erase(std::remove(cm->views.begin(), cm->views.end(), v), cm->views.end());
     }
-    {   // wait for a view call in progress; the mutex is released before the delete
-        std::lock_guard<std::mutex> lk(v->mu);
-        if (v->stream) (void)hipStreamSynchronize(v->stream);
-    }
+    v->quiesce();  // a view call in progress; the mutex is released before the delete
     view_free(v);
     delete v;
     return GNS_OK;
@@ -3681,15 +3616,8 @@ int gns_cm_view_refresh(gns_cm_view *v) {
     GNS_HIP(hipMemcpyAsync(v->S, cm->S, bytes, hipMemcpyDeviceToDevice, cm->stream));
     GNS_HIP(hipMemcpyAsync(v->Fc, cm->Fc, bytes, hipMemcpyDeviceToDevice, cm->stream));
     GNS_HIP(hipMemcpyAsync(v->Fs, cm->Fs, bytes, hipMemcpyDeviceToDevice, cm->stream));
-    GNS_HIP(hipEventRecord(v->ready, cm->stream));
-    GNS_HIP(hipStreamWaitEvent(v->stream, v->ready, 0));
+    GNS_TRY(v->publish(cm->stream));
     v->period = cm->period.load();
-    return GNS_OK;
-}
-
-static int view_check(gns_cm_view *v) {
-    if (v->period == ~0u) { set_error("view never refreshed"); return GNS_E_ARG; }
-    if (v->period != v->cm->period.load()) { set_error("view is stale: the handle was reset; refresh it"); return GNS_E_ARG; }
     return GNS_OK;
 }
 
@@ -3706,14 +3634,9 @@ int gns_cm_view_heavy_hitters(gns_cm_view *v, uint8_t *count_flows, uint32_t *co
 }
 
 int gns_cm_view_query(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out) {
-    if (!v || (n && (!keys || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    gns_cm *cm = v->cm;
-    if (stride < cm->K) { set_error("stride < key_bytes"); return GNS_E_ARG; }
-    GNS_TRY(set_device(cm->device));
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
     std::lock_guard<std::mutex> lk(v->mu);
-    GNS_TRY(view_check(v));
-    return cm_query_impl(cm, v->stream, v->rd, v->C, v->Fc, v->S, v->Fs, keys, stride, n, out);
+    return cm_query_impl(v->cm, v->stream, v->rd, v->C, v->Fc, v->S, v->Fs, keys, stride, n, out, false, v);
 }
 
 int gns_cm_reset(gns_cm *cm) {
@@ -3864,9 +3787,7 @@ int gns_cm_reclaim(gns_cm *cm) {
 
 int gns_cm_dict_stats(gns_cm *cm, uint64_t out[8]) {
     if (!cm || !out) return GNS_E_ARG;
-    out[0] = cm->n_reclaim; out[1] = cm->n_dropped; out[2] = cm->last_live; out[3] = cm->claimed;
-    out[4] = (uint64_t)(cm->reclaim_ms * 1000.0); out[5] = cm->n_retry;
-    out[6] = cm->dict_slots; out[7] = cm->n_grow;
+    cm->FlowDict::stats(out);
     return GNS_OK;
 }
 
@@ -3879,14 +3800,7 @@ int gns_cm_set_timing(gns_cm *cm, int on) {
 int gns_cm_stage_times(gns_cm *cm, double ms[8], uint64_t launches[8], int reset) {
     if (!cm) return GNS_E_ARG;
     GNS_TRY(set_device(cm->device));
-    cm->timer.collect();
-    for (int i = 0; i < 8; i++) {
-        if (ms) ms[i] = cm->timer.ms[i];
-        if (launches) launches[i] = cm->timer.launches[i];
-    }
-    if (reset) {
-        for (int i = 0; i < 8; i++) { cm->timer.ms[i] = 0; cm->timer.launches[i] = 0; }
-    }
+    cm->timer.report(ms, launches, reset);
     return GNS_OK;
 }
 

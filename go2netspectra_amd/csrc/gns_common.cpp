@@ -128,9 +128,134 @@ int FlowDict::reclaim(DictIds *ids, int n, uint64_t min_slots, hipStream_t s) {
     return GNS_OK;
 }
 
+void FlowDict::stats(uint64_t out[8]) const {
+    out[0] = n_reclaim; out[1] = n_dropped; out[2] = last_live; out[3] = claimed;
+    out[4] = (uint64_t)(reclaim_ms * 1000.0); out[5] = n_retry;
+    out[6] = dict_slots; out[7] = n_grow;
+}
+
 void FlowDict::free_all() {
     dfree(D.rec); dfree(dctl); dfree(stats_bak);
     dsc.free_all();
+}
+
+int PinnedOut::reserve(size_t bytes) {
+    for (hipEvent_t &e : ev)
+        if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("view event");
+            return GNS_E_HIP;
+        }
+    if (bytes <= pin_n && pin) return GNS_OK;
+    if (pin) (void)hipHostFree(pin);
+    pin = nullptr;
+    pin_n = 0;
+    const size_t want = std::max<size_t>(2 * bytes, 2 * kPinChunk);
+    if (hipHostMalloc(reinterpret_cast<void **>(&pin), want, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hipHostMalloc(%zu bytes) failed", want);
+        return GNS_E_OOM;
+    }
+    pin_n = want;
+    return GNS_OK;
+}
+
+int PinnedOut::copy_out(void *dst, const void *src, size_t bytes, hipStream_t s, size_t sw, size_t dw) {
+    const size_t piece = pin_piece(kPinChunk, sw), n = pin_pieces(bytes, piece);
+    for (size_t j = 0; j <= n; j++) {
+        if (j < n) {
+            GNS_HIP(hipMemcpyAsync(pin + (j & 1) * kPinChunk, static_cast<const uint8_t *>(src) + pin_off(j, piece),
+                                   pin_len(j, piece, bytes), hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipEventRecord(ev[j & 1], s));
+        }
+        if (j > 0) {
+            GNS_HIP(hipEventSynchronize(ev[(j - 1) & 1]));
+            pin_land(static_cast<uint8_t *>(dst), pin + ((j - 1) & 1) * kPinChunk, j - 1, piece, bytes, sw, dw);
+        }
+    }
+    return GNS_OK;
+}
+
+void PinnedOut::free_all() {
+    if (pin) (void)hipHostFree(pin);
+    pin = nullptr;
+    pin_n = 0;
+    for (hipEvent_t &e : ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+}
+
+void QueryStage::free_all() {
+    dfree(qkeys); dfree(qout);
+    qkeys = nullptr; qout = nullptr;
+    qkeys_n = qout_n = 0;
+}
+
+int query_keys(int device, hipStream_t s, QueryStage &st, const char *what, const uint8_t *keys, uint32_t stride,
+               uint32_t key_bytes, uint64_t n, uint64_t *out, bool dev, const LaunchFn &launch) {
+    if (n && (!keys || !out)) { set_error("null argument"); return GNS_E_ARG; }
+    if (n == 0) return GNS_OK;
+    if (stride < key_bytes) { set_error("%s query: stride %u < key bytes %u", what, stride, key_bytes); return GNS_E_ARG; }
+    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
+    GNS_TRY(set_device(device));
+    const size_t kb = (size_t)n * stride, ob = (size_t)n * 8, koff = (ob + 15) & ~(size_t)15;
+    const uint8_t *hk = keys;  // what the copies read and write: the caller's memory, or the pinned
+    uint64_t *ho = out;        // staging {answers, keys at koff}
+    if (!dev) {
+        GNS_TRY(grow_buf(&st.qkeys, st.qkeys_n, (uint64_t)kb));
+        GNS_TRY(grow_buf(&st.qout, st.qout_n, n));
+        if (st.pin) {
+            GNS_TRY(st.pin->reserve(koff + kb));
+            memcpy(st.pin->pin + koff, keys, kb);
+            hk = st.pin->pin + koff;
+            ho = reinterpret_cast<uint64_t *>(st.pin->pin);
+        }
+    }
+    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(st.qkeys, hk, kb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        const int rc = launch(dev ? keys : st.qkeys, dev ? out : st.qout);
+        if (rc != GNS_OK) {  // (a view that cannot answer) the key copy may not outlive the caller's array
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && !dev) e = hipMemcpyAsync(ho, st.qout, ob, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { set_error("%s query: %s", what, hipGetErrorString(e)); return GNS_E_HIP; }
+    if (ho != out) memcpy(out, ho, ob);
+    return GNS_OK;
+}
+
+int ViewCore::init() {
+    int lo_pri = 0, hi_pri = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
+    if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
+        hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("view stream/event");
+        return GNS_E_HIP;
+    }
+    return GNS_OK;
+}
+
+int ViewCore::publish(hipStream_t handle_stream) {
+    GNS_HIP(hipEventRecord(ready, handle_stream));
+    GNS_HIP(hipStreamWaitEvent(stream, ready, 0));
+    return GNS_OK;
+}
+
+void ViewCore::quiesce() {
+    std::lock_guard<std::mutex> lk(mu);
+    if (stream) (void)hipStreamSynchronize(stream);
+}
+
+void ViewCore::destroy() {
+    if (ready) (void)hipEventDestroy(ready);
+    if (stream) (void)hipStreamDestroy(stream);
+    ready = nullptr;
+    stream = nullptr;
 }
 
 int stats_save(unsigned long long *bak, const unsigned long long *stats, hipStream_t s) {
@@ -296,6 +421,22 @@ int StageTimer::collect() {
         pool.push_back(p.b);
     }
     pending.clear();
+    return GNS_OK;
+}
+
+void StageTimer::report(double *ms_out, uint64_t *launches_out, int reset) {
+    collect();
+    for (int i = 0; i < kStages; i++) {
+        if (ms_out) ms_out[i] = ms[i];
+        if (launches_out) launches_out[i] = launches[i];
+        if (reset) { ms[i] = 0; launches[i] = 0; }
+    }
+}
+
+int handle_flush(int device, hipStream_t stream, StageTimer &timer) {
+    GNS_TRY(set_device(device));
+    GNS_HIP(hipStreamSynchronize(stream));
+    timer.collect();
     return GNS_OK;
 }
 

@@ -1,7 +1,8 @@
 // gns_common.hpp -- host-side plumbing shared by the engines: error reporting,
 // the device check and set, device buffers, per-stage HIP-event timing, advancing
 // and staging of host inputs into device memory, and the flow dictionary's
-// ownership, reclaim and batch recovery, and its key resolution for the imports.
+// ownership, reclaim and batch recovery, and its key resolution for the imports;
+// and the read side: pinned copy-out, the point-query call and a view's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,12 +12,14 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/gns_sketch.h"
 #include "gns_device.cuh"
 #include "gns_keys.cuh"
+#include "gns_pinchunk.hpp"
 
 namespace gns {
 
@@ -108,11 +111,27 @@ struct CompactInput {
     int stage_side(InputDesc &in, hipStream_t s);
     // 16-byte form: the wire lengths of d's first m records (device memory) unpacked
     // on stream s, d.sizes pointed at them.  The 20-byte form is left as it is.
-    int unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s);
+    // (reserve: room for at least that many records, so that later batches do not reallocate)
+    int unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s, uint64_t reserve = 0);
+    // the same into room the caller owns (a staged batch's)
+    static int unpack_sizes_into(const uint32_t *rec16, uint64_t m, uint32_t *dst, hipStream_t s);
     void free_all();
 };
 // The descriptor of a gns_*_insert_compact call (wirelen == NULL: the 16-byte form).
 InputDesc compact_desc(const uint8_t *rec16, const uint32_t *wirelen, const uint8_t *side64, uint64_t n_side);
+// ... of a gns_*_insert_tuples call (the null checks are the engine's) and of gns_*_insert_headers
+inline InputDesc tuples_desc(const gns_tuples &t, bool with_length) {
+    InputDesc in{};
+    in.src16 = t.src16; in.dst16 = t.dst16; in.sport = t.sport; in.dport = t.dport; in.proto = t.proto;
+    in.sizes = with_length ? t.length : nullptr;
+    return in;
+}
+inline InputDesc headers_desc(const uint8_t *hdr, const uint32_t *wirelen) {
+    InputDesc in{};
+    in.hdr = reinterpret_cast<const uint32_t *>(hdr);
+    in.sizes = wirelen;
+    return in;
+}
 
 // Flow-key plan from a configured layout (task.go:265-300, :327-338).
 int make_plan(const gns_layout &l, uint32_t key_bytes, KeyPlanN *out);
@@ -136,8 +155,12 @@ struct StageTimer {
     void begin(int stage, hipEvent_t *a);
     void end(int stage, hipEvent_t a);
     int collect();  // synchronizes pending events and accumulates
+    // gns_*_stage_times: collects, copies the totals out (either may be null), clears them on reset
+    void report(double *ms_out, uint64_t *launches_out, int reset);
     void destroy();
 };
+// gns_*_flush: everything queued on the handle's stream has run, its stage times are collected
+int handle_flush(int device, hipStream_t stream, StageTimer &timer);
 
 // gns_*_set_timing's argument: 0 off, GNS_TIMING_MASK | stage bits = only those stages (fewer
 // events inside a batch), any other nonzero value = every stage
@@ -239,9 +262,6 @@ struct KeyResolve {
 };
 // GNS_E_FULL: the claims crossed D.cap (the abort flag D.ctl[1] and *full_word are
 // raised, ids are incomplete): the caller grows the table, clears *full_word and
-
-// GNS_E_FULL: the claims crossed D.cap (the abort flag D.ctl[1] and *full_word are
-// raised, ids are incomplete): the caller grows the table, clears *full_word and
 // re-runs the call.  *claimed = D.ctl[0]; each round is timed as one launch of
 // `stage` when a timer is given.  Synchronizes s.
 int dict_resolve_keys(const DictDev &D, uint32_t &epoch, const KeyResolve &r, KeyResolveScratch &sc, hipStream_t s,
@@ -270,6 +290,7 @@ struct FlowDict {
     // Rebuild keeping the flows that `ids` name (and remapping them).  The table
     // doubles while the live flows exceed a quarter of it, and to at least min_slots.
     int reclaim(DictIds *ids, int n, uint64_t min_slots, hipStream_t s);
+    void stats(uint64_t out[8]) const;  // gns_*_dict_stats
     void free_all();
 };
 
@@ -295,6 +316,56 @@ struct DictRecovery {
     std::function<int(uint64_t)> reclaim;                 // the engine's reclaim (min_slots)
     // fresh: the dictionary was rebuilt right before this batch
     int batch(const InputDesc &d, uint64_t m, bool fresh) const;
+};
+
+// --- the read side ---------------------------------------------------------
+// Device bytes -> pageable host memory through two pinned chunks, one in flight while
+// the other is copied out: a copy to pageable memory blocks in the runtime, which may
+// not happen under a reader while the handle ingests.  (The arithmetic: gns_pinchunk.hpp.)
+constexpr size_t kPinChunk = 4u << 20;
+struct PinnedOut {
+    uint8_t *pin = nullptr;
+    size_t pin_n = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // a chunk's copy has landed
+    // at least `bytes` of pinned memory (grow-only, to twice the request, never below two
+    // chunks) and the events
+    int reserve(size_t bytes);
+    // complete on return.  sw != 0: rows of sw source bytes of which the first dw go out
+    int copy_out(void *dst, const void *src, size_t bytes, hipStream_t s, size_t sw = 0, size_t dw = 0);
+    void free_all();
+};
+
+// Grow-only device staging of a host point query's keys and answers: no allocation or
+// free -- hipFree synchronizes the device -- once warm.  pin: host keys and answers
+// pass through that pinned memory (a view's: see PinnedOut).
+struct QueryStage {
+    uint8_t *qkeys = nullptr;
+    uint64_t *qout = nullptr;
+    uint64_t qkeys_n = 0, qout_n = 0;
+    PinnedOut *pin = nullptr;
+    void free_all();
+};
+// The point query of every engine and view: n keys of key_bytes at `stride` -> out[n],
+// host memory or (dev) device memory, where the call returns once the answers are
+// written.  launch(dk, dout) enqueues the engine's kernel on s over the device keys
+// and answers; the checks, the staging, the sync and the error mapping are here.
+using LaunchFn = std::function<int(const uint8_t *dk, uint64_t *dout)>;
+int query_keys(int device, hipStream_t s, QueryStage &st, const char *what, const uint8_t *keys, uint32_t stride,
+               uint32_t key_bytes, uint64_t n, uint64_t *out, bool dev, const LaunchFn &launch);
+
+// What a snapshot view owns besides its copy of the state: a stream of the device's
+// highest priority (a reader's small launches are dispatched ahead of the ingest
+// pipeline's queued workgroups), the event that orders it behind a refresh, and the
+// mutex between refresh and readers (a refresh waits for the reader call in progress).
+struct ViewCore {
+    hipStream_t stream = nullptr;
+    hipEvent_t ready = nullptr;
+    std::mutex mu;
+    int init();
+    // what is queued on the handle's stream so far is the view's state: readers wait for it
+    int publish(hipStream_t handle_stream);
+    void quiesce();  // destroy: waits for the reader call in progress (its stream is synchronized)
+    void destroy();
 };
 
 // gns_frame.cpp: one captured frame -> one 64-byte record for the device

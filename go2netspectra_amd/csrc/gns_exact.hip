@@ -1330,7 +1330,6 @@ using namespace gns;
 // its buffers only grow, to twice the request, and every host copy goes through pinned
 // staging -- hipFree synchronizes the device and a copy to pageable memory blocks in the
 // runtime, and neither may happen under a reader while the handle ingests.
-constexpr size_t kPinChunk = 4u << 20;
 struct ExRead {
     bool keep = false;
     ExQFilter *df = nullptr;
@@ -1339,9 +1338,7 @@ struct ExRead {
     ExHhRow *rows[2] = {nullptr, nullptr};
     uint8_t *tmp = nullptr, *dk = nullptr;
     uint64_t df_n = 0, da_n = 0, dv_n = 0, dh_n = 0, rows_n[2] = {0, 0}, tmp_n = 0, dk_n = 0;
-    uint8_t *pin = nullptr;  // keep: pinned host staging, two chunks
-    size_t pin_n = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // keep: a chunk's copy has landed
+    PinnedOut po;  // keep: pinned host staging
 
     template <class T>
     int buf(T **p, uint64_t &have, uint64_t need) {
@@ -1354,62 +1351,21 @@ struct ExRead {
         have = n;
         return GNS_OK;
     }
-    int reserve_pin(size_t bytes) {
-        if (bytes <= pin_n && pin) return GNS_OK;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr;
-        pin_n = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&pin), bytes, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("hipHostMalloc(%zu bytes) failed", bytes);
-            return GNS_E_OOM;
-        }
-        pin_n = bytes;
-        return GNS_OK;
-    }
     int init_keep() {
         keep = true;
-        for (int i = 0; i < 2; i++)
-            if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-                set_error("view event");
-                return GNS_E_HIP;
-            }
-        return reserve_pin(2 * kPinChunk);
+        return po.reserve(2 * kPinChunk);
     }
     void free_all() {
         dfree(df); dfree(da); dfree(dv); dfree(dh); dfree(rows[0]); dfree(rows[1]); dfree(tmp); dfree(dk);
         df = nullptr; da = dv = nullptr; dh = nullptr; rows[0] = rows[1] = nullptr; tmp = dk = nullptr;
         df_n = da_n = dv_n = dh_n = rows_n[0] = rows_n[1] = tmp_n = dk_n = 0;
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr;
-        pin_n = 0;
-        for (int i = 0; i < 2; i++) {
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-            ev[i] = nullptr;
-        }
+        po.free_all();
     }
     // Device bytes -> the caller's host memory.  !keep: straight out (the caller synchronizes
-    // the stream).  keep: through the pinned buffer, one half in flight while the other is
-    // copied out; complete on return.
+    // the stream).  keep: through the pinned buffer; complete on return.
     int copy_out(void *dst, const void *src, size_t bytes, hipStream_t s) {
-        if (!keep) {
-            GNS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-            return GNS_OK;
-        }
-        const size_t half = pin_n / 2, nchunk = (bytes + half - 1) / half;
-        for (size_t j = 0; j <= nchunk; j++) {
-            if (j < nchunk) {
-                const size_t off = j * half;
-                GNS_HIP(hipMemcpyAsync(pin + (j & 1) * half, static_cast<const uint8_t *>(src) + off,
-                                       std::min(half, bytes - off), hipMemcpyDeviceToHost, s));
-                GNS_HIP(hipEventRecord(ev[j & 1], s));
-            }
-            if (j > 0) {
-                const size_t i = j - 1, off = i * half;
-                GNS_HIP(hipEventSynchronize(ev[i & 1]));
-                memcpy(static_cast<uint8_t *>(dst) + off, pin + (i & 1) * half, std::min(half, bytes - off));
-            }
-        }
+        if (keep) return po.copy_out(dst, src, bytes, s);
+        GNS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
         return GNS_OK;
     }
 };
@@ -1452,17 +1408,15 @@ struct gns_ex {
     uint32_t *h_pin = nullptr;
     HostStage stage;
     CompactInput compact;  // compact records: the staged side array, the 16-byte form's sizes
+    QueryStage qs;         // host queries' keys and answers on the device
     StageTimer timer;
 };
 
 // A dense copy of the flows one refresh selected: records at stride RW and the four
 // exported state arrays, `cap` rows of room, the row count on the device (*total) until a
 // reader fetches it.  Nothing in it points into the handle's table.
-struct gns_ex_view {
+struct gns_ex_view : ViewCore {
     gns_ex *ex = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;
-    std::mutex mu;         // refresh vs readers: a refresh waits for the reader call in progress
     bool fresh = false;    // refreshed at least once
     bool counted = false;  // n holds this refresh's row count
     uint64_t n = 0;
@@ -1482,6 +1436,7 @@ void ex_free_all(gns_ex *ex) {
     dfree(ex->f.start); dfree(ex->f.end); dfree(ex->pend[0]); dfree(ex->pend[1]);
     dfree(ex->pcnt[0]); dfree(ex->pcnt[1]); dfree(ex->ptotal); dfree(ex->stats); ex->stage.free_all();
     ex->compact.free_all();
+    ex->qs.free_all();
     dfree(ex->sk[0]); dfree(ex->sk[1]); dfree(ex->ph); dfree(ex->pgs); dfree(ex->pb);
     dfree(ex->hot_ids); dfree(ex->touch); dfree(ex->hot_tab); dfree(ex->hpart); dfree(ex->hctl); dfree(ex->ccnt);
     dfree(ex->dctl); dfree(ex->stats_bak); ex->dsc.free_all();
@@ -1785,9 +1740,9 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
     ExQFilter *hf;
     unsigned long long *ha;
     if (rd.keep) {  // staged in the view's pinned buffer: accumulators, then filters
-        GNS_TRY(rd.reserve_pin(acc_bytes + flt_bytes));
-        ha = reinterpret_cast<unsigned long long *>(rd.pin);
-        hf = reinterpret_cast<ExQFilter *>(rd.pin + acc_bytes);
+        GNS_TRY(rd.po.reserve(acc_bytes + flt_bytes));
+        ha = reinterpret_cast<unsigned long long *>(rd.po.pin);
+        hf = reinterpret_cast<ExQFilter *>(rd.po.pin + acc_bytes);
     } else {
         vf.resize(nf);
         va.resize((size_t)nf * kQAcc);
@@ -1871,7 +1826,7 @@ int ex_heavy_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, S
     std::vector<uint32_t> vh;
     uint32_t *hist;
     if (rd.keep) {
-        hist = reinterpret_cast<uint32_t *>(rd.pin);  // (two chunks of room: never smaller than the histogram)
+        hist = reinterpret_cast<uint32_t *>(rd.po.pin);  // (two chunks of room: never smaller than the histogram)
     } else {
         vh.resize(kQBands);
         hist = vh.data();
@@ -1940,8 +1895,7 @@ void exv_free(gns_ex_view *v) {
     exv_free_rows(v->D, v->f);
     dfree(v->scan); dfree(v->total);
     v->rd.free_all();
-    if (v->ready) (void)hipEventDestroy(v->ready);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
+    v->destroy();
 }
 
 // Room for `need` rows.  Growing is an ingest-side matter: new tables first (a failure
@@ -1971,7 +1925,7 @@ int exv_reserve(gns_ex_view *v, uint64_t need) {
 int exv_rows(gns_ex_view *v) {
     if (!v->fresh) { set_error("view never refreshed"); return GNS_E_ARG; }
     if (!v->counted) {
-        uint32_t *h = reinterpret_cast<uint32_t *>(v->rd.pin);
+        uint32_t *h = reinterpret_cast<uint32_t *>(v->rd.po.pin);
         GNS_HIP(hipMemcpyAsync(h, v->total, 4, hipMemcpyDeviceToHost, v->stream));
         GNS_HIP(hipStreamSynchronize(v->stream));
         v->n = std::min<uint64_t>(*h, v->cap);
@@ -2077,8 +2031,7 @@ int gns_ex_insert_tuples(gns_ex *ex, const gns_tuples *t, const uint8_t *ipver, 
         set_error("null tuple array"); return GNS_E_ARG;
     }
     ExIn x{};
-    x.in.src16 = t->src16; x.in.dst16 = t->dst16; x.in.sport = t->sport; x.in.dport = t->dport;
-    x.in.proto = t->proto; x.in.sizes = t->length;
+    x.in = tuples_desc(*t, true);
     x.ipver = ipver; x.ts = ts_ns;
     return ex_insert<IN_TUPLE>(ex, x, n, where);
 }
@@ -2087,8 +2040,7 @@ int gns_ex_insert_headers(gns_ex *ex, const uint8_t *hdr, const uint32_t *wirele
                           uint64_t n, gns_mem where) {
     if (!ex || (n && (!hdr || !wirelen || !ts_ns))) { set_error("null argument"); return GNS_E_ARG; }
     ExIn x{};
-    x.in.hdr = reinterpret_cast<const uint32_t *>(hdr);
-    x.in.sizes = wirelen;
+    x.in = headers_desc(hdr, wirelen);
     x.ts = ts_ns;
     return ex_insert<IN_HDR>(ex, x, n, where);
 }
@@ -2108,42 +2060,17 @@ int gns_ex_insert_compact(gns_ex *ex, const uint8_t *rec16, const uint32_t *wire
 
 int gns_ex_flush(gns_ex *ex) {
     if (!ex) return GNS_E_ARG;
-    GNS_TRY(set_device(ex->device));
-    GNS_HIP(hipStreamSynchronize(ex->stream));
-    ex->timer.collect();
-    return GNS_OK;
+    return handle_flush(ex->device, ex->stream, ex->timer);
 }
 
 static int ex_query_impl(gns_ex *ex, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
-    if (!ex || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    if (stride < ex->K) { set_error("stride < key bytes"); return GNS_E_ARG; }
-    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_device(ex->device));
-    uint8_t *dk = nullptr;
-    uint64_t *dout = nullptr;
-    if (dev) {
-        dk = const_cast<uint8_t *>(flows);
-        dout = out;
-    } else {
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&dk), n * stride));
-        int rc = dalloc(reinterpret_cast<void **>(&dout), n * 8);
-        if (rc) { dfree(dk); return rc; }
-    }
-    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(dk, flows, n * stride, hipMemcpyHostToDevice, ex->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_ex_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ex->stream, dk, stride, n,
-                           ex->K, ex->D, ex->f, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, ex->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ex->stream);
-    if (!dev) {
-        dfree(dk);
-        dfree(dout);
-    }
-    if (e != hipSuccess) { set_error("exact query: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
+    if (!ex) { set_error("null argument"); return GNS_E_ARG; }
+    return query_keys(ex->device, ex->stream, ex->qs, "exact", flows, stride, ex->K, n, out, dev,
+                      [&](const uint8_t *dk, uint64_t *dout) -> int {
+                          hipLaunchKernelGGL(k_ex_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ex->stream, dk,
+                                             stride, n, ex->K, ex->D, ex->f, dout);
+                          return GNS_OK;
+                      });
 }
 
 int gns_ex_query(gns_ex *ex, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
@@ -2246,14 +2173,7 @@ int gns_ex_view_create(gns_ex *ex, gns_ex_view **out) {
     v->D.rec = nullptr; v->D.ctl = nullptr; v->D.mask = 0; v->D.cap = 0;
     int rc = GNS_OK;
     do {
-        // the device's highest priority, as a Count-Min view's stream: a reader's small
-        // launches are dispatched ahead of the ingest pipeline's queued workgroups
-        int lo_pri = 0, hi_pri = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
-        if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess) {
-            set_error("view stream/event"); rc = GNS_E_HIP; break;
-        }
+        if ((rc = v->init()) != GNS_OK) break;
         if ((rc = v->rd.init_keep()) != GNS_OK || (rc = dalloc_t(&v->total, 4)) != GNS_OK) break;
     } while (0);
     if (rc) { exv_free(v); delete v; return rc; }
@@ -2264,11 +2184,9 @@ int gns_ex_view_create(gns_ex *ex, gns_ex_view **out) {
 int gns_ex_view_destroy(gns_ex_view *v) {
     if (!v) return GNS_OK;
     (void)hipSetDevice(v->ex->device);
-    {   // wait for a reader call in progress; the mutex is released before the delete
-        std::lock_guard<std::mutex> lk(v->mu);
-        if (v->stream) (void)hipStreamSynchronize(v->stream);
-        // (freeing the tables waits for a refresh still running on the handle's stream)
-    }
+    // a reader call in progress; the mutex is released before the delete (freeing the tables
+    // waits for a refresh still running on the handle's stream)
+    v->quiesce();
     exv_free(v);
     delete v;
     return GNS_OK;
@@ -2307,8 +2225,7 @@ int gns_ex_view_refresh(gns_ex_view *v, uint64_t since, uint64_t *cursor) {
     }
     // the rows are the state after every insert and merge issued so far and before any
     // later one; the view's stream waits for them
-    GNS_HIP(hipEventRecord(v->ready, s));
-    GNS_HIP(hipStreamWaitEvent(v->stream, v->ready, 0));
+    GNS_TRY(v->publish(s));
     v->fresh = true;
     v->counted = false;
     if (cursor) *cursor = pos;
@@ -2461,12 +2378,7 @@ int gns_ex_set_timing(gns_ex *ex, int on) {
 int gns_ex_stage_times(gns_ex *ex, double ms[8], uint64_t launches[8], int reset) {
     if (!ex) return GNS_E_ARG;
     GNS_TRY(set_device(ex->device));
-    ex->timer.collect();
-    for (int i = 0; i < 8; i++) {
-        if (ms) ms[i] = ex->timer.ms[i];
-        if (launches) launches[i] = ex->timer.launches[i];
-    }
-    if (reset) for (int i = 0; i < 8; i++) { ex->timer.ms[i] = 0; ex->timer.launches[i] = 0; }
+    ex->timer.report(ms, launches, reset);
     return GNS_OK;
 }
 

@@ -93,18 +93,23 @@ int CompactInput::stage_side(InputDesc &in, hipStream_t s) {
     return GNS_OK;
 }
 
-int CompactInput::unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s) {
+int CompactInput::unpack_sizes_into(const uint32_t *rec16, uint64_t m, uint32_t *dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_unpack_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, rec16, m, dst);
+    GNS_HIP(hipGetLastError());
+    return GNS_OK;
+}
+
+int CompactInput::unpack_sizes(InputDesc &d, uint64_t m, hipStream_t s, uint64_t reserve) {
     if (!d.rec_len || m == 0) return GNS_OK;
     if (sizes_n < m) {
         GNS_HIP(hipStreamSynchronize(s));  // an earlier batch may still read the array
         dfree(sizes);
         sizes = nullptr;
         sizes_n = 0;
-        GNS_TRY(dalloc_t(&sizes, m));
-        sizes_n = m;
+        GNS_TRY(dalloc_t(&sizes, std::max(m, reserve)));
+        sizes_n = std::max(m, reserve);
     }
-    hipLaunchKernelGGL(k_unpack_sizes, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d.rec16, m, sizes);
-    GNS_HIP(hipGetLastError());
+    GNS_TRY(unpack_sizes_into(d.rec16, m, sizes, s));
     d.sizes = sizes;
     return GNS_OK;
 }

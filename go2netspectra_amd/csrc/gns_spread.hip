@@ -449,6 +449,7 @@ struct gns_exs {
     DictScratch dsc;
     HostStage stage;
     CompactInput compact;        // compact records: the staged side array, the 16-byte form's sizes
+    QueryStage qs;               // host queries' keys and answers on the device
     StageTimer timer;
     HhScratch hh;
 };
@@ -459,6 +460,7 @@ void exs_free_all(gns_exs *h) {
     dfree(h->P.rec); dfree(h->F.rec); dfree(h->spread); dfree(h->ident); dfree(h->ctl); dfree(h->ptotal);
     dfree(h->pend[0]); dfree(h->pend[1]); dfree(h->pcnt[0]); dfree(h->pcnt[1]); dfree(h->stats); h->stage.free_all();
     h->compact.free_all();
+    h->qs.free_all();
     dfree(h->xbuf);
     h->dsc.free_all();
     h->hh.free_all();
@@ -854,18 +856,13 @@ int gns_exs_insert_tuples(gns_exs *h, const gns_tuples *t, uint64_t n, gns_mem w
     if (!h || !t) { set_error("null argument"); return GNS_E_ARG; }
     if (!h->has_layout) { set_error("handle created without field layouts: keys input only"); return GNS_E_ARG; }
     if (n && (!t->src16 || !t->dst16 || !t->sport || !t->dport || !t->proto)) { set_error("null tuple array"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.src16 = t->src16; in.dst16 = t->dst16; in.sport = t->sport; in.dport = t->dport; in.proto = t->proto;
-    return exs_insert<IN_TUPLE>(h, in, n, where);
+    return exs_insert<IN_TUPLE>(h, tuples_desc(*t, false), n, where);
 }
 
 int gns_exs_insert_headers(gns_exs *h, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n, gns_mem where) {
     if (!h || (n && (!hdr || !wirelen))) { set_error("null argument"); return GNS_E_ARG; }
     if (!h->has_layout) { set_error("handle created without field layouts: keys input only"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.hdr = reinterpret_cast<const uint32_t *>(hdr);
-    in.sizes = wirelen;
-    return exs_insert<IN_HDR>(h, in, n, where);
+    return exs_insert<IN_HDR>(h, headers_desc(hdr, wirelen), n, where);
 }
 
 int gns_spread_insert_compact(gns_exs *h, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
@@ -882,41 +879,17 @@ int gns_spread_insert_compact(gns_exs *h, const uint8_t *rec16, const uint32_t *
 
 int gns_exs_flush(gns_exs *h) {
     if (!h) return GNS_E_ARG;
-    GNS_TRY(set_device(h->device));
-    GNS_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
-    return GNS_OK;
+    return handle_flush(h->device, h->stream, h->timer);
 }
 
 static int exs_query_impl(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
-    if (!h || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    if (stride < h->Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
-    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_device(h->device));
-    uint8_t *dk = nullptr;
-    uint64_t *dout = nullptr;
-    if (dev) {
-        dk = const_cast<uint8_t *>(flows);
-        dout = out;
-    } else {
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&dk), n * stride));
-        int rc = dalloc(reinterpret_cast<void **>(&dout), n * 8);
-        if (rc) { dfree(dk); return rc; }
-    }
-    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(dk, flows, n * stride, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_exs_query, dim3(exs_grid(n)), dim3(256), 0, h->stream, dk, stride, n, h->F, h->spread, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (!dev) {
-        dfree(dk);
-        dfree(dout);
-    }
-    if (e != hipSuccess) { set_error("spread query: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
+    if (!h) { set_error("null argument"); return GNS_E_ARG; }
+    return query_keys(h->device, h->stream, h->qs, "spread", flows, stride, h->Kf, n, out, dev,
+                      [&](const uint8_t *dk, uint64_t *dout) -> int {
+                          hipLaunchKernelGGL(k_exs_query, dim3(exs_grid(n)), dim3(256), 0, h->stream, dk, stride, n, h->F,
+                                             h->spread, dout);
+                          return GNS_OK;
+                      });
 }
 
 int gns_exs_query(gns_exs *h, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
@@ -1107,12 +1080,7 @@ int gns_exs_set_timing(gns_exs *h, int on) {
 int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset) {
     if (!h) return GNS_E_ARG;
     GNS_TRY(set_device(h->device));
-    h->timer.collect();
-    for (int i = 0; i < 8; i++) {
-        if (ms) ms[i] = h->timer.ms[i];
-        if (launches) launches[i] = h->timer.launches[i];
-    }
-    if (reset) for (int i = 0; i < 8; i++) { h->timer.ms[i] = 0; h->timer.launches[i] = 0; }
+    h->timer.report(ms, launches, reset);
     return GNS_OK;
 }
 

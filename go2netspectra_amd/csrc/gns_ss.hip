@@ -1612,6 +1612,7 @@ struct gns_ss : FlowDict {
     uint32_t *h_pin = nullptr;
     HostStage stage;
     CompactInput compact;        // compact records: the staged side array, the 16-byte form's sizes
+    QueryStage qs;               // host queries' keys and answers on the device
     StageTimer timer;
     HhScratch hh;                // HeavyHitters' device list buffers (gns_hh.hpp), filled on first use
 };
@@ -1625,6 +1626,7 @@ void ss_free_all(gns_ss *ss) {
     dfree(ss->cval); dfree(ss->sval); dfree(ss->shist); dfree(ss->spart); dfree(ss->sorder);
     dfree(ss->counts); dfree(ss->heads); dfree(ss->hlen); dfree(ss->sprof); dfree(ss->cblk); dfree(ss->stats); ss->stage.free_all();
     ss->compact.free_all();
+    ss->qs.free_all();
     ss->FlowDict::free_all();
     ss->hh.free_all();
     if (ss->h_pin) (void)hipHostFree(ss->h_pin);
@@ -2056,18 +2058,12 @@ int gns_ss_insert_keys(gns_ss *ss, const uint8_t *flows, uint32_t fstride, const
 int gns_ss_insert_tuples(gns_ss *ss, const gns_tuples *t, uint64_t n, gns_mem where) {
     if (!ss || !t) { set_error("null argument"); return GNS_E_ARG; }
     if (n && (!t->src16 || !t->dst16 || !t->sport || !t->dport || !t->proto)) { set_error("null tuple array"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.src16 = t->src16; in.dst16 = t->dst16; in.sport = t->sport; in.dport = t->dport; in.proto = t->proto;
-    in.sizes = t->length;
-    return ss_insert<IN_TUPLE>(ss, in, n, where);
+    return ss_insert<IN_TUPLE>(ss, tuples_desc(*t, true), n, where);
 }
 
 int gns_ss_insert_headers(gns_ss *ss, const uint8_t *hdr, const uint32_t *wirelen, uint64_t n, gns_mem where) {
     if (!ss || (n && (!hdr || !wirelen))) { set_error("null argument"); return GNS_E_ARG; }
-    InputDesc in{};
-    in.hdr = reinterpret_cast<const uint32_t *>(hdr);
-    in.sizes = wirelen;
-    return ss_insert<IN_HDR>(ss, in, n, where);
+    return ss_insert<IN_HDR>(ss, headers_desc(hdr, wirelen), n, where);
 }
 
 int gns_ss_insert_compact(gns_ss *ss, const uint8_t *rec16, const uint32_t *wirelen, uint64_t n,
@@ -2083,42 +2079,17 @@ int gns_ss_insert_compact(gns_ss *ss, const uint8_t *rec16, const uint32_t *wire
 
 int gns_ss_flush(gns_ss *ss) {
     if (!ss) return GNS_E_ARG;
-    GNS_TRY(set_device(ss->device));
-    GNS_HIP(hipStreamSynchronize(ss->stream));
-    ss->timer.collect();
-    return GNS_OK;
+    return handle_flush(ss->device, ss->stream, ss->timer);
 }
 
 static int ss_query_impl(gns_ss *ss, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
-    if (!ss || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n == 0) return GNS_OK;
-    if (stride < ss->g.Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
-    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_device(ss->device));
-    uint8_t *dk = nullptr;
-    uint64_t *dout = nullptr;
-    if (dev) {
-        dk = const_cast<uint8_t *>(flows);
-        dout = out;
-    } else {
-        GNS_TRY(dalloc(reinterpret_cast<void **>(&dk), n * stride));
-        int rc = dalloc(reinterpret_cast<void **>(&dout), n * 8);
-        if (rc) { dfree(dk); return rc; }
-    }
-    SsQueryArgs a{dk, stride, n, ss->g, ss->D, ss->values, ss->keys, dout};
-    hipError_t e = dev ? hipSuccess : hipMemcpyAsync(dk, flows, n * stride, hipMemcpyHostToDevice, ss->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_ss_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ss->stream, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, ss->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ss->stream);
-    if (!dev) {
-        dfree(dk);
-        dfree(dout);
-    }
-    if (e != hipSuccess) { set_error("ss query: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
+    if (!ss) { set_error("null argument"); return GNS_E_ARG; }
+    return query_keys(ss->device, ss->stream, ss->qs, "ss", flows, stride, ss->g.Kf, n, out, dev,
+                      [&](const uint8_t *dk, uint64_t *dout) -> int {
+                          SsQueryArgs a{dk, stride, n, ss->g, ss->D, ss->values, ss->keys, dout};
+                          hipLaunchKernelGGL(k_ss_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ss->stream, a);
+                          return GNS_OK;
+                      });
 }
 
 int gns_ss_query(gns_ss *ss, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out) {
@@ -2298,9 +2269,7 @@ int gns_ss_reclaim(gns_ss *ss) {
 
 int gns_ss_dict_stats(gns_ss *ss, uint64_t out[8]) {
     if (!ss || !out) return GNS_E_ARG;
-    out[0] = ss->n_reclaim; out[1] = ss->n_dropped; out[2] = ss->last_live; out[3] = ss->claimed;
-    out[4] = (uint64_t)(ss->reclaim_ms * 1000.0); out[5] = ss->n_retry;
-    out[6] = ss->dict_slots; out[7] = ss->n_grow;
+    ss->FlowDict::stats(out);
     return GNS_OK;
 }
 
@@ -2313,12 +2282,7 @@ int gns_ss_set_timing(gns_ss *ss, int on) {
 int gns_ss_stage_times(gns_ss *ss, double ms[8], uint64_t launches[8], int reset) {
     if (!ss) return GNS_E_ARG;
     GNS_TRY(set_device(ss->device));
-    ss->timer.collect();
-    for (int i = 0; i < 8; i++) {
-        if (ms) ms[i] = ss->timer.ms[i];
-        if (launches) launches[i] = ss->timer.launches[i];
-    }
-    if (reset) for (int i = 0; i < 8; i++) { ss->timer.ms[i] = 0; ss->timer.launches[i] = 0; }
+    ss->timer.report(ms, launches, reset);
     return GNS_OK;
 }
 
@@ -2331,13 +2295,8 @@ int gns_ss_stage_times(gns_ss *ss, double ms[8], uint64_t launches[8], int reset
 // sketch/task.go:177,187-243).  A view is the exact view's shape:
 // self-contained rows, so reset, reclaim, growth and import leave it readable.
 // ===========================================================================
-constexpr size_t kSsvPinChunk = 4u << 20;
-
-struct gns_ss_view {
+struct gns_ss_view : ViewCore {
     gns_ss *ss = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;
-    std::mutex mu;            // refresh vs readers: a refresh waits for the reader call in progress
     bool fresh = false;       // refreshed at least once
     bool state = false;       // the last refresh carried GNS_SS_VIEW_STATE
     SsGeom g{};
@@ -2350,15 +2309,11 @@ struct gns_ss_view {
     uint64_t records = 0;                      // the generator position at the refresh
     uint32_t *words = nullptr;                 // [0] refresh: an id named no slot; [1] the list's length
     // readers' grow-only scratch
-    uint8_t *qk = nullptr;
-    uint64_t *qo = nullptr;
-    uint64_t qk_n = 0, qo_n = 0;
+    QueryStage qs;
     uint8_t *rows = nullptr, *orows = nullptr;  // the list as emitted / in canonical order
     uint64_t rows_n = 0, orows_n = 0, rows_cap = 0;  // bytes, bytes, rows
     HhScratch hh;                               // the order's scratch
-    uint8_t *pin = nullptr;                     // pinned staging: two chunks (exports), or one piece (lists, queries)
-    size_t pin_n = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    PinnedOut po;                               // pinned staging: two chunks (exports), or one piece (lists, queries)
     uint32_t *hsm = nullptr;                    // pinned: [0] bad flag, [1] list length, [2..7] counters
 };
 
@@ -2366,60 +2321,11 @@ namespace {
 
 void ssv_free(gns_ss_view *v) {
     dfree(v->vals); dfree(v->kw); dfree(v->regs); dfree(v->pbits); dfree(v->ctr); dfree(v->words);
-    dfree(v->qk); dfree(v->qo); dfree(v->rows); dfree(v->orows);
+    v->qs.free_all(); dfree(v->rows); dfree(v->orows);
     v->hh.free_all();
-    if (v->pin) (void)hipHostFree(v->pin);
+    v->po.free_all();
     if (v->hsm) (void)hipHostFree(v->hsm);
-    for (int i = 0; i < 2; i++)
-        if (v->ev[i]) (void)hipEventDestroy(v->ev[i]);
-    if (v->ready) (void)hipEventDestroy(v->ready);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-}
-
-// pinned staging of at least `bytes` (grow-only, to twice the request)
-int ssv_pin(gns_ss_view *v, size_t bytes) {
-    if (bytes <= v->pin_n && v->pin) return GNS_OK;
-    if (v->pin) (void)hipHostFree(v->pin);
-    v->pin = nullptr;
-    v->pin_n = 0;
-    const size_t want = std::max<size_t>(2 * bytes, 2 * kSsvPinChunk);
-    if (hipHostMalloc(reinterpret_cast<void **>(&v->pin), want, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hipHostMalloc(%zu bytes) failed", want);
-        return GNS_E_OOM;
-    }
-    v->pin_n = want;
-    return GNS_OK;
-}
-
-// Device bytes -> the caller's host memory through the two pinned chunks, one in flight
-// while the other is copied out (gns_ex_view_snapshot's scheme); complete on return.
-// sw != 0: the source is rows of sw bytes of which the first dw go out (key words -> key bytes).
-int ssv_copy_out(gns_ss_view *v, void *dst, const void *src, size_t bytes, size_t sw = 0, size_t dw = 0) {
-    size_t half = kSsvPinChunk;
-    if (sw) half -= half % sw;
-    const size_t nchunk = (bytes + half - 1) / half;
-    uint8_t *d = static_cast<uint8_t *>(dst);
-    for (size_t j = 0; j <= nchunk; j++) {
-        if (j < nchunk) {
-            const size_t off = j * half;
-            GNS_HIP(hipMemcpyAsync(v->pin + (j & 1) * kSsvPinChunk, static_cast<const uint8_t *>(src) + off,
-                                   std::min(half, bytes - off), hipMemcpyDeviceToHost, v->stream));
-            GNS_HIP(hipEventRecord(v->ev[j & 1], v->stream));
-        }
-        if (j > 0) {
-            const size_t i = j - 1, off = i * half, m = std::min(half, bytes - off);
-            GNS_HIP(hipEventSynchronize(v->ev[i & 1]));
-            const uint8_t *p = v->pin + (i & 1) * kSsvPinChunk;
-            if (!sw || sw == dw) {
-                memcpy(d + (sw ? off / sw * dw : off), p, m);
-            } else {
-                uint8_t *o = d + off / sw * dw;
-                for (size_t r = 0; r < m / sw; r++) memcpy(o + r * dw, p + r * sw, dw);
-            }
-        }
-    }
-    return GNS_OK;
+    v->destroy();
 }
 
 SsViewDev ssv_dev(const gns_ss_view *v) { return SsViewDev{v->g, v->Kw, v->vals, v->kw}; }
@@ -2436,34 +2342,18 @@ int ssv_bad_id() {
 }
 
 int ssv_query_impl(gns_ss_view *v, const uint8_t *flows, uint32_t stride, uint64_t n, uint64_t *out, bool dev) {
-    if (!v || (n && (!flows || !out))) { set_error("null argument"); return GNS_E_ARG; }
-    if (n && stride < v->g.Kf) { set_error("stride < flow_bytes"); return GNS_E_ARG; }
-    if (dev && ((uintptr_t)out & 7u) != 0) { set_error("answers not 8-byte aligned"); return GNS_E_ARG; }
-    GNS_TRY(set_device(v->ss->device));
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(ssv_ready(v));
-    if (n == 0) return GNS_OK;
-    hipStream_t s = v->stream;
-    const uint8_t *dk = flows;
-    uint64_t *dout = out;
-    const size_t kb = (size_t)n * stride, ob = (size_t)n * 8, koff = (ob + 15) & ~(size_t)15;
-    if (!dev) {
-        GNS_TRY(grow_buf(&v->qk, v->qk_n, (uint64_t)kb));
-        GNS_TRY(grow_buf(&v->qo, v->qo_n, n));
-        GNS_TRY(ssv_pin(v, koff + kb));
-        memcpy(v->pin + koff, flows, kb);
-        GNS_HIP(hipMemcpyAsync(v->qk, v->pin + koff, kb, hipMemcpyHostToDevice, s));
-        dk = v->qk;
-        dout = v->qo;
-    }
-    hipLaunchKernelGGL(k_ssv_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dk, stride, n, ssv_dev(v), dout);
-    GNS_HIP(hipGetLastError());
-    if (!dev) GNS_HIP(hipMemcpyAsync(v->pin, v->qo, ob, hipMemcpyDeviceToHost, s));
-    GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 4, hipMemcpyDeviceToHost, s));
-    GNS_HIP(hipStreamSynchronize(s));
-    if (v->hsm[0]) return ssv_bad_id();
-    if (!dev) memcpy(out, v->pin, ob);
-    return GNS_OK;
+    v->hsm[0] = 0;
+    GNS_TRY(query_keys(v->ss->device, v->stream, v->qs, "ss view", flows, stride, v->g.Kf, n, out, dev,
+                       [&](const uint8_t *dk, uint64_t *dout) -> int {
+                           hipLaunchKernelGGL(k_ssv_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, dk,
+                                              stride, n, ssv_dev(v), dout);
+                           GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 4, hipMemcpyDeviceToHost, v->stream));
+                           return GNS_OK;
+                       }));
+    return v->hsm[0] ? ssv_bad_id() : GNS_OK;
 }
 
 // The view's list in canonical order on the device: *n_out = the full length.  Under v->mu.
@@ -2501,8 +2391,8 @@ int ssv_list(gns_ss_view *v, uint64_t cap, uint8_t *rows_dev, bool to_host, uint
     if (to_host) {
         const size_t b = (size_t)std::min<uint64_t>(n, cap) * W;
         if (b) {
-            GNS_TRY(ssv_pin(v, b));
-            GNS_HIP(hipMemcpyAsync(v->pin, dst, b, hipMemcpyDeviceToHost, s));
+            GNS_TRY(v->po.reserve(b));
+            GNS_HIP(hipMemcpyAsync(v->po.pin, dst, b, hipMemcpyDeviceToHost, s));
         }
     }
     GNS_HIP(hipStreamSynchronize(s));
@@ -2523,22 +2413,16 @@ int gns_ss_view_create(gns_ss *ss, gns_ss_view **out) {
     v->thr = ss->thr;
     v->Kw = std::max<uint32_t>((ss->g.Kf + 3) / 4, 1);
     v->cells = (uint64_t)ss->g.d * ss->g.w;
+    v->qs.pin = &v->po;  // host queries' keys and answers pass through the pinned staging
     int rc = GNS_OK;
     do {
-        // the device's highest priority, as the other views' streams: a reader's small
-        // launches are dispatched ahead of the ingest pipeline's queued workgroups
-        int lo_pri = 0, hi_pri = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
-        if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, hi_pri) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ev[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ev[1], hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&v->hsm), 64, hipHostMallocDefault) != hipSuccess) {
+        if ((rc = v->init()) != GNS_OK) break;
+        if (hipHostMalloc(reinterpret_cast<void **>(&v->hsm), 64, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             set_error("view stream/event"); rc = GNS_E_HIP; break;
         }
         if ((rc = dalloc_t(&v->vals, v->cells)) != GNS_OK || (rc = dalloc_t(&v->kw, v->cells * v->Kw)) != GNS_OK ||
-            (rc = dalloc_t(&v->words, 4)) != GNS_OK || (rc = ssv_pin(v, 2 * kSsvPinChunk)) != GNS_OK) break;
+            (rc = dalloc_t(&v->words, 4)) != GNS_OK || (rc = v->po.reserve(2 * kPinChunk)) != GNS_OK) break;
         // the list's rows and the order's scratch for 64K flows up front; longer lists grow them
         const uint32_t W = ss->g.Kf + 4;
         const uint64_t nr = std::min<uint64_t>(v->cells, 1u << 16);
@@ -2560,11 +2444,9 @@ int gns_ss_view_create(gns_ss *ss, gns_ss_view **out) {
 int gns_ss_view_destroy(gns_ss_view *v) {
     if (!v) return GNS_OK;
     (void)hipSetDevice(v->ss->device);
-    {   // wait for a reader call in progress; the mutex is released before the delete
-        std::lock_guard<std::mutex> lk(v->mu);
-        if (v->stream) (void)hipStreamSynchronize(v->stream);
-        // (freeing the arrays waits for a refresh still running on the handle's stream)
-    }
+    // a reader call in progress; the mutex is released before the delete (freeing the arrays
+    // waits for a refresh still running on the handle's stream)
+    v->quiesce();
     ssv_free(v);
     delete v;
     return GNS_OK;
@@ -2598,8 +2480,7 @@ int gns_ss_view_refresh(gns_ss_view *v, uint32_t flags) {
     }
     // the arrays are the state after every insert issued so far and before any later
     // one; the view's stream waits for them
-    GNS_HIP(hipEventRecord(v->ready, s));
-    GNS_HIP(hipStreamWaitEvent(v->stream, v->ready, 0));
+    GNS_TRY(v->publish(s));
     v->records = ss->pkt;
     v->state = st;
     v->fresh = true;
@@ -2626,7 +2507,7 @@ int gns_ss_view_heavy_hitters(gns_ss_view *v, uint8_t *flows, uint32_t *spreads,
     const uint64_t m = std::min(n, cap);
     const uint32_t K = v->g.Kf, W = K + 4;
     for (uint64_t i = 0; i < m; i++) {
-        const uint8_t *r = v->pin + i * W;
+        const uint8_t *r = v->po.pin + i * W;
         if (flows && K) memcpy(flows + i * K, r, K);
         if (spreads) memcpy(spreads + i, r + K, 4);
     }
@@ -2662,10 +2543,10 @@ int gns_ss_view_export_state(gns_ss_view *v, uint32_t *values, uint8_t *keys, ui
     if (v->hsm[0]) return ssv_bad_id();
     if (counters) memcpy(counters, v->hsm + 2, 24);
     if (records) *records = v->records;
-    if (values) GNS_TRY(ssv_copy_out(v, values, v->vals, cells * 4));
-    if (keys && v->g.Kf) GNS_TRY(ssv_copy_out(v, keys, v->kw, cells * v->Kw * 4, (size_t)v->Kw * 4, v->g.Kf));
-    if (regs) GNS_TRY(ssv_copy_out(v, regs, v->regs, cells * v->g.m));
-    if (pbits) GNS_TRY(ssv_copy_out(v, pbits, v->pbits, cells * 8));
+    if (values) GNS_TRY(v->po.copy_out(values, v->vals, cells * 4, s));
+    if (keys && v->g.Kf) GNS_TRY(v->po.copy_out(keys, v->kw, cells * v->Kw * 4, s, (size_t)v->Kw * 4, v->g.Kf));
+    if (regs) GNS_TRY(v->po.copy_out(regs, v->regs, cells * v->g.m, s));
+    if (pbits) GNS_TRY(v->po.copy_out(pbits, v->pbits, cells * 8, s));
     return GNS_OK;
 }
 

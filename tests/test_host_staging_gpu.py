@@ -236,3 +236,138 @@ def test_super_spread_host_batch_reclaims_retries_and_splits(gpu, oracle):
     assert ds["retried_batches"] > 0 and ds["reclaims"] > 0, ds
     assert ss.counters()["dict_full"] == 0
     assert_same_list([(h.Flow, h.Count) for h in ss.heavy_hitters().Count], orc.heavy())
+
+
+# --- point queries through the shared staging (query_keys) ----------------------
+SENTINEL = 0xEEEEEEEEEEEEEEEE
+
+
+def query_engine(name, w):
+    """(the object to close last, raw handle, host query, device query or None, keys [>= 257, K],
+    what a handle without a device query is compared with)."""
+    from go2netspectra_amd import CountMin, ExactSpread, SuperSpread, _lib
+    from go2netspectra_amd.exact import ExactAggregator
+    L = _lib.load()
+    rng = np.random.default_rng(len(name))
+    b = w["batch"]
+    if name in ("cm", "cm_view"):
+        seeds = np.random.default_rng(3).integers(0, 2**32, 3, dtype=np.uint64).astype(np.uint32)
+        h = CountMin(1 << 14, 3, 4000, 8, seeds=seeds, key_bytes=37)
+        h.insert_keys(w["keys"], w["wl"])
+        present = w["keys"]
+        fns = (L.gns_cm_query, L.gns_cm_query_device)
+    elif name in ("ss", "ss_view"):
+        seeds = np.random.default_rng(4).integers(0, 2**32, 2, dtype=np.uint64).astype(np.uint32)
+        h = SuperSpread(512, 2, 2, 32, 5, seeds=seeds, flow_bytes=16, elem_bytes=16)
+        h.insert_keys(b.src16, b.dst16)
+        present = b.src16
+        fns = (L.gns_ss_query, L.gns_ss_query_device)
+    elif name == "exact":
+        h = ExactAggregator(FIVE)
+        h.insert_tuples(b)
+        present, v4 = w["keys"].copy(), b.ipver == 4
+        for off in (0, 16):  # an IPv4 flow is found through its IPv4-mapped form (task.go:298-326)
+            present[v4, off + 12:off + 16] = w["keys"][v4, off:off + 4]
+            present[v4, off:off + 10] = 0
+            present[v4, off + 10:off + 12] = 0xFF
+        fns = (L.gns_ex_query, L.gns_ex_query_device)
+    else:
+        h = ExactSpread(None, None, flow_bytes=16, elem_bytes=16)
+        h.insert_keys(b.src16, b.dst16)
+        present = b.src16
+        fns = (L.gns_exs_query, L.gns_exs_query_device)
+    h.flush()
+    present = np.unique(present, axis=0)
+    keys = np.concatenate([present[:250], rng.integers(0, 256, (257 - min(250, len(present)), present.shape[1]),
+                                                       dtype=np.uint8)])
+    keys = np.ascontiguousarray(keys[rng.permutation(len(keys))])
+    if name == "cm_view":
+        v = h.view()
+        v.refresh()
+        want = h.query_many(dev(keys)).cpu().numpy().view(np.uint64)  # the handle at the refresh point
+        return (v, h), v._h, L.gns_cm_view_query, None, keys, want
+    if name == "ss_view":
+        v = h.view()
+        v.refresh()
+        return (v, h), v._h, L.gns_ss_view_query, L.gns_ss_view_query_device, keys, None
+    return (h,), h._h, fns[0], fns[1], keys, None
+
+
+@pytest.mark.parametrize("name", ["cm", "ss", "exact", "spread", "cm_view", "ss_view"])
+def test_host_and_device_queries_agree(gpu, world, name):
+    """A query of host keys (staged through the handle's grow-only scratch; a SuperSpread view's
+    through its pinned memory) answers what the query of the same keys in device memory does,
+    at one key, a full block and one past it; the argument checks are the same for both."""
+    import torch
+    from go2netspectra_amd import _lib
+    owners, h, host_fn, dev_fn, keys, want = query_engine(name, world)
+    K = keys.shape[1]
+    dkeys = dev(keys)
+    torch.cuda.synchronize()
+
+    def host(n, lo=0, stride=K):
+        out = np.full(n + 1, SENTINEL, np.uint64)
+        return host_fn(h, keys[lo:].ctypes.data, stride, n, out.ctypes.data), out
+
+    def device(n, stride=K, skew=0):
+        out = torch.full((n + 2,), -1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        code = dev_fn(h, dkeys.data_ptr(), stride, n, out.data_ptr() + skew)
+        return code, out.cpu().numpy().view(np.uint64)
+
+    answers = {}
+    for n in (257, 1, 256):  # the largest first: the later calls reuse its scratch
+        code, got = host(n)
+        assert code == 0 and got[n] == SENTINEL
+        answers[n] = got[:n]
+        if dev_fn is not None:
+            code, d = device(n)
+            assert code == 0 and d[n] == 2**64 - 1
+            want_n = d[:n]
+        else:
+            want_n = want[:n]
+        assert np.array_equal(got[:n], want_n), f"{name}: host and device answers differ at n={n}"
+    # not a comparison of zeros: 250 of the keys were inserted (a sketch answers for those that own a cell)
+    assert int((answers[257] != 0).sum()) >= 26
+    assert np.array_equal(answers[1], answers[257][:1]) and np.array_equal(answers[256], answers[257][:256])
+    code, one = host(1, lo=200)  # one key after 257: the larger scratch is reused
+    assert code == 0 and one[0] == answers[257][200] and one[1] == SENTINEL
+    # n = 0 is fine and writes nothing; a stride below the key size is an argument error
+    code, got = host(0)
+    assert code == 0 and got[0] == SENTINEL
+    assert host(4, stride=K - 1)[0] == _lib.GNS_E_ARG
+    if dev_fn is not None:
+        code, d = device(0)
+        assert code == 0 and (d == 2**64 - 1).all()
+        assert device(4, stride=K - 1)[0] == _lib.GNS_E_ARG
+        code, d = device(4, skew=4)  # answers not 8-byte aligned
+        assert code == _lib.GNS_E_ARG and (d == 2**64 - 1).all()
+    for x in owners:
+        x.close()
+
+
+def test_count_min_compact16_host_reuses_both_buffers(gpu, world):
+    """Count-Min's 16-byte compact records from host memory in one call of four staged batches
+    at the smallest batch the handle takes (one chunk; cm_insert's cold first batch is
+    min(batch, max(64 chunks, batch / 32)) = the batch there): buffer 0, 1, 0, 1 with a ragged
+    tail, the sizes unpacked into each staged batch.  The state is that of the same records
+    inserted from device memory in two calls."""
+    from go2netspectra_amd import CountMin, compact_headers
+    w = world
+    n = 3 * CHUNK + 777
+    hdr = np.concatenate([w["hdr"], w["hdr"][:n - N]])
+    wl = np.concatenate([w["wl"], w["wl"][:n - N]])
+    rec, side = compact_headers(dev(hdr), dev(wl), rec_len=True)
+    assert len(rec) == n and len(side) > 0
+    hrec, hside = rec.cpu().numpy(), side.cpu().numpy()
+    seeds = np.random.default_rng(3).integers(0, 2**32, 3, dtype=np.uint64).astype(np.uint32)
+    a, b = (CountMin(1024, 3, 4000, 8, seeds=seeds, batch_packets=CHUNK, flow_fields=FIVE) for _ in range(2))
+    a.insert_compact(hrec, None, hside)
+    b.insert_compact(rec[:n // 3], None, side)
+    b.insert_compact(rec[n // 3:], None, side)
+    a.flush()
+    b.flush()
+    for name, x, y in zip(("C", "S", "FPc", "FPs"), a.export_state(), b.export_state()):
+        assert np.array_equal(x, y), name
+    c = same_counters(a, b, ["inserted", "dropped", "unsupported", "dict_full", "ovf_full"])
+    assert c["inserted"] == n

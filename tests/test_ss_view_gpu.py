@@ -198,6 +198,36 @@ def test_checkpoint_during_ingest(gpu, oracle, tmp_path):
         x.close()
 
 
+def test_export_spans_more_than_two_pinned_chunks(gpu):
+    """The view's export goes out through two 4 MiB pinned chunks.  Nine-byte flows are three
+    key words a cell (12-byte rows of which 9 go out; 4 MiB is no multiple of 12), and
+    4 * 2^18 cells make 12 MiB of them: four pieces, so both chunks are used twice and every
+    piece but the first starts inside the destination at an offset that is no multiple of the
+    chunk.  The handle's own export takes another route (ids -> bytes on the device), so the
+    two agree only if every piece landed where it belongs."""
+    from go2netspectra_amd import SuperSpread
+    rng = np.random.default_rng(99)
+    w, d, m, Kf, Ke = 1 << 18, 4, 32, 9, 4
+    seeds = rng.integers(0, 2**32, d, dtype=np.uint64).astype(np.uint32)
+    ss = SuperSpread(w, d, 1, m, 5, 0.5, 1.08, flow_bytes=Kf, elem_bytes=Ke, seeds=seeds, hll_master=HLL_MASTER,
+                     rng_seed=RNG_SEED)
+    fl, el, _ = spread_stream(rng, 6000, 3000, Kf, Ke)
+    ss.insert_keys(fl, el)
+    view = ss.view()
+    view.refresh(state=True)
+    want = ss.export_state()  # the same point: nothing is inserted after the refresh
+    got = view.export_state()
+    assert int((want[0] != 0).sum()) > 1000  # cells all over the rows hold flows
+    owned = np.flatnonzero(want[0])
+    assert owned.min() < (1 << 18) and owned.max() > 3 * (1 << 18)  # in the first and in the last piece
+    for name, a, b in zip(("values", "keys", "regs", "pbits"), got, want):
+        if name == "pbits":
+            a, b = a.view(np.uint64), b.view(np.uint64)  # bit patterns
+        assert a.shape == b.shape and np.array_equal(a, b), f"{name}: {int((a != b).sum())} entries differ"
+    view.close()
+    ss.close()
+
+
 def test_edges(gpu, oracle):
     from go2netspectra_amd import GnsError, _lib
     rng = np.random.default_rng(13)
