@@ -53,6 +53,7 @@ EXPORTED = [
     "gns_ss_insert_compact", "gns_spread_insert_compact", "gns_ex_insert_compact", "gns_pack_pcap_compact_ts",
     "gns_ss_view_create", "gns_ss_view_destroy", "gns_ss_view_refresh", "gns_ss_view_query",
     "gns_ss_view_query_device", "gns_ss_view_heavy_hitters", "gns_ss_view_heavy_rows", "gns_ss_view_export_state",
+    "gns_cm_view_refresh_at", "gns_cm_view_query_device", "gns_cm_view_heavy_rows", "gns_cm_view_export_state",
 ]
 
 
@@ -238,6 +239,10 @@ def load() -> ct.CDLL:
         "gns_ss_view_query_device": ([vp, vp, u32, u64, vp], i32),
         "gns_ss_view_heavy_hitters": ([vp, vp, vp, vp], i32), "gns_ss_view_heavy_rows": ([vp, vp, vp], i32),
         "gns_ss_view_export_state": ([vp, vp, vp, vp, vp, vp, vp], i32),
+        "gns_cm_view_refresh_at": ([vp, u32], i32),
+        "gns_cm_view_query_device": ([vp, vp, u32, u64, vp], i32),
+        "gns_cm_view_heavy_rows": ([vp, vp, vp, vp, vp], i32),
+        "gns_cm_view_export_state": ([vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -294,6 +299,7 @@ def dict_stats(fn, h) -> dict:
 
 GNS_TIMING_MASK = 0x100
 GNS_SS_VIEW_STATE = 1  # gns_ss_view_refresh: also capture registers, pbits, counters, generator position
+GNS_CM_VIEW_DETACH = 1  # gns_cm_view_refresh_at: resolve the snapshot's flows into the view's own key table
 
 
 def timing_arg(on, stages, names) -> int:

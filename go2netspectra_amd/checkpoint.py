@@ -105,8 +105,9 @@ def check_meta(saved: dict, live: dict) -> None:
 
 def save(obj, path) -> None:
     """Export ``obj``'s state (after its pending inserts) into one file.  A SuperSpreadView
-    refreshed with state=True writes the file its SuperSpread would have written at the
-    refresh -- from any thread, while the sketch keeps ingesting."""
+    refreshed with state=True, or a CountMinView refreshed with detach=True, writes the file
+    its sketch would have written at the refresh -- from any thread, while the sketch keeps
+    ingesting."""
     if type(obj).__name__ == "SuperSpreadView":
         meta = describe(obj.parent)
         v, k, r, p = obj.export_state()
@@ -114,6 +115,13 @@ def save(obj, path) -> None:
         meta["counters"] = [c["inserted"], c["dropped"], c["unsupported"]]
         meta["records"] = c["records"]
         write(path, meta, {"values": v, "keys": np.ascontiguousarray(k), "regs": r, "pbits": p.view(np.uint64)})
+        return
+    if type(obj).__name__ == "CountMinView":  # a detached snapshot: the file of the refresh point
+        meta = describe(obj.parent)
+        c = obj.counters()  # raises on a plain snapshot, before anything is exported
+        C, S, Fc, Fs = obj.export_state()
+        meta["counters"] = [int(c["inserted"]), int(c["dropped"]), int(c["unsupported"])]
+        write(path, meta, {"C": C, "S": S, "FPc": np.ascontiguousarray(Fc), "FPs": np.ascontiguousarray(Fs)})
         return
     meta = describe(obj)
     cls = meta["class"]

@@ -2800,6 +2800,138 @@ __global__ __launch_bounds__(256) void k_query(QueryArgs a) {
     a.out[p] = (uint64_t)ct << 32 | sz;
 }
 
+// ---------------------------------------------------------------------------
+// Detached snapshot view (gns_cm_view_refresh_at, GNS_CM_VIEW_DETACH): the flows
+// the buckets name, resolved out of the dictionary into a compact key table, so
+// that the view reads no handle state afterwards.  On the handle's stream:
+//   D1 k_cmv_mark    every cell id of Fc / Fs sets mark[id] (plain stores)
+//   D2 k_cmv_count   per block of 256 slots: the number marked (wave ballots)
+//   D3 k_tscan_*     exclusive offsets of the blocks, the total (gns_scan.cuh;
+//                    the (bin, block) order is slot order, as in the exact view)
+//   D4 k_cmv_gather  marked slot -> table row `dense` = block offset + rank;
+//                    the slot's word becomes remap[slot] = dense
+//   D5 k_cmv_remap   v->F[c] = remap[cm->F[c]] for both arrays (read once)
+// An id that is no dictionary slot is not dereferenced and raises *bad, which the
+// next reader call reports as GNS_E_HIP (k_hh_best's convention).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kCvBins = 256;
+constexpr uint32_t kCvItems = 4;  // cells per lane of D1 / D5
+__device__ __forceinline__ uint64_t cmv_cell(uint32_t i, uint32_t nb) { return (uint64_t)(i % nb) * kCvBins + i / nb; }
+
+__global__ __launch_bounds__(256) void k_cmv_mark(const uint32_t *Fc, const uint32_t *Fs, uint64_t cells, uint64_t slots,
+                                                  uint32_t *mark, uint32_t *bad) {
+    const uint64_t c0 = (uint64_t)blockIdx.x * 256 * kCvItems + threadIdx.x;
+    bool oob = false;
+#pragma unroll
+    for (uint32_t i = 0; i < kCvItems; i++) {
+        const uint64_t c = c0 + (uint64_t)i * 256;
+        if (c >= cells) break;
+        const uint32_t a = Fc[c], b = Fs[c];
+        if (a != GNS_ID_NONE) { if (a < slots) mark[a] = 1u; else oob = true; }
+        if (b != GNS_ID_NONE) { if (b < slots) mark[b] = 1u; else oob = true; }
+    }
+    if (oob) atomicOr(bad, 1u);
+}
+
+// grid = nb * kCvBins blocks (>= the slot blocks; the cells past them count 0)
+__global__ __launch_bounds__(256) void k_cmv_count(const uint32_t *mark, uint64_t slots, uint32_t nb, uint32_t *cnt) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + tid;
+    const uint64_t m = __ballot(s < slots && mark[s] != 0u);
+    if ((tid & 63u) == 0) s_w[tid >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (tid == 0) cnt[cmv_cell(blockIdx.x, nb)] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// T: the view's key table (cap rows of T.RW words).  mark[s] becomes remap[s]: the
+// dense row of a marked slot (GNS_ID_NONE past cap, which raises *bad: cap >= the
+// claimed slots >= the marked ones).
+__global__ __launch_bounds__(256) void k_cmv_gather(DictDev D, uint64_t slots, uint32_t *mark, uint32_t nb,
+                                                    const uint32_t *off, DictDev T, uint64_t cap, uint32_t *bad) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + tid;
+    const bool sel = s < slots && mark[s] != 0u;
+    const uint64_t m = __ballot(sel);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!sel) return;
+    uint64_t r = off[cmv_cell(blockIdx.x, nb)] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; w++) r += s_w[w];
+    if (r >= cap) {
+        mark[s] = GNS_ID_NONE;
+        atomicOr(bad, 1u);
+        return;
+    }
+    mark[s] = (uint32_t)r;
+    const uint4 *q = reinterpret_cast<const uint4 *>(D.rec + s * D.RW);
+    uint4 *o = reinterpret_cast<uint4 *>(T.rec + r * T.RW);
+    // {tag, key words} fill at most 11 words: the last quarter of a 16-word row holds nothing
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (4u * i < T.RW) o[i] = i < 3 ? q[i] : make_uint4(0, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_cmv_remap(const uint32_t *Fc, const uint32_t *Fs, uint64_t cells, uint64_t slots,
+                                                   const uint32_t *remap, uint32_t *vFc, uint32_t *vFs) {
+    const uint64_t c0 = (uint64_t)blockIdx.x * 256 * kCvItems + threadIdx.x;
+#pragma unroll
+    for (uint32_t i = 0; i < kCvItems; i++) {
+        const uint64_t c = c0 + (uint64_t)i * 256;
+        if (c >= cells) break;
+        const uint32_t a = Fc[c], b = Fs[c];
+        vFc[c] = a < slots ? remap[a] : GNS_ID_NONE;  // GNS_ID_NONE is no slot
+        vFs[c] = b < slots ? remap[b] : GNS_ID_NONE;
+    }
+}
+
+// Query (count_min.go:160-174) of a detached snapshot: no dictionary.  A cell's
+// fingerprint equals the key iff its dense id is a table row whose key words are
+// the key's -- ids first, then words, never zero bytes: an empty cell is not the
+// flow whose key is all zero bytes.  `rows` bounds the ids (the table's capacity).
+struct CmvQueryArgs {
+    const uint8_t *keys;
+    uint32_t stride, aligned;
+    uint64_t n;
+    uint32_t K;
+    CmGeom g;
+    DictDev T;
+    uint64_t rows;
+    const uint32_t *C, *Fc, *S, *Fs;
+    uint64_t *out;
+};
+
+__global__ __launch_bounds__(256) void k_cmv_query(CmvQueryArgs a) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.n) return;
+    uint32_t kw[GNS_KWMAX];
+    load_key_bytes<GNS_KWMAX>(a.keys + p * a.stride, a.K, a.aligned != 0, kw);
+    const uint32_t nkw = (a.K + 3) >> 2;
+    // the rows of one flow name one table row: compare words once per distinct id
+    uint32_t hit = GNS_ID_NONE, miss = GNS_ID_NONE;
+    const auto same = [&](uint32_t id) -> bool {
+        if (id == GNS_ID_NONE || id >= a.rows) return false;
+        if (id == hit) return true;
+        if (id == miss) return false;
+        uint32_t r[12];
+        load_record(a.T, id, r);
+        bool eq = true;
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++)
+            if ((uint32_t)i < nkw) eq = eq && (r[1 + i] == kw[i]);
+        if (eq) hit = id; else miss = id;
+        return eq;
+    };
+    uint32_t sz = 0, ct = 0;
+    for (uint32_t rr = 0; rr < a.g.d; rr++) {
+        const uint64_t c = (uint64_t)rr * a.g.w + row_index(a.g, mm3_n<GNS_KWMAX>(kw, a.K, a.g.seeds[rr]));
+        if (same(a.Fs[c])) sz = max(sz, a.S[c]);
+        if (same(a.Fc[c])) ct = max(ct, a.C[c]);
+    }
+    a.out[p] = (uint64_t)ct << 32 | sz;
+}
+
 }  // namespace gns
 
 // ===========================================================================
@@ -2868,22 +3000,46 @@ struct gns_cm : FlowDict {
     StageTimer timer;
 };
 
+enum : uint32_t { kViewPlain = 0, kViewDetached = 1 };
+constexpr uint64_t kCmvPiece = 1u << 18;  // cells per piece of a view's fingerprint export
+
 struct gns_cm_view : ViewCore {
     gns_cm *cm = nullptr;
     uint32_t *C = nullptr, *S = nullptr, *Fc = nullptr, *Fs = nullptr;
     CmRead rd;
     uint32_t period = ~0u;  // handle period of the snapshot (~0: never refreshed)
+    // What the snapshot's Fc / Fs hold: dictionary slots (plain: readers go through the
+    // handle's live dictionary) or rows of the view's own key table (detached: readers
+    // touch no handle state).  Written under mu by the refresh; the handle's reset,
+    // reclaim and import read it without the mutex to skip detached views.
+    std::atomic<uint32_t> kind{kViewPlain};
+    // detached snapshot (grow-only, allocated by the first detached refresh)
+    DictDev T{};                         // the key table as a dictionary without hashing: rec, RW, K
+    uint64_t tab_cap = 0;                // its rows
+    uint32_t *remap = nullptr;           // [dict slots] mark, then slot -> dense row
+    uint64_t remap_n = 0;
+    uint32_t *scan = nullptr;            // D2's block counts / offsets, then the scan's group sums and bin totals
+    uint64_t scan_n = 0;
+    uint32_t *words = nullptr;           // [0] refresh: an id named no slot, [1] the number of flows (rows in use)
+    unsigned long long *ctr = nullptr;   // [3] the handle's counters at the refresh
+    uint8_t *xbytes = nullptr;           // export: one piece's key bytes
+    uint64_t xbytes_n = 0;
+    PinnedOut po;                        // pinned staging: two chunks (exports), or one piece (queries)
+    uint32_t *hsm = nullptr;             // pinned: [0] bad flag, [2..7] counters
 };
 
-// Holds every registered view's mutex: no view call is running (each one
-// synchronizes its stream before it returns), so the handle may rewrite what
-// the views read (the flow dictionary) and bump the period they check.
+// Holds the mutex of every registered view that reads handle state: none of their
+// calls is running (each one synchronizes its stream before it returns), so the
+// handle may rewrite what they read (the flow dictionary) and bump the period they
+// check.  A detached snapshot reads nothing of the handle: it is skipped, and its
+// reader in progress is not waited for.
 struct ViewsQuiesced {
     std::unique_lock<std::mutex> reg;
     std::vector<std::unique_lock<std::mutex>> locks;
     explicit ViewsQuiesced(gns_cm *cm) : reg(cm->views_mu) {
         locks.reserve(cm->views.size());
-        for (gns_cm_view *v : cm->views) locks.emplace_back(v->mu);
+        for (gns_cm_view *v : cm->views)
+            if (v->kind.load() != kViewDetached) locks.emplace_back(v->mu);
     }
 };
 
@@ -2938,15 +3094,20 @@ int cm_reset_state(gns_cm *cm) {
 // view of the current period) still names (gns_dict.hip).  Views are quiesced
 // and their snapshots remapped with the buckets, so a view answers exactly as
 // before; a stale view (taken before a reset) names nothing: it answers
-// GNS_E_ARG until refreshed, which overwrites its ids.  The table doubles
-// while the live flows exceed a quarter of it, and to at least min_slots.
+// GNS_E_ARG until refreshed, which overwrites its ids.  A detached snapshot
+// holds rows of its own key table, not slots: it is neither remapped nor does
+// it keep a flow alive.  The table doubles while the live flows exceed a
+// quarter of it, and to at least min_slots.
 int cm_reclaim(gns_cm *cm, uint64_t min_slots = 0) {
     ViewsQuiesced q(cm);
     const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
     std::vector<DictIds> ids{{cm->Fc, cells}, {cm->Fs, cells}};
     const uint32_t period = cm->period.load();
     for (gns_cm_view *v : cm->views)
-        if (v->period == period) { ids.push_back({v->Fc, cells}); ids.push_back({v->Fs, cells}); }
+        if (v->kind.load() != kViewDetached && v->period == period) {
+            ids.push_back({v->Fc, cells});
+            ids.push_back({v->Fs, cells});
+        }
     return cm->reclaim(ids.data(), (int)ids.size(), min_slots, cm->stream);
 }
 
@@ -3477,8 +3638,24 @@ int gns_cm_flush(gns_cm *cm) {
 // a view can answer (under v->mu)
 static int view_check(gns_cm_view *v) {
     if (v->period == ~0u) { set_error("view never refreshed"); return GNS_E_ARG; }
+    if (v->kind.load() == kViewDetached) return GNS_OK;  // nothing of it points into the handle
     if (v->period != v->cm->period.load()) { set_error("view is stale: the handle was reset; refresh it"); return GNS_E_ARG; }
     return GNS_OK;
+}
+
+static bool view_detached(const gns_cm_view *v) { return v && v->kind.load() == kViewDetached; }
+
+// detached snapshot, under v->mu: the refresh's bad-id word on its way into the pinned
+// mirror (view_bad_id reads it once the stream is synchronized)
+static int view_bad_fetch(gns_cm_view *v) {
+    v->hsm[0] = 0;
+    if (view_detached(v)) GNS_HIP(hipMemcpyAsync(v->hsm, v->words, 4, hipMemcpyDeviceToHost, v->stream));
+    return GNS_OK;
+}
+static int view_bad_id(const gns_cm_view *v) {
+    if (!v->hsm[0]) return GNS_OK;
+    set_error("view refresh: a bucket's flow id named no dictionary slot (corrupt state)");
+    return GNS_E_HIP;
 }
 
 // Query (count_min.go:160-174) of n keys against state (C, Fc, S, Fs) on stream st
@@ -3488,16 +3665,28 @@ static int cm_query_impl(gns_cm *cm, hipStream_t st, CmRead &sc, const uint32_t 
                          uint64_t *out, bool dev, gns_cm_view *v = nullptr) {
     const auto launch = [&](const uint8_t *dk, uint64_t *dout) -> int {
         if (v) GNS_TRY(view_check(v));
+        const uint32_t aligned = (stride % 4 == 0 && stride >= ((cm->K + 3) & ~3u) && ((uintptr_t)dk & 3u) == 0);
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (view_detached(v)) {  // the view's key table instead of the dictionary
+            CmvQueryArgs a{};
+            a.keys = dk; a.stride = stride; a.aligned = aligned;
+            a.n = n; a.K = cm->K; a.g = cm->g; a.T = v->T; a.rows = v->tab_cap;
+            a.C = C; a.Fc = Fc; a.S = S; a.Fs = Fs; a.out = dout;
+            hipLaunchKernelGGL(k_cmv_query, grid, dim3(256), 0, st, a);
+            return view_bad_fetch(v);
+        }
         QueryArgs a{};
         a.keys = dk;
         a.stride = stride;
-        a.aligned = (stride % 4 == 0 && stride >= ((cm->K + 3) & ~3u) && ((uintptr_t)dk & 3u) == 0);
+        a.aligned = aligned;
         a.n = n; a.K = cm->K; a.g = cm->g; a.D = cm->D;
         a.C = C; a.Fc = Fc; a.S = S; a.Fs = Fs; a.out = dout;
-        hipLaunchKernelGGL(k_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_query, grid, dim3(256), 0, st, a);
         return GNS_OK;
     };
-    return query_keys(cm->device, st, sc.q, "cm", keys, stride, cm->K, n, out, dev, launch);
+    if (v) v->hsm[0] = 0;
+    GNS_TRY(query_keys(cm->device, st, sc.q, "cm", keys, stride, cm->K, n, out, dev, launch));
+    return v ? view_bad_id(v) : GNS_OK;
 }
 
 extern "C" {
@@ -3561,8 +3750,46 @@ int gns_cm_heavy_rows(gns_cm *cm, uint8_t *count_rows, uint64_t *n_count, uint8_
 // ---------------------------------------------------------------------------
 static void view_free(gns_cm_view *v) {
     dfree(v->C); dfree(v->S); dfree(v->Fc); dfree(v->Fs);
+    dfree(v->T.rec); dfree(v->remap); dfree(v->scan); dfree(v->words); dfree(v->ctr); dfree(v->xbytes);
     v->rd.free_all();
+    v->po.free_all();
+    if (v->hsm) (void)hipHostFree(v->hsm);
     v->destroy();
+}
+
+// One list of a view, under v->mu after view_check: ids are dictionary slots resolved
+// through the live dictionary (plain), or rows of the view's key table (detached).
+static int view_heavy_one(gns_cm_view *v, const uint32_t *val, const uint32_t *fp, uint32_t thr, uint8_t *flows,
+                          uint32_t *vals, uint64_t *n_io, uint8_t *rows_dev = nullptr) {
+    gns_cm *cm = v->cm;
+    if (!view_detached(v)) return cm_heavy_one(cm, v->stream, v->rd, val, fp, thr, flows, vals, n_io, rows_dev);
+    return hh_heavy_list(v->rd.hh, v->stream, v->T, v->tab_cap, cm->K, (uint64_t)cm->g.d * cm->g.w, val, fp, thr, flows,
+                         vals, n_io, rows_dev);
+}
+
+// Buffers of a detached refresh (grow-only; under v->mu, on the ingest thread): mark /
+// remap words and the scan for `slots` dictionary slots, table rows for `rows` flows.
+// A table that grows also sizes the list's per-flow words here, so that no reader
+// allocates them while the handle ingests.
+static int view_reserve_detached(gns_cm_view *v, uint64_t slots, uint64_t rows, uint64_t scan_words) {
+    gns_cm *cm = v->cm;
+    if (!v->words) {
+        GNS_TRY(dalloc_t(&v->words, 4));
+        GNS_TRY(dalloc_t(&v->ctr, 3));
+    }
+    if (slots > v->remap_n || !v->remap) GNS_TRY(grow_buf(&v->remap, v->remap_n, slots));
+    if (scan_words > v->scan_n || !v->scan) GNS_TRY(grow_buf(&v->scan, v->scan_n, scan_words));
+    if (rows > v->tab_cap || !v->T.rec) {
+        const uint32_t RW = std::min<uint32_t>(cm->D.RW, 16);
+        uint64_t have = v->tab_cap * RW;
+        v->tab_cap = 0;
+        GNS_TRY(grow_buf(&v->T.rec, have, rows * RW));
+        v->tab_cap = have / RW;
+        v->T.RW = RW;
+        v->T.K = cm->K;
+        GNS_TRY(hh_reserve(v->rd.hh, (uint64_t)cm->g.d * cm->g.w, std::max(v->tab_cap, cm->dict_slots), cm->K, v->stream));
+    }
+    return GNS_OK;
 }
 
 int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
@@ -3578,6 +3805,13 @@ int gns_cm_view_create(gns_cm *cm, gns_cm_view **out) {
             (rc = dalloc_t(&v->Fs, cells)))
             break;
         if ((rc = v->init()) != GNS_OK) break;
+        if (hipHostMalloc(reinterpret_cast<void **>(&v->hsm), 64, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("view pinned words"); rc = GNS_E_HIP; break;
+        }
+        memset(v->hsm, 0, 64);
+        if ((rc = v->po.reserve(2 * kPinChunk)) != GNS_OK) break;
+        v->rd.q.pin = &v->po;  // host queries' keys and answers pass through the pinned staging
         if ((rc = hh_reserve(v->rd.hh, cells, cm->dict_slots, cm->K, v->stream)) != GNS_OK) break;
         if (hipStreamSynchronize(v->stream) != hipSuccess) { set_error("view sync"); rc = GNS_E_HIP; break; }
     } while (0);
@@ -3618,6 +3852,47 @@ int gns_cm_view_refresh(gns_cm_view *v) {
     GNS_HIP(hipMemcpyAsync(v->Fs, cm->Fs, bytes, hipMemcpyDeviceToDevice, cm->stream));
     GNS_TRY(v->publish(cm->stream));
     v->period = cm->period.load();
+    v->kind.store(kViewPlain);
+    return GNS_OK;
+}
+
+int gns_cm_view_refresh_at(gns_cm_view *v, uint32_t flags) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    if (flags & ~GNS_CM_VIEW_DETACH) { set_error("view refresh: unknown flags 0x%x", flags); return GNS_E_ARG; }
+    if (!(flags & GNS_CM_VIEW_DETACH)) return gns_cm_view_refresh(v);
+    gns_cm *cm = v->cm;
+    GNS_TRY(set_device(cm->device));
+    std::lock_guard<std::mutex> lk(v->mu);  // no reader is using the snapshot
+    const uint64_t cells = (uint64_t)cm->g.d * cm->g.w, slots = cm->dict_slots;
+    // the flows the buckets name are claimed slots, and at most two per cell
+    const uint64_t rows = std::max<uint64_t>(std::min<uint64_t>(cm->claimed, 2 * cells), 1);
+    const uint32_t nblk = (uint32_t)((slots + 255) / 256);
+    const uint32_t nb = (nblk + kCvBins - 1) / kCvBins, ngrp = (nb + kTGrp - 1) / kTGrp;
+    v->period = ~0u;  // not readable until the whole refresh is queued
+    GNS_TRY(view_reserve_detached(v, slots, rows, (uint64_t)nb * kCvBins + (uint64_t)ngrp * kCvBins + kCvBins));
+    uint32_t *cnt = v->scan, *part = cnt + (uint64_t)nb * kCvBins, *tot = part + (uint64_t)ngrp * kCvBins;
+    hipStream_t s = cm->stream;
+    const dim3 cgrid((unsigned)((cells + 256 * kCvItems - 1) / (256 * kCvItems)));
+    GNS_HIP(hipMemsetAsync(v->remap, 0, slots * 4, s));
+    GNS_HIP(hipMemsetAsync(v->words, 0, 8, s));
+    hipLaunchKernelGGL(k_cmv_mark, cgrid, dim3(256), 0, s, cm->Fc, cm->Fs, cells, slots, v->remap, v->words);
+    hipLaunchKernelGGL(k_cmv_count, dim3(nb * kCvBins), dim3(256), 0, s, v->remap, slots, nb, cnt);
+    hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kCvBins, part);
+    hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, s, part, ngrp, kCvBins, tot);
+    hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, s, tot, kCvBins, v->words + 1);
+    hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kCvBins, part, tot);
+    hipLaunchKernelGGL(k_cmv_gather, dim3(nblk), dim3(256), 0, s, cm->D, slots, v->remap, nb, cnt, v->T, v->tab_cap,
+                       v->words);
+    hipLaunchKernelGGL(k_cmv_remap, cgrid, dim3(256), 0, s, cm->Fc, cm->Fs, cells, slots, v->remap, v->Fc, v->Fs);
+    GNS_HIP(hipGetLastError());
+    GNS_HIP(hipMemcpyAsync(v->C, cm->C, cells * 4, hipMemcpyDeviceToDevice, s));
+    GNS_HIP(hipMemcpyAsync(v->S, cm->S, cells * 4, hipMemcpyDeviceToDevice, s));
+    GNS_HIP(hipMemcpyAsync(v->ctr, cm->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    // the snapshot is the state after every insert issued so far and before any later
+    // one; the view's stream waits for it
+    GNS_TRY(v->publish(s));
+    v->kind.store(kViewDetached);
+    v->period = cm->period.load();
     return GNS_OK;
 }
 
@@ -3628,9 +3903,71 @@ int gns_cm_view_heavy_hitters(gns_cm_view *v, uint8_t *count_flows, uint32_t *co
     GNS_TRY(set_device(cm->device));
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(view_check(v));
-    GNS_TRY(cm_heavy_one(cm, v->stream, v->rd, v->C, v->Fc, cm->ct, count_flows, counts, n_count));
-    GNS_TRY(cm_heavy_one(cm, v->stream, v->rd, v->S, v->Fs, cm->st, size_flows, sizes, n_size));
+    GNS_TRY(view_bad_fetch(v));  // read behind the first synchronization of the list
+    GNS_TRY(view_heavy_one(v, v->C, v->Fc, cm->ct, count_flows, counts, n_count));
+    GNS_TRY(view_bad_id(v));
+    GNS_TRY(view_heavy_one(v, v->S, v->Fs, cm->st, size_flows, sizes, n_size));
     return GNS_OK;
+}
+
+int gns_cm_view_heavy_rows(gns_cm_view *v, uint8_t *count_rows, uint64_t *n_count, uint8_t *size_rows,
+                           uint64_t *n_size) {
+    if (!v || !n_count || !n_size || (*n_count && !count_rows) || (*n_size && !size_rows)) {
+        set_error("null argument"); return GNS_E_ARG;
+    }
+    gns_cm *cm = v->cm;
+    GNS_TRY(set_device(cm->device));
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(view_check(v));
+    GNS_TRY(view_bad_fetch(v));
+    uint8_t dummy_c = 0, dummy_s = 0;  // a zero-capacity call only reports the lengths
+    GNS_TRY(view_heavy_one(v, v->C, v->Fc, cm->ct, nullptr, nullptr, n_count, count_rows ? count_rows : &dummy_c));
+    GNS_TRY(view_bad_id(v));
+    GNS_TRY(view_heavy_one(v, v->S, v->Fs, cm->st, nullptr, nullptr, n_size, size_rows ? size_rows : &dummy_s));
+    return GNS_OK;
+}
+
+int gns_cm_view_export_state(gns_cm_view *v, uint32_t *C, uint32_t *S, uint8_t *FPc, uint8_t *FPs, uint64_t *counters) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    gns_cm *cm = v->cm;
+    std::lock_guard<std::mutex> lk(v->mu);
+    GNS_TRY(view_check(v));
+    const bool det = view_detached(v);
+    if (counters && !det) {
+        set_error("view export: the last refresh was not detached, it carries no counters");
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(cm->device));
+    hipStream_t s = v->stream;
+    const uint64_t cells = (uint64_t)cm->g.d * cm->g.w;
+    GNS_TRY(view_bad_fetch(v));
+    if (counters) GNS_HIP(hipMemcpyAsync(v->hsm + 2, v->ctr, 24, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    GNS_TRY(view_bad_id(v));
+    if (counters) memcpy(counters, v->hsm + 2, 24);
+    GNS_TRY(v->po.reserve(2 * kPinChunk));
+    if (C) GNS_TRY(v->po.copy_out(C, v->C, cells * 4, s));
+    if (S) GNS_TRY(v->po.copy_out(S, v->S, cells * 4, s));
+    // fingerprints: ids -> key bytes, a piece at a time (GNS_ID_NONE -> zero bytes)
+    const DictDev &D = det ? v->T : cm->D;
+    if ((FPc || FPs) && cm->K) GNS_TRY(grow_buf(&v->xbytes, v->xbytes_n, std::min(cells, kCmvPiece) * cm->K));
+    for (int which = 0; which < 2 && cm->K; which++) {
+        uint8_t *dst = which ? FPs : FPc;
+        const uint32_t *ids = which ? v->Fs : v->Fc;
+        if (!dst) continue;
+        for (uint64_t off = 0; off < cells; off += kCmvPiece) {
+            const uint64_t m = std::min(kCmvPiece, cells - off);
+            GNS_TRY(hh_ids_to_dev_bytes(s, D, ids + off, m, v->xbytes));
+            GNS_TRY(v->po.copy_out(dst + off * cm->K, v->xbytes, m * cm->K, s));  // complete on return
+        }
+    }
+    return GNS_OK;
+}
+
+int gns_cm_view_query_device(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out) {
+    if (!v) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(v->mu);
+    return cm_query_impl(v->cm, v->stream, v->rd, v->C, v->Fc, v->S, v->Fs, keys, stride, n, out, true, v);
 }
 
 int gns_cm_view_query(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out) {
@@ -3643,7 +3980,8 @@ int gns_cm_reset(gns_cm *cm) {
     if (!cm) return GNS_E_ARG;
     GNS_TRY(set_device(cm->device));
     // a view call that passed its period check still reads the dictionary: wait
-    // for it before the dictionary is cleared (views answer GNS_E_ARG afterwards)
+    // for it before the dictionary is cleared (plain views answer GNS_E_ARG afterwards;
+    // a detached snapshot reads nothing of the handle: it is neither waited for nor staled)
     ViewsQuiesced q(cm);
     cm->period.fetch_add(1);
     GNS_TRY(cm_reset_state(cm));

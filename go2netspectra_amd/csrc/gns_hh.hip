@@ -296,6 +296,13 @@ int hh_ids_to_host_bytes(HhScratch &sc, hipStream_t st, const DictDev &D, const 
     return GNS_OK;
 }
 
+int hh_ids_to_dev_bytes(hipStream_t st, const DictDev &D, const uint32_t *d_ids, uint64_t n, uint8_t *d_out) {
+    if (n == 0 || D.K == 0) return GNS_OK;
+    hipLaunchKernelGGL(k_ids_to_bytes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_ids, n, D, d_out);
+    GNS_HIP(hipGetLastError());
+    return GNS_OK;
+}
+
 // HeavyHitters (count_min.go:178-247): a flow's max over its buckets reaches the
 // threshold iff one of its buckets does, so only cells >= threshold are
 // candidates; dedupe by fingerprint keeping the max; sort value desc.

@@ -61,6 +61,8 @@ int hh_heavy_list(HhScratch &sc, hipStream_t st, const DictDev &D, uint64_t dict
 // flow ids -> key bytes in host memory (GNS_ID_NONE -> zero bytes, the reference's reset FP)
 int hh_ids_to_host_bytes(HhScratch &sc, hipStream_t st, const DictDev &D, const uint32_t *d_ids, uint64_t n,
                          uint8_t *host);
+// the same into device memory (n * D.K bytes), enqueued on st: a view's chunked export
+int hh_ids_to_dev_bytes(hipStream_t st, const DictDev &D, const uint32_t *d_ids, uint64_t n, uint8_t *d_out);
 // The canonical order (value desc, flow bytes asc) of n packed device rows [flow (K) | u32
 // value] -> out_rows (device, not `rows`), with the caller's scratch on stream st: enqueued,
 // no copy to the host, the stream is not synchronized at the end (gns_hh_order_rows is this

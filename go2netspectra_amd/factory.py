@@ -111,13 +111,17 @@ class Manager:
         ExactView): the read side of the snapshotter / alerter thread."""
         return [t.view() for t in self.tasks()]
 
-    def refresh_views(self, views, state: bool = False) -> None:
+    def refresh_views(self, views, state: bool = False, detach: bool = False) -> None:
         """Ingest side: refresh every view at this point of the stream (asynchronous).
-        state=True: the SuperSpread views also capture what a checkpoint needs."""
-        from .sketch import SuperSpreadView
+        state=True: the SuperSpread views also capture what a checkpoint needs.
+        detach=True: the Count-Min views take detached snapshots, which stay readable
+        across reset_all() and can be checkpointed (save_from)."""
+        from .sketch import CountMinView, SuperSpreadView
         for v in views:
             if isinstance(v, SuperSpreadView):
                 v.refresh(state=state)
+            elif isinstance(v, CountMinView):
+                v.refresh(detach=detach)
             else:
                 v.refresh()
 

@@ -130,21 +130,51 @@ def _cm_heavy_record(arrays, key_bytes) -> "HeavyRecord":
                        Count=[HeavyCount(bytes(cf[i, :kb]), int(cv[i])) for i in range(len(cv))])
 
 
+def _cm_heavy_rows_device(fn, h, key_bytes, device):
+    """gns_cm_heavy_rows / gns_cm_view_heavy_rows -> two DEVICE tensors of packed rows
+    [flow | u32 value] (count list, size list; uint8 [n, key_bytes + 4]) in canonical order."""
+    import torch
+    dev = torch.device("cuda", device)
+    W = key_bytes + 4
+    nc, ns = ct.c_uint64(0), ct.c_uint64(0)
+    check(fn(h, None, ct.byref(nc), None, ct.byref(ns)))
+    while True:
+        cr = torch.empty((max(nc.value, 1), W), dtype=torch.uint8, device=dev)
+        sr = torch.empty((max(ns.value, 1), W), dtype=torch.uint8, device=dev)
+        c2, s2 = ct.c_uint64(cr.shape[0]), ct.c_uint64(sr.shape[0])
+        check(fn(h, cr.data_ptr(), ct.byref(c2), sr.data_ptr(), ct.byref(s2)))
+        if c2.value <= cr.shape[0] and s2.value <= sr.shape[0]:
+            return cr[: c2.value], sr[: s2.value]
+        nc, ns = c2, s2  # the lists changed between the calls (a view's refresh; kept for safety on a handle)
+
+
 class CountMinView:
     """Snapshot of a CountMin taken at a point of its insert stream (refresh()),
     queried from any thread while the handle keeps inserting: the read side of
     BASELINE configs[4] ("queries concurrent with ingest").  The reference's
     snapshotter reads live buckets under concurrent inserts (manager.go:139-159);
-    a view answers exactly what the handle would have answered at the refresh."""
+    a view answers exactly what the handle would have answered at the refresh.
+
+    A plain snapshot names flows by dictionary id: the handle's reset() and
+    import_state() stale it.  refresh(detach=True) resolves the flows into the view's
+    own key table instead: the snapshot then stays readable after reset(), reclaim(),
+    dictionary growth and import_state() until the next refresh (list a window's heavy
+    hitters on another thread while the handle already counts the next window), and it
+    carries the counters, i.e. a checkpoint (checkpoint.save(view, path))."""
 
     def __init__(self, cm: "CountMin"):
         self._L = cm._L
         self._cm = cm
         self.key_bytes = cm.key_bytes
+        self.width, self.depth, self.device = cm.width, cm.depth, cm.device
         self._hh_hint = [0, 0]
         h = ct.c_void_p()
         check(self._L.gns_cm_view_create(cm._h, ct.byref(h)))
         self._h = h
+
+    @property
+    def parent(self) -> "CountMin":
+        return self._cm
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -157,9 +187,13 @@ class CountMinView:
         except Exception:
             pass
 
-    def refresh(self) -> None:
-        """Ingest side: snapshot the state after every insert issued so far (asynchronous)."""
-        check(self._L.gns_cm_view_refresh(self._h))
+    def refresh(self, detach: bool = False) -> None:
+        """Ingest side: snapshot the state after every insert issued so far (asynchronous).
+        detach=True: a detached snapshot (gns_cm_view_refresh_at, GNS_CM_VIEW_DETACH)."""
+        if detach:
+            check(self._L.gns_cm_view_refresh_at(self._h, _lib.GNS_CM_VIEW_DETACH))
+        else:
+            check(self._L.gns_cm_view_refresh(self._h))
 
     def heavy_hitters_arrays(self):
         return _cm_heavy_arrays(self._L.gns_cm_view_heavy_hitters, self._h, self.key_bytes, self._hh_hint)
@@ -167,7 +201,33 @@ class CountMinView:
     def heavy_hitters(self) -> "HeavyRecord":
         return _cm_heavy_record(self.heavy_hitters_arrays(), self.key_bytes)
 
-    def query_many(self, keys) -> np.ndarray:
+    def heavy_hitters_rows_device(self):
+        """CountMin.heavy_hitters_rows_device at the refresh: (count rows, size rows) on the device."""
+        return _cm_heavy_rows_device(self._L.gns_cm_view_heavy_rows, self._h, self.key_bytes, self.device)
+
+    def export_state(self):
+        """(C, S, FPc, FPs) as CountMin.export_state at the refresh."""
+        n = self.depth * self.width
+        K = max(self.key_bytes, 1)
+        C = np.empty(n, np.uint32)
+        S = np.empty(n, np.uint32)
+        Fc = np.zeros((n, K), np.uint8)
+        Fs = np.zeros((n, K), np.uint8)
+        check(self._L.gns_cm_view_export_state(self._h, C.ctypes.data, S.ctypes.data, Fc.ctypes.data, Fs.ctypes.data,
+                                               None))
+        return C, S, Fc[:, : self.key_bytes], Fs[:, : self.key_bytes]
+
+    def counters(self) -> dict:
+        """inserted / dropped / unsupported at the refresh (a detached snapshot only)."""
+        cnt = (ct.c_uint64 * 3)()
+        check(self._L.gns_cm_view_export_state(self._h, None, None, None, None, cnt))
+        return {"inserted": int(cnt[0]), "dropped": int(cnt[1]), "unsupported": int(cnt[2])}
+
+    def query_many(self, keys):
+        """CountMin.query_many at the refresh (numpy in -> numpy out, device tensor in ->
+        device int64 tensor out)."""
+        if _lib.is_device(keys):
+            return _lib.query_device(self._L.gns_cm_view_query_device, self._h, keys)
         keys = _host(keys, np.uint8)
         n = keys.shape[0]
         out = np.zeros(n, dtype=np.uint64)
@@ -310,19 +370,7 @@ class CountMin:
         """HeavyHitters as two DEVICE tensors of packed rows [flow | u32 value] (count list,
         size list; uint8 [n, key_bytes + 4]) in canonical order: the multi-GPU window exchange
         all-gathers them and merges on the device (dist.allgather_heavy_rows)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        W = self.key_bytes + 4
-        nc, ns = ct.c_uint64(0), ct.c_uint64(0)
-        check(self._L.gns_cm_heavy_rows(self._h, None, ct.byref(nc), None, ct.byref(ns)))
-        while True:
-            cr = torch.empty((max(nc.value, 1), W), dtype=torch.uint8, device=dev)
-            sr = torch.empty((max(ns.value, 1), W), dtype=torch.uint8, device=dev)
-            c2, s2 = ct.c_uint64(cr.shape[0]), ct.c_uint64(sr.shape[0])
-            check(self._L.gns_cm_heavy_rows(self._h, cr.data_ptr(), ct.byref(c2), sr.data_ptr(), ct.byref(s2)))
-            if c2.value <= cr.shape[0] and s2.value <= sr.shape[0]:
-                return cr[: c2.value], sr[: s2.value]
-            nc, ns = c2, s2  # the lists changed between the calls (cannot on one handle; kept for safety)
+        return _cm_heavy_rows_device(self._L.gns_cm_heavy_rows, self._h, self.key_bytes, self.device)
 
     def view(self) -> "CountMinView":
         """A snapshot view whose heavy hitters / queries run concurrently with

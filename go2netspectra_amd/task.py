@@ -162,8 +162,9 @@ class SketchTask:
         return view.heavy_hitters()
 
     def save_from(self, view, path) -> None:
-        """save() from a SuperSpreadView refreshed with state=True: the checkpoint of the
-        refresh point, written while the task keeps ingesting."""
+        """save() from a SuperSpreadView refreshed with state=True, or from a CountMinView
+        refreshed with detach=True: the checkpoint of the refresh point, written while the
+        task keeps ingesting."""
         from . import checkpoint
         checkpoint.save(view, path)
 

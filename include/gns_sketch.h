@@ -259,6 +259,60 @@ int gns_cm_view_heavy_hitters(gns_cm_view *v, uint8_t *count_flows, uint32_t *co
                               uint8_t *size_flows, uint32_t *sizes, uint64_t *n_size);
 int gns_cm_view_query(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out);
 
+/* Detached snapshot: gns_cm_view_refresh_at(v, GNS_CM_VIEW_DETACH) resolves what
+ * the view needs out of the flow dictionary at the refresh, so that afterwards
+ * nothing in the view points into the handle (the reference's resetter runs
+ * independently of its snapshotter, manager.go:161-193 against :116-159: list a
+ * window's heavy hitters from another thread while the handle has already been
+ * reset and counts the next window).  flags == 0 is gns_cm_view_refresh.
+ *   - Refresh.  An ingest-side call like gns_cm_view_refresh, everything enqueued
+ *     on the handle's stream, no host synchronization: every flow id a bucket
+ *     names is marked (one word per dictionary slot), the marked slots are counted
+ *     and scanned into dense indices in slot order, their records {tag, key words}
+ *     are gathered into the view's compact key table (row `dense`), and the view's
+ *     fingerprint arrays hold dense indices instead of slots (GNS_ID_NONE kept).
+ *     The counters and the handle's counters [0..2] are copied with them.  The
+ *     view's buffers are grow-only and sized from host-known bounds: the
+ *     dictionary's slots for the mark / remap words, the claimed slots (at most
+ *     2*depth*width) for the table.  A refresh that outgrows them allocates (and
+ *     frees, which synchronizes the device); any other refresh allocates nothing.
+ *     It takes the view's mutex, so it waits for a reader call in progress.
+ *   - Readers.  gns_cm_view_heavy_hitters, gns_cm_view_query and the three calls
+ *     below run on the view's own stream with its own grow-only scratch and pinned
+ *     staging.  On a detached snapshot they read no handle state: a fingerprint
+ *     matches a key iff the cell's dense id is not GNS_ID_NONE and the table row's
+ *     key words equal the key's (an empty cell never matches, the all-zero key
+ *     included).  Every answer is what the handle's call would have answered at
+ *     the refresh: gns_cm_view_query[_device] = gns_cm_query[_device];
+ *     gns_cm_view_heavy_hitters = gns_cm_heavy_hitters (canonical order, capacity
+ *     rule); gns_cm_view_heavy_rows = gns_cm_heavy_rows (packed DEVICE rows; a
+ *     list longer than *n is reported and not written; a NULL array with *n == 0
+ *     asks for the length); gns_cm_view_export_state = gns_cm_export_state plus
+ *     gns_cm_counters' [0..2].  On a plain snapshot the three calls go through the
+ *     live dictionary and obey the stale rule above; `counters` of a plain
+ *     snapshot is GNS_E_ARG before any device call.  Null outputs are skipped.
+ *   - Lifetime.  A detached snapshot is NOT staled by gns_cm_reset,
+ *     gns_cm_reclaim, dictionary growth or gns_cm_import_state: it answers the
+ *     refresh-point state until the next refresh, and those calls do not wait for
+ *     a reader call in progress on it.  A reclaim neither remaps it nor keeps the
+ *     flows alive that only it names.  A plain refresh of the same view brings
+ *     back the plain behaviour exactly.  Several views of one handle are
+ *     independent.
+ *   - Errors.  A null view, a null out (n > 0), a null n_count / n_size and
+ *     stride < key_bytes are GNS_E_ARG before any device call; so are unknown
+ *     flags.  A bucket whose id named no dictionary slot at the refresh (corrupt
+ *     state) is not dereferenced; the next reader call answers GNS_E_HIP.
+ * Memory of a detached snapshot: the plain 16 bytes per bucket, 4 bytes per
+ * dictionary slot, one 64-byte record row (16 bytes for keys up to 12 bytes) per
+ * live flow, and the scan's words (about 4 bytes per 256 slots). */
+#define GNS_CM_VIEW_DETACH 1u
+int gns_cm_view_refresh_at(gns_cm_view *v, uint32_t flags);
+int gns_cm_view_query_device(gns_cm_view *v, const uint8_t *keys, uint32_t stride, uint64_t n, uint64_t *out);
+int gns_cm_view_heavy_rows(gns_cm_view *v, uint8_t *count_rows, uint64_t *n_count, uint8_t *size_rows,
+                           uint64_t *n_size);
+int gns_cm_view_export_state(gns_cm_view *v, uint32_t *C, uint32_t *S, uint8_t *FPc, uint8_t *FPs,
+                             uint64_t *counters /* [3] */);
+
 /* ------------------------------------------------------------------ */
 /* SuperSpread (super_spread.go)                                      */
 /* ------------------------------------------------------------------ */

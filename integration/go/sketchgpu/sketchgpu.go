@@ -460,6 +460,49 @@ func (w *View) Query(flow []byte) uint64 {
 	return uint64(out)
 }
 
+// RefreshDetached snapshots like Refresh, and resolves the flows the buckets name into the
+// view's own key table (gns_cm_view_refresh_at, GNS_CM_VIEW_DETACH): the snapshot then stays
+// readable after the sketch's Reset, ImportState and dictionary reclaim until the next
+// refresh -- the resetter is independent of the snapshotter (manager.go:161-193) -- and
+// carries the counters for ExportState.  Owner goroutine only.
+func (w *View) RefreshDetached() error {
+	return lastErr(C.gns_cm_view_refresh_at(w.v, C.GNS_CM_VIEW_DETACH))
+}
+
+// QueryDevice answers n device-resident keys into device memory (gns_cm_view_query_device).
+func (w *View) QueryDevice(keys unsafe.Pointer, stride uint32, n uint64, out unsafe.Pointer) error {
+	return lastErr(C.gns_cm_view_query_device(w.v, (*C.uint8_t)(keys), C.uint32_t(stride), C.uint64_t(n),
+		(*C.uint64_t)(out)))
+}
+
+// HeavyRows writes the two lists as packed device rows [flow | u32] (capacities capCount,
+// capSize); it returns the full lengths, and writes no list that exceeds its capacity.
+func (w *View) HeavyRows(countRows unsafe.Pointer, capCount uint64, sizeRows unsafe.Pointer,
+	capSize uint64) (uint64, uint64, error) {
+	nc, ns := C.uint64_t(capCount), C.uint64_t(capSize)
+	err := lastErr(C.gns_cm_view_heavy_rows(w.v, (*C.uint8_t)(countRows), &nc, (*C.uint8_t)(sizeRows), &ns))
+	return uint64(nc), uint64(ns), err
+}
+
+// ExportState returns the arrays CountMin.ImportState takes, as of the last refresh; cells =
+// depth*width as given to NewCountMin (defaults resolved).  The counters need the last
+// refresh to be RefreshDetached; withCounters false leaves them zero and works on either kind.
+func (w *View) ExportState(cells int, withCounters bool) (cnt, size []uint32, fpc, fps []byte,
+	counters [3]uint64, err error) {
+	cnt = make([]uint32, cells+1)
+	size = make([]uint32, cells+1)
+	fpc = make([]byte, cells*w.keyBytes+1)
+	fps = make([]byte, cells*w.keyBytes+1)
+	var cp *C.uint64_t
+	if withCounters {
+		cp = (*C.uint64_t)(unsafe.Pointer(&counters[0]))
+	}
+	err = lastErr(C.gns_cm_view_export_state(w.v, (*C.uint32_t)(unsafe.Pointer(&cnt[0])),
+		(*C.uint32_t)(unsafe.Pointer(&size[0])), (*C.uint8_t)(unsafe.Pointer(&fpc[0])),
+		(*C.uint8_t)(unsafe.Pointer(&fps[0])), cp))
+	return cnt[:cells], size[:cells], fpc[:cells*w.keyBytes], fps[:cells*w.keyBytes], counters, err
+}
+
 // Close releases the snapshot (before the CountMin it views).
 func (w *View) Close() { C.gns_cm_view_destroy(w.v) }
 
