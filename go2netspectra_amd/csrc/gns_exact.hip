@@ -1320,6 +1320,161 @@ __global__ __launch_bounds__(256) void k_ex_merge_times(const uint32_t *ids, uin
     if (f.last[id] == base + i + 1) f.end[id] = end[i];
 }
 
+// ---------------------------------------------------------------------------
+// Roll-up (gns_ex_rollup): the flows of a source table projected onto the key
+// layout of another handle and merged there group by group.  The reference
+// answers a coarser question with one task per key layout, every task fed every
+// packet (manager.go:232-244), or with GROUP BY over stored rows
+// (querier.go:251-319); here the coarser table is derived from the resident one.
+// Per piece of source slots:
+//   R1 k_exr_project  occupied slot -> dense row {projected key, pkts, bytes,
+//                     first, last, start, end} (wave ballot, one atomic per wave)
+//   R2 dict_resolve_keys on the destination (merge's growth-and-retry loop)
+//   R3 k_exr_add      counts add, first / last = min / max of the positions
+//                     mapped behind the destination's stream end
+//   R4 k_exr_times    the row that holds a group's first / last position gives
+//                     it its start / end
+// first / last are monotone under R3 across pieces, so a later piece with a
+// smaller first overwrites start and one with a larger first writes nothing;
+// positions are unique per record across flows, so no two rows of a group tie.
+// ---------------------------------------------------------------------------
+struct ExrPlan {
+    uint32_t K, KW;   // destination key bytes / words (a row's key takes KW words)
+    uint8_t g[40];    // source key byte of destination key byte j
+};
+struct ExrRows {
+    uint32_t *keys, *ids, *cnt;
+    unsigned long long *pkts, *bytes, *first, *last;
+    long long *start, *end;
+};
+
+// grid covers slots [s0, s1); at most s1 - s0 rows are appended (R.cnt zeroed by the host)
+__global__ __launch_bounds__(256) void k_exr_project(DictDev S, FlowState sf, uint64_t s0, uint64_t s1, ExrPlan pl,
+                                                     ExrRows R) {
+    // a lane's key words, read back byte by byte through the plan: each lane touches only
+    // its own column, so no barrier is needed and a wave without flows may leave
+    __shared__ uint32_t s_k[GNS_KWMAX][256];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint64_t s = s0 + (uint64_t)blockIdx.x * 256 + tid;
+    unsigned long long pk = 0;
+    uint32_t r[12];
+    bool occ = false;
+    if (s < s1) {
+        load_record(S, (uint32_t)s, r);
+        pk = sf.pkts[s];
+        occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
+    }
+    const uint64_t m = __ballot(occ);
+    if (m == 0) return;
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(R.cnt, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    if (!occ) return;
+    const uint64_t row = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if ((uint32_t)i >= pl.KW) break;  // uniform
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = 4 * i + b;
+            if ((uint32_t)j < pl.K) {
+                const uint32_t g = pl.g[j];  // uniform: a scalar load of the kernel argument
+                v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & 0xFFu) << (8 * b);
+            }
+        }
+        R.keys[row * pl.KW + i] = v;
+    }
+    R.pkts[row] = pk; R.bytes[row] = sf.bytes[s]; R.first[row] = sf.first[s]; R.last[row] = sf.last[s];
+    R.start[row] = sf.start[s]; R.end[row] = sf.end[s];
+}
+
+// R3.  A roll-up to a few groups would send every row's four atomics to a few addresses.
+// Rows of one id are combined before anything leaves the CU (as k_exq_aggregate): the ids
+// most lanes of a wave share are reduced across the wave, every id goes through a small LDS
+// table of the workgroup's partials, and the table leaves as one set of global atomics per id
+// and workgroup.  An id that finds no room in the table goes to global memory directly (many
+// groups: those atomics do not collide).  Integer add / min / max: bit-exact in any order.
+constexpr uint32_t kExrTabBits = 9, kExrTab = 1u << kExrTabBits;
+constexpr int kExrPeel = 6;  // wave reductions per row of 64: the ids of at least 4 lanes
+
+struct ExrLds {
+    uint32_t id[kExrTab];
+    unsigned long long pk[kExrTab], by[kExrTab], fi[kExrTab], la[kExrTab];
+};
+
+__device__ __forceinline__ void exr_merge(ExrLds &t, const FlowState &f, uint32_t id, unsigned long long pk,
+                                          unsigned long long by, unsigned long long fi, unsigned long long la) {
+    uint32_t h = (id * 0x9E3779B1u) >> (32 - kExrTabBits);
+    for (int p = 0; p < 4; p++) {
+        const uint32_t old = atomicCAS(&t.id[h], GNS_ID_NONE, id);
+        if (old == GNS_ID_NONE || old == id) {
+            atomicAdd(&t.pk[h], pk);
+            atomicAdd(&t.by[h], by);
+            atomicMin(&t.fi[h], fi);
+            atomicMax(&t.la[h], la);
+            return;
+        }
+        h = (h + 1u) & (kExrTab - 1u);
+    }
+    atomicAdd(&f.pkts[id], pk);
+    atomicAdd(&f.bytes[id], by);
+    atomicMin(&f.first[id], fi);
+    atomicMax(&f.last[id], la);
+}
+
+__global__ __launch_bounds__(256) void k_exr_add(ExrRows R, uint64_t n, unsigned long long B, FlowState f) {
+    __shared__ ExrLds t;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t i = tid; i < kExrTab; i += 256) { t.id[i] = GNS_ID_NONE; t.pk[i] = 0; t.by[i] = 0; t.fi[i] = ~0ull; t.la[i] = 0; }
+    __syncthreads();
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < n; i0 += (uint64_t)gridDim.x * 256) {  // block-uniform
+        const uint64_t i = i0 + tid;
+        uint32_t id = GNS_ID_NONE;
+        unsigned long long pk = 0, by = 0, fi = ~0ull, la = 0;
+        if (i < n) id = R.ids[i];
+        bool pending = id != GNS_ID_NONE;
+        if (pending) { pk = R.pkts[i]; by = R.bytes[i]; fi = B + R.first[i]; la = B + R.last[i]; }
+        uint64_t todo = __ballot(pending);
+        for (int round = 0; round < kExrPeel && todo; round++) {  // wave-uniform
+            const int lead = __ffsll((unsigned long long)todo) - 1;
+            const uint32_t lid = (uint32_t)__shfl((int)id, lead);
+            const bool in = pending && id == lid;
+            const uint64_t same = __ballot(in);
+            todo &= ~same;
+            if (__popcll(same) < 4) continue;  // these lanes merge their own rows below
+            const unsigned long long tp = __ockl_wfred_add_u64(in ? pk : 0ull);
+            const unsigned long long tb = __ockl_wfred_add_u64(in ? by : 0ull);
+            const unsigned long long tf = __ockl_wfred_min_u64(in ? fi : ~0ull);
+            const unsigned long long tl = __ockl_wfred_max_u64(in ? la : 0ull);
+            if ((int)lane == lead) exr_merge(t, f, lid, tp, tb, tf, tl);
+            pending = pending && !in;
+        }
+        if (pending) exr_merge(t, f, id, pk, by, fi, la);
+    }
+    __syncthreads();
+    for (uint32_t h = tid; h < kExrTab; h += 256) {
+        const uint32_t id = t.id[h];
+        if (id == GNS_ID_NONE) continue;
+        atomicAdd(&f.pkts[id], t.pk[h]);
+        atomicAdd(&f.bytes[id], t.by[h]);
+        atomicMin(&f.first[id], t.fi[h]);
+        atomicMax(&f.last[id], t.la[h]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_exr_times(ExrRows R, uint64_t n, unsigned long long B, FlowState f) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = R.ids[i];
+    if (id == GNS_ID_NONE) return;
+    if (f.first[id] == B + R.first[i]) f.start[id] = R.start[i];
+    if (f.last[id] == B + R.last[i]) f.end[id] = R.end[i];
+}
+
 }  // namespace gns
 
 using namespace gns;
@@ -2337,6 +2492,122 @@ int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const
     if (rc != GNS_OK) (void)hipStreamSynchronize(s);
     dfree(ids);
     sc.free_all();
+    return rc;
+}
+
+namespace {
+
+// the key field tuple byte t belongs to (make_plan's numbering)
+const char *exr_field_name(uint32_t t) {
+    return t < 16 ? "SrcIP" : t < 32 ? "DstIP" : t < 34 ? "SrcPort" : t < 36 ? "DstPort" : "Protocol";
+}
+
+// Byte gather between two layouts: every byte of dst's key from the first place src's key
+// holds it.  GNS_E_ARG when a field of dst is not part of src.
+int exr_make_plan(const KeyPlanN &src, const KeyPlanN &dst, ExrPlan *pl) {
+    memset(pl, 0, sizeof(*pl));
+    pl->K = dst.K;
+    pl->KW = (dst.K + 3) / 4;
+    for (uint32_t j = 0; j < dst.K; j++) {
+        uint32_t i = 0;
+        while (i < src.K && src.src[i] != dst.src[j]) i++;
+        if (i == src.K) {
+            set_error("rollup: key field %s is not part of the source's layout", exr_field_name(dst.src[j]));
+            return GNS_E_ARG;
+        }
+        pl->g[j] = (uint8_t)i;
+    }
+    return GNS_OK;
+}
+
+void exr_free(ExrRows &R) {
+    dfree(R.keys); dfree(R.ids); dfree(R.cnt); dfree(R.pkts); dfree(R.bytes); dfree(R.first); dfree(R.last);
+    dfree(R.start); dfree(R.end);
+    R = ExrRows{};
+}
+
+}  // namespace
+
+int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    if (dst == src) { set_error("rollup: dst and src are the same handle"); return GNS_E_ARG; }
+    if (dst->device != src->device) {
+        set_error("rollup: dst is on device %d, src on device %d", dst->device, src->device);
+        return GNS_E_ARG;
+    }
+    ExrPlan pl;
+    GNS_TRY(exr_make_plan(src->kp, dst->kp, &pl));
+    GNS_TRY(set_device(dst->device));
+    uint64_t piece = kResolvePiece;
+    if (const char *env = getenv("GNS_EX_ROLLUP_PIECE")) {  // tests: small tables span many pieces
+        const unsigned long long v = strtoull(env, nullptr, 10);
+        if (v) piece = std::min<uint64_t>(v, kResolvePiece);
+    }
+    piece = std::min<uint64_t>(piece, src->slots);
+    if (out) out[0] = out[1] = 0;
+    hipStream_t s = dst->stream;
+    ExrRows R{};
+    KeyResolveScratch sc;
+    hipEvent_t ev = nullptr;
+    uint64_t projected = 0, added = 0;
+    bool wrote = false;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = dalloc_t(&R.keys, piece * pl.KW)) || (rc = dalloc_t(&R.ids, piece)) || (rc = dalloc_t(&R.cnt, 4)) ||
+            (rc = dalloc_t(&R.pkts, piece)) || (rc = dalloc_t(&R.bytes, piece)) || (rc = dalloc_t(&R.first, piece)) ||
+            (rc = dalloc_t(&R.last, piece)) || (rc = dalloc_t(&R.start, piece)) || (rc = dalloc_t(&R.end, piece)))
+            return rc;
+        // after src's pending batches
+        GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        GNS_HIP(hipEventRecord(ev, src->stream));
+        GNS_HIP(hipStreamWaitEvent(s, ev, 0));
+        const unsigned long long B = dst->pkt + dst->merged;  // source positions lie behind dst's stream end
+        for (uint64_t s0 = 0; s0 < src->slots; s0 += piece) {
+            const uint64_t s1 = std::min<uint64_t>(s0 + piece, src->slots);
+            GNS_HIP(hipMemsetAsync(R.cnt, 0, 4, s));
+            hipLaunchKernelGGL(k_exr_project, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D, src->f, s0,
+                               s1, pl, R);
+            GNS_HIP(hipGetLastError());
+            GNS_HIP(hipMemcpyAsync(dst->h_pin, R.cnt, 4, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipStreamSynchronize(s));
+            const uint64_t m = std::min<uint64_t>(dst->h_pin[0], s1 - s0);
+            if (m == 0) continue;
+            if (dst->claimed >= dst->slots / 2) GNS_TRY(ex_grow(dst));  // keep the load <= ~1/2
+            KeyResolve r{};
+            r.keys = reinterpret_cast<const uint8_t *>(R.keys); r.stride = 4 * pl.KW; r.n = m; r.live = KEYS_VAL64;
+            r.vals = R.pkts; r.ids = R.ids;
+            r.full_word = dst->stats + 3;
+            uint64_t before;
+            for (;;) {  // no state is written before every id of the piece is known
+                before = dst->claimed;
+                const int rc2 = dict_resolve_keys(dst->D, dst->epoch, r, sc, s, &dst->claimed, &dst->timer, 1);
+                if (rc2 != GNS_E_FULL) { GNS_TRY(rc2); break; }
+                GNS_HIP(hipMemsetAsync(dst->stats + 3, 0, sizeof(unsigned long long), s));
+                dst->n_retry++;
+                GNS_TRY(ex_grow(dst));  // the state earlier pieces wrote follows the table; this piece's claims are dropped
+            }
+            added += dst->claimed - before;
+            wrote = true;
+            hipLaunchKernelGGL(k_exr_add, dim3((unsigned)std::min<uint64_t>((m + 255) / 256, 1024)), dim3(256), 0, s, R, m,
+                               B, dst->f);
+            hipLaunchKernelGGL(k_exr_times, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, R, m, B, dst->f);
+            GNS_HIP(hipGetLastError());
+            projected += m;
+        }
+        return GNS_OK;
+    };
+    int rc = run();
+    if (rc == GNS_OK || wrote) {
+        // the positions handed out are spent, whatever happened after the first piece
+        dst->merged += src->pkt + src->merged;
+        const int rc2 = ex_hot_clear(dst);  // the next batch re-picks the designated flows
+        if (rc == GNS_OK) rc = rc2;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == GNS_OK) { set_error("rollup: stream synchronize failed"); rc = GNS_E_HIP; }
+    if (ev) (void)hipEventDestroy(ev);
+    exr_free(R);
+    sc.free_all();
+    if (rc == GNS_OK && out) { out[0] = projected; out[1] = added; }
     return rc;
 }
 

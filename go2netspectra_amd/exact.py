@@ -255,6 +255,28 @@ def apply_delta(state: dict, arrays) -> dict:
     return out
 
 
+def rollup_plan(src_fields: Sequence[str], dst_fields: Sequence[str]) -> List[int]:
+    """The byte gather of a roll-up, as gns_ex_rollup builds it: for every byte of the key laid
+    out by ``dst_fields``, the offset of that byte in the key laid out by ``src_fields`` (a
+    field repeated in src is read at its first occurrence, one repeated in dst is copied once
+    per occurrence).  ValueError when a field of dst is not part of src: GNS_E_ARG in C."""
+    at, off = {}, 0
+    for f in src_fields:
+        size = _lib.FIELD_SIZE.get(f, 0)  # unknown names contribute no bytes (task.go:335-336)
+        if size:
+            at.setdefault(f, off)
+        off += size
+    plan: List[int] = []
+    for f in dst_fields:
+        size = _lib.FIELD_SIZE.get(f, 0)
+        if size == 0:
+            continue
+        if f not in at:
+            raise ValueError(f"rollup: key field {f} is not part of the source's layout")
+        plan.extend(range(at[f], at[f] + size))
+    return plan
+
+
 class ExactView:
     """Snapshot view of an ExactAggregator (gns_ex_view_*): a dense copy of the table, or of
     the flows touched since a cursor, taken at a point of the insert stream (``refresh``) and
@@ -312,6 +334,7 @@ class ExactAggregator:
         self._L = _lib.load()
         self.key_fields = list(key_fields)
         self.key_bytes = sum(_lib.FIELD_SIZE.get(f, 0) for f in self.key_fields)
+        self.device = device
         p = _lib.ExParams()
         p.key = _lib.Layout.of(self.key_fields)
         p.max_flows, p.batch_packets, p.device = max_flows, batch_packets, device
@@ -435,6 +458,34 @@ class ExactAggregator:
         if n:
             check(self._L.gns_ex_merge(self._h, *[_ptr(a) for a in arrs], n, where))
 
+    def rollup_from(self, src: "ExactAggregator"):
+        """gns_ex_rollup: re-key the flows of ``src`` onto this handle's layout, on the device.
+        The flows that share one projected key enter as one pseudo-record under the rule of
+        ``merge``: summed counts, the start of the constituent earliest and the end of the one
+        latest in src's stream.  Into an empty handle the result equals an aggregator of this
+        layout fed src's packets.  src is only read.  Returns (flows of src projected, flows
+        new in this handle)."""
+        if not isinstance(src, ExactAggregator):
+            raise TypeError("rollup_from takes an ExactAggregator")
+        if src is not self:  # (dst is src: GNS_E_ARG from the library)
+            rollup_plan(src.key_fields, self.key_fields)
+        out = (ct.c_uint64 * 2)()
+        check(self._L.gns_ex_rollup(self._h, src._h, out))
+        return int(out[0]), int(out[1])
+
+    def rollup(self, key_fields: Sequence[str], **kw) -> "ExactAggregator":
+        """A new aggregator on the same device keyed on ``key_fields`` (fields of this handle's
+        layout, in any order) and filled by ``rollup_from(self)``; ``kw`` as the constructor's."""
+        rollup_plan(self.key_fields, key_fields)
+        kw.setdefault("device", self.device)
+        dst = ExactAggregator(key_fields, **kw)
+        try:
+            dst.rollup_from(self)
+        except Exception:
+            dst.close()
+            raise
+        return dst
+
     def aggregate(self, filters) -> List[Summary]:
         """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
         arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
@@ -497,13 +548,14 @@ class ExactTask:
     """model.Task of the exact aggregator (exact/task.go)."""
 
     def __init__(self, name: str, key_fields: Sequence[str], num_shards: int = 0, device: int = 0,
-                 max_flows: int = 0, batch_packets: int = 0):
+                 max_flows: int = 0, batch_packets: int = 0, agg: Optional[ExactAggregator] = None):
         if num_shards == 0 or num_shards >= 32768:  # task.go:85-87
             num_shards = DEFAULT_SHARDS
         self.name_ = name
         self.key_fields = list(key_fields)
         self.shard_count = num_shards
-        self.agg = ExactAggregator(self.key_fields, max_flows=max_flows, batch_packets=batch_packets, device=device)
+        self.agg = agg if agg is not None else ExactAggregator(self.key_fields, max_flows=max_flows,
+                                                               batch_packets=batch_packets, device=device)
 
     def name(self) -> str:
         return self.name_
@@ -566,6 +618,13 @@ class ExactTask:
         view.refresh(), the interval's changed flows after view.refresh(cursor).  May run on
         another thread while the task keeps ingesting."""
         return self.snapshot(view.snapshot_arrays())
+
+    def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, **kw) -> "ExactTask":
+        """A full task keyed on ``key_fields`` (fields of this task's key, in any order) holding
+        this task's flows re-keyed on the device (ExactAggregator.rollup): what a task configured
+        with that key and fed the same packets holds.  It takes packets, queries, views and
+        checkpoints like any other task."""
+        return ExactTask(name, key_fields, num_shards, agg=self.agg.rollup(key_fields, **kw))
 
     def reset(self) -> None:
         self.agg.reset()

@@ -646,6 +646,50 @@ int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_n
  * flows exactly as ingested ones. */
 int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
                  const uint64_t *pkts, const uint64_t *bytes, uint64_t n, gns_mem where);
+/* Roll-up: re-key the flows of src onto dst's key layout, on the device.  The
+ * reference answers a coarser question ("bytes per source address") with one task
+ * per key layout, every task fed every packet (manager.go:232-244), or with GROUP BY
+ * over stored rows (querier.go:251-319); here the coarser table is derived from the
+ * resident one, after the traffic has arrived.
+ *   - Layouts.  Every field of dst's layout must occur in src's; dst's fields may be
+ *     fewer, equal or a permutation, in any order.  A field repeated in dst is copied
+ *     once per occurrence, from src's first occurrence.  Keys stay in the canonical
+ *     16-byte-IP form: the projection is a byte gather between the two layouts.
+ *   - What it does.  Every flow gns_ex_snapshot(src) would list at the call (after
+ *     src's pending batches) is projected onto dst's layout; the flows sharing one
+ *     projected key form a group, and each group enters dst under the rule of
+ *     gns_ex_merge as ONE pseudo-record: pkts and bytes are the group's sums (u64
+ *     wrap), start is the start of the constituent whose first packet is earliest in
+ *     src's stream, end the end of the one whose last packet is latest.  A key new to
+ *     dst takes both; a key already in dst keeps its start, takes the group's end, and
+ *     its counts add.  Consequence: a roll-up into an empty dst equals a handle of
+ *     dst's layout fed the same inserts and merges as src, in keys, start, end, pkts
+ *     and bytes -- with non-monotonic timestamps too, since start / end follow stream
+ *     order, not min / max.  With equal layouts it is the device-to-device union of
+ *     two shards.  (As in gns_ex_merge a flow exists iff it has packets: a group whose
+ *     packet sum wraps to exactly 0 is not a flow.)
+ *   - Positions.  src's stream positions are mapped behind dst's current stream end,
+ *     and dst's position then advances by src's stream length (records inserted + rows
+ *     merged since src was created): later inserts into dst come after every rolled-up
+ *     flow, a dst view cursor taken before the call selects exactly the groups, and
+ *     dst's per-flow positions stay exact, so dst can itself be a roll-up source.
+ *   - out (may be NULL): [0] source flows projected, [1] flows new in dst.
+ *   - Side effects.  src is read only: table, counters and cursors are unchanged.  Of
+ *     dst's gns_ex_counters only [4] flows moves; dst grows as for gns_ex_merge.  The
+ *     work runs in pieces of 2^20 source slots (GNS_EX_ROLLUP_PIECE in the
+ *     environment, read at the call, sets another piece size: for tests only, so that
+ *     small tables span many pieces); an error after the first piece (out of memory,
+ *     a table at its 2^30-slot limit) leaves dst with the pieces merged so far.
+ *   - Calling rules.  Synchronous, and an ingest-side call on BOTH handles: no other
+ *     thread may insert into src or dst during it.  The device work is ordered after
+ *     src's stream and runs on dst's.
+ *   - GNS_E_ARG, dst untouched: a null handle (before any device call), dst == src, a
+ *     field of dst that src's layout lacks, handles on different devices.  An empty
+ *     src is GNS_OK and moves no flows.
+ *   - Not offered: a view as source (view rows carry no stream positions, and adding
+ *     them would change the views' documented memory); a delta roll-up ("since": rows
+ *     are cumulative, so a delta is not additive); a distinct-flow count per group. */
+int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]);
 int gns_ex_reset(gns_ex *ex);
 /* out[8]: inserted, dropped, unsupported, dictionary full, flows, records, batches, 0 */
 int gns_ex_counters(gns_ex *ex, uint64_t out[8]);

@@ -967,6 +967,24 @@ func (e *Exact) Merge(keys []byte, start, end []int64, pkts, bytes []uint64) err
 		(*C.uint64_t)(unsafe.Pointer(&bytes[0])), C.uint64_t(n), C.GNS_MEM_HOST))
 }
 
+// RollupFrom re-keys the flows of src onto this table's key layout on the device
+// (gns_ex_rollup): the flows of src that share one projected key enter as one pseudo-record
+// under the rule of Merge, with the group's summed counts, the start of its earliest and the
+// end of its latest constituent in src's stream order.  Every field of this table's layout
+// must be part of src's.  Into an empty table the result equals a task keyed on this layout
+// and fed src's packets.  src is only read; neither table may take inserts during the call.
+// projected = flows of src, added = flows new in this table.
+func (e *Exact) RollupFrom(src *Exact) (projected, added uint64, err error) {
+	if src == nil {
+		return 0, 0, errors.New("sketchgpu: RollupFrom of a nil source")
+	}
+	var out [2]C.uint64_t
+	if err = lastErr(C.gns_ex_rollup(e.h, src.h, &out[0])); err != nil {
+		return 0, 0, err
+	}
+	return uint64(out[0]), uint64(out[1]), nil
+}
+
 // Reset is exact.Task.Reset (task.go:194-210).
 func (e *Exact) Reset() { C.gns_ex_reset(e.h) }
 
