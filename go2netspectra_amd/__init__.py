@@ -10,7 +10,8 @@ from . import checkpoint
 from ._lib import GnsError, build, load
 from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_config
 from .exact import (ExactAggregator, ExactTask, ExactView, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
-                    TaskSummary, apply_delta, make_filter, merge_summaries, rollup_plan)
+                    TaskSummary, apply_delta, make_filter, merge_summaries, rollup_plan, spread_rollup_plan,
+                    to16_to_encodeflow)
 from .factory import Manager, TaskGroup, create, register_aggregator
 from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
@@ -25,5 +26,5 @@ __all__ = [
     "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "apply_delta", "CompactBatch",
-    "SuperSpreadView", "rollup_plan",
+    "SuperSpreadView", "rollup_plan", "spread_rollup_plan", "to16_to_encodeflow",
 ]

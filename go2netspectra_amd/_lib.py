@@ -54,7 +54,7 @@ EXPORTED = [
     "gns_ss_view_create", "gns_ss_view_destroy", "gns_ss_view_refresh", "gns_ss_view_query",
     "gns_ss_view_query_device", "gns_ss_view_heavy_hitters", "gns_ss_view_heavy_rows", "gns_ss_view_export_state",
     "gns_cm_view_refresh_at", "gns_cm_view_query_device", "gns_cm_view_heavy_rows", "gns_cm_view_export_state",
-    "gns_ex_rollup",
+    "gns_ex_rollup", "gns_spread_rollup",
 ]
 
 
@@ -224,6 +224,7 @@ def load() -> ct.CDLL:
         "gns_ss_import_state": ([vp, vp, vp, vp, vp, u64, vp], i32),
         "gns_ex_merge": ([vp, vp, vp, vp, vp, vp, u64, i32], i32),
         "gns_ex_rollup": ([vp, vp, vp], i32),
+        "gns_spread_rollup": ([vp, vp, u64, vp, vp], i32),
         "gns_ex_view_create": ([vp, vp], i32), "gns_ex_view_destroy": ([vp], i32),
         "gns_ex_view_refresh": ([vp, u64, vp], i32),
         "gns_ex_view_snapshot": ([vp, vp, vp, vp, vp, vp, vp], i32),

@@ -49,6 +49,7 @@
 #include <rocprim/device/device_merge_sort.hpp>
 
 #include "gns_common.hpp"
+#include "gns_exsrc.hpp"
 #include "gns_scan.cuh"
 #include "gns_xcd.cuh"
 
@@ -1566,6 +1567,18 @@ struct gns_ex {
     QueryStage qs;         // host queries' keys and answers on the device
     StageTimer timer;
 };
+
+// the table as another engine's kernels may read it (gns_exsrc.hpp)
+void gns::ex_table_ref(const gns_ex *ex, ExTableRef *out) {
+    out->device = ex->device;
+    out->stream = ex->stream;
+    out->kp = ex->kp;
+    out->D = ex->D;
+    out->slots = ex->slots;
+    out->pkts = ex->f.pkts;
+    out->first = ex->f.first;
+    out->pos = ex->pkt + ex->merged;  // the next stream position (ex_run_batch, gns_ex_merge)
+}
 
 // A dense copy of the flows one refresh selected: records at stride RW and the four
 // exported state arrays, `cap` rows of room, the row count on the device (*total) until a

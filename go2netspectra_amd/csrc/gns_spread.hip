@@ -46,6 +46,13 @@
 // traffic; merge_from does both between two handles on the device.  Cursors are
 // generation << 32 | epoch; a reset and the epoch's wrap (k_exs_retag) start a
 // new generation.
+//
+// Spread roll-up (gns_spread_rollup, DESIGN.md §4e "Spread roll-up"): the distinct
+// (flow, element) pairs of a stream are the projection of its distinct flow keys
+// whenever both layouts are made of fields of an exact aggregator's key.
+// k_spr_project turns pieces of such an aggregator's table into staged pair rows --
+// IP fields from the aggregator's To16 form back to EncodeFlow form -- and the rows
+// enter through the merge mode of k_exs_pass.
 #include <cstdlib>
 #include <cstring>
 
@@ -56,6 +63,7 @@
 
 #include "gns_common.hpp"
 #include "gns_ctl.cuh"
+#include "gns_exsrc.hpp"
 #include "gns_hh.hpp"
 
 namespace gns {
@@ -356,6 +364,132 @@ __global__ __launch_bounds__(256) void k_exs_export(PairDev P, uint64_t beg, uin
             run += c;
         }
         if (live[it] && j < cap) pair_store_row<NW, LW, WORDS>(P, r[it], Kf, j, flows, elems);
+    }
+}
+
+// Spread roll-up, projection: the flows of slots [beg, end) of an exact aggregator's
+// table -- k_exr_project's occupancy rule (tag and pkts nonzero), first >= since -- as
+// pair rows appended behind the *count rows already staged.  Ranking and reservation
+// are k_exs_export's: kSprIt runs of 256 slots per workgroup, a ballot per wave and
+// run, ONE atomic per workgroup.  A selected lane copies its key words into its own
+// LDS column (no other lane touches it: no barrier), rewrites the IP fields the
+// layouts read from To16 to EncodeFlow form there, and gathers the flow row and the
+// element row byte by byte through the plan (copied into LDS once per workgroup),
+// each row into words of its own, so a split inside a word costs nothing.
+// Rows at or past cap are counted and not written.
+struct SprPlan {
+    uint32_t Kf, Ke;         // the destination's flow / element key bytes
+    uint32_t nip;            // IP fields of the source key that the layouts read
+    uint8_t ipoff[4];        // their byte offsets in the source key (first occurrences)
+    union {                  // source key byte of flow / element key byte j; as words for the copy into LDS
+        struct { uint8_t gf[40], ge[40]; };
+        uint32_t gw[20];
+    };
+};
+constexpr int kSprIt = 4;
+
+// ::ffff:a.b.c.d -> a.b.c.d + 12 zero bytes in the 16 key bytes at offset o (uniform) of the
+// lane's column; every other value stays
+__device__ __forceinline__ void spr_encode_ip(uint32_t (*s_k)[256], uint32_t tid, uint32_t o) {
+    if ((o & 3u) == 0u) {
+        const uint32_t w = o >> 2;
+        if (s_k[w][tid] == 0u && s_k[w + 1][tid] == 0u && s_k[w + 2][tid] == 0xFFFF0000u) {
+            s_k[w][tid] = s_k[w + 3][tid];
+            s_k[w + 1][tid] = 0u; s_k[w + 2][tid] = 0u; s_k[w + 3][tid] = 0u;
+        }
+    } else {
+        uint8_t *col = reinterpret_cast<uint8_t *>(&s_k[0][tid]);  // key byte b: word b / 4 of the column, byte b % 4
+        auto at = [&](uint32_t b) -> uint8_t & { return col[(size_t)(b >> 2) * (256 * 4) + (b & 3u)]; };
+        uint32_t z = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 10; k++) z |= at(o + k);
+        if (z == 0u && at(o + 10) == 0xFFu && at(o + 11) == 0xFFu) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) at(o + k) = at(o + 12 + k);
+#pragma unroll
+            for (uint32_t k = 4; k < 16; k++) at(o + k) = 0;
+        }
+    }
+}
+
+// WORDS: K is a multiple of 4 and the row word-aligned
+// g: the row's gather staged in LDS (one broadcast read per byte: as scalars the 74 plan bytes
+// of the widest layout, live across the unrolled runs, spilled 270 SGPRs)
+template <bool WORDS>
+__device__ __forceinline__ void spr_store_row(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *g_row, uint32_t K,
+                                              uint8_t *row) {
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if (4u * i >= K) break;  // uniform
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = 4 * i + b;
+            if ((uint32_t)j < K) {
+                const uint32_t g = g_row[j];
+                v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & 0xFFu) << (8 * b);
+            }
+        }
+        if constexpr (WORDS) {
+            reinterpret_cast<uint32_t *>(row)[i] = v;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if ((uint32_t)(4 * i + b) < K) row[4 * i + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
+template <bool WORDS>
+__global__ __launch_bounds__(256) void k_spr_project(DictDev S, const unsigned long long *pkts,
+                                                     const unsigned long long *first, uint64_t beg, uint64_t end,
+                                                     unsigned long long since, SprPlan pl, uint8_t *flows, uint8_t *elems,
+                                                     uint64_t cap, uint32_t *count) {
+    constexpr int IT = kSprIt;
+    __shared__ uint32_t s_k[GNS_KWMAX][256];
+    __shared__ uint32_t s_cnt[IT * 4], s_base;
+    __shared__ uint32_t s_gw[20];  // flow gather, then element gather
+    const uint8_t *s_g = reinterpret_cast<const uint8_t *>(s_gw);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t s0 = beg + (uint64_t)blockIdx.x * (256 * IT) + tid;
+    if (tid < 20) s_gw[tid] = pl.gw[tid];
+    uint64_t m[IT];
+    bool live[IT];
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        const uint64_t s = s0 + (uint64_t)it * 256;
+        live[it] = s < end && S.rec[s * S.RW] != 0u && pkts[s] != 0ull && first[s] >= since;
+        m[it] = __ballot(live[it]);
+        if (lane == 0) s_cnt[it * 4 + wave] = (uint32_t)__popcll(m[it]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (int k = 0; k < IT * 4; k++) tot += s_cnt[k];
+        s_base = tot ? atomicAdd(count, tot) : 0u;
+    }
+    __syncthreads();
+    uint64_t run = s_base;  // rows of the workgroup's (run, wave) cells before this lane's
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        uint64_t j = run + (uint32_t)__popcll(m[it] & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint32_t c = s_cnt[it * 4 + w];
+            if ((uint32_t)w < wave) j += c;
+            run += c;
+        }
+        if (!live[it] || j >= cap) continue;
+        uint32_t r[12];
+        load_record(S, (uint32_t)(s0 + (uint64_t)it * 256), r);
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+#pragma unroll
+        for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
+            if ((uint32_t)f < pl.nip) spr_encode_ip(s_k, tid, pl.ipoff[f]);
+        spr_store_row<WORDS>(s_k, tid, s_g, pl.Kf, flows + j * pl.Kf);
+        spr_store_row<WORDS>(s_k, tid, s_g + 40, pl.Ke, elems + j * pl.Ke);
     }
 }
 
@@ -752,6 +886,38 @@ int exs_read_count(gns_exs *h, uint64_t *out) {
     return GNS_OK;
 }
 
+// --- spread roll-up ----------------------------------------------------------
+// the key field tuple byte t belongs to (make_plan's numbering)
+const char *spr_field_name(uint32_t t) {
+    return t < 16 ? "SrcIP" : t < 32 ? "DstIP" : t < 34 ? "SrcPort" : t < 36 ? "DstPort" : "Protocol";
+}
+
+// Byte gathers from the source's key to the destination's flow and element keys (pair = flow ‖
+// elem, the first Kf bytes the flow's): every byte from the first place the source's key holds
+// it.  GNS_E_ARG when a field of the destination is not part of the source.
+int spr_make_plan(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, SprPlan *pl) {
+    memset(pl, 0, sizeof(*pl));
+    pl->Kf = Kf;
+    pl->Ke = pair.K - Kf;
+    for (uint32_t j = 0; j < pair.K; j++) {
+        const uint32_t t = pair.src[j];
+        uint32_t i = 0;
+        while (i < src.K && src.src[i] != t) i++;
+        if (i == src.K) {
+            set_error("spread rollup: %s field %s is not part of the source's key layout", j < Kf ? "flow" : "element",
+                      spr_field_name(t));
+            return GNS_E_ARG;
+        }
+        (j < Kf ? pl->gf[j] : pl->ge[j - Kf]) = (uint8_t)i;
+        if (t == 0 || t == 16) {  // the first byte of an IP field: its 16 bytes are converted once
+            uint32_t f = 0;
+            while (f < pl->nip && pl->ipoff[f] != i) f++;
+            if (f == pl->nip) pl->ipoff[pl->nip++] = (uint8_t)i;
+        }
+    }
+    return GNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1050,6 +1216,75 @@ int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *c
         staged = 0;
     }
     if (cursor) *cursor = at;
+    return GNS_OK;
+}
+
+int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *cursor, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    if (!dst->has_layout) {
+        set_error("spread rollup: dst was created without field layouts (key sizes only): nothing names the fields to project");
+        return GNS_E_ARG;
+    }
+    ExTableRef S;
+    ex_table_ref(src, &S);
+    SprPlan pl;
+    GNS_TRY(spr_make_plan(S.kp, dst->kpm, dst->Kf, &pl));
+    if (dst->device != S.device) {
+        set_error("spread rollup: dst is on device %d, src on device %d", dst->device, S.device);
+        return GNS_E_ARG;
+    }
+    if (since > S.pos) {
+        set_error("spread rollup: since %llu is beyond src's stream position %llu", (unsigned long long)since,
+                  (unsigned long long)S.pos);
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(dst->device));
+    uint64_t piece = kExsPiece;
+    if (const char *env = getenv("GNS_SPREAD_ROLLUP_PIECE")) {  // tests: small tables span many pieces
+        const unsigned long long v = strtoull(env, nullptr, 10);
+        if (v) piece = std::min<uint64_t>(v, kExsPiece);
+    }
+    hipStream_t s = dst->stream;
+    // src is read at this point of its own stream (after its pending batches), by kernels on dst's stream
+    hipEvent_t ev;
+    GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, S.stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
+    (void)hipEventDestroy(ev);
+    if (e != hipSuccess) { set_error("spread rollup: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    // Pieces of src's table are projected one behind the other into the staging rows; once more
+    // than one piece's worth of rows is staged (the next piece might not fit: a piece appends at
+    // most `piece` rows, and the buffer holds two pieces of 2^20) they are merged, in device
+    // batches of dst.
+    uint8_t *df, *de;
+    GNS_TRY(exs_stage_rows(dst, kExsStageRows, &df, &de));
+    const bool words = dst->Kf % 4 == 0 && (dst->Km - dst->Kf) % 4 == 0 && (((uintptr_t)df | (uintptr_t)de) & 3u) == 0;
+    const uint64_t pairs0 = dst->pclaimed;
+    uint64_t staged = 0, projected = 0;
+    for (uint64_t beg = 0; beg < S.slots; beg += piece) {
+        const uint64_t end = std::min(S.slots, beg + piece);
+        if (staged == 0) GNS_HIP(hipMemsetAsync(dst->ctl + 6, 0, 4, s));
+        {
+            ScopedStage st(dst->timer, 3);
+            const dim3 g((unsigned)((end - beg + 256 * kSprIt - 1) / (256 * kSprIt))), b(256);
+            if (words) hipLaunchKernelGGL((k_spr_project<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
+                                          (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
+            else hipLaunchKernelGGL((k_spr_project<false>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
+                                    (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
+            GNS_HIP(hipGetLastError());
+        }
+        GNS_TRY(exs_read_count(dst, &staged));
+        staged = std::min(staged, kExsStageRows);  // (rows past the capacity are counted, not written: cannot happen)
+        if (staged <= piece && end < S.slots) continue;
+        InputDesc in{};
+        in.keys = df; in.stride = dst->Kf; in.keys2 = de; in.stride2 = dst->Km - dst->Kf;
+        for (uint64_t off = 0; off < staged; off += dst->bmax)
+            GNS_TRY(exs_batch<IN_KEYS>(dst, advance(in, off), std::min(dst->bmax, staged - off), true));
+        projected += staged;
+        staged = 0;
+    }
+    if (cursor) *cursor = S.pos;
+    if (out) { out[0] = projected; out[1] = dst->pclaimed - pairs0; }
     return GNS_OK;
 }
 

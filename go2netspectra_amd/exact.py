@@ -98,6 +98,44 @@ def ip_to16(ip) -> bytes:
     return (bytes(10) + b"\xff\xff" + a.packed) if a.version == 4 else a.packed
 
 
+def to16_to_encodeflow(keys, fields: Sequence[str]) -> np.ndarray:
+    """Key rows [n, K] laid out by ``fields`` with IPs in To16 form (this engine's keys) ->
+    the same rows in EncodeFlow form (the keys of ExactSpread and SuperSpread), the conversion
+    gns_spread_rollup applies: an IP field holding ::ffff:a.b.c.d becomes a.b.c.d + 12 zero
+    bytes, every other IP value (genuine IPv6, :: included) and every port / protocol byte is
+    copied.  The inverse of ``ip_to16`` on 4-byte addresses."""
+    keys = np.ascontiguousarray(keys, np.uint8)
+    K = sum(_lib.FIELD_SIZE.get(f, 0) for f in fields)
+    keys = keys.reshape(-1, K) if K else keys.reshape(len(keys), 0)
+    out = keys.copy()
+    off = 0
+    for f in fields:
+        size = _lib.FIELD_SIZE.get(f, 0)
+        if f in ("SrcIP", "DstIP"):
+            ip = keys[:, off:off + 16]
+            mapped = (ip[:, :10] == 0).all(1) & (ip[:, 10:12] == 0xFF).all(1)
+            out[mapped, off:off + 4] = ip[mapped, 12:16]
+            out[mapped, off + 4:off + 16] = 0
+        off += size
+    return out
+
+
+def spread_rollup_plan(src_fields: Sequence[str], flow_fields: Sequence[str], elem_fields: Sequence[str]):
+    """The two byte gathers of a spread roll-up, as gns_spread_rollup builds them: (flow plan,
+    element plan), each a ``rollup_plan`` from the key laid out by ``src_fields``.  ValueError
+    naming the field when a flow or element field is not part of src, or when either layout
+    is empty (a handle made from key sizes alone names no fields): GNS_E_ARG in C."""
+    if not list(flow_fields or []) or not list(elem_fields or []):
+        raise ValueError("spread rollup: the spread handle has no flow / element field lists (key sizes only)")
+    plans = []
+    for what, fields in (("flow", flow_fields), ("element", elem_fields)):
+        try:
+            plans.append(rollup_plan(src_fields, fields))
+        except ValueError as e:
+            raise ValueError(f"spread {e} ({what} layout)") from None
+    return plans[0], plans[1]
+
+
 def _small_int(name: str, v, hi: int) -> int:
     v = int(v)
     if not 0 <= v <= hi:
@@ -486,6 +524,23 @@ class ExactAggregator:
             raise
         return dst
 
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], **kw):
+        """A new ExactSpread on the same device -- distinct ``elem_fields`` values per
+        ``flow_fields`` value, both made of fields of this handle's key -- filled by
+        ``ExactSpread.rollup_from(self)``: what a spread handle of those layouts fed the same
+        packets holds (IPv4-mapped arrivals counted with their IPv4 address).  ``kw`` as
+        ExactSpread's constructor."""
+        from .spread import ExactSpread
+        spread_rollup_plan(self.key_fields, flow_fields, elem_fields)
+        kw.setdefault("device", self.device)
+        dst = ExactSpread(flow_fields, elem_fields, **kw)
+        try:
+            dst.rollup_from(self)
+        except Exception:
+            dst.close()
+            raise
+        return dst
+
     def aggregate(self, filters) -> List[Summary]:
         """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
         arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
@@ -625,6 +680,11 @@ class ExactTask:
         with that key and fed the same packets holds.  It takes packets, queries, views and
         checkpoints like any other task."""
         return ExactTask(name, key_fields, num_shards, agg=self.agg.rollup(key_fields, **kw))
+
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], **kw):
+        """The exact spread table of this task's flows (ExactAggregator.spread): SuperSpread's
+        ground truth for those layouts without a spread engine on the ingest path."""
+        return self.agg.spread(flow_fields, elem_fields, **kw)
 
     def reset(self) -> None:
         self.agg.reset()

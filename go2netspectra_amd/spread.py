@@ -225,6 +225,25 @@ class ExactSpread:
         check(self._L.gns_pairs_merge_from(self._h, other._h, since, ct.byref(cur)))
         return int(cur.value)
 
+    def rollup_from(self, src, since: int = 0):
+        """gns_spread_rollup: union with the (flow, element) pairs of the flows an
+        ExactAggregator holds, projected onto this handle's layouts on the device and converted
+        from its To16 keys to EncodeFlow form.  Into an empty handle the result equals a handle of
+        these layouts fed src's packets (an IPv4-mapped arrival counted with its IPv4 address).
+        ``since`` (a cursor this call or ``ExactView.refresh`` returned for src) projects only the
+        flows first seen after that point; chained into the same handle that keeps it equal to a
+        full roll-up.  src is only read.  Returns (src's cursor, flows projected, pairs new here)."""
+        from .exact import ExactAggregator, spread_rollup_plan
+        if not isinstance(src, ExactAggregator):
+            raise TypeError("rollup_from takes an ExactAggregator")
+        if since < 0:
+            raise ValueError("since is a stream position (unsigned)")
+        spread_rollup_plan(src.key_fields, self.flow_fields, self.elem_fields)
+        cur = ct.c_uint64(0)
+        out = (ct.c_uint64 * 2)()
+        check(self._L.gns_spread_rollup(self._h, src._h, since, ct.byref(cur), out))
+        return int(cur.value), int(out[0]), int(out[1])
+
     def save(self, path) -> None:
         """The whole pair set into one checkpoint file (checkpoint.save)."""
         from . import checkpoint
@@ -253,7 +272,7 @@ class ExactSpread:
                  "grow_us"]
         return {k: int(s[i]) for i, k in enumerate(names)}
 
-    STAGES = ["insert", "resolve", "grow", "unused3", "unused4", "total"]
+    STAGES = ["insert", "resolve", "grow", "project", "unused4", "total"]  # project: rollup_from's projection
 
     def set_timing(self, on: bool = True, stages=None) -> None:
         check(self._L.gns_exs_set_timing(self._h, _lib.timing_arg(on, stages, self.STAGES)))

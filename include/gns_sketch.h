@@ -688,7 +688,8 @@ int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const
  *     src is GNS_OK and moves no flows.
  *   - Not offered: a view as source (view rows carry no stream positions, and adding
  *     them would change the views' documented memory); a delta roll-up ("since": rows
- *     are cumulative, so a delta is not additive); a distinct-flow count per group. */
+ *     are cumulative, so a delta is not additive).  (A distinct-flow count per group
+ *     is gns_spread_rollup with src's whole key as the element layout.) */
 int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]);
 int gns_ex_reset(gns_ex *ex);
 /* out[8]: inserted, dropped, unsupported, dictionary full, flows, records, batches, 0 */
@@ -856,7 +857,8 @@ int gns_exs_counters(gns_exs *h, uint64_t out[8]);
  * incl. the device work), [7] 0 */
 int gns_exs_dict_stats(gns_exs *h, uint64_t out[8]);
 int gns_exs_set_timing(gns_exs *h, int on);
-/* stages: 0 insert (first pass), 1 resolve rounds, 2 table growth, 5 total */
+/* stages: 0 insert (first pass), 1 resolve rounds, 2 table growth, 3 roll-up projection
+ * (the device work of gns_spread_rollup before its merge batches), 5 total (of a batch) */
 int gns_exs_stage_times(gns_exs *h, double ms[8], uint64_t launches[8], int reset);
 
 /* Pair set export and union: the exact spread engine's state interface.  A spread
@@ -902,6 +904,67 @@ int gns_pairs_merge(gns_exs *h, const uint8_t *flows, uint32_t fstride, const ui
  * without a dense copy of the whole set (staged in pieces of 2^20 table slots).  *cursor
  * (may be NULL): src's point, for the next delta. */
 int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *cursor);
+
+/* Spread roll-up: the pair set of an exact spread table derived from the resident
+ * flow table of an exact aggregator, on the device, after the traffic has gone.  The
+ * distinct (flow, element) pairs of a stream are the projection of its distinct flow
+ * keys whenever the flow and element fields are fields of the aggregator's key:
+ * "distinct DstIPs per SrcIP", "distinct DstPorts per (SrcIP, DstIP)", and -- with
+ * src's whole key as the element layout -- "flows per source address" all follow from
+ * a five-tuple table.  (Named outside the gns_exs_ and gns_pairs_ families, whose symbol
+ * lists are pinned, as gns_spread_insert_compact is.)
+ *   - What it does.  Every flow gns_ex_snapshot(src) would list at the call (after
+ *     src's pending batches) is projected onto dst's flow layout and onto dst's
+ *     element layout, the two key rows are converted to EncodeFlow form, and the
+ *     pairs enter dst as a union under the rules of gns_pairs_merge: duplicates
+ *     inside the call and pairs already held count once; counters [0], [1], [2], [6]
+ *     and [7] do not move, [4] rises by the pairs actually added, [5] follows the flow
+ *     table; the tables grow before each device batch as in ingest; merged pairs are
+ *     stamped with the merge's epoch, so gns_pairs_export(dst, since = ...) deltas
+ *     pass them on.
+ *   - Layouts.  Every field of dst's flow layout and of its element layout must
+ *     occur in src's key layout, in any order; a field repeated in dst is copied once
+ *     per occurrence, each from src's first occurrence (as gns_ex_rollup).  A dst
+ *     created without field lists (flow_bytes / elem_bytes only) is refused: nothing
+ *     names the fields to project.
+ *   - Key form.  The aggregator stores IPs in To16 form, this engine in EncodeFlow
+ *     form.  An IP field whose 16 bytes are ten zero bytes, ff ff, then a b c d is
+ *     written as a b c d + 12 zero bytes; every other value is copied as is; ports
+ *     and protocol are copied.  Consequence: into an empty dst the result equals a
+ *     spread handle of those layouts fed the same packets -- keys, spreads, pair set
+ *     and heavy list.  Deviation: a packet that carries an IPv4-mapped address in a
+ *     16-byte net.IP is ONE key with the IPv4 address here (the aggregator already
+ *     merged them, see gns_ex_*); it would be a separate key in a spread handle fed
+ *     directly.  Note also that 0.0.0.0 and :: are both 16 zero bytes in EncodeFlow
+ *     form, here as in a directly fed handle.
+ *   - since / cursor.  since == 0 projects every flow.  since == a cursor this call
+ *     or gns_ex_view_refresh returned for src projects only the flows whose first
+ *     stream position is >= since: the flows new after that point.  A pair is new
+ *     after that point only if every flow that projects onto it is new, so the delta
+ *     projection is a superset of the new pairs and the union removes the rest;
+ *     chaining since = the previous cursor into the same dst therefore keeps dst equal
+ *     to a full roll-up.  *cursor (may be NULL) is src's next stream position
+ *     (records inserted + rows merged), the value gns_ex_view_refresh returns; since
+ *     beyond it is GNS_E_ARG.  Positions never restart: after gns_ex_reset(src) an old
+ *     cursor selects every flow of the new period.  dst is a union: it keeps the
+ *     pairs of earlier periods until the caller resets it.
+ *   - out (may be NULL): [0] source flows projected, [1] pairs new in dst.
+ *   - Calling rules.  Synchronous, and an ingest-side call on BOTH handles: no other
+ *     thread may insert into src or dst during it.  src is read only: table, counters
+ *     and cursors are unchanged.  src is read at an event of its own stream, by work
+ *     on dst's stream (as gns_pairs_merge_from).  The work runs in pieces of 2^20
+ *     source slots, gathered until more than a piece's worth of rows is staged and
+ *     then merged in device batches of dst (GNS_SPREAD_ROLLUP_PIECE in the
+ *     environment, read at the call, sets a smaller piece: for tests only, so that
+ *     small tables span many pieces and merges).
+ *   - GNS_E_ARG before any device call, dst untouched: a null handle, a dst without
+ *     field lists, a dst field that src's key lacks (gns_last_error names it), handles
+ *     on different devices, since beyond src's position.  An empty src is GNS_OK and
+ *     moves nothing.
+ *   - An error after the first merged batch (out of memory, a table at its slot
+ *     limit) leaves dst with the pairs merged so far; a union is idempotent, so
+ *     repeating the call is safe. */
+int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *cursor, uint64_t out[2]);
 
 /* Device buffers for callers without a device allocator of their own (the cgo
  * binding's ThriftDecoder: gns_thrift_decode writes device records that
