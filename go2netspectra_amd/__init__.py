@@ -10,8 +10,8 @@ from . import checkpoint
 from ._lib import GnsError, build, load
 from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_config
 from .exact import (ExactAggregator, ExactTask, ExactView, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
-                    TaskSummary, apply_delta, make_filter, merge_summaries, rollup_plan, spread_rollup_plan,
-                    to16_to_encodeflow)
+                    TaskSummary, apply_delta, discount_heavy_prefixes, make_filter, make_prefix, mask_keys, mask_prefix,
+                    merge_summaries, prefix_plan, rollup_plan, spread_rollup_plan, to16_to_encodeflow)
 from .factory import Manager, TaskGroup, create, register_aggregator
 from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
@@ -27,4 +27,5 @@ __all__ = [
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "apply_delta", "CompactBatch",
     "SuperSpreadView", "rollup_plan", "spread_rollup_plan", "to16_to_encodeflow",
+    "mask_prefix", "mask_keys", "prefix_plan", "make_prefix", "discount_heavy_prefixes",
 ]

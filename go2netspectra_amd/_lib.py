@@ -55,6 +55,7 @@ EXPORTED = [
     "gns_ss_view_query_device", "gns_ss_view_heavy_hitters", "gns_ss_view_heavy_rows", "gns_ss_view_export_state",
     "gns_cm_view_refresh_at", "gns_cm_view_query_device", "gns_cm_view_heavy_rows", "gns_cm_view_export_state",
     "gns_ex_rollup", "gns_spread_rollup",
+    "gns_ex_rollup_prefix", "gns_spread_rollup_prefix", "gns_ex_aggregate_cidr", "gns_ex_view_aggregate_cidr",
 ]
 
 
@@ -110,6 +111,14 @@ class ExParams(ct.Structure):
 class ExFilter(ct.Structure):  # gns_ex_filter: 44 bytes
     _fields_ = [("mask", ct.c_uint32), ("src16", ct.c_uint8 * 16), ("dst16", ct.c_uint8 * 16),
                 ("sport", ct.c_uint16), ("dport", ct.c_uint16), ("proto", ct.c_uint8), ("_pad", ct.c_uint8 * 3)]
+
+
+class ExCidr(ct.Structure):  # gns_ex_cidr: 48 bytes; bits of the 16-byte To16 form, 128 = equality
+    _fields_ = [("f", ExFilter), ("src_bits", ct.c_uint8), ("dst_bits", ct.c_uint8), ("_pad", ct.c_uint8 * 2)]
+
+
+class Prefix(ct.Structure):  # gns_prefix: bits kept of SrcIP / DstIP, per address class
+    _fields_ = [("src_v4", ct.c_uint8), ("src_v6", ct.c_uint8), ("dst_v4", ct.c_uint8), ("dst_v6", ct.c_uint8)]
 
 
 class ExSummary(ct.Structure):  # gns_ex_summary: 56 bytes
@@ -225,6 +234,10 @@ def load() -> ct.CDLL:
         "gns_ex_merge": ([vp, vp, vp, vp, vp, vp, u64, i32], i32),
         "gns_ex_rollup": ([vp, vp, vp], i32),
         "gns_spread_rollup": ([vp, vp, u64, vp, vp], i32),
+        "gns_ex_rollup_prefix": ([vp, vp, vp, vp], i32),
+        "gns_spread_rollup_prefix": ([vp, vp, vp, vp, u64, vp, vp], i32),
+        "gns_ex_aggregate_cidr": ([vp, vp, u32, vp], i32),
+        "gns_ex_view_aggregate_cidr": ([vp, vp, u32, vp], i32),
         "gns_ex_view_create": ([vp, vp], i32), "gns_ex_view_destroy": ([vp], i32),
         "gns_ex_view_refresh": ([vp, u64, vp], i32),
         "gns_ex_view_snapshot": ([vp, vp, vp, vp, vp, vp, vp], i32),

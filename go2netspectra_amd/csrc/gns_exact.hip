@@ -1393,6 +1393,66 @@ __global__ __launch_bounds__(256) void k_exr_project(DictDev S, FlowState sf, ui
     R.start[row] = sf.start[s]; R.end[row] = sf.end[s];
 }
 
+// Prefix roll-up (gns_ex_rollup_prefix): R1 with the projected key's IP fields masked to a
+// prefix.  Per destination key byte the plan holds the gather index g, the IP field the byte
+// belongs to (0 SrcIP, 1 DstIP, 2 none) and two mask bytes: m4 applies when the field's value
+// is IPv4 (::ffff:a.b.c.d: bytes 0..11 kept, the prefix counted in bytes 12..15), m6 when it
+// is anything else; bytes outside IP fields carry 0xff in both.  A lane takes one IPv4 flag
+// per IP field of its source key -- spr_encode_ip's test, on the unmasked bytes -- and writes
+// byte & (v4[field] ? m4 : m6): branch-free, any bit length, IP fields at any offset.  The
+// plan sits in LDS (one broadcast read per table byte): its 160 bytes as kernel-argument
+// scalars would be live across the unrolled gather, where the 74 bytes of k_spr_project's
+// spilled 270 SGPRs.
+struct ExrPxPlan {
+    uint32_t K, KW;      // destination key bytes / words
+    uint8_t ipoff[4];    // byte offset of SrcIP / DstIP in the source key; 0xFF: not read
+    union {              // as words for the copy into LDS
+        struct { uint8_t g[40], fld[40], m4[40], m6[40]; };
+        uint32_t w[40];
+    };
+};
+
+// grid covers slots [s0, s1); at most s1 - s0 rows are appended (R.cnt zeroed by the host)
+__global__ __launch_bounds__(256) void k_exr_project_px(DictDev S, FlowState sf, uint64_t s0, uint64_t s1, ExrPxPlan pl,
+                                                        ExrRows R) {
+    __shared__ uint32_t s_k[GNS_KWMAX][256];  // a lane's key words: each lane touches only its own column
+    __shared__ uint32_t s_pw[40];             // g, fld, m4, m6
+    const uint8_t *s_g = reinterpret_cast<const uint8_t *>(s_pw);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid < 40) s_pw[tid] = pl.w[tid];
+    __syncthreads();  // before any wave leaves
+    const uint64_t s = s0 + (uint64_t)blockIdx.x * 256 + tid;
+    unsigned long long pk = 0;
+    uint32_t r[12];
+    bool occ = false;
+    if (s < s1) {
+        load_record(S, (uint32_t)s, r);
+        pk = sf.pkts[s];
+        occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
+    }
+    const uint64_t m = __ballot(occ);
+    if (m == 0) return;
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(R.cnt, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    if (!occ) return;
+    const uint64_t row = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+    uint32_t v4 = 0;  // bit f: IP field f of this flow is IPv4
+#pragma unroll
+    for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
+        if (pl.ipoff[f] != 0xFFu) v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if ((uint32_t)i >= pl.KW) break;  // uniform
+        R.keys[row * pl.KW + i] = px_masked_word(s_k, tid, s_g, v4, pl.K, i);
+    }
+    R.pkts[row] = pk; R.bytes[row] = sf.bytes[s]; R.first[row] = sf.first[s]; R.last[row] = sf.last[s];
+    R.start[row] = sf.start[s]; R.end[row] = sf.end[s];
+}
+
 // R3.  A roll-up to a few groups would send every row's four atomics to a few addresses.
 // Rows of one id are combined before anything leaves the CU (as k_exq_aggregate): the ids
 // most lanes of a wave share are reduced across the wave, every id goes through a small LDS
@@ -1885,21 +1945,45 @@ struct ExTable {
     uint64_t rows;
 };
 
-int ex_filters_check(const gns_ex_filter *filters, uint32_t nf) {
+// A batch of filters as the two public forms hand it over: gns_ex_filter (every masked field
+// compared whole) or gns_ex_cidr (the filter first, then the leading bits of the two IP fields
+// that take part).  Equality is the 128-bit case.
+struct ExFilters {
+    const uint8_t *base;
+    size_t stride;
+    bool cidr;
+    ExFilters(const gns_ex_filter *f) : base(reinterpret_cast<const uint8_t *>(f)), stride(sizeof(gns_ex_filter)), cidr(false) {}
+    ExFilters(const gns_ex_cidr *f) : base(reinterpret_cast<const uint8_t *>(f)), stride(sizeof(gns_ex_cidr)), cidr(true) {}
+    const gns_ex_filter &at(uint32_t i) const { return *reinterpret_cast<const gns_ex_filter *>(base + i * stride); }
+    uint32_t bits(uint32_t i, uint32_t fld) const {  // fld: GNS_F_SRCIP or GNS_F_DSTIP
+        if (!cidr) return 128;
+        const gns_ex_cidr &c = *reinterpret_cast<const gns_ex_cidr *>(base + i * stride);
+        return fld == GNS_F_SRCIP ? c.src_bits : c.dst_bits;
+    }
+};
+
+int ex_filters_check(const ExFilters &filters, uint32_t nf) {
     constexpr uint32_t kFieldBits = (1u << GNS_F_SRCIP) | (1u << GNS_F_DSTIP) | (1u << GNS_F_SRCPORT) |
                                     (1u << GNS_F_DSTPORT) | (1u << GNS_F_PROTO);
-    for (uint32_t i = 0; i < nf; i++)
-        if (filters[i].mask & ~kFieldBits) {
-            set_error("filter %u: mask 0x%x has bits outside the five key fields", i, filters[i].mask);
+    for (uint32_t i = 0; i < nf; i++) {
+        if (filters.at(i).mask & ~kFieldBits) {
+            set_error("filter %u: mask 0x%x has bits outside the five key fields", i, filters.at(i).mask);
             return GNS_E_ARG;
         }
+        if (filters.bits(i, GNS_F_SRCIP) > 128 || filters.bits(i, GNS_F_DSTIP) > 128) {
+            set_error("filter %u: prefix of %u / %u bits (0..128 of the 16-byte form)", i, filters.bits(i, GNS_F_SRCIP),
+                      filters.bits(i, GNS_F_DSTIP));
+            return GNS_E_ARG;
+        }
+    }
     return GNS_OK;
 }
 
 // gns_ex_aggregate over table T (the argument checks are the caller's; nf != 0)
 int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer,
-                    const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
-    // per filter: the 37 tuple bytes (make_plan's numbering) and which of them are masked;
+                    const ExFilters &filters, uint32_t nf, gns_ex_summary *out) {
+    // per filter: the 37 tuple bytes (make_plan's numbering), which fields are masked and, bit
+    // for bit, how much of each byte takes part (an IP field under a prefix: its leading bits);
     // the layout's byte plan carries them to their place in the record's key words
     static const struct { uint32_t base, len; } kSpan[6] = {{0, 0}, {0, 16}, {16, 16}, {32, 2}, {34, 2}, {36, 1}};
     const size_t acc_bytes = (size_t)nf * kQAcc * 8, flt_bytes = (size_t)nf * sizeof(ExQFilter);
@@ -1918,29 +2002,34 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
         ha = va.data();
     }
     for (uint32_t i = 0; i < nf; i++) {
-        const gns_ex_filter &q = filters[i];
-        uint8_t tb[40] = {0}, tm[40] = {0};
+        const gns_ex_filter &q = filters.at(i);
+        uint8_t tb[40] = {0}, tm[40] = {0}, want[40] = {0};
         memcpy(tb, q.src16, 16);
         memcpy(tb + 16, q.dst16, 16);
         tb[32] = (uint8_t)(q.sport >> 8); tb[33] = (uint8_t)q.sport;
         tb[34] = (uint8_t)(q.dport >> 8); tb[35] = (uint8_t)q.dport;
         tb[36] = q.proto;
         for (uint32_t fld = GNS_F_SRCIP; fld <= GNS_F_PROTO; fld++)
-            if (q.mask >> fld & 1u) memset(tm + kSpan[fld].base, 0xFF, kSpan[fld].len);
+            if (q.mask >> fld & 1u) {
+                memset(want + kSpan[fld].base, 1, kSpan[fld].len);
+                const uint32_t bits = fld <= GNS_F_DSTIP ? filters.bits(i, fld) : 8 * kSpan[fld].len;
+                for (uint32_t b = 0; b < kSpan[fld].len; b++)
+                    tm[kSpan[fld].base + b] = 8 * b + 8 <= bits ? 0xFF : 8 * b >= bits ? 0 : (uint8_t)(0xFF00u >> (bits - 8 * b));
+            }
         ExQFilter &w = hf[i];
         memset(&w, 0, sizeof(w));
         uint8_t seen[40] = {0};
         for (uint32_t j = 0; j < ex->K; j++) {
             const uint32_t t = ex->kp.src[j];
-            if (t >= 37 || !tm[t]) continue;
+            if (t >= 37 || !want[t]) continue;
             seen[t] = 1;
-            w.m[j >> 2] |= 0xFFu << (8 * (j & 3));
-            w.v[j >> 2] |= (uint32_t)tb[t] << (8 * (j & 3));
+            w.m[j >> 2] |= (uint32_t)tm[t] << (8 * (j & 3));
+            w.v[j >> 2] |= (uint32_t)(tb[t] & tm[t]) << (8 * (j & 3));  // address bits below the prefix are ignored
         }
         // a masked field outside the key is a NULL column (writer_clickhouse.go:142-148):
         // `NULL = ?` selects nothing -> a pair no word satisfies
         for (uint32_t t = 0; t < 37; t++)
-            if (tm[t] && !seen[t]) { w.m[0] = 0u; w.v[0] = 1u; break; }
+            if (want[t] && !seen[t]) { w.m[0] = 0u; w.v[0] = 1u; break; }
         for (uint32_t j = 0; j < kQAcc; j++) ha[(size_t)i * kQAcc + j] = exq_acc_init(j);
     }
     if (T.rows != 0) {  // (a view without rows: every answer is the initial one)
@@ -2302,8 +2391,9 @@ int gns_ex_snapshot(gns_ex *ex, uint8_t *keys, int64_t *start_ns, int64_t *end_n
     return GNS_OK;
 }
 
-int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
-    if (!ex || (nf && (!filters || !out))) { set_error("null argument"); return GNS_E_ARG; }
+namespace {
+static int ex_aggregate(gns_ex *ex, const ExFilters &filters, uint32_t nf, gns_ex_summary *out) {
+    if (!ex || (nf && (!filters.base || !out))) { set_error("null argument"); return GNS_E_ARG; }
     GNS_TRY(ex_filters_check(filters, nf));
     if (nf == 0) return GNS_OK;
     GNS_TRY(set_device(ex->device));
@@ -2311,6 +2401,15 @@ int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_
     const int rc = ex_aggregate_on(ex, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, filters, nf, out);
     rd.free_all();
     return rc;
+}
+}  // namespace
+
+int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
+    return ex_aggregate(ex, ExFilters(filters), nf, out);
+}
+
+int gns_ex_aggregate_cidr(gns_ex *ex, const gns_ex_cidr *filters, uint32_t nf, gns_ex_summary *out) {
+    return ex_aggregate(ex, ExFilters(filters), nf, out);
 }
 
 int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit, uint8_t *keys,
@@ -2428,14 +2527,24 @@ int gns_ex_view_snapshot(gns_ex_view *v, uint8_t *keys, int64_t *start_ns, int64
     return GNS_OK;
 }
 
-int gns_ex_view_aggregate(gns_ex_view *v, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
-    if (!v || (nf && (!filters || !out))) { set_error("null argument"); return GNS_E_ARG; }
+namespace {
+static int exv_aggregate(gns_ex_view *v, const ExFilters &filters, uint32_t nf, gns_ex_summary *out) {
+    if (!v || (nf && (!filters.base || !out))) { set_error("null argument"); return GNS_E_ARG; }
     GNS_TRY(ex_filters_check(filters, nf));
     GNS_TRY(set_device(v->ex->device));
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(exv_rows(v));
     if (nf == 0) return GNS_OK;
     return ex_aggregate_on(v->ex, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, filters, nf, out);
+}
+}  // namespace
+
+int gns_ex_view_aggregate(gns_ex_view *v, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out) {
+    return exv_aggregate(v, ExFilters(filters), nf, out);
+}
+
+int gns_ex_view_aggregate_cidr(gns_ex_view *v, const gns_ex_cidr *filters, uint32_t nf, gns_ex_summary *out) {
+    return exv_aggregate(v, ExFilters(filters), nf, out);
 }
 
 int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, uint64_t limit, uint8_t *keys,
@@ -2539,17 +2648,40 @@ void exr_free(ExrRows &R) {
     R = ExrRows{};
 }
 
-}  // namespace
+// The gather of exr_make_plan with the mask tables of px (checked by the caller): a prefix for
+// a field dst's layout lacks leaves no trace.
+int exr_make_px_plan(const KeyPlanN &src, const KeyPlanN &dst, const gns_prefix &px, ExrPxPlan *pp) {
+    ExrPlan pl;
+    GNS_TRY(exr_make_plan(src, dst, &pl));
+    memset(pp, 0, sizeof(*pp));
+    pp->K = pl.K;
+    pp->KW = pl.KW;
+    memset(pp->ipoff, 0xFF, sizeof(pp->ipoff));
+    const uint32_t v4[2] = {px.src_v4, px.dst_v4}, v6[2] = {px.src_v6, px.dst_v6};
+    for (uint32_t j = 0; j < dst.K; j++) {
+        const uint32_t t = dst.src[j];
+        pp->g[j] = pl.g[j];
+        if (t >= 32) { pp->fld[j] = 2; pp->m4[j] = pp->m6[j] = 0xFF; continue; }
+        const uint32_t f = t >> 4, b = t & 15u;
+        pp->fld[j] = (uint8_t)f;
+        pp->m4[j] = b < 12 ? 0xFF : px_prefix_byte(v4[f], b - 12);
+        pp->m6[j] = px_prefix_byte(v6[f], b);
+        if (b == 0) pp->ipoff[f] = pl.g[j];  // fields are gathered whole: the field starts here in src's key
+    }
+    return GNS_OK;
+}
 
-int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]) {
-    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+// gns_ex_rollup (px == nullptr) and gns_ex_rollup_prefix behind their argument checks
+static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t out[2]) {
     if (dst == src) { set_error("rollup: dst and src are the same handle"); return GNS_E_ARG; }
     if (dst->device != src->device) {
         set_error("rollup: dst is on device %d, src on device %d", dst->device, src->device);
         return GNS_E_ARG;
     }
     ExrPlan pl;
+    ExrPxPlan pp;
     GNS_TRY(exr_make_plan(src->kp, dst->kp, &pl));
+    if (px) GNS_TRY(exr_make_px_plan(src->kp, dst->kp, *px, &pp));
     GNS_TRY(set_device(dst->device));
     uint64_t piece = kResolvePiece;
     if (const char *env = getenv("GNS_EX_ROLLUP_PIECE")) {  // tests: small tables span many pieces
@@ -2578,8 +2710,12 @@ int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]) {
         for (uint64_t s0 = 0; s0 < src->slots; s0 += piece) {
             const uint64_t s1 = std::min<uint64_t>(s0 + piece, src->slots);
             GNS_HIP(hipMemsetAsync(R.cnt, 0, 4, s));
-            hipLaunchKernelGGL(k_exr_project, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D, src->f, s0,
-                               s1, pl, R);
+            if (px)
+                hipLaunchKernelGGL(k_exr_project_px, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D,
+                                   src->f, s0, s1, pp, R);
+            else
+                hipLaunchKernelGGL(k_exr_project, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D, src->f, s0,
+                                   s1, pl, R);
             GNS_HIP(hipGetLastError());
             GNS_HIP(hipMemcpyAsync(dst->h_pin, R.cnt, 4, hipMemcpyDeviceToHost, s));
             GNS_HIP(hipStreamSynchronize(s));
@@ -2622,6 +2758,19 @@ int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]) {
     sc.free_all();
     if (rc == GNS_OK && out) { out[0] = projected; out[1] = added; }
     return rc;
+}
+
+}  // namespace
+
+int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    return exr_rollup(dst, src, nullptr, out);
+}
+
+int gns_ex_rollup_prefix(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(px_check_prefix(px, "rollup"));
+    return exr_rollup(dst, src, px, out);
 }
 
 int gns_ex_reset(gns_ex *ex) {

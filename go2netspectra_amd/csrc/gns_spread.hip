@@ -493,6 +493,98 @@ __global__ __launch_bounds__(256) void k_spr_project(DictDev S, const unsigned l
     }
 }
 
+// Prefix spread roll-up (gns_spread_rollup_prefix): k_spr_project with the IP fields of the
+// flow row and of the element row masked to a prefix, each row by tables of its own -- the
+// prime uses read one field twice ("distinct source hosts per source /24": flow = SrcIP
+// under /24, element = SrcIP whole).  The masks are defined on the To16 bytes, so a lane
+// takes its IPv4 flag per IP field BEFORE spr_encode_ip rewrites the column; after the
+// rewrite an IPv4 address sits in bytes 0..3 of the field, and m4 is laid out for that
+// (EncodeFlow) form.  Per row byte: gather index g, IP field fld (0 SrcIP, 1 DstIP, 2 none),
+// m4 / m6 as in k_exr_project_px; the tables sit in LDS.
+struct SprPxPlan {
+    uint32_t Kf, Ke;
+    uint8_t ipoff[4];        // byte offset of SrcIP / DstIP in the source key; 0xFF: not read
+    union {                  // flow row: g, fld, m4, m6; then the element row's four; as words for the copy into LDS
+        uint8_t t[8][40];
+        uint32_t w[80];
+    };
+};
+
+// t_row: the row's g, fld, m4, m6 tables (40 bytes each, in LDS); v4: bit f = IP field f is IPv4
+template <bool WORDS>
+__device__ __forceinline__ void spr_store_row_px(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *t_row, uint32_t v4,
+                                                 uint32_t K, uint8_t *row) {
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if (4u * i >= K) break;  // uniform
+        const uint32_t v = px_masked_word(s_k, tid, t_row, v4, K, i);
+        if constexpr (WORDS) {
+            reinterpret_cast<uint32_t *>(row)[i] = v;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if ((uint32_t)(4 * i + b) < K) row[4 * i + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
+template <bool WORDS>
+__global__ __launch_bounds__(256) void k_spr_project_px(DictDev S, const unsigned long long *pkts,
+                                                        const unsigned long long *first, uint64_t beg, uint64_t end,
+                                                        unsigned long long since, SprPxPlan pl, uint8_t *flows,
+                                                        uint8_t *elems, uint64_t cap, uint32_t *count) {
+    constexpr int IT = kSprIt;
+    __shared__ uint32_t s_k[GNS_KWMAX][256];
+    __shared__ uint32_t s_cnt[IT * 4], s_base;
+    __shared__ uint32_t s_pw[80];
+    const uint8_t *s_t = reinterpret_cast<const uint8_t *>(s_pw);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t s0 = beg + (uint64_t)blockIdx.x * (256 * IT) + tid;
+    if (tid < 80) s_pw[tid] = pl.w[tid];
+    uint64_t m[IT];
+    bool live[IT];
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        const uint64_t s = s0 + (uint64_t)it * 256;
+        live[it] = s < end && S.rec[s * S.RW] != 0u && pkts[s] != 0ull && first[s] >= since;
+        m[it] = __ballot(live[it]);
+        if (lane == 0) s_cnt[it * 4 + wave] = (uint32_t)__popcll(m[it]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (int k = 0; k < IT * 4; k++) tot += s_cnt[k];
+        s_base = tot ? atomicAdd(count, tot) : 0u;
+    }
+    __syncthreads();
+    uint64_t run = s_base;  // rows of the workgroup's (run, wave) cells before this lane's
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        uint64_t j = run + (uint32_t)__popcll(m[it] & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint32_t c = s_cnt[it * 4 + w];
+            if ((uint32_t)w < wave) j += c;
+            run += c;
+        }
+        if (!live[it] || j >= cap) continue;
+        uint32_t r[12];
+        load_record(S, (uint32_t)(s0 + (uint64_t)it * 256), r);
+#pragma unroll
+        for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+        uint32_t v4 = 0;
+#pragma unroll
+        for (int f = 0; f < 2; f++)  // SrcIP, DstIP: the class is the To16 value's, taken before the rewrite
+            if (pl.ipoff[f] != 0xFFu) {
+                v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
+                spr_encode_ip(s_k, tid, pl.ipoff[f]);
+            }
+        spr_store_row_px<WORDS>(s_k, tid, s_t, v4, pl.Kf, flows + j * pl.Kf);
+        spr_store_row_px<WORDS>(s_k, tid, s_t + 160, v4, pl.Ke, elems + j * pl.Ke);
+    }
+}
+
 // epoch wrap: every live tag of a table becomes 1, older than every epoch the new generation hands out
 __global__ __launch_bounds__(256) void k_exs_retag(uint32_t *rec, uint64_t slots, uint32_t RW) {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -918,6 +1010,32 @@ int spr_make_plan(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, SprPla
     return GNS_OK;
 }
 
+// spr_make_plan's gathers with the mask tables of the two prefixes (checked by the caller)
+int spr_make_px_plan(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, const gns_prefix &fpx, const gns_prefix &epx,
+                     SprPxPlan *pp) {
+    SprPlan pl;
+    GNS_TRY(spr_make_plan(src, pair, Kf, &pl));
+    memset(pp, 0, sizeof(*pp));
+    pp->Kf = pl.Kf;
+    pp->Ke = pl.Ke;
+    memset(pp->ipoff, 0xFF, sizeof(pp->ipoff));
+    for (uint32_t j = 0; j < pair.K; j++) {
+        const bool flow = j < Kf;
+        const uint32_t t = pair.src[j], k = flow ? j : j - Kf;
+        uint8_t(*tab)[40] = pp->t + (flow ? 0 : 4);
+        const uint8_t g = flow ? pl.gf[k] : pl.ge[k];
+        tab[0][k] = g;
+        if (t >= 32) { tab[1][k] = 2; tab[2][k] = tab[3][k] = 0xFF; continue; }
+        const gns_prefix &px = flow ? fpx : epx;
+        const uint32_t f = t >> 4, b = t & 15u;
+        tab[1][k] = (uint8_t)f;
+        tab[2][k] = b < 4 ? px_prefix_byte(f ? px.dst_v4 : px.src_v4, b) : 0xFF;  // EncodeFlow form: a.b.c.d + 12 zero bytes
+        tab[3][k] = px_prefix_byte(f ? px.dst_v6 : px.src_v6, b);
+        if (b == 0) pp->ipoff[f] = g;
+    }
+    return GNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1219,8 +1337,10 @@ int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *c
     return GNS_OK;
 }
 
-int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *cursor, uint64_t out[2]) {
-    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+namespace {
+// gns_spread_rollup (no prefixes) and gns_spread_rollup_prefix behind their argument checks
+static int spr_rollup(gns_exs *dst, gns_ex *src, const gns_prefix *fpx, const gns_prefix *epx, uint64_t since, uint64_t *cursor,
+               uint64_t out[2]) {
     if (!dst->has_layout) {
         set_error("spread rollup: dst was created without field layouts (key sizes only): nothing names the fields to project");
         return GNS_E_ARG;
@@ -1228,7 +1348,9 @@ int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *curso
     ExTableRef S;
     ex_table_ref(src, &S);
     SprPlan pl;
+    SprPxPlan pp;
     GNS_TRY(spr_make_plan(S.kp, dst->kpm, dst->Kf, &pl));
+    if (fpx) GNS_TRY(spr_make_px_plan(S.kp, dst->kpm, dst->Kf, *fpx, *epx, &pp));
     if (dst->device != S.device) {
         set_error("spread rollup: dst is on device %d, src on device %d", dst->device, S.device);
         return GNS_E_ARG;
@@ -1267,8 +1389,12 @@ int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *curso
         {
             ScopedStage st(dst->timer, 3);
             const dim3 g((unsigned)((end - beg + 256 * kSprIt - 1) / (256 * kSprIt))), b(256);
-            if (words) hipLaunchKernelGGL((k_spr_project<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
-                                          (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
+            if (fpx && words) hipLaunchKernelGGL((k_spr_project_px<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
+                                                 (unsigned long long)since, pp, df, de, kExsStageRows, dst->ctl + 6);
+            else if (fpx) hipLaunchKernelGGL((k_spr_project_px<false>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
+                                             (unsigned long long)since, pp, df, de, kExsStageRows, dst->ctl + 6);
+            else if (words) hipLaunchKernelGGL((k_spr_project<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
+                                               (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
             else hipLaunchKernelGGL((k_spr_project<false>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
                                     (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
             GNS_HIP(hipGetLastError());
@@ -1286,6 +1412,20 @@ int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *curso
     if (cursor) *cursor = S.pos;
     if (out) { out[0] = projected; out[1] = dst->pclaimed - pairs0; }
     return GNS_OK;
+}
+}  // namespace
+
+int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *cursor, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    return spr_rollup(dst, src, nullptr, nullptr, since, cursor, out);
+}
+
+int gns_spread_rollup_prefix(gns_exs *dst, gns_ex *src, const gns_prefix *flow_px, const gns_prefix *elem_px,
+                             uint64_t since, uint64_t *cursor, uint64_t out[2]) {
+    if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(px_check_prefix(flow_px, "spread rollup"));
+    GNS_TRY(px_check_prefix(elem_px, "spread rollup"));
+    return spr_rollup(dst, src, flow_px, elem_px, since, cursor, out);
 }
 
 int gns_exs_counters(gns_exs *h, uint64_t out[8]) {

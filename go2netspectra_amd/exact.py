@@ -120,6 +120,99 @@ def to16_to_encodeflow(keys, fields: Sequence[str]) -> np.ndarray:
     return out
 
 
+def _prefix_bits(what: str, v):
+    """(IPv4 bits, IPv6 bits) of one field's prefix: None keeps the field whole, a lone int is the
+    IPv4 length with IPv6 kept whole, a pair gives both."""
+    if v is None:
+        return 32, 128
+    if isinstance(v, (int, np.integer)):
+        v = (v, 128)
+    v = tuple(v)
+    if len(v) != 2:
+        raise ValueError(f"prefix of {what}: an IPv4 length or (IPv4 length, IPv6 length)")
+    v4, v6 = int(v[0]), int(v[1])
+    if not (0 <= v4 <= 32 and 0 <= v6 <= 128):
+        raise ValueError(f"prefix of {what}: ({v4}, {v6}) outside (0..32, 0..128)")
+    return v4, v6
+
+
+def make_prefix(prefix) -> "_lib.Prefix":
+    """gns_prefix of ``{"SrcIP": (24, 48), "DstIP": 16}``: per IP field the leading bits kept of an
+    IPv4 and of an IPv6 value (``_prefix_bits``); a field left out, and None, keep everything."""
+    prefix = dict(prefix or {})
+    for k in prefix:
+        if k not in ("SrcIP", "DstIP"):
+            raise ValueError(f"prefix: {k!r} is not an IP field (SrcIP, DstIP)")
+    px = _lib.Prefix()
+    px.src_v4, px.src_v6 = _prefix_bits("SrcIP", prefix.get("SrcIP"))
+    px.dst_v4, px.dst_v6 = _prefix_bits("DstIP", prefix.get("DstIP"))
+    return px
+
+
+def _prefix_byte(bits: int, b: int) -> int:
+    """The mask byte of byte ``b`` of a value whose leading ``bits`` bits are kept."""
+    k = min(max(bits - 8 * b, 0), 8)
+    return (0xFF00 >> k) & 0xFF
+
+
+def mask_prefix(keys16, v4_bits: int, v6_bits: int) -> np.ndarray:
+    """The mask of gns_ex_rollup_prefix on IP values [n, 16] in To16 form: a value that is IPv4
+    (bytes 0..9 zero, bytes 10, 11 ff ff) keeps bytes 0..11 and the leading ``v4_bits`` bits of
+    bytes 12..15, every other value keeps its leading ``v6_bits`` bits; the rest are zeroed.  Only
+    trailing bits are cleared: no value changes class, the mask is idempotent, and a coarser
+    mask over a finer one is the coarser one."""
+    v4_bits, v6_bits = _prefix_bits("mask_prefix", (v4_bits, v6_bits))
+    keys = np.ascontiguousarray(keys16, np.uint8).reshape(-1, 16)
+    m4 = np.array([0xFF] * 12 + [_prefix_byte(v4_bits, b) for b in range(4)], np.uint8)
+    m6 = np.array([_prefix_byte(v6_bits, b) for b in range(16)], np.uint8)
+    v4 = (keys[:, :10] == 0).all(1) & (keys[:, 10:12] == 0xFF).all(1)
+    return keys & np.where(v4[:, None], m4[None, :], m6[None, :])
+
+
+def mask_keys(keys, fields: Sequence[str], prefix) -> np.ndarray:
+    """Key rows [n, K] laid out by ``fields`` (IPs in To16 form) with every IP field masked by
+    ``prefix`` (``make_prefix``'s argument): ``mask_prefix`` per field, other bytes copied."""
+    px = make_prefix(prefix)
+    bits = {"SrcIP": (px.src_v4, px.src_v6), "DstIP": (px.dst_v4, px.dst_v6)}
+    K = sum(_lib.FIELD_SIZE.get(f, 0) for f in fields)
+    out = np.ascontiguousarray(keys, np.uint8).reshape(-1, K).copy()
+    off = 0
+    for f in fields:
+        if f in bits:
+            out[:, off:off + 16] = mask_prefix(out[:, off:off + 16], *bits[f])
+        off += _lib.FIELD_SIZE.get(f, 0)
+    return out
+
+
+def prefix_plan(src_fields: Sequence[str], dst_fields: Sequence[str], prefix=None, encodeflow: bool = False):
+    """The tables of a masked gather, as gns_ex_rollup_prefix builds them (``encodeflow``: as
+    gns_spread_rollup_prefix builds them for one row): per byte j of the key laid out by
+    ``dst_fields``, (g, field, m4, m6) -- ``rollup_plan``'s source offset, the IP field the byte
+    belongs to (0 SrcIP, 1 DstIP, 2 none), and the mask byte applied when that field's value is
+    IPv4 / is not.  Bytes outside IP fields carry 0xff in both.  For a To16 key m4 keeps bytes
+    0..11 and counts the prefix in bytes 12..15; for an EncodeFlow row the IPv4 address sits in
+    bytes 0..3 and the prefix is counted there."""
+    g = rollup_plan(src_fields, dst_fields)
+    px = make_prefix(prefix)
+    bits = {"SrcIP": (0, px.src_v4, px.src_v6), "DstIP": (1, px.dst_v4, px.dst_v6)}
+    field, m4, m6 = [], [], []
+    for f in dst_fields:
+        size = _lib.FIELD_SIZE.get(f, 0)
+        if f not in bits:
+            field += [2] * size
+            m4 += [0xFF] * size
+            m6 += [0xFF] * size
+            continue
+        i, v4, v6 = bits[f]
+        field += [i] * 16
+        if encodeflow:
+            m4 += [_prefix_byte(v4, b) for b in range(4)] + [0xFF] * 12
+        else:
+            m4 += [0xFF] * 12 + [_prefix_byte(v4, b) for b in range(4)]
+        m6 += [_prefix_byte(v6, b) for b in range(16)]
+    return g, field, m4, m6
+
+
 def spread_rollup_plan(src_fields: Sequence[str], flow_fields: Sequence[str], elem_fields: Sequence[str]):
     """The two byte gathers of a spread roll-up, as gns_spread_rollup builds them: (flow plan,
     element plan), each a ``rollup_plan`` from the key laid out by ``src_fields``.  ValueError
@@ -143,14 +236,29 @@ def _small_int(name: str, v, hi: int) -> int:
     return v
 
 
-def make_filter(src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None) -> "_lib.ExFilter":
+def parse_cidr(ip):
+    """(To16 bytes, leading bits of the 16-byte form that must match) of an address or a CIDR
+    string: "10.1.0.0/16" -> 96 + 16 bits, "2001:db8::/32" -> 32, an address without a length ->
+    128.  The address is kept as written: bits below the prefix are ignored by the filter."""
+    if isinstance(ip, str) and "/" in ip:
+        a = ipaddress.ip_interface(ip)
+        return ip_to16(str(a.ip)), a.network.prefixlen + (96 if a.version == 4 else 0)
+    return ip_to16(ip), 128
+
+
+def make_filter(src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None):
     """gns_ex_filter of an AggregationRequest (querier.go:19-26, :143-170): every field
-    given must equal the flow's; None (and "" for an IP, as the reference) leaves it open."""
+    given must equal the flow's; None (and "" for an IP, as the reference) leaves it open.
+    An IP given as a CIDR string ("10.1.0.0/16", "2001:db8::/32") must match in its prefix only;
+    the result is then a gns_ex_cidr (``_lib.ExCidr``), which every call that takes a filter
+    accepts too."""
     f = _lib.ExFilter()
+    bits = {"SrcIP": 128, "DstIP": 128}
     for name, ip, dst in (("SrcIP", src_ip, f.src16), ("DstIP", dst_ip, f.dst16)):
         if ip is None or (isinstance(ip, str) and ip == ""):
             continue
-        dst[:] = list(ip_to16(ip))
+        b16, bits[name] = parse_cidr(ip)
+        dst[:] = list(b16)
         f.mask |= 1 << _lib.FIELD_IDS[name]
     if src_port is not None:
         f.sport = _small_int("SrcPort", src_port, 0xFFFF)
@@ -161,14 +269,34 @@ def make_filter(src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol
     if protocol is not None:
         f.proto = _small_int("Protocol", protocol, 0xFF)
         f.mask |= 1 << _lib.FIELD_IDS["Protocol"]
+    if bits["SrcIP"] != 128 or bits["DstIP"] != 128:
+        return as_cidr(f, bits["SrcIP"], bits["DstIP"])
     return f
+
+
+def as_cidr(f, src_bits: int = 128, dst_bits: int = 128) -> "_lib.ExCidr":
+    """gns_ex_cidr of a filter: SrcIP / DstIP compared in their leading bits of the 16-byte form
+    (an IPv4 /24 is 120; 128 is equality).  An ExCidr is returned as it is."""
+    if isinstance(f, _lib.ExCidr):
+        return f
+    c = _lib.ExCidr()
+    ct.memmove(ct.byref(c.f), ct.byref(f), ct.sizeof(_lib.ExFilter))
+    c.src_bits, c.dst_bits = _small_int("SrcIP bits", src_bits, 128), _small_int("DstIP bits", dst_bits, 128)
+    return c
+
+
+def _filter_parts(f):
+    """(gns_ex_filter, SrcIP bits, DstIP bits) of either kind of filter."""
+    if isinstance(f, _lib.ExCidr):
+        return f.f, int(f.src_bits), int(f.dst_bits)
+    return f, 128, 128
 
 
 _FLOW_KEY_ARG = {"SrcIP": "src_ip", "DstIP": "dst_ip", "SrcPort": "src_port", "DstPort": "dst_port",
                  "Protocol": "protocol"}
 
 
-def filter_from_flow_keys(flow_keys) -> "_lib.ExFilter":
+def filter_from_flow_keys(flow_keys):
     """gns_ex_filter of TraceFlowRequest.FlowKeys (appendTraceFlowFilters, querier.go:172-188)."""
     for k in sorted(flow_keys):
         if k not in _FLOW_KEY_ARG:
@@ -177,12 +305,16 @@ def filter_from_flow_keys(flow_keys) -> "_lib.ExFilter":
 
 
 def check_filter(f) -> None:
+    f, sb, db = _filter_parts(f)
     if int(f.mask) & ~_FIELD_MASK:
         raise ValueError(f"filter mask {int(f.mask):#x} has bits outside the five key fields")
+    if sb > 128 or db > 128:
+        raise ValueError(f"filter prefix of {sb} / {db} bits (0..128 of the 16-byte form)")
 
 
 def filter_fields(f) -> List[str]:
     """Names of the fields a filter constrains."""
+    f = _filter_parts(f)[0]
     return [n for n in FLOW_KEYS if int(f.mask) >> _lib.FIELD_IDS[n] & 1]
 
 
@@ -195,13 +327,16 @@ def filter_key_bytes(f, key_fields: Sequence[str]):
     want = set(filter_fields(f))
     if not want <= set(key_fields):
         return None
+    f, sb, db = _filter_parts(f)
+    bits = {"SrcIP": sb, "DstIP": db}
     vals = {"SrcIP": bytes(f.src16), "DstIP": bytes(f.dst16), "SrcPort": struct.pack(">H", f.sport),
             "DstPort": struct.pack(">H", f.dport), "Protocol": bytes([f.proto])}
     mask, value = bytearray(), bytearray()
     for name in key_fields:
         size = _lib.FIELD_SIZE.get(name, 0)
-        mask += (b"\xff" if name in want else b"\x00") * size
-        value += vals[name] if name in want else bytes(size)
+        m = bytes(_prefix_byte(bits.get(name, 8 * size), b) if name in want else 0 for b in range(size))
+        mask += m
+        value += bytes(v & k for v, k in zip(vals[name], m))  # address bits below a prefix are ignored
     return np.frombuffer(bytes(mask), np.uint8), np.frombuffer(bytes(value), np.uint8)
 
 
@@ -250,16 +385,20 @@ def _snapshot_arrays(fn, h, key_bytes: int):
     return keys[:m, :key_bytes], st[:m], en[:m], pk[:m], by[:m]
 
 
-def _aggregate(fn, h, filters) -> List[Summary]:
-    flt = [f if isinstance(f, _lib.ExFilter) else make_filter(**f) for f in filters]
+def _aggregate(fn, fn_cidr, h, filters) -> List[Summary]:
+    """One batch through gns_ex[_view]_aggregate, or through its _cidr form when any filter of
+    the batch is a gns_ex_cidr (the others enter it with 128 bits: equality)."""
+    flt = [f if isinstance(f, (_lib.ExFilter, _lib.ExCidr)) else make_filter(**f) for f in filters]
     for f in flt:
         check_filter(f)
     n = len(flt)
     if n == 0:
         return []
-    arr = (_lib.ExFilter * n)(*flt)
     out = (_lib.ExSummary * n)()
-    check(fn(h, arr, n, out))
+    if any(isinstance(f, _lib.ExCidr) for f in flt):
+        check(fn_cidr(h, (_lib.ExCidr * n)(*[as_cidr(f) for f in flt]), n, out))
+    else:
+        check(fn(h, (_lib.ExFilter * n)(*flt), n, out))
     return [Summary(int(o.flows), int(o.packets), int(o.bytes), int(o.first_ns), int(o.last_ns),
                     int(o.max_packets), int(o.max_bytes)) for o in out]
 
@@ -290,6 +429,52 @@ def apply_delta(state: dict, arrays) -> dict:
     out = dict(state)
     for i in range(len(pk)):
         out[bytes(keys[i])] = (int(st[i]), int(en[i]), int(pk[i]), int(by[i]))
+    return out
+
+
+def check_levels(levels):
+    """The levels of hierarchical heavy hitters as a list of (IPv4 bits, IPv6 bits), finest
+    first; ValueError unless each level is at most as long as the one before in both classes."""
+    levels = [_prefix_bits("level", lv) for lv in levels]
+    if not levels:
+        raise ValueError("hierarchical heavy hitters: no levels")
+    for a, b in zip(levels, levels[1:]):
+        if b[0] > a[0] or b[1] > a[1]:
+            raise ValueError(f"hierarchical heavy hitters: level {b} is not coarser than {a}")
+    return levels
+
+
+def discount_heavy_prefixes(lists, levels, threshold: int):
+    """The host step of hierarchical heavy hitters.  ``lists[l]`` = (keys [n, 16] To16 bytes
+    masked to ``levels[l]``, totals [n]) of the prefixes of level l whose total is >= threshold
+    (``heavy_hitters`` of the level's table), finest level first.  From finest to coarsest, a
+    prefix's conditioned count is its total minus the totals of the reported prefixes below it
+    that have no reported prefix strictly between; it is reported iff that is >= threshold.  A
+    prefix heavy by its total alone and discounted below the threshold is not reported and
+    discounts nothing.  The lists suffice: a conditioned count never exceeds the total, so every
+    reported prefix, and with it everything that discounts an ancestor, is in its level's list.
+    Returns per level [(key bytes, total, conditioned), ...] in the list's order."""
+    levels = check_levels(levels)
+    if len(lists) != len(levels):
+        raise ValueError("hierarchical heavy hitters: one list per level")
+    open_, out = [], []  # open_: [key bytes, total] of reported prefixes no reported ancestor covers yet
+    for (keys, totals), lv in zip(lists, levels):
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, 16)
+        below: Dict[bytes, List[int]] = {}
+        if open_:
+            up = mask_prefix(np.frombuffer(b"".join(k for k, _ in open_), np.uint8).reshape(-1, 16), *lv)
+            for i, row in enumerate(up):
+                below.setdefault(row.tobytes(), []).append(i)
+        rows, covered = [], set()
+        for k, t in zip(keys, totals):
+            k, t = k.tobytes(), int(t)
+            kids = below.get(k, [])
+            cond = t - sum(open_[i][1] for i in kids)
+            if cond >= threshold:
+                rows.append((k, t, cond))
+                covered.update(kids)
+        open_ = [o for i, o in enumerate(open_) if i not in covered] + [[k, t] for k, t, _ in rows]
+        out.append(rows)
     return out
 
 
@@ -358,7 +543,7 @@ class ExactView:
 
     def aggregate(self, filters) -> List[Summary]:
         """ExactAggregator.aggregate over the view's rows."""
-        return _aggregate(self._L.gns_ex_view_aggregate, self._h, filters)
+        return _aggregate(self._L.gns_ex_view_aggregate, self._L.gns_ex_view_aggregate_cidr, self._h, filters)
 
     def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0):
         """ExactAggregator.heavy_hitters over the view's rows."""
@@ -496,61 +681,101 @@ class ExactAggregator:
         if n:
             check(self._L.gns_ex_merge(self._h, *[_ptr(a) for a in arrs], n, where))
 
-    def rollup_from(self, src: "ExactAggregator"):
+    def rollup_from(self, src: "ExactAggregator", prefix=None):
         """gns_ex_rollup: re-key the flows of ``src`` onto this handle's layout, on the device.
         The flows that share one projected key enter as one pseudo-record under the rule of
         ``merge``: summed counts, the start of the constituent earliest and the end of the one
         latest in src's stream.  Into an empty handle the result equals an aggregator of this
         layout fed src's packets.  src is only read.  Returns (flows of src projected, flows
-        new in this handle)."""
+        new in this handle).
+
+        ``prefix`` (gns_ex_rollup_prefix): ``{"SrcIP": (24, 48), "DstIP": 16}`` masks the projected
+        key's IP fields to their leading bits -- (IPv4 bits, IPv6 bits), a lone int the IPv4
+        length with IPv6 kept whole -- as ``mask_prefix`` does; the result then equals an
+        aggregator of this layout fed src's packets with their addresses masked.  A prefix for
+        a field this layout lacks is ignored.  None takes the unmasked entry point."""
         if not isinstance(src, ExactAggregator):
             raise TypeError("rollup_from takes an ExactAggregator")
         if src is not self:  # (dst is src: GNS_E_ARG from the library)
             rollup_plan(src.key_fields, self.key_fields)
         out = (ct.c_uint64 * 2)()
-        check(self._L.gns_ex_rollup(self._h, src._h, out))
+        if prefix is None:
+            check(self._L.gns_ex_rollup(self._h, src._h, out))
+        else:
+            px = make_prefix(prefix)
+            check(self._L.gns_ex_rollup_prefix(self._h, src._h, ct.byref(px), out))
         return int(out[0]), int(out[1])
 
-    def rollup(self, key_fields: Sequence[str], **kw) -> "ExactAggregator":
+    def rollup(self, key_fields: Sequence[str], prefix=None, **kw) -> "ExactAggregator":
         """A new aggregator on the same device keyed on ``key_fields`` (fields of this handle's
-        layout, in any order) and filled by ``rollup_from(self)``; ``kw`` as the constructor's."""
+        layout, in any order) and filled by ``rollup_from(self, prefix)``; ``kw`` as the
+        constructor's."""
         rollup_plan(self.key_fields, key_fields)
+        if prefix is not None:
+            make_prefix(prefix)
         kw.setdefault("device", self.device)
         dst = ExactAggregator(key_fields, **kw)
         try:
-            dst.rollup_from(self)
+            dst.rollup_from(self, prefix)
         except Exception:
             dst.close()
             raise
         return dst
 
-    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], **kw):
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], flow_prefix=None, elem_prefix=None, **kw):
         """A new ExactSpread on the same device -- distinct ``elem_fields`` values per
         ``flow_fields`` value, both made of fields of this handle's key -- filled by
         ``ExactSpread.rollup_from(self)``: what a spread handle of those layouts fed the same
-        packets holds (IPv4-mapped arrivals counted with their IPv4 address).  ``kw`` as
-        ExactSpread's constructor."""
+        packets holds (IPv4-mapped arrivals counted with their IPv4 address).  ``flow_prefix`` /
+        ``elem_prefix`` (``rollup_from``'s ``prefix``) mask the IP fields of the flow / element
+        row: hosts per source /24 is ``spread(["SrcIP"], ["SrcIP"], flow_prefix={"SrcIP": 24})``.
+        ``kw`` as ExactSpread's constructor."""
         from .spread import ExactSpread
         spread_rollup_plan(self.key_fields, flow_fields, elem_fields)
         kw.setdefault("device", self.device)
         dst = ExactSpread(flow_fields, elem_fields, **kw)
         try:
-            dst.rollup_from(self)
+            dst.rollup_from(self, flow_prefix=flow_prefix, elem_prefix=elem_prefix)
         except Exception:
             dst.close()
             raise
         return dst
 
     def aggregate(self, filters) -> List[Summary]:
-        """gns_ex_aggregate: one Summary per filter (``make_filter`` values, or dicts of its
-        arguments) from one device scan per 64 filters; nothing but the answers leaves the GPU."""
-        return _aggregate(self._L.gns_ex_aggregate, self._h, filters)
+        """gns_ex_aggregate: one Summary per filter (``make_filter`` values, equality or CIDR, or
+        dicts of its arguments) from one device scan per 64 filters; nothing but the answers
+        leaves the GPU."""
+        return _aggregate(self._L.gns_ex_aggregate, self._L.gns_ex_aggregate_cidr, self._h, filters)
 
     def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0):
         """gns_ex_heavy_hitters: (keys [n, K] canonical bytes, values uint64 [n]) of the flows
         with PacketCount (metric 0) / ByteCount (metric 1) >= threshold, value descending, ties
         by key bytes ascending, cut to ``limit`` rows when limit != 0."""
         return _heavy_hitters(self._L.gns_ex_heavy_hitters, self._h, self.key_bytes, metric, threshold, limit)
+
+    def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int):
+        """Exact hierarchical heavy hitters of one IP field: ``levels`` is a list of (IPv4 bits,
+        IPv6 bits) from finest to coarsest, e.g. [(32, 128), (24, 64), (16, 48), (8, 32)].  The
+        table is rolled up to ``[field]`` at the finest level, each coarser level from the one
+        before it, all on the device; ``heavy_hitters(metric, threshold)`` of every level is
+        then discounted on the host (``discount_heavy_prefixes``).  Returns, per level, the list
+        of (prefix key bytes, total, conditioned count) of the prefixes reported, in the
+        canonical list order.  Counts are Python ints; totals are assumed below 2^64."""
+        if field not in ("SrcIP", "DstIP"):
+            raise ValueError(f"hierarchical heavy hitters: {field!r} is not an IP field")
+        levels = check_levels(levels)
+        if threshold < 1:
+            raise ValueError("hierarchical heavy hitters: threshold must be at least 1")
+        lists, made, cur = [], [], self
+        try:
+            for lv in levels:
+                cur = cur.rollup([field], prefix={field: lv})
+                made.append(cur)
+                lists.append(cur.heavy_hitters(metric, threshold))
+        finally:
+            for a in made:
+                a.close()
+        return discount_heavy_prefixes(lists, levels, threshold)
 
     def reset(self) -> None:
         check(self._L.gns_ex_reset(self._h))
@@ -674,17 +899,21 @@ class ExactTask:
         another thread while the task keeps ingesting."""
         return self.snapshot(view.snapshot_arrays())
 
-    def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, **kw) -> "ExactTask":
+    def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, prefix=None, **kw) -> "ExactTask":
         """A full task keyed on ``key_fields`` (fields of this task's key, in any order) holding
         this task's flows re-keyed on the device (ExactAggregator.rollup): what a task configured
-        with that key and fed the same packets holds.  It takes packets, queries, views and
-        checkpoints like any other task."""
-        return ExactTask(name, key_fields, num_shards, agg=self.agg.rollup(key_fields, **kw))
+        with that key and fed the same packets -- their addresses masked by ``prefix``, when one is
+        given -- holds.  It takes packets, queries, views and checkpoints like any other task."""
+        return ExactTask(name, key_fields, num_shards, agg=self.agg.rollup(key_fields, prefix=prefix, **kw))
 
-    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], **kw):
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], flow_prefix=None, elem_prefix=None, **kw):
         """The exact spread table of this task's flows (ExactAggregator.spread): SuperSpread's
         ground truth for those layouts without a spread engine on the ingest path."""
-        return self.agg.spread(flow_fields, elem_fields, **kw)
+        return self.agg.spread(flow_fields, elem_fields, flow_prefix=flow_prefix, elem_prefix=elem_prefix, **kw)
+
+    def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int):
+        """ExactAggregator.hierarchical_heavy_hitters of this task's table."""
+        return self.agg.hierarchical_heavy_hitters(field, levels, metric, threshold)
 
     def reset(self) -> None:
         self.agg.reset()

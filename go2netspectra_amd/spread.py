@@ -225,15 +225,19 @@ class ExactSpread:
         check(self._L.gns_pairs_merge_from(self._h, other._h, since, ct.byref(cur)))
         return int(cur.value)
 
-    def rollup_from(self, src, since: int = 0):
+    def rollup_from(self, src, since: int = 0, flow_prefix=None, elem_prefix=None):
         """gns_spread_rollup: union with the (flow, element) pairs of the flows an
         ExactAggregator holds, projected onto this handle's layouts on the device and converted
         from its To16 keys to EncodeFlow form.  Into an empty handle the result equals a handle of
         these layouts fed src's packets (an IPv4-mapped arrival counted with its IPv4 address).
         ``since`` (a cursor this call or ``ExactView.refresh`` returned for src) projects only the
         flows first seen after that point; chained into the same handle that keeps it equal to a
-        full roll-up.  src is only read.  Returns (src's cursor, flows projected, pairs new here)."""
-        from .exact import ExactAggregator, spread_rollup_plan
+        full roll-up.  src is only read.  Returns (src's cursor, flows projected, pairs new here).
+
+        ``flow_prefix`` / ``elem_prefix`` (gns_spread_rollup_prefix; ``ExactAggregator.rollup_from``'s
+        ``prefix``) mask the IP fields of the flow row / the element row to their leading bits, on
+        the To16 bytes src stores and before the conversion.  Both None: the unmasked entry point."""
+        from .exact import ExactAggregator, make_prefix, spread_rollup_plan
         if not isinstance(src, ExactAggregator):
             raise TypeError("rollup_from takes an ExactAggregator")
         if since < 0:
@@ -241,7 +245,12 @@ class ExactSpread:
         spread_rollup_plan(src.key_fields, self.flow_fields, self.elem_fields)
         cur = ct.c_uint64(0)
         out = (ct.c_uint64 * 2)()
-        check(self._L.gns_spread_rollup(self._h, src._h, since, ct.byref(cur), out))
+        if flow_prefix is None and elem_prefix is None:
+            check(self._L.gns_spread_rollup(self._h, src._h, since, ct.byref(cur), out))
+        else:
+            fpx, epx = make_prefix(flow_prefix), make_prefix(elem_prefix)
+            check(self._L.gns_spread_rollup_prefix(self._h, src._h, ct.byref(fpx), ct.byref(epx), since, ct.byref(cur),
+                                                   out))
         return int(cur.value), int(out[0]), int(out[1])
 
     def save(self, path) -> None:

@@ -691,6 +691,28 @@ int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const
  *     are cumulative, so a delta is not additive).  (A distinct-flow count per group
  *     is gns_spread_rollup with src's whole key as the element layout.) */
 int gns_ex_rollup(gns_ex *dst, gns_ex *src, uint64_t out[2]);
+/* Prefix roll-up: gns_ex_rollup with the projected key's IP fields masked to a prefix --
+ * "bytes per source /24", "which /16 is the flood coming from" -- on the device.
+ *   - The mask applies to an IP field in the form the key stores it, the 16 bytes of
+ *     net.IP.To16().  A value is IPv4 iff bytes 0..9 are zero and bytes 10, 11 are ff ff.
+ *     An IPv4 value keeps bytes 0..11 and the leading *_v4 bits (0..32) of bytes 12..15;
+ *     every other value keeps its leading *_v6 bits (0..128); the rest are zeroed.  Only
+ *     trailing bits are cleared, so no value changes class, the mask is idempotent, and a
+ *     coarser mask over a finer one is the coarser one (coarser in both classes).  v4 = 0
+ *     sends every IPv4 address to ::ffff:0.0.0.0, v6 = 0 every other address to ::.
+ *     Ports and protocol are never masked.
+ *   - Everything else is gns_ex_rollup's: layouts, one pseudo-record per group under the
+ *     rule of gns_ex_merge, start / end in stream order, positions mapped behind dst's
+ *     stream end, out, pieces (GNS_EX_ROLLUP_PIECE), calling rules.  Consequence: into an
+ *     empty dst the result equals a handle of dst's layout fed src's packets WITH THEIR
+ *     ADDRESSES MASKED, in keys, start, end, pkts and bytes.  With {32,128,32,128} it
+ *     equals gns_ex_rollup bit for bit.  A prefix for a field dst's layout lacks is ignored.
+ *   - dst is a full handle, and can be the source of a coarser prefix roll-up:
+ *     /24 -> /16 -> /8 chained equals each rolled up directly from the flow table.
+ *   - GNS_E_ARG, dst untouched: gns_ex_rollup's cases; px == NULL, *_v4 > 32 or
+ *     *_v6 > 128 (after the null-handle check and before any device call). */
+typedef struct gns_prefix { uint8_t src_v4, src_v6, dst_v4, dst_v6; } gns_prefix;   /* bits kept; {32,128,32,128} keeps all */
+int gns_ex_rollup_prefix(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t out[2]);
 int gns_ex_reset(gns_ex *ex);
 /* out[8]: inserted, dropped, unsupported, dictionary full, flows, records, batches, 0 */
 int gns_ex_counters(gns_ex *ex, uint64_t out[8]);
@@ -731,6 +753,14 @@ typedef struct gns_ex_summary {
  * over the table answers 64 filters; a longer batch takes ceil(nf / 64) passes.
  * nf == 0 is a no-op.  GNS_E_ARG: a null pointer, mask bits outside the five fields. */
 int gns_ex_aggregate(gns_ex *ex, const gns_ex_filter *filters, uint32_t nf, gns_ex_summary *out /* [nf] */);
+/* CIDR filters: a gns_ex_filter whose masked SrcIP / DstIP must match only in their leading
+ * src_bits / dst_bits bits of the 16-byte To16 form -- an IPv4 /24 is 96 + 24 = 120, 128 is
+ * gns_ex_filter's equality, 0 matches every flow whose key has the field.  Bits of the
+ * filter's address below the prefix are ignored.  The bits of a field the mask leaves open
+ * mean nothing.  Everything else is gns_ex_aggregate's (a masked field outside the handle's
+ * layout matches nothing; 64 filters per pass); GNS_E_ARG also for bits above 128. */
+typedef struct gns_ex_cidr { gns_ex_filter f; uint8_t src_bits, dst_bits, _pad[2]; } gns_ex_cidr;  /* bits of the To16 form, 0..128 */
+int gns_ex_aggregate_cidr(gns_ex *ex, const gns_ex_cidr *filters, uint32_t nf, gns_ex_summary *out /* [nf] */);
 /* QueryHeavyHitters ... ORDER BY LatestValue DESC LIMIT ? (querier.go:191-248), and the
  * truth side of Count-Min's heavy hitters (cm_test.go:124-137).
  * metric 0: PacketCount, 1: ByteCount.  Flows with value >= threshold, in the canonical list order
@@ -783,6 +813,8 @@ int gns_ex_view_refresh(gns_ex_view *v, uint64_t since, uint64_t *cursor);
 int gns_ex_view_snapshot(gns_ex_view *v, uint8_t *keys, int64_t *start_ns, int64_t *end_ns,
                          uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
 int gns_ex_view_aggregate(gns_ex_view *v, const gns_ex_filter *f, uint32_t nf, gns_ex_summary *out);
+/* gns_ex_aggregate_cidr over the view's rows, under the rules of gns_ex_view_aggregate */
+int gns_ex_view_aggregate_cidr(gns_ex_view *v, const gns_ex_cidr *f, uint32_t nf, gns_ex_summary *out);
 int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, uint64_t limit,
                               uint8_t *keys, uint64_t *values, uint64_t *n_io);
 
@@ -965,6 +997,22 @@ int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *c
  *     limit) leaves dst with the pairs merged so far; a union is idempotent, so
  *     repeating the call is safe. */
 int gns_spread_rollup(gns_exs *dst, gns_ex *src, uint64_t since, uint64_t *cursor, uint64_t out[2]);
+/* Prefix spread roll-up: gns_spread_rollup with the IP fields of the flow row masked by
+ * flow_px and those of the element row by elem_px (gns_prefix and its mask: see
+ * gns_ex_rollup_prefix).  Both masks apply to the To16 bytes src stores, before the
+ * EncodeFlow rewrite.  The two sides are separate because the prime uses read one field
+ * twice under different masks:
+ *   "distinct source hosts per source /24":  flow = SrcIP under {24,..}, element = SrcIP whole;
+ *   "distinct /24s contacted per host":      flow = SrcIP whole, element = DstIP under {..,24,..}.
+ * The result equals a spread handle of those layouts fed src's packets with their addresses
+ * masked that way.  Everything else -- union semantics, counters, since / cursor (a delta is
+ * a superset of the pairs that changed), out, pieces (GNS_SPREAD_ROLLUP_PIECE), the
+ * IPv4-mapped deviation and the 0.0.0.0 / :: note -- is gns_spread_rollup's.  A prefix for a
+ * field the row's layout lacks is ignored.  GNS_E_ARG, dst untouched: gns_spread_rollup's
+ * cases; a null prefix, *_v4 > 32 or *_v6 > 128 (after the null-handle check and before
+ * any device call). */
+int gns_spread_rollup_prefix(gns_exs *dst, gns_ex *src, const gns_prefix *flow_px, const gns_prefix *elem_px,
+                             uint64_t since, uint64_t *cursor, uint64_t out[2]);
 
 /* Device buffers for callers without a device allocator of their own (the cgo
  * binding's ThriftDecoder: gns_thrift_decode writes device records that

@@ -985,6 +985,97 @@ func (e *Exact) RollupFrom(src *Exact) (projected, added uint64, err error) {
 	return uint64(out[0]), uint64(out[1]), nil
 }
 
+// Prefix is gns_prefix: the leading bits kept of SrcIP and DstIP by a prefix roll-up, per
+// address class.  A value that is IPv4 in its To16 form (::ffff:a.b.c.d) keeps its leading
+// SrcV4 / DstV4 bits (0..32), every other value its leading SrcV6 / DstV6 bits (0..128).
+// FullPrefix keeps everything.
+type Prefix struct {
+	SrcV4, SrcV6, DstV4, DstV6 uint8
+}
+
+// FullPrefix masks nothing: RollupPrefixFrom with it equals RollupFrom.
+var FullPrefix = Prefix{32, 128, 32, 128}
+
+// RollupPrefixFrom is RollupFrom with the projected key's IP fields masked to px
+// (gns_ex_rollup_prefix): "bytes per source /24" is a table keyed on SrcIP rolled up with
+// Prefix{24, 64, 32, 128}.  Into an empty table the result equals a task keyed on this layout
+// and fed src's packets with their addresses masked.  A prefix for a field this layout lacks is
+// ignored.  The result is a full table, and can itself be the source of a coarser roll-up.
+func (e *Exact) RollupPrefixFrom(src *Exact, px Prefix) (projected, added uint64, err error) {
+	if src == nil {
+		return 0, 0, errors.New("sketchgpu: RollupPrefixFrom of a nil source")
+	}
+	cp := C.gns_prefix{src_v4: C.uint8_t(px.SrcV4), src_v6: C.uint8_t(px.SrcV6), dst_v4: C.uint8_t(px.DstV4),
+		dst_v6: C.uint8_t(px.DstV6)}
+	var out [2]C.uint64_t
+	if err = lastErr(C.gns_ex_rollup_prefix(e.h, src.h, &cp, &out[0])); err != nil {
+		return 0, 0, err
+	}
+	return uint64(out[0]), uint64(out[1]), nil
+}
+
+// ExactCIDR is gns_ex_cidr: an ExactFilter whose SrcIP / DstIP, when set, need not match in
+// their trailing SrcHostBits / DstHostBits bits (0..128 of the 16-byte To16 form).  The zero
+// value is ExactFilter's equality, so ExactCIDR{ExactFilter: f} selects what f selects; an IPv4
+// /24 is 8 host bits, an IPv6 /48 is 80, and 128 matches every flow whose key has the field.
+// Address bits inside the host part are ignored.
+type ExactCIDR struct {
+	ExactFilter
+	SrcHostBits, DstHostBits uint8
+}
+
+// CIDROf is the ExactCIDR of a net.IPNet per address (nil: the field stays open).
+func CIDROf(src, dst *net.IPNet) ExactCIDR {
+	var c ExactCIDR
+	if src != nil {
+		ones, bits := src.Mask.Size()
+		c.SrcIP, c.SrcHostBits = src.IP, uint8(bits-ones)
+	}
+	if dst != nil {
+		ones, bits := dst.Mask.Size()
+		c.DstIP, c.DstHostBits = dst.IP, uint8(bits-ones)
+	}
+	return c
+}
+
+// exactCIDRs lays the filters out as gns_ex_cidr.
+func exactCIDRs(filters []ExactCIDR) ([]C.gns_ex_cidr, error) {
+	plain := make([]ExactFilter, len(filters))
+	for i, f := range filters {
+		plain[i] = f.ExactFilter
+	}
+	cf, err := exactFilters(plain)
+	if err != nil {
+		return nil, err
+	}
+	cc := make([]C.gns_ex_cidr, len(filters))
+	for i, f := range filters {
+		if f.SrcHostBits > 128 || f.DstHostBits > 128 {
+			return nil, fmt.Errorf("sketchgpu: filter %d: %d / %d host bits of a 128-bit address", i, f.SrcHostBits, f.DstHostBits)
+		}
+		cc[i].f = cf[i]
+		cc[i].src_bits, cc[i].dst_bits = C.uint8_t(128-f.SrcHostBits), C.uint8_t(128-f.DstHostBits)
+	}
+	return cc, nil
+}
+
+// AggregateCIDR is Aggregate with prefix matches on the IP fields (gns_ex_aggregate_cidr).
+func (e *Exact) AggregateCIDR(filters []ExactCIDR) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cc, err := exactCIDRs(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_aggregate_cidr(e.h, &cc[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
+}
+
 // Reset is exact.Task.Reset (task.go:194-210).
 func (e *Exact) Reset() { C.gns_ex_reset(e.h) }
 
@@ -1051,6 +1142,23 @@ func (w *ExactView) Aggregate(filters []ExactFilter) ([]ExactSummary, error) {
 	}
 	cs := make([]C.gns_ex_summary, n)
 	if err := lastErr(C.gns_ex_view_aggregate(w.v, &cf[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
+}
+
+// AggregateCIDR is Exact.AggregateCIDR over the view's rows (gns_ex_view_aggregate_cidr).
+func (w *ExactView) AggregateCIDR(filters []ExactCIDR) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cc, err := exactCIDRs(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_view_aggregate_cidr(w.v, &cc[0], C.uint32_t(n), &cs[0])); err != nil {
 		return nil, err
 	}
 	return exactSummaries(cs), nil
