@@ -50,6 +50,24 @@ int set_device(int device) {
     return GNS_OK;
 }
 
+int stream_wait_now(hipStream_t waiter, hipStream_t on, const char *what) {
+    hipEvent_t ev;
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) {
+        e = hipEventRecord(ev, on);
+        if (e == hipSuccess) e = hipStreamWaitEvent(waiter, ev, 0);
+        (void)hipEventDestroy(ev);  // the wait is queued: the runtime keeps what it needs
+    }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+uint64_t test_piece(const char *env_name, uint64_t dflt) {
+    const char *env = getenv(env_name);
+    const unsigned long long v = env ? strtoull(env, nullptr, 10) : 0;
+    return v ? std::min<uint64_t>(v, dflt) : dflt;
+}
+
 InputDesc advance(const InputDesc &in, uint64_t off) {
     InputDesc d = in;
     if (d.hdr) d.hdr += off * 16;

@@ -69,6 +69,14 @@ int check_device(int device);
 // framework's: it must not fail this call's launch checks) and sets the device.
 int set_device(int device);
 
+// Stream `waiter` waits for what is queued on stream `on` now: one handle's kernels reading
+// another's state at this point of its stream.  GNS_E_HIP with "<what>: <runtime's text>".
+int stream_wait_now(hipStream_t waiter, hipStream_t on, const char *what);
+
+// Test-only piece size of a roll-up (GNS_EX_ROLLUP_PIECE, GNS_SPREAD_ROLLUP_PIECE: small
+// tables span many pieces): the variable's value when it is set, nonzero and below dflt.
+uint64_t test_piece(const char *env_name, uint64_t dflt);
+
 // `in` from record `off` on: every per-record array that is set.
 InputDesc advance(const InputDesc &in, uint64_t off);
 

@@ -1339,9 +1339,24 @@ __global__ __launch_bounds__(256) void k_ex_merge_times(const uint32_t *ids, uin
 // smaller first overwrites start and one with a larger first writes nothing;
 // positions are unique per record across flows, so no two rows of a group tie.
 // ---------------------------------------------------------------------------
+// The plan as R1 takes it.  Plain: the gather alone, read as kernel-argument scalars.
+// PX (gns_ex_rollup_prefix: the projected key's IP fields masked to a prefix): the whole
+// RollRow, which the kernel keeps in LDS (one broadcast read per table byte) -- its 160 bytes
+// as kernel-argument scalars would be live across the unrolled gather, where the 74 bytes of
+// k_spr_project's spilled 270 SGPRs.
+template <bool PX>
 struct ExrPlan {
-    uint32_t K, KW;   // destination key bytes / words (a row's key takes KW words)
-    uint8_t g[40];    // source key byte of destination key byte j
+    uint32_t K, KW;  // destination key bytes / words (a row's key takes KW words)
+    uint8_t t[40];   // proj_word<false>'s table: source key byte of destination key byte j
+};
+template <>
+struct ExrPlan<true> {
+    uint32_t K, KW;
+    uint8_t ipoff[4];  // byte offset of SrcIP / DstIP in the source key; 0xFF: not read
+    union {            // proj_word<true>'s tables; as words for the copy into LDS
+        uint8_t t[sizeof(RollRow)];
+        uint32_t w[sizeof(RollRow) / 4];
+    };
 };
 struct ExrRows {
     uint32_t *keys, *ids, *cnt;
@@ -1349,13 +1364,23 @@ struct ExrRows {
     long long *start, *end;
 };
 
-// grid covers slots [s0, s1); at most s1 - s0 rows are appended (R.cnt zeroed by the host)
-__global__ __launch_bounds__(256) void k_exr_project(DictDev S, FlowState sf, uint64_t s0, uint64_t s1, ExrPlan pl,
+// grid covers slots [s0, s1); at most s1 - s0 rows are appended (R.cnt zeroed by the host).
+// PX: a lane takes one IPv4 flag per IP field of its source key -- spr_encode_ip's test, on the
+// unmasked bytes -- and proj_word<true> masks by it: IP fields at any offset.
+template <bool PX>
+__global__ __launch_bounds__(256) void k_exr_project(DictDev S, FlowState sf, uint64_t s0, uint64_t s1, ExrPlan<PX> pl,
                                                      ExrRows R) {
-    // a lane's key words, read back byte by byte through the plan: each lane touches only
-    // its own column, so no barrier is needed and a wave without flows may leave
-    __shared__ uint32_t s_k[GNS_KWMAX][256];
+    __shared__ uint32_t s_k[GNS_KWMAX][256];  // proj_fill_column
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint8_t *t;
+    if constexpr (PX) {
+        __shared__ uint32_t s_pw[40];  // g, fld, m4, m6
+        if (tid < 40) s_pw[tid] = pl.w[tid];
+        __syncthreads();  // before any wave leaves
+        t = reinterpret_cast<const uint8_t *>(s_pw);
+    } else {
+        t = pl.t;  // uniform: scalar loads of the kernel argument
+    }
     const uint64_t s = s0 + (uint64_t)blockIdx.x * 256 + tid;
     unsigned long long pk = 0;
     uint32_t r[12];
@@ -1373,81 +1398,17 @@ __global__ __launch_bounds__(256) void k_exr_project(DictDev S, FlowState sf, ui
     base = __shfl(base, leader);
     if (!occ) return;
     const uint64_t row = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
-#pragma unroll
-    for (int i = 0; i < GNS_KWMAX; i++) {
-        if ((uint32_t)i >= pl.KW) break;  // uniform
-        uint32_t v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = 4 * i + b;
-            if ((uint32_t)j < pl.K) {
-                const uint32_t g = pl.g[j];  // uniform: a scalar load of the kernel argument
-                v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & 0xFFu) << (8 * b);
-            }
-        }
-        R.keys[row * pl.KW + i] = v;
-    }
-    R.pkts[row] = pk; R.bytes[row] = sf.bytes[s]; R.first[row] = sf.first[s]; R.last[row] = sf.last[s];
-    R.start[row] = sf.start[s]; R.end[row] = sf.end[s];
-}
-
-// Prefix roll-up (gns_ex_rollup_prefix): R1 with the projected key's IP fields masked to a
-// prefix.  Per destination key byte the plan holds the gather index g, the IP field the byte
-// belongs to (0 SrcIP, 1 DstIP, 2 none) and two mask bytes: m4 applies when the field's value
-// is IPv4 (::ffff:a.b.c.d: bytes 0..11 kept, the prefix counted in bytes 12..15), m6 when it
-// is anything else; bytes outside IP fields carry 0xff in both.  A lane takes one IPv4 flag
-// per IP field of its source key -- spr_encode_ip's test, on the unmasked bytes -- and writes
-// byte & (v4[field] ? m4 : m6): branch-free, any bit length, IP fields at any offset.  The
-// plan sits in LDS (one broadcast read per table byte): its 160 bytes as kernel-argument
-// scalars would be live across the unrolled gather, where the 74 bytes of k_spr_project's
-// spilled 270 SGPRs.
-struct ExrPxPlan {
-    uint32_t K, KW;      // destination key bytes / words
-    uint8_t ipoff[4];    // byte offset of SrcIP / DstIP in the source key; 0xFF: not read
-    union {              // as words for the copy into LDS
-        struct { uint8_t g[40], fld[40], m4[40], m6[40]; };
-        uint32_t w[40];
-    };
-};
-
-// grid covers slots [s0, s1); at most s1 - s0 rows are appended (R.cnt zeroed by the host)
-__global__ __launch_bounds__(256) void k_exr_project_px(DictDev S, FlowState sf, uint64_t s0, uint64_t s1, ExrPxPlan pl,
-                                                        ExrRows R) {
-    __shared__ uint32_t s_k[GNS_KWMAX][256];  // a lane's key words: each lane touches only its own column
-    __shared__ uint32_t s_pw[40];             // g, fld, m4, m6
-    const uint8_t *s_g = reinterpret_cast<const uint8_t *>(s_pw);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    if (tid < 40) s_pw[tid] = pl.w[tid];
-    __syncthreads();  // before any wave leaves
-    const uint64_t s = s0 + (uint64_t)blockIdx.x * 256 + tid;
-    unsigned long long pk = 0;
-    uint32_t r[12];
-    bool occ = false;
-    if (s < s1) {
-        load_record(S, (uint32_t)s, r);
-        pk = sf.pkts[s];
-        occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
-    }
-    const uint64_t m = __ballot(occ);
-    if (m == 0) return;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(R.cnt, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (!occ) return;
-    const uint64_t row = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+    proj_fill_column(s_k, tid, r);
     uint32_t v4 = 0;  // bit f: IP field f of this flow is IPv4
+    if constexpr (PX) {
 #pragma unroll
-    for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
-        if (pl.ipoff[f] != 0xFFu) v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
+        for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
+            if (pl.ipoff[f] != 0xFFu) v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
+    }
 #pragma unroll
     for (int i = 0; i < GNS_KWMAX; i++) {
         if ((uint32_t)i >= pl.KW) break;  // uniform
-        R.keys[row * pl.KW + i] = px_masked_word(s_k, tid, s_g, v4, pl.K, i);
+        R.keys[row * pl.KW + i] = proj_word<PX>(s_k, tid, t, v4, pl.K, i);
     }
     R.pkts[row] = pk; R.bytes[row] = sf.bytes[s]; R.first[row] = sf.first[s]; R.last[row] = sf.last[s];
     R.start[row] = sf.start[s]; R.end[row] = sf.end[s];
@@ -2014,7 +1975,7 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
                 memset(want + kSpan[fld].base, 1, kSpan[fld].len);
                 const uint32_t bits = fld <= GNS_F_DSTIP ? filters.bits(i, fld) : 8 * kSpan[fld].len;
                 for (uint32_t b = 0; b < kSpan[fld].len; b++)
-                    tm[kSpan[fld].base + b] = 8 * b + 8 <= bits ? 0xFF : 8 * b >= bits ? 0 : (uint8_t)(0xFF00u >> (bits - 8 * b));
+                    tm[kSpan[fld].base + b] = px_prefix_byte(bits, b);
             }
         ExQFilter &w = hf[i];
         memset(&w, 0, sizeof(w));
@@ -2191,6 +2152,26 @@ int exv_rows(gns_ex_view *v) {
     return GNS_OK;
 }
 
+// The ids of a piece of m key rows (device memory, <= kResolvePiece; row i is live when
+// vals[i] != 0) on ex's table, which grows as the rows need: no state is written before every
+// id of the piece is known.  *added, when given, grows by the slots the piece claimed.
+int ex_resolve_rows(gns_ex *ex, const uint8_t *keys, uint32_t stride, uint64_t m, const unsigned long long *vals,
+                    uint32_t *ids, KeyResolveScratch &sc, uint64_t *added) {
+    hipStream_t s = ex->stream;
+    if (ex->claimed >= ex->slots / 2) GNS_TRY(ex_grow(ex));  // keep the load <= ~1/2
+    KeyResolve r{};
+    r.keys = keys; r.stride = stride; r.n = m; r.live = KEYS_VAL64; r.vals = vals; r.ids = ids;
+    r.full_word = ex->stats + 3;
+    for (;;) {
+        const uint64_t before = ex->claimed;
+        const int rc = dict_resolve_keys(ex->D, ex->epoch, r, sc, s, &ex->claimed, &ex->timer, 1);
+        if (rc == GNS_OK && added) *added += ex->claimed - before;
+        if (rc != GNS_E_FULL) return rc;
+        GNS_HIP(hipMemsetAsync(ex->stats + 3, 0, sizeof(unsigned long long), s));
+        ex->n_retry++;
+        GNS_TRY(ex_grow(ex));  // the state already written follows the table; the piece's claims are dropped
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -2588,17 +2569,7 @@ int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const
                 stage_add(l, db, m * 8, &db);
                 GNS_TRY(ex->stage.copy(l, s));
             }
-            if (ex->claimed >= ex->slots / 2) GNS_TRY(ex_grow(ex));  // keep the load <= ~1/2
-            KeyResolve r{};
-            r.keys = dk; r.stride = ex->K; r.n = m; r.live = KEYS_VAL64; r.vals = dp; r.ids = ids;
-            r.full_word = ex->stats + 3;
-            for (;;) {  // no state is written before every id of the piece is known
-                const int rc = dict_resolve_keys(ex->D, ex->epoch, r, sc, s, &ex->claimed, &ex->timer, 1);
-                if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
-                GNS_HIP(hipMemsetAsync(ex->stats + 3, 0, sizeof(unsigned long long), s));
-                ex->n_retry++;
-                GNS_TRY(ex_grow(ex));  // the flow state follows the table; the piece's claims are dropped
-            }
+            GNS_TRY(ex_resolve_rows(ex, dk, ex->K, m, dp, ids, sc, nullptr));
             const unsigned long long base = ex->pkt + ex->merged;
             const dim3 grid((unsigned)((m + 255) / 256));
             hipLaunchKernelGGL(k_ex_merge_add, grid, dim3(256), 0, s, ids, m, dp, db, base, ex->f);
@@ -2619,56 +2590,10 @@ int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const
 
 namespace {
 
-// the key field tuple byte t belongs to (make_plan's numbering)
-const char *exr_field_name(uint32_t t) {
-    return t < 16 ? "SrcIP" : t < 32 ? "DstIP" : t < 34 ? "SrcPort" : t < 36 ? "DstPort" : "Protocol";
-}
-
-// Byte gather between two layouts: every byte of dst's key from the first place src's key
-// holds it.  GNS_E_ARG when a field of dst is not part of src.
-int exr_make_plan(const KeyPlanN &src, const KeyPlanN &dst, ExrPlan *pl) {
-    memset(pl, 0, sizeof(*pl));
-    pl->K = dst.K;
-    pl->KW = (dst.K + 3) / 4;
-    for (uint32_t j = 0; j < dst.K; j++) {
-        uint32_t i = 0;
-        while (i < src.K && src.src[i] != dst.src[j]) i++;
-        if (i == src.K) {
-            set_error("rollup: key field %s is not part of the source's layout", exr_field_name(dst.src[j]));
-            return GNS_E_ARG;
-        }
-        pl->g[j] = (uint8_t)i;
-    }
-    return GNS_OK;
-}
-
 void exr_free(ExrRows &R) {
     dfree(R.keys); dfree(R.ids); dfree(R.cnt); dfree(R.pkts); dfree(R.bytes); dfree(R.first); dfree(R.last);
     dfree(R.start); dfree(R.end);
     R = ExrRows{};
-}
-
-// The gather of exr_make_plan with the mask tables of px (checked by the caller): a prefix for
-// a field dst's layout lacks leaves no trace.
-int exr_make_px_plan(const KeyPlanN &src, const KeyPlanN &dst, const gns_prefix &px, ExrPxPlan *pp) {
-    ExrPlan pl;
-    GNS_TRY(exr_make_plan(src, dst, &pl));
-    memset(pp, 0, sizeof(*pp));
-    pp->K = pl.K;
-    pp->KW = pl.KW;
-    memset(pp->ipoff, 0xFF, sizeof(pp->ipoff));
-    const uint32_t v4[2] = {px.src_v4, px.dst_v4}, v6[2] = {px.src_v6, px.dst_v6};
-    for (uint32_t j = 0; j < dst.K; j++) {
-        const uint32_t t = dst.src[j];
-        pp->g[j] = pl.g[j];
-        if (t >= 32) { pp->fld[j] = 2; pp->m4[j] = pp->m6[j] = 0xFF; continue; }
-        const uint32_t f = t >> 4, b = t & 15u;
-        pp->fld[j] = (uint8_t)f;
-        pp->m4[j] = b < 12 ? 0xFF : px_prefix_byte(v4[f], b - 12);
-        pp->m6[j] = px_prefix_byte(v6[f], b);
-        if (b == 0) pp->ipoff[f] = pl.g[j];  // fields are gathered whole: the field starts here in src's key
-    }
-    return GNS_OK;
 }
 
 // gns_ex_rollup (px == nullptr) and gns_ex_rollup_prefix behind their argument checks
@@ -2678,22 +2603,29 @@ static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t o
         set_error("rollup: dst is on device %d, src on device %d", dst->device, src->device);
         return GNS_E_ARG;
     }
-    ExrPlan pl;
-    ExrPxPlan pp;
-    GNS_TRY(exr_make_plan(src->kp, dst->kp, &pl));
-    if (px) GNS_TRY(exr_make_px_plan(src->kp, dst->kp, *px, &pp));
-    GNS_TRY(set_device(dst->device));
-    uint64_t piece = kResolvePiece;
-    if (const char *env = getenv("GNS_EX_ROLLUP_PIECE")) {  // tests: small tables span many pieces
-        const unsigned long long v = strtoull(env, nullptr, 10);
-        if (v) piece = std::min<uint64_t>(v, kResolvePiece);
+    ExrPlan<false> pl{};  // the one the call takes is filled
+    ExrPlan<true> pp{};
+    pl.K = pp.K = dst->kp.K;
+    pl.KW = pp.KW = (dst->kp.K + 3) / 4;
+    int miss;
+    if (px) {
+        RollRow row;
+        memset(pp.ipoff, 0xFF, sizeof(pp.ipoff));
+        miss = roll_tables(src->kp.src, src->kp.K, dst->kp.src, dst->kp.K, px, false, &row, pp.ipoff);
+        memcpy(pp.t, &row, sizeof(pp.t));
+    } else {
+        miss = roll_gather(src->kp.src, src->kp.K, dst->kp.src, dst->kp.K, pl.t);
     }
-    piece = std::min<uint64_t>(piece, src->slots);
+    if (miss >= 0) {
+        set_error("rollup: key field %s is not part of the source's layout", tuple_field_name(dst->kp.src[miss]));
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(dst->device));
+    const uint64_t piece = std::min<uint64_t>(test_piece("GNS_EX_ROLLUP_PIECE", kResolvePiece), src->slots);
     if (out) out[0] = out[1] = 0;
     hipStream_t s = dst->stream;
     ExrRows R{};
     KeyResolveScratch sc;
-    hipEvent_t ev = nullptr;
     uint64_t projected = 0, added = 0;
     bool wrote = false;
     auto run = [&]() -> int {
@@ -2702,40 +2634,20 @@ static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t o
             (rc = dalloc_t(&R.pkts, piece)) || (rc = dalloc_t(&R.bytes, piece)) || (rc = dalloc_t(&R.first, piece)) ||
             (rc = dalloc_t(&R.last, piece)) || (rc = dalloc_t(&R.start, piece)) || (rc = dalloc_t(&R.end, piece)))
             return rc;
-        // after src's pending batches
-        GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        GNS_HIP(hipEventRecord(ev, src->stream));
-        GNS_HIP(hipStreamWaitEvent(s, ev, 0));
+        GNS_TRY(stream_wait_now(s, src->stream, "rollup"));  // after src's pending batches
         const unsigned long long B = dst->pkt + dst->merged;  // source positions lie behind dst's stream end
         for (uint64_t s0 = 0; s0 < src->slots; s0 += piece) {
             const uint64_t s1 = std::min<uint64_t>(s0 + piece, src->slots);
             GNS_HIP(hipMemsetAsync(R.cnt, 0, 4, s));
-            if (px)
-                hipLaunchKernelGGL(k_exr_project_px, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D,
-                                   src->f, s0, s1, pp, R);
-            else
-                hipLaunchKernelGGL(k_exr_project, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0, s, src->D, src->f, s0,
-                                   s1, pl, R);
+            const dim3 grid((unsigned)((s1 - s0 + 255) / 256));
+            if (px) hipLaunchKernelGGL(k_exr_project<true>, grid, dim3(256), 0, s, src->D, src->f, s0, s1, pp, R);
+            else hipLaunchKernelGGL(k_exr_project<false>, grid, dim3(256), 0, s, src->D, src->f, s0, s1, pl, R);
             GNS_HIP(hipGetLastError());
             GNS_HIP(hipMemcpyAsync(dst->h_pin, R.cnt, 4, hipMemcpyDeviceToHost, s));
             GNS_HIP(hipStreamSynchronize(s));
             const uint64_t m = std::min<uint64_t>(dst->h_pin[0], s1 - s0);
             if (m == 0) continue;
-            if (dst->claimed >= dst->slots / 2) GNS_TRY(ex_grow(dst));  // keep the load <= ~1/2
-            KeyResolve r{};
-            r.keys = reinterpret_cast<const uint8_t *>(R.keys); r.stride = 4 * pl.KW; r.n = m; r.live = KEYS_VAL64;
-            r.vals = R.pkts; r.ids = R.ids;
-            r.full_word = dst->stats + 3;
-            uint64_t before;
-            for (;;) {  // no state is written before every id of the piece is known
-                before = dst->claimed;
-                const int rc2 = dict_resolve_keys(dst->D, dst->epoch, r, sc, s, &dst->claimed, &dst->timer, 1);
-                if (rc2 != GNS_E_FULL) { GNS_TRY(rc2); break; }
-                GNS_HIP(hipMemsetAsync(dst->stats + 3, 0, sizeof(unsigned long long), s));
-                dst->n_retry++;
-                GNS_TRY(ex_grow(dst));  // the state earlier pieces wrote follows the table; this piece's claims are dropped
-            }
-            added += dst->claimed - before;
+            GNS_TRY(ex_resolve_rows(dst, reinterpret_cast<const uint8_t *>(R.keys), 4 * pl.KW, m, R.pkts, R.ids, sc, &added));
             wrote = true;
             hipLaunchKernelGGL(k_exr_add, dim3((unsigned)std::min<uint64_t>((m + 255) / 256, 1024)), dim3(256), 0, s, R, m,
                                B, dst->f);
@@ -2753,7 +2665,6 @@ static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t o
         if (rc == GNS_OK) rc = rc2;
     }
     if (hipStreamSynchronize(s) != hipSuccess && rc == GNS_OK) { set_error("rollup: stream synchronize failed"); rc = GNS_E_HIP; }
-    if (ev) (void)hipEventDestroy(ev);
     exr_free(R);
     sc.free_all();
     if (rc == GNS_OK && out) { out[0] = projected; out[1] = added; }

@@ -1,9 +1,10 @@
 // gns_exsrc.hpp -- what another engine may see of an exact aggregator's resident
 // table (gns_exact.hip keeps struct gns_ex private): a read-only reference for
 // kernels that project its flows elsewhere (gns_spread_rollup in gns_spread.hip).
-// Also the one definition of the prefix mask both roll-ups apply (gns_ex_rollup_prefix,
-// gns_spread_rollup_prefix): the address-class test, the mask byte, the range check and the
-// masked byte gather.
+// Also the device half of the projection both roll-ups share (gns_ex_rollup[_prefix],
+// gns_spread_rollup[_prefix]; the plan is gns_rollplan.hpp's): a lane's LDS key column, the
+// address-class test, the EncodeFlow rewrite, the gathered word and the stored row; and the
+// range check of a gns_prefix.
 // Internal: not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 
 #include "gns_common.hpp"
 #include "gns_keys.cuh"
+#include "gns_rollplan.hpp"
 
 struct gns_ex;
 
@@ -30,14 +32,6 @@ struct ExTableRef {
 };
 
 void ex_table_ref(const gns_ex *ex, ExTableRef *out);
-
-// --- the prefix mask -----------------------------------------------------------
-// the mask byte of byte b of a value whose leading `bits` bits are kept
-inline uint8_t px_prefix_byte(uint32_t bits, uint32_t b) {
-    if (8 * b + 8 <= bits) return 0xFF;
-    if (8 * b >= bits) return 0;
-    return (uint8_t)(0xFF00u >> (bits - 8 * b));
-}
 
 // GNS_E_ARG for a null gns_prefix or one outside {0..32, 0..128, 0..32, 0..128}
 inline int px_check_prefix(const gns_prefix *px, const char *what) {
@@ -64,22 +58,91 @@ __device__ __forceinline__ bool px_is_v4(const uint32_t (*s_k)[256], uint32_t ti
     return z == 0u && at(o + 10) == 0xFFu && at(o + 11) == 0xFFu;
 }
 
-// Word i of a K-byte row gathered from the lane's column and masked.  t: the row's tables, 40
-// bytes each -- gather index g, IP field fld (0 SrcIP, 1 DstIP, 2 none), m4, m6; v4: bit f set
-// when IP field f of this flow is IPv4.  Byte j = column byte g[j] & (v4[fld[j]] ? m4[j] : m6[j]).
-__device__ __forceinline__ uint32_t px_masked_word(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *t, uint32_t v4,
-                                                   uint32_t K, int i) {
+// ::ffff:a.b.c.d -> a.b.c.d + 12 zero bytes in the 16 key bytes at offset o (uniform) of the
+// lane's column; every other value stays
+__device__ __forceinline__ void spr_encode_ip(uint32_t (*s_k)[256], uint32_t tid, uint32_t o) {
+    if ((o & 3u) == 0u) {
+        const uint32_t w = o >> 2;
+        if (s_k[w][tid] == 0u && s_k[w + 1][tid] == 0u && s_k[w + 2][tid] == 0xFFFF0000u) {
+            s_k[w][tid] = s_k[w + 3][tid];
+            s_k[w + 1][tid] = 0u; s_k[w + 2][tid] = 0u; s_k[w + 3][tid] = 0u;
+        }
+    } else {
+        uint8_t *col = reinterpret_cast<uint8_t *>(&s_k[0][tid]);  // key byte b: word b / 4 of the column, byte b % 4
+        auto at = [&](uint32_t b) -> uint8_t & { return col[(size_t)(b >> 2) * (256 * 4) + (b & 3u)]; };
+        uint32_t z = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 10; k++) z |= at(o + k);
+        if (z == 0u && at(o + 10) == 0xFFu && at(o + 11) == 0xFFu) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) at(o + k) = at(o + 12 + k);
+#pragma unroll
+            for (uint32_t k = 4; k < 16; k++) at(o + k) = 0;
+        }
+    }
+}
+
+// The key words of record r (load_record's: r[0] is the tag) into the lane's own column, to be
+// read back byte by byte through the plan.  No other lane touches the column, so no barrier is
+// needed and a wave without flows may leave.
+__device__ __forceinline__ void proj_fill_column(uint32_t (*s_k)[256], uint32_t tid, const uint32_t *r) {
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
+}
+
+// Word i of a K-byte row gathered from the lane's column.  t: the row's gather index g, one
+// byte per row byte.  PX: masked as well -- t is a whole RollRow (g, fld, m4, m6 at 40 bytes
+// each) and v4 has bit f set when IP field f of this flow is IPv4:
+// byte j = column byte g[j] & (v4[fld[j]] ? m4[j] : m6[j]), branch-free, any bit length.
+template <bool PX>
+__device__ __forceinline__ uint32_t proj_word(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *t, uint32_t v4,
+                                              uint32_t K, int i) {
     uint32_t v = 0;
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const int j = 4 * i + b;
         if ((uint32_t)j < K) {
-            const uint32_t g = t[j], f = t[40 + j];
-            const uint32_t mk = (v4 >> f & 1u) ? t[80 + j] : t[120 + j];
+            const uint32_t g = t[j];
+            uint32_t mk = 0xFFu;
+            if constexpr (PX) mk = (v4 >> t[40 + j] & 1u) ? t[80 + j] : t[120 + j];
             v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & mk) << (8 * b);
         }
     }
     return v;
+}
+
+// A K-byte row of proj_word's words to `row`.  WORDS: K is a multiple of 4 and the row
+// word-aligned; otherwise byte stores, so a row may start and end inside a word.
+template <bool PX, bool WORDS>
+__device__ __forceinline__ void proj_store_row(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *t, uint32_t v4,
+                                               uint32_t K, uint8_t *row) {
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if (4u * i >= K) break;  // uniform
+        uint32_t v = 0;
+        if constexpr (PX) {
+            v = proj_word<true>(s_k, tid, t, v4, K, i);
+        } else {
+            // proj_word<false>, written out: through the call the compiler leaves this loop over the
+            // words rolled in k_spr_project<false, true> (2764 instructions against 6745); written
+            // out, that kernel is instruction for instruction what it was
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int j = 4 * i + b;
+                if ((uint32_t)j < K) {
+                    const uint32_t g = t[j];
+                    v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & 0xFFu) << (8 * b);
+                }
+            }
+        }
+        if constexpr (WORDS) {
+            reinterpret_cast<uint32_t *>(row)[i] = v;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if ((uint32_t)(4 * i + b) < K) row[4 * i + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
 }
 
 }  // namespace gns

@@ -377,170 +377,55 @@ __global__ __launch_bounds__(256) void k_exs_export(PairDev P, uint64_t beg, uin
 // element row byte by byte through the plan (copied into LDS once per workgroup),
 // each row into words of its own, so a split inside a word costs nothing.
 // Rows at or past cap are counted and not written.
+//
+// PX (gns_spread_rollup_prefix): the IP fields of the flow row and of the element row masked
+// to a prefix, each row by tables of its own -- the prime uses read one field twice
+// ("distinct source hosts per source /24": flow = SrcIP under /24, element = SrcIP whole).
+// The masks are defined on the To16 bytes, so a lane takes its IPv4 flag per IP field BEFORE
+// spr_encode_ip rewrites the column; after the rewrite an IPv4 address sits in bytes 0..3 of
+// the field, and m4 is laid out for that (EncodeFlow) form.
+//
+// The plan: per row (flow, then element) the tables proj_word<PX> reads -- the gather g alone,
+// or a whole RollRow.  They sit in LDS (one broadcast read per byte): as scalars the 74 plan
+// bytes of the widest layout, live across the unrolled runs, spilled 270 SGPRs.
+// The IP fields either row reads: PX keeps them per field, as roll_tables gives them; the plain
+// plan keeps a count and a list (iplist), which the generated code depends on (below).
+template <bool PX>
 struct SprPlan {
+    static constexpr int kRow = 40;  // bytes of a row's tables
     uint32_t Kf, Ke;         // the destination's flow / element key bytes
-    uint32_t nip;            // IP fields of the source key that the layouts read
-    uint8_t ipoff[4];        // their byte offsets in the source key (first occurrences)
-    union {                  // source key byte of flow / element key byte j; as words for the copy into LDS
-        struct { uint8_t gf[40], ge[40]; };
-        uint32_t gw[20];
+    uint32_t nip;            // IP fields of the source key that the rows read
+    uint8_t iplist[4];       // their byte offsets in the source key, in any order
+    union {                  // as words for the copy into LDS
+        uint8_t t[2][kRow];
+        uint32_t w[2 * kRow / 4];
+    };
+};
+template <>
+struct SprPlan<true> {
+    static constexpr int kRow = (int)sizeof(RollRow);
+    uint32_t Kf, Ke;
+    uint8_t ipoff[4];        // byte offset of SrcIP / DstIP in the source key; 0xFF: not read by either row
+    union {
+        uint8_t t[2][kRow];
+        uint32_t w[2 * kRow / 4];
     };
 };
 constexpr int kSprIt = 4;
 
-// ::ffff:a.b.c.d -> a.b.c.d + 12 zero bytes in the 16 key bytes at offset o (uniform) of the
-// lane's column; every other value stays
-__device__ __forceinline__ void spr_encode_ip(uint32_t (*s_k)[256], uint32_t tid, uint32_t o) {
-    if ((o & 3u) == 0u) {
-        const uint32_t w = o >> 2;
-        if (s_k[w][tid] == 0u && s_k[w + 1][tid] == 0u && s_k[w + 2][tid] == 0xFFFF0000u) {
-            s_k[w][tid] = s_k[w + 3][tid];
-            s_k[w + 1][tid] = 0u; s_k[w + 2][tid] = 0u; s_k[w + 3][tid] = 0u;
-        }
-    } else {
-        uint8_t *col = reinterpret_cast<uint8_t *>(&s_k[0][tid]);  // key byte b: word b / 4 of the column, byte b % 4
-        auto at = [&](uint32_t b) -> uint8_t & { return col[(size_t)(b >> 2) * (256 * 4) + (b & 3u)]; };
-        uint32_t z = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 10; k++) z |= at(o + k);
-        if (z == 0u && at(o + 10) == 0xFFu && at(o + 11) == 0xFFu) {
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) at(o + k) = at(o + 12 + k);
-#pragma unroll
-            for (uint32_t k = 4; k < 16; k++) at(o + k) = 0;
-        }
-    }
-}
-
-// WORDS: K is a multiple of 4 and the row word-aligned
-// g: the row's gather staged in LDS (one broadcast read per byte: as scalars the 74 plan bytes
-// of the widest layout, live across the unrolled runs, spilled 270 SGPRs)
-template <bool WORDS>
-__device__ __forceinline__ void spr_store_row(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *g_row, uint32_t K,
-                                              uint8_t *row) {
-#pragma unroll
-    for (int i = 0; i < GNS_KWMAX; i++) {
-        if (4u * i >= K) break;  // uniform
-        uint32_t v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = 4 * i + b;
-            if ((uint32_t)j < K) {
-                const uint32_t g = g_row[j];
-                v |= ((s_k[g >> 2][tid] >> (8u * (g & 3u))) & 0xFFu) << (8 * b);
-            }
-        }
-        if constexpr (WORDS) {
-            reinterpret_cast<uint32_t *>(row)[i] = v;
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if ((uint32_t)(4 * i + b) < K) row[4 * i + b] = (uint8_t)(v >> (8 * b));
-        }
-    }
-}
-
-template <bool WORDS>
+template <bool PX, bool WORDS>
 __global__ __launch_bounds__(256) void k_spr_project(DictDev S, const unsigned long long *pkts,
                                                      const unsigned long long *first, uint64_t beg, uint64_t end,
-                                                     unsigned long long since, SprPlan pl, uint8_t *flows, uint8_t *elems,
-                                                     uint64_t cap, uint32_t *count) {
-    constexpr int IT = kSprIt;
+                                                     unsigned long long since, SprPlan<PX> pl, uint8_t *flows,
+                                                     uint8_t *elems, uint64_t cap, uint32_t *count) {
+    constexpr int IT = kSprIt, NW = 2 * SprPlan<PX>::kRow / 4;
     __shared__ uint32_t s_k[GNS_KWMAX][256];
     __shared__ uint32_t s_cnt[IT * 4], s_base;
-    __shared__ uint32_t s_gw[20];  // flow gather, then element gather
-    const uint8_t *s_g = reinterpret_cast<const uint8_t *>(s_gw);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t s0 = beg + (uint64_t)blockIdx.x * (256 * IT) + tid;
-    if (tid < 20) s_gw[tid] = pl.gw[tid];
-    uint64_t m[IT];
-    bool live[IT];
-#pragma unroll
-    for (int it = 0; it < IT; it++) {
-        const uint64_t s = s0 + (uint64_t)it * 256;
-        live[it] = s < end && S.rec[s * S.RW] != 0u && pkts[s] != 0ull && first[s] >= since;
-        m[it] = __ballot(live[it]);
-        if (lane == 0) s_cnt[it * 4 + wave] = (uint32_t)__popcll(m[it]);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int k = 0; k < IT * 4; k++) tot += s_cnt[k];
-        s_base = tot ? atomicAdd(count, tot) : 0u;
-    }
-    __syncthreads();
-    uint64_t run = s_base;  // rows of the workgroup's (run, wave) cells before this lane's
-#pragma unroll
-    for (int it = 0; it < IT; it++) {
-        uint64_t j = run + (uint32_t)__popcll(m[it] & ((1ull << lane) - 1ull));
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const uint32_t c = s_cnt[it * 4 + w];
-            if ((uint32_t)w < wave) j += c;
-            run += c;
-        }
-        if (!live[it] || j >= cap) continue;
-        uint32_t r[12];
-        load_record(S, (uint32_t)(s0 + (uint64_t)it * 256), r);
-#pragma unroll
-        for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
-#pragma unroll
-        for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
-            if ((uint32_t)f < pl.nip) spr_encode_ip(s_k, tid, pl.ipoff[f]);
-        spr_store_row<WORDS>(s_k, tid, s_g, pl.Kf, flows + j * pl.Kf);
-        spr_store_row<WORDS>(s_k, tid, s_g + 40, pl.Ke, elems + j * pl.Ke);
-    }
-}
-
-// Prefix spread roll-up (gns_spread_rollup_prefix): k_spr_project with the IP fields of the
-// flow row and of the element row masked to a prefix, each row by tables of its own -- the
-// prime uses read one field twice ("distinct source hosts per source /24": flow = SrcIP
-// under /24, element = SrcIP whole).  The masks are defined on the To16 bytes, so a lane
-// takes its IPv4 flag per IP field BEFORE spr_encode_ip rewrites the column; after the
-// rewrite an IPv4 address sits in bytes 0..3 of the field, and m4 is laid out for that
-// (EncodeFlow) form.  Per row byte: gather index g, IP field fld (0 SrcIP, 1 DstIP, 2 none),
-// m4 / m6 as in k_exr_project_px; the tables sit in LDS.
-struct SprPxPlan {
-    uint32_t Kf, Ke;
-    uint8_t ipoff[4];        // byte offset of SrcIP / DstIP in the source key; 0xFF: not read
-    union {                  // flow row: g, fld, m4, m6; then the element row's four; as words for the copy into LDS
-        uint8_t t[8][40];
-        uint32_t w[80];
-    };
-};
-
-// t_row: the row's g, fld, m4, m6 tables (40 bytes each, in LDS); v4: bit f = IP field f is IPv4
-template <bool WORDS>
-__device__ __forceinline__ void spr_store_row_px(const uint32_t (*s_k)[256], uint32_t tid, const uint8_t *t_row, uint32_t v4,
-                                                 uint32_t K, uint8_t *row) {
-#pragma unroll
-    for (int i = 0; i < GNS_KWMAX; i++) {
-        if (4u * i >= K) break;  // uniform
-        const uint32_t v = px_masked_word(s_k, tid, t_row, v4, K, i);
-        if constexpr (WORDS) {
-            reinterpret_cast<uint32_t *>(row)[i] = v;
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if ((uint32_t)(4 * i + b) < K) row[4 * i + b] = (uint8_t)(v >> (8 * b));
-        }
-    }
-}
-
-template <bool WORDS>
-__global__ __launch_bounds__(256) void k_spr_project_px(DictDev S, const unsigned long long *pkts,
-                                                        const unsigned long long *first, uint64_t beg, uint64_t end,
-                                                        unsigned long long since, SprPxPlan pl, uint8_t *flows,
-                                                        uint8_t *elems, uint64_t cap, uint32_t *count) {
-    constexpr int IT = kSprIt;
-    __shared__ uint32_t s_k[GNS_KWMAX][256];
-    __shared__ uint32_t s_cnt[IT * 4], s_base;
-    __shared__ uint32_t s_pw[80];
+    __shared__ uint32_t s_pw[NW];  // the flow row's tables, then the element row's
     const uint8_t *s_t = reinterpret_cast<const uint8_t *>(s_pw);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t s0 = beg + (uint64_t)blockIdx.x * (256 * IT) + tid;
-    if (tid < 80) s_pw[tid] = pl.w[tid];
+    if (tid < NW) s_pw[tid] = pl.w[tid];
     uint64_t m[IT];
     bool live[IT];
 #pragma unroll
@@ -571,17 +456,25 @@ __global__ __launch_bounds__(256) void k_spr_project_px(DictDev S, const unsigne
         if (!live[it] || j >= cap) continue;
         uint32_t r[12];
         load_record(S, (uint32_t)(s0 + (uint64_t)it * 256), r);
+        proj_fill_column(s_k, tid, r);
+        uint32_t v4 = 0;  // bit f: IP field f of this flow is IPv4
+        if constexpr (PX) {
 #pragma unroll
-        for (int i = 0; i < GNS_KWMAX; i++) s_k[i][tid] = r[1 + i];
-        uint32_t v4 = 0;
+            for (int f = 0; f < 2; f++)  // SrcIP, DstIP: a key of <= 37 bytes holds two IP fields at most
+                if (pl.ipoff[f] != 0xFFu) {
+                    v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;  // the To16 value's class
+                    spr_encode_ip(s_k, tid, pl.ipoff[f]);
+                }
+        } else {
+            // the fields as a count and a list (the order does not matter: they are rewritten
+            // independently): with the loop above the byte-store instantiation spills 114 SGPRs
+            // instead of 112, and this form keeps both plain instantiations the code they were
 #pragma unroll
-        for (int f = 0; f < 2; f++)  // SrcIP, DstIP: the class is the To16 value's, taken before the rewrite
-            if (pl.ipoff[f] != 0xFFu) {
-                v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
-                spr_encode_ip(s_k, tid, pl.ipoff[f]);
-            }
-        spr_store_row_px<WORDS>(s_k, tid, s_t, v4, pl.Kf, flows + j * pl.Kf);
-        spr_store_row_px<WORDS>(s_k, tid, s_t + 160, v4, pl.Ke, elems + j * pl.Ke);
+            for (int f = 0; f < 2; f++)
+                if ((uint32_t)f < pl.nip) spr_encode_ip(s_k, tid, pl.iplist[f]);
+        }
+        proj_store_row<PX, WORDS>(s_k, tid, s_t, v4, pl.Kf, flows + j * pl.Kf);
+        proj_store_row<PX, WORDS>(s_k, tid, s_t + SprPlan<PX>::kRow, v4, pl.Ke, elems + j * pl.Ke);
     }
 }
 
@@ -978,61 +871,43 @@ int exs_read_count(gns_exs *h, uint64_t *out) {
     return GNS_OK;
 }
 
-// --- spread roll-up ----------------------------------------------------------
-// the key field tuple byte t belongs to (make_plan's numbering)
-const char *spr_field_name(uint32_t t) {
-    return t < 16 ? "SrcIP" : t < 32 ? "DstIP" : t < 34 ? "SrcPort" : t < 36 ? "DstPort" : "Protocol";
-}
-
-// Byte gathers from the source's key to the destination's flow and element keys (pair = flow ‖
-// elem, the first Kf bytes the flow's): every byte from the first place the source's key holds
-// it.  GNS_E_ARG when a field of the destination is not part of the source.
-int spr_make_plan(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, SprPlan *pl) {
-    memset(pl, 0, sizeof(*pl));
-    pl->Kf = Kf;
-    pl->Ke = pair.K - Kf;
-    for (uint32_t j = 0; j < pair.K; j++) {
-        const uint32_t t = pair.src[j];
-        uint32_t i = 0;
-        while (i < src.K && src.src[i] != t) i++;
-        if (i == src.K) {
-            set_error("spread rollup: %s field %s is not part of the source's key layout", j < Kf ? "flow" : "element",
-                      spr_field_name(t));
-            return GNS_E_ARG;
-        }
-        (j < Kf ? pl->gf[j] : pl->ge[j - Kf]) = (uint8_t)i;
-        if (t == 0 || t == 16) {  // the first byte of an IP field: its 16 bytes are converted once
-            uint32_t f = 0;
-            while (f < pl->nip && pl->ipoff[f] != i) f++;
-            if (f == pl->nip) pl->ipoff[pl->nip++] = (uint8_t)i;
-        }
-    }
+// the `staged` rows of exs_stage_rows' buffer merged into h, in device batches of h
+int exs_merge_staged(gns_exs *h, const uint8_t *flows, const uint8_t *elems, uint64_t staged) {
+    InputDesc in{};
+    in.keys = flows; in.stride = h->Kf; in.keys2 = elems; in.stride2 = h->Km - h->Kf;
+    for (uint64_t off = 0; off < staged; off += h->bmax)
+        GNS_TRY(exs_batch<IN_KEYS>(h, advance(in, off), std::min(h->bmax, staged - off), true));
     return GNS_OK;
 }
 
-// spr_make_plan's gathers with the mask tables of the two prefixes (checked by the caller)
-int spr_make_px_plan(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, const gns_prefix &fpx, const gns_prefix &epx,
-                     SprPxPlan *pp) {
-    SprPlan pl;
-    GNS_TRY(spr_make_plan(src, pair, Kf, &pl));
+// --- spread roll-up ----------------------------------------------------------
+// Both plans of a spread roll-up from the source's key to the destination's flow and element
+// keys (pair = flow ‖ elem, the first Kf bytes the flow's): roll_tables per row, the flow row
+// under fpx and the element row under epx (nullptr: no mask), laid out for the EncodeFlow form.
+// GNS_E_ARG when a field of the destination is not part of the source.
+int spr_make_plans(const KeyPlanN &src, const KeyPlanN &pair, uint32_t Kf, const gns_prefix *fpx, const gns_prefix *epx,
+                   SprPlan<false> *pl, SprPlan<true> *pp) {
+    memset(pl, 0, sizeof(*pl));
     memset(pp, 0, sizeof(*pp));
-    pp->Kf = pl.Kf;
-    pp->Ke = pl.Ke;
+    pp->Kf = Kf;
+    pp->Ke = pair.K - Kf;
     memset(pp->ipoff, 0xFF, sizeof(pp->ipoff));
-    for (uint32_t j = 0; j < pair.K; j++) {
-        const bool flow = j < Kf;
-        const uint32_t t = pair.src[j], k = flow ? j : j - Kf;
-        uint8_t(*tab)[40] = pp->t + (flow ? 0 : 4);
-        const uint8_t g = flow ? pl.gf[k] : pl.ge[k];
-        tab[0][k] = g;
-        if (t >= 32) { tab[1][k] = 2; tab[2][k] = tab[3][k] = 0xFF; continue; }
-        const gns_prefix &px = flow ? fpx : epx;
-        const uint32_t f = t >> 4, b = t & 15u;
-        tab[1][k] = (uint8_t)f;
-        tab[2][k] = b < 4 ? px_prefix_byte(f ? px.dst_v4 : px.src_v4, b) : 0xFF;  // EncodeFlow form: a.b.c.d + 12 zero bytes
-        tab[3][k] = px_prefix_byte(f ? px.dst_v6 : px.src_v6, b);
-        if (b == 0) pp->ipoff[f] = g;
+    for (int r = 0; r < 2; r++) {
+        const uint8_t *dst = pair.src + (r ? Kf : 0);
+        RollRow row;
+        const int miss = roll_tables(src.src, src.K, dst, r ? pp->Ke : Kf, r ? epx : fpx, true, &row, pp->ipoff);
+        if (miss >= 0) {
+            set_error("spread rollup: %s field %s is not part of the source's key layout", r ? "element" : "flow",
+                      tuple_field_name(dst[miss]));
+            return GNS_E_ARG;
+        }
+        memcpy(pp->t[r], &row, sizeof(row));
+        memcpy(pl->t[r], row.g, sizeof(row.g));
     }
+    pl->Kf = pp->Kf;
+    pl->Ke = pp->Ke;
+    for (int f = 0; f < 2; f++)
+        if (pp->ipoff[f] != 0xFF) pl->iplist[pl->nip++] = pp->ipoff[f];
     return GNS_OK;
 }
 
@@ -1309,12 +1184,7 @@ int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *c
     GNS_TRY(exs_check_since(src, since));
     GNS_TRY(set_device(dst->device));
     // src is read at this point of its own stream, by kernels on dst's stream
-    hipEvent_t ev;
-    GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ev, src->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
-    (void)hipEventDestroy(ev);
-    if (e != hipSuccess) { set_error("merge_from: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    GNS_TRY(stream_wait_now(dst->stream, src->stream, "merge_from"));
     const uint64_t at = exs_cursor(src);
     // Pieces of src's table are compacted one behind the other into the staging rows; once more
     // than one piece's worth is staged (the next piece might not fit) they are merged, in device
@@ -1327,10 +1197,7 @@ int gns_pairs_merge_from(gns_exs *dst, gns_exs *src, uint64_t since, uint64_t *c
         GNS_TRY(exs_export_range(src, beg, end, (uint32_t)since, df, de, kExsStageRows, dst->ctl + 6, dst->stream, staged != 0));
         GNS_TRY(exs_read_count(dst, &staged));
         if (staged <= kExsPiece && end < src->pslots) continue;
-        InputDesc in{};
-        in.keys = df; in.stride = dst->Kf; in.keys2 = de; in.stride2 = dst->Km - dst->Kf;
-        for (uint64_t off = 0; off < staged; off += dst->bmax)
-            GNS_TRY(exs_batch<IN_KEYS>(dst, advance(in, off), std::min(dst->bmax, staged - off), true));
+        GNS_TRY(exs_merge_staged(dst, df, de, staged));
         staged = 0;
     }
     if (cursor) *cursor = at;
@@ -1347,10 +1214,9 @@ static int spr_rollup(gns_exs *dst, gns_ex *src, const gns_prefix *fpx, const gn
     }
     ExTableRef S;
     ex_table_ref(src, &S);
-    SprPlan pl;
-    SprPxPlan pp;
-    GNS_TRY(spr_make_plan(S.kp, dst->kpm, dst->Kf, &pl));
-    if (fpx) GNS_TRY(spr_make_px_plan(S.kp, dst->kpm, dst->Kf, *fpx, *epx, &pp));
+    SprPlan<false> pl;
+    SprPlan<true> pp;
+    GNS_TRY(spr_make_plans(S.kp, dst->kpm, dst->Kf, fpx, epx, &pl, &pp));
     if (dst->device != S.device) {
         set_error("spread rollup: dst is on device %d, src on device %d", dst->device, S.device);
         return GNS_E_ARG;
@@ -1361,19 +1227,10 @@ static int spr_rollup(gns_exs *dst, gns_ex *src, const gns_prefix *fpx, const gn
         return GNS_E_ARG;
     }
     GNS_TRY(set_device(dst->device));
-    uint64_t piece = kExsPiece;
-    if (const char *env = getenv("GNS_SPREAD_ROLLUP_PIECE")) {  // tests: small tables span many pieces
-        const unsigned long long v = strtoull(env, nullptr, 10);
-        if (v) piece = std::min<uint64_t>(v, kExsPiece);
-    }
+    const uint64_t piece = test_piece("GNS_SPREAD_ROLLUP_PIECE", kExsPiece);
     hipStream_t s = dst->stream;
     // src is read at this point of its own stream (after its pending batches), by kernels on dst's stream
-    hipEvent_t ev;
-    GNS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ev, S.stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
-    (void)hipEventDestroy(ev);
-    if (e != hipSuccess) { set_error("spread rollup: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    GNS_TRY(stream_wait_now(s, S.stream, "spread rollup"));
     // Pieces of src's table are projected one behind the other into the staging rows; once more
     // than one piece's worth of rows is staged (the next piece might not fit: a piece appends at
     // most `piece` rows, and the buffer holds two pieces of 2^20) they are merged, in device
@@ -1389,23 +1246,18 @@ static int spr_rollup(gns_exs *dst, gns_ex *src, const gns_prefix *fpx, const gn
         {
             ScopedStage st(dst->timer, 3);
             const dim3 g((unsigned)((end - beg + 256 * kSprIt - 1) / (256 * kSprIt))), b(256);
-            if (fpx && words) hipLaunchKernelGGL((k_spr_project_px<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
-                                                 (unsigned long long)since, pp, df, de, kExsStageRows, dst->ctl + 6);
-            else if (fpx) hipLaunchKernelGGL((k_spr_project_px<false>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
-                                             (unsigned long long)since, pp, df, de, kExsStageRows, dst->ctl + 6);
-            else if (words) hipLaunchKernelGGL((k_spr_project<true>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
-                                               (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
-            else hipLaunchKernelGGL((k_spr_project<false>), g, b, 0, s, S.D, S.pkts, S.first, beg, end,
-                                    (unsigned long long)since, pl, df, de, kExsStageRows, dst->ctl + 6);
+            auto launch = [&](auto kernel, const auto &plan) {
+                hipLaunchKernelGGL(kernel, g, b, 0, s, S.D, S.pkts, S.first, beg, end, (unsigned long long)since, plan, df, de,
+                                   kExsStageRows, dst->ctl + 6);
+            };
+            if (fpx) launch(words ? k_spr_project<true, true> : k_spr_project<true, false>, pp);
+            else launch(words ? k_spr_project<false, true> : k_spr_project<false, false>, pl);
             GNS_HIP(hipGetLastError());
         }
         GNS_TRY(exs_read_count(dst, &staged));
         staged = std::min(staged, kExsStageRows);  // (rows past the capacity are counted, not written: cannot happen)
         if (staged <= piece && end < S.slots) continue;
-        InputDesc in{};
-        in.keys = df; in.stride = dst->Kf; in.keys2 = de; in.stride2 = dst->Km - dst->Kf;
-        for (uint64_t off = 0; off < staged; off += dst->bmax)
-            GNS_TRY(exs_batch<IN_KEYS>(dst, advance(in, off), std::min(dst->bmax, staged - off), true));
+        GNS_TRY(exs_merge_staged(dst, df, de, staged));
         projected += staged;
         staged = 0;
     }
