@@ -56,6 +56,8 @@ EXPORTED = [
     "gns_cm_view_refresh_at", "gns_cm_view_query_device", "gns_cm_view_heavy_rows", "gns_cm_view_export_state",
     "gns_ex_rollup", "gns_spread_rollup",
     "gns_ex_rollup_prefix", "gns_spread_rollup_prefix", "gns_ex_aggregate_cidr", "gns_ex_view_aggregate_cidr",
+    "gns_ex_hist_create", "gns_ex_hist_destroy", "gns_ex_hist_append", "gns_ex_hist_times", "gns_ex_hist_stats",
+    "gns_ex_hist_aggregate", "gns_ex_hist_aggregate_cidr", "gns_ex_hist_heavy_hitters", "gns_ex_hist_snapshot",
 ]
 
 
@@ -106,6 +108,10 @@ class SsParams(ct.Structure):
 
 class ExParams(ct.Structure):
     _fields_ = [("key", Layout), ("max_flows", ct.c_uint64), ("batch_packets", ct.c_uint64), ("device", ct.c_int)]
+
+
+class ExHistParams(ct.Structure):  # gns_ex_hist_params: initial capacities, both grow
+    _fields_ = [("key", Layout), ("max_rows", ct.c_uint64), ("max_flows", ct.c_uint64), ("device", ct.c_int)]
 
 
 class ExFilter(ct.Structure):  # gns_ex_filter: 44 bytes
@@ -259,6 +265,13 @@ def load() -> ct.CDLL:
         "gns_cm_view_query_device": ([vp, vp, u32, u64, vp], i32),
         "gns_cm_view_heavy_rows": ([vp, vp, vp, vp, vp], i32),
         "gns_cm_view_export_state": ([vp, vp, vp, vp, vp, vp], i32),
+        "gns_ex_hist_create": ([vp, vp], i32), "gns_ex_hist_destroy": ([vp], i32),
+        "gns_ex_hist_append": ([vp, vp, ct.c_int64, vp], i32),
+        "gns_ex_hist_times": ([vp, vp, vp], i32), "gns_ex_hist_stats": ([vp, vp], i32),
+        "gns_ex_hist_aggregate": ([vp, vp, vp, u32, vp], i32),
+        "gns_ex_hist_aggregate_cidr": ([vp, vp, vp, u32, vp], i32),
+        "gns_ex_hist_heavy_hitters": ([vp, vp, i32, u64, u64, vp, vp, vp], i32),
+        "gns_ex_hist_snapshot": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -34,6 +34,8 @@
 //   D   k_exh_*        designate the next batch's heavy flows
 //   Q   k_exq_aggregate  filtered aggregates of the resident table (gns_ex_aggregate)
 //   HH  k_exq_hh_*     flows above a threshold, ordered, cut to a limit (gns_ex_heavy_hitters)
+//   A   k_exh_link     a view's rows appended to a history's log (gns_ex_hist_append); Q, HH
+//                      and V answer over the log as of a snapshot (gns_ex_hist_*)
 // A Zipf batch touches a flow in many places; per-block LDS aggregation of
 // every flow left the tail flows to global atomics, three per packet; sorting
 // every packet (rocPRIM radix sort of 100M words) made the sort the largest
@@ -50,6 +52,7 @@
 
 #include "gns_common.hpp"
 #include "gns_exsrc.hpp"
+#include "gns_histplan.hpp"
 #include "gns_scan.cuh"
 #include "gns_xcd.cuh"
 
@@ -1004,29 +1007,62 @@ __global__ __launch_bounds__(256) void k_ex_gather(const uint32_t *ids, uint64_t
 // ---------------------------------------------------------------------------
 constexpr uint32_t kVBins = 256;
 __device__ __forceinline__ uint64_t exv_cell(uint32_t i, uint32_t nb) { return (uint64_t)(i % nb) * kVBins + i / nb; }
+// (ExSelSince / ExSelAsOf: the row-selection policies, declared here for V1 / V3 and described
+// with the query plane below)
+struct ExSelSince {
+    static constexpr bool kVersioned = false;
+    unsigned long long since;
+};
+struct ExSelAsOf {
+    static constexpr bool kVersioned = true;
+    const uint32_t *written, *superseded;
+    uint32_t s;
+    __device__ __forceinline__ void test(uint64_t row, bool &seen, bool &live) const {
+        const uint32_t a = written[row], b = superseded[row];
+        seen = a <= s;
+        live = seen && s < b;
+    }
+};
+template <class SEL>
 __device__ __forceinline__ bool exv_selected(const DictDev &D, const FlowState &f, uint64_t s, uint64_t slots,
-                                             unsigned long long since) {
-    return s < slots && D.rec[s * D.RW] != 0u && f.pkts[s] != 0ull && f.last[s] > since;
+                                             const SEL &sel) {
+    if constexpr (SEL::kVersioned) {  // a history's as-of snapshot: the live rows, in log order
+        bool seen = false, live = false;
+        if (s < slots) sel.test(s, seen, live);
+        return live;
+    } else {
+        return s < slots && D.rec[s * D.RW] != 0u && f.pkts[s] != 0ull && f.last[s] > sel.since;
+    }
 }
 // grid = nb * kVBins blocks (>= the slot blocks; the cells past them count 0)
-__global__ __launch_bounds__(256) void k_exv_count(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
-                                                   uint32_t nb, uint32_t *cnt) {
+template <class SEL>
+__device__ __forceinline__ void exv_count_block(const DictDev &D, uint64_t slots, const FlowState &f, const SEL &sl,
+                                                uint32_t nb, uint32_t *cnt) {
     __shared__ uint32_t s_w[4];
     const uint32_t tid = threadIdx.x;
-    const bool sel = exv_selected(D, f, (uint64_t)blockIdx.x * 256 + tid, slots, since);
+    const bool sel = exv_selected(D, f, (uint64_t)blockIdx.x * 256 + tid, slots, sl);
     const uint64_t m = __ballot(sel);
     if ((tid & 63u) == 0) s_w[tid >> 6] = (uint32_t)__popcll(m);
     __syncthreads();
     if (tid == 0) cnt[exv_cell(blockIdx.x, nb)] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
+__global__ __launch_bounds__(256) void k_exv_count(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
+                                                   uint32_t nb, uint32_t *cnt) {
+    exv_count_block(D, slots, f, ExSelSince{since}, nb, cnt);
+}
+__global__ __launch_bounds__(256) void k_exhv_count(DictDev D, uint64_t slots, FlowState f, ExSelAsOf sel, uint32_t nb,
+                                                    uint32_t *cnt) {
+    exv_count_block(D, slots, f, sel, nb, cnt);
+}
 // V: the view's tables (cap rows each); a row past cap is not written (cap >= the claimed slots >= the rows)
-__global__ __launch_bounds__(256) void k_exv_write(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
-                                                   uint32_t nb, const uint32_t *off, DictDev V, FlowState vf,
-                                                   uint64_t cap) {
+template <class SEL>
+__device__ __forceinline__ void exv_write_block(const DictDev &D, uint64_t slots, const FlowState &f, const SEL &sl,
+                                                uint32_t nb, const uint32_t *off, const DictDev &V,
+                                                const FlowState &vf, uint64_t cap) {
     __shared__ uint32_t s_w[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t s = (uint64_t)blockIdx.x * 256 + tid;
-    const bool sel = exv_selected(D, f, s, slots, since);
+    const bool sel = exv_selected(D, f, s, slots, sl);
     const uint64_t m = __ballot(sel);
     if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
     __syncthreads();
@@ -1041,6 +1077,15 @@ __global__ __launch_bounds__(256) void k_exv_write(DictDev D, uint64_t slots, Fl
     for (int i = 0; i < 4; i++)
         if (4u * i < D.RW) o[i] = i < 3 ? q[i] : make_uint4(0, 0, 0, 0);
     vf.pkts[r] = f.pkts[s]; vf.bytes[r] = f.bytes[s]; vf.start[r] = f.start[s]; vf.end[r] = f.end[s];
+}
+__global__ __launch_bounds__(256) void k_exv_write(DictDev D, uint64_t slots, FlowState f, unsigned long long since,
+                                                   uint32_t nb, const uint32_t *off, DictDev V, FlowState vf,
+                                                   uint64_t cap) {
+    exv_write_block(D, slots, f, ExSelSince{since}, nb, off, V, vf, cap);
+}
+__global__ __launch_bounds__(256) void k_exhv_write(DictDev D, uint64_t slots, FlowState f, ExSelAsOf sel, uint32_t nb,
+                                                    const uint32_t *off, DictDev V, FlowState vf, uint64_t cap) {
+    exv_write_block(D, slots, f, sel, nb, off, V, vf, cap);
 }
 
 // ---------------------------------------------------------------------------
@@ -1091,10 +1136,33 @@ __device__ __forceinline__ unsigned long long exq_lane_u64(unsigned long long v,
 // the lanes filter q matched, then walks the slots any filter matched -- their state
 // words broadcast from the owning lane -- and merges those its ballot names.  One walk
 // serves all 64 filters, and nothing is reduced before the scan ends.
-template <bool WIDE>
+//
+// SEL is the row-selection policy of the scans (Q, HH1 / HH2, V1 / V3):
+//   ExSelOcc    the live table and a view's rows: an occupied slot with packets
+//   ExSelSince  V1 / V3 of a view: ExSelOcc and touched after a stream position
+//   ExSelAsOf   a history's log as of snapshot s: a row is SEEN when written <= s and LIVE when
+//               also s < superseded.  The version words are read first, and a wave none of
+//               whose rows is seen loads neither records nor state: an interval outside the
+//               query costs 8 B per row.  Sums and lists take the live rows, min / max the
+//               seen ones (TraceFlow has no argMax).
+// A scan kernel takes its policy as a trailing parameter pack: none for ExSelOcc, so the live
+// table's and the views' instantiations keep their argument list.
+struct ExSelOcc {
+    static constexpr bool kVersioned = false;
+};
+__device__ __forceinline__ ExSelOcc exq_sel() { return ExSelOcc{}; }
+__device__ __forceinline__ const ExSelAsOf &exq_sel(const ExSelAsOf &sel) { return sel; }
+template <class... SL> struct ExSelPick { using type = ExSelOcc; };
+template <> struct ExSelPick<ExSelAsOf> { using type = ExSelAsOf; };
+template <class... SL>
+using ExSelOf = typename ExSelPick<SL...>::type;
+
+template <bool WIDE, class... SL>
 __global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots, FlowState f,
                                                        const ExQFilter *__restrict__ flt, uint32_t nf,
-                                                       unsigned long long *__restrict__ acc) {
+                                                       unsigned long long *__restrict__ acc, SL... sl) {
+    using SEL = ExSelOf<SL...>;
+    [[maybe_unused]] const SEL sel = exq_sel(sl...);
     __shared__ unsigned long long s_a[kQBatch][kQAcc];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t i = tid; i < nf * kQAcc; i += 256) s_a[i / kQAcc][i % kQAcc] = exq_acc_init(i % kQAcc);
@@ -1106,13 +1174,26 @@ __global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots
         uint32_t r[12];
         unsigned long long pk = 0, by = 0, st = ~0ull, en = 0;
         bool occ = false;
-        if (s < slots) {
-            load_record(D, (uint32_t)s, r);
-            pk = f.pkts[s]; by = f.bytes[s];
-            st = (unsigned long long)f.start[s] ^ kQSign; en = (unsigned long long)f.end[s] ^ kQSign;
-            occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
+        [[maybe_unused]] bool cur = false;  // versioned: the row is live (occ: it is seen)
+        if constexpr (SEL::kVersioned) {
+            if (s < slots) sel.test(s, occ, cur);
+            if (!__ballot(occ)) continue;  // wave-uniform: nothing seen, nothing loaded
+            if (occ) {  // (a log row is a view's row: occupied, with packets)
+                load_record(D, (uint32_t)s, r);
+                pk = f.pkts[s]; by = f.bytes[s];
+                st = (unsigned long long)f.start[s] ^ kQSign; en = (unsigned long long)f.end[s] ^ kQSign;
+            }
+        } else {
+            if (s < slots) {
+                load_record(D, (uint32_t)s, r);
+                pk = f.pkts[s]; by = f.bytes[s];
+                st = (unsigned long long)f.start[s] ^ kQSign; en = (unsigned long long)f.end[s] ^ kQSign;
+                occ = r[0] != 0u && pk != 0ull;  // k_ex_list's occupancy rule
+            }
+            if (!__ballot(occ)) continue;  // wave-uniform
         }
-        if (!__ballot(occ)) continue;  // wave-uniform
+        [[maybe_unused]] uint64_t curm = 0;  // versioned: the live rows of the wave
+        if constexpr (SEL::kVersioned) curm = __ballot(cur);
         unsigned long long mine = 0;   // WIDE: the lanes filter `lane` matched
         bool any = false;
         for (uint32_t q = 0; q < nf; q++) {
@@ -1132,14 +1213,17 @@ __global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots
                 any = any || hit;
             } else {
                 if (!hm) continue;  // wave-uniform: every lane takes part in the reductions below
-                const unsigned long long tp = __ockl_wfred_add_u64(hit ? pk : 0ull);
-                const unsigned long long tb = __ockl_wfred_add_u64(hit ? by : 0ull);
+                bool add = hit;  // the row enters COUNT / SUM
+                uint64_t am = hm;
+                if constexpr (SEL::kVersioned) { add = hit && cur; am = hm & curm; }
+                const unsigned long long tp = __ockl_wfred_add_u64(add ? pk : 0ull);
+                const unsigned long long tb = __ockl_wfred_add_u64(add ? by : 0ull);
                 const unsigned long long ts = __ockl_wfred_min_u64(hit ? st : ~0ull);
                 const unsigned long long te = __ockl_wfred_max_u64(hit ? en : 0ull);
                 const unsigned long long mp = __ockl_wfred_max_u64(hit ? pk : 0ull);
                 const unsigned long long mb = __ockl_wfred_max_u64(hit ? by : 0ull);
                 if (lane == 0) {
-                    atomicAdd(&s_a[q][0], (unsigned long long)__popcll(hm));
+                    atomicAdd(&s_a[q][0], (unsigned long long)__popcll(am));
                     atomicAdd(&s_a[q][1], tp);
                     atomicAdd(&s_a[q][2], tb);
                     atomicMin(&s_a[q][3], ts);
@@ -1157,15 +1241,19 @@ __global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots
                 const unsigned long long pj = exq_lane_u64(pk, j), bj = exq_lane_u64(by, j);
                 const unsigned long long sj = exq_lane_u64(st, j), ej = exq_lane_u64(en, j);
                 if (mine >> j & 1ull) {
-                    a_n += 1; a_pk += pj; a_by += bj;
+                    bool add = true;  // versioned: only a live row enters COUNT / SUM
+                    if constexpr (SEL::kVersioned) add = curm >> j & 1ull;
+                    if (add) { a_n += 1; a_pk += pj; a_by += bj; }
                     a_st = min(a_st, sj); a_en = max(a_en, ej);
                     a_mp = max(a_mp, pj); a_mb = max(a_mb, bj);
                 }
             }
         }
     }
+    // something to merge: a row counted; versioned: a row seen (every row has packets, so
+    // max(PacketCount) != 0), which a block may hold without the live row of the same key
     if constexpr (WIDE) {
-        if (lane < nf && a_n != 0ull) {
+        if (lane < nf && (SEL::kVersioned ? a_mp : a_n) != 0ull) {
             atomicAdd(&s_a[lane][0], a_n);
             atomicAdd(&s_a[lane][1], a_pk);
             atomicAdd(&s_a[lane][2], a_by);
@@ -1176,7 +1264,7 @@ __global__ __launch_bounds__(256) void k_exq_aggregate(DictDev D, uint64_t slots
         }
     }
     __syncthreads();
-    if (tid < nf && s_a[tid][0] != 0ull) {
+    if (tid < nf && s_a[tid][SEL::kVersioned ? 5 : 0] != 0ull) {
         unsigned long long *a = acc + (uint64_t)tid * kQAcc;
         atomicAdd(&a[0], s_a[tid][0]);
         atomicAdd(&a[1], s_a[tid][1]);
@@ -1218,34 +1306,47 @@ struct ExHhLess {
         return false;
     }
 };
+template <class SEL>
 __device__ __forceinline__ bool exq_hh_take(const DictDev &D, const FlowState &f, uint64_t s, uint64_t slots, int metric,
-                                            unsigned long long thr, unsigned long long &v) {
+                                            unsigned long long thr, unsigned long long &v, const SEL &sel) {
     if (s >= slots) return false;
-    const unsigned long long pk = f.pkts[s];
-    v = metric ? f.bytes[s] : pk;
-    return D.rec[s * D.RW] != 0u && pk != 0ull && v >= thr;
+    if constexpr (SEL::kVersioned) {  // the list holds the live rows; the others load no state
+        bool seen, live;
+        sel.test(s, seen, live);
+        if (!live) return false;
+        v = metric ? f.bytes[s] : f.pkts[s];
+        return v >= thr;
+    } else {
+        const unsigned long long pk = f.pkts[s];
+        v = metric ? f.bytes[s] : pk;
+        return D.rec[s * D.RW] != 0u && pk != 0ull && v >= thr;
+    }
 }
+template <class... SL>
 __global__ __launch_bounds__(256) void k_exq_hh_hist(DictDev D, uint64_t slots, FlowState f, int metric,
-                                                     unsigned long long thr, uint32_t *hist) {
+                                                     unsigned long long thr, uint32_t *hist, SL... sl) {
+    [[maybe_unused]] const ExSelOf<SL...> sel = exq_sel(sl...);
     __shared__ uint32_t h[kQBands];
     for (uint32_t i = threadIdx.x; i < kQBands; i += 256) h[i] = 0;
     __syncthreads();
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * 256) {
         unsigned long long v;
-        if (exq_hh_take(D, f, s, slots, metric, thr, v)) atomicAdd(&h[exq_band(v)], 1u);
+        if (exq_hh_take(D, f, s, slots, metric, thr, v, sel)) atomicAdd(&h[exq_band(v)], 1u);
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < kQBands; i += 256)
         if (h[i]) atomicAdd(&hist[i], h[i]);
 }
+template <class... SL>
 __global__ __launch_bounds__(256) void k_exq_hh_collect(DictDev D, uint64_t slots, FlowState f, int metric,
                                                         unsigned long long thr, uint32_t band, ExHhRow *rows,
-                                                        uint32_t *cnt, uint32_t cap) {
+                                                        uint32_t *cnt, uint32_t cap, SL... sl) {
+    [[maybe_unused]] const ExSelOf<SL...> sel = exq_sel(sl...);
     const uint32_t lane = __lane_id();
     for (uint64_t s0 = (uint64_t)blockIdx.x * 256; s0 < slots; s0 += (uint64_t)gridDim.x * 256) {  // block-uniform
         const uint64_t s = s0 + threadIdx.x;
         unsigned long long v = 0;
-        const bool take = exq_hh_take(D, f, s, slots, metric, thr, v) && exq_band(v) >= band;
+        const bool take = exq_hh_take(D, f, s, slots, metric, thr, v, sel) && exq_band(v) >= band;
         const uint64_t m = __ballot(take);
         if (!m) continue;
         const int leader = __ffsll((unsigned long long)m) - 1;
@@ -1292,6 +1393,72 @@ __global__ __launch_bounds__(256) void k_ex_init(FlowState f, uint64_t slots) {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= slots) return;
     f.pkts[s] = 0; f.bytes[s] = 0; f.first[s] = ~0ull; f.last[s] = 0; f.start[s] = 0; f.end[s] = 0;
+}
+
+// ---------------------------------------------------------------------------
+// History (gns_ex_hist_*): an append-only log of snapshot rows.  A log row is a view's row
+// -- record at stride RW, start, end, pkts, bytes -- with two version words: the snapshot
+// that wrote it and the snapshot that next wrote the same key (kHistOpen: none yet).  The key
+// index is a dictionary of the history's own with one head word per slot, the newest log row
+// of that key.  "The latest row of each flow as of snapshot s" is then
+// written <= s < superseded, tested in the scans of the query plane (ExSelAsOf).
+//   A1 dict_resolve_keys  the view's key words -> index slots (growth and retry as gns_ex_merge)
+//   A2 k_exh_link         view row i -> log row base + i, stamped written = S; the row is
+//                         swapped into its key's head word and the row it displaced is
+//                         stamped superseded = S.  Keys are distinct within a view, so no two
+//                         lanes touch one head word.
+// Nothing the link writes is visible to a query before the host publishes S: rows at and
+// beyond the published count are outside every scan, and a displaced row stays live for every
+// s < S.
+// ---------------------------------------------------------------------------
+struct ExHistLog {
+    DictDev L;    // rec / RW / K: the records
+    FlowState f;  // pkts, bytes, start, end (first / last stay NULL)
+    uint32_t *written, *superseded;
+    uint64_t cap;
+};
+__global__ __launch_bounds__(256) void k_exh_link(DictDev V, FlowState vf, uint64_t n, const uint32_t *ids,
+                                                  uint32_t *head, uint32_t slots, ExHistLog G, uint64_t base, uint32_t S,
+                                                  uint32_t *fresh) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t r = base + i;
+    uint32_t id = GNS_ID_NONE;
+    bool isnew = false;
+    if (i < n && r < G.cap) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(V.rec + i * V.RW);
+        uint4 *o = reinterpret_cast<uint4 *>(G.L.rec + r * V.RW);
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+            if (4u * w < V.RW) o[w] = q[w];
+        G.f.pkts[r] = vf.pkts[i]; G.f.bytes[r] = vf.bytes[i]; G.f.start[r] = vf.start[i]; G.f.end[r] = vf.end[i];
+        G.written[r] = S;
+        G.superseded[r] = kHistOpen;
+        id = ids[i];
+        if (id < slots) {  // (always: every id of the append was resolved before the link)
+            const uint32_t old = head[id];
+            head[id] = (uint32_t)r;
+            if (old == kHistOpen) isnew = true;
+            else if (old < base) G.superseded[old] = S;
+        }
+    }
+    const uint64_t m = __ballot(isnew);  // keys new to the history: one add per wave
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(fresh, (uint32_t)__popcll(m));
+}
+// index growth: a key's head word follows its record to the new slot (gns_dict.hip remap)
+__global__ __launch_bounds__(256) void k_exh_permute(const uint32_t *oh, uint64_t slots, const uint32_t *remap,
+                                                     uint32_t *nh) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= slots) return;
+    const uint32_t t = remap[s];
+    if (t >= kDictMarked) return;
+    nh[t] = oh[s];
+}
+// the slots that hold a key of a published snapshot name themselves (dict_rebuild's mark list);
+// a slot claimed by an append that did not complete names nothing and is dropped
+__global__ __launch_bounds__(256) void k_exh_heads(const uint32_t *head, uint64_t slots, uint32_t *ids) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= slots) return;
+    ids[s] = head[s] != kHistOpen ? (uint32_t)s : GNS_ID_NONE;
 }
 
 // gns_ex_merge: row i is one pseudo-record at stream position base + i.  Counts add
@@ -1618,6 +1785,38 @@ struct gns_ex_view : ViewCore {
     ExRead rd;
 };
 
+// The history of one key layout: the log, the key index and its head words, and the reader's
+// scratch.  Its stream, mutex and pinned staging are its own, as a view's: appends and queries
+// from any thread are serialised by the mutex and allocate nothing once warm.
+struct gns_ex_hist : ViewCore {
+    int device = 0;
+    KeyPlanN kp{};
+    uint32_t K = 0;
+    HistPlan plan;             // timestamps, published rows (host)
+    ExHistLog log{};           // cap rows of room
+    DictDev D{};               // the key index
+    uint64_t slots = 0, claimed = 0, keys = 0;
+    uint32_t *head = nullptr;  // [slots] newest log row of the slot's key (kHistOpen: none)
+    uint32_t *dctl = nullptr;
+    unsigned long long *full = nullptr;  // the index's dictionary-full word
+    uint32_t epoch = 0;
+    DictScratch dsc;
+    KeyResolveScratch rsc;
+    uint32_t *ids = nullptr;   // the index slots of the rows being appended
+    uint64_t ids_n = 0;
+    uint32_t *mark = nullptr;  // k_exh_heads' list during an index growth
+    uint64_t mark_n = 0;
+    uint32_t *fresh = nullptr; // keys the running append added
+    uint64_t n_index_grow = 0, n_log_grow = 0;
+    // as-of snapshot: V1's counts and the scan's sums, the total, the compacted rows
+    uint32_t *scan = nullptr, *total = nullptr;
+    uint64_t scan_n = 0;
+    DictDev SD{};
+    FlowState sf{};
+    uint64_t scap = 0;
+    ExRead rd;
+};
+
 namespace {
 
 void ex_free_all(gns_ex *ex) {
@@ -1941,8 +2140,9 @@ int ex_filters_check(const ExFilters &filters, uint32_t nf) {
 }
 
 // gns_ex_aggregate over table T (the argument checks are the caller's; nf != 0)
-int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer,
-                    const ExFilters &filters, uint32_t nf, gns_ex_summary *out) {
+// asof: T is a history's log, answered as of that snapshot
+int ex_aggregate_on(const KeyPlanN &kp, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer,
+                    const ExFilters &filters, uint32_t nf, gns_ex_summary *out, const ExSelAsOf *asof = nullptr) {
     // per filter: the 37 tuple bytes (make_plan's numbering), which fields are masked and, bit
     // for bit, how much of each byte takes part (an IP field under a prefix: its leading bits);
     // the layout's byte plan carries them to their place in the record's key words
@@ -1980,8 +2180,8 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
         ExQFilter &w = hf[i];
         memset(&w, 0, sizeof(w));
         uint8_t seen[40] = {0};
-        for (uint32_t j = 0; j < ex->K; j++) {
-            const uint32_t t = ex->kp.src[j];
+        for (uint32_t j = 0; j < kp.K; j++) {
+            const uint32_t t = kp.src[j];
             if (t >= 37 || !want[t]) continue;
             seen[t] = 1;
             w.m[j >> 2] |= (uint32_t)tm[t] << (8 * (j & 3));
@@ -2006,7 +2206,13 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
             const unsigned grid = (unsigned)std::min<uint64_t>((T.rows + 255) / 256, 2048);
             for (uint32_t p0 = 0; p0 < nf; p0 += kQBatch) {
                 const uint32_t nb = std::min(kQBatch, nf - p0);
-                if (nb > kQNarrow)
+                if (asof && nb > kQNarrow)
+                    hipLaunchKernelGGL((k_exq_aggregate<true, ExSelAsOf>), dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, df + p0,
+                                       nb, da + (size_t)p0 * kQAcc, *asof);
+                else if (asof)
+                    hipLaunchKernelGGL((k_exq_aggregate<false, ExSelAsOf>), dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, df + p0,
+                                       nb, da + (size_t)p0 * kQAcc, *asof);
+                else if (nb > kQNarrow)
                     hipLaunchKernelGGL(k_exq_aggregate<true>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, df + p0,
                                        nb, da + (size_t)p0 * kQAcc);
                 else
@@ -2032,8 +2238,9 @@ int ex_aggregate_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &r
 }
 
 // gns_ex_heavy_hitters over table T (the argument checks are the caller's)
-int ex_heavy_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer, int metric,
-                uint64_t threshold, uint64_t limit, uint8_t *keys, uint64_t *values, uint64_t *n_io) {
+int ex_heavy_on(uint32_t K, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer, int metric,
+                uint64_t threshold, uint64_t limit, uint8_t *keys, uint64_t *values, uint64_t *n_io,
+                const ExSelAsOf *asof = nullptr) {
     if (T.rows == 0) {  // a view without rows
         *n_io = 0;
         return GNS_OK;
@@ -2053,8 +2260,12 @@ int ex_heavy_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, S
     if (e == hipSuccess) {
         std::optional<ScopedStage> stg;
         if (timer) stg.emplace(*timer, 6);
-        hipLaunchKernelGGL(k_exq_hh_hist, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
-                           (unsigned long long)threshold, dh);
+        if (asof)
+            hipLaunchKernelGGL(k_exq_hh_hist<ExSelAsOf>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, dh, *asof);
+        else
+            hipLaunchKernelGGL(k_exq_hh_hist<>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, dh);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(hist, dh, kQBands * 4, hipMemcpyDeviceToHost, s);
@@ -2078,24 +2289,28 @@ int ex_heavy_on(const gns_ex *ex, const ExTable &T, hipStream_t s, ExRead &rd, S
     GNS_TRY(rd.buf(&rd.rows[0], rd.rows_n[0], nrows));
     GNS_TRY(rd.buf(&rd.rows[1], rd.rows_n[1], nrows));
     GNS_TRY(rd.buf(&rd.tmp, rd.tmp_n, tmp_bytes));
-    GNS_TRY(rd.buf(&rd.dk, rd.dk_n, len * std::max<uint32_t>(ex->K, 1)));
+    GNS_TRY(rd.buf(&rd.dk, rd.dk_n, len * std::max<uint32_t>(K, 1)));
     GNS_TRY(rd.buf(&rd.dv, rd.dv_n, len));
     {
         std::optional<ScopedStage> stg;
         if (timer) stg.emplace(*timer, 6);
-        hipLaunchKernelGGL(k_exq_hh_collect, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
-                           (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows);
+        if (asof)
+            hipLaunchKernelGGL(k_exq_hh_collect<ExSelAsOf>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows, *asof);
+        else
+            hipLaunchKernelGGL(k_exq_hh_collect<>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows);
         e = hipGetLastError();
         if (e == hipSuccess)
             e = rocprim::merge_sort(rd.tmp, tmp_bytes, rd.rows[0], rd.rows[1], (size_t)nrows, ExHhLess(), s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_exq_hh_out, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, rd.rows[1], len,
-                               ex->K, rd.dk, rd.dv);
+                               K, rd.dk, rd.dv);
             e = hipGetLastError();
         }
     }
     if (e != hipSuccess) { set_error("exact heavy hitters: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    if (keys) GNS_TRY(rd.copy_out(keys, rd.dk, len * ex->K, s));
+    if (keys) GNS_TRY(rd.copy_out(keys, rd.dk, len * K, s));
     if (values) GNS_TRY(rd.copy_out(values, rd.dv, len * 8, s));
     GNS_HIP(hipStreamSynchronize(s));
     return GNS_OK;
@@ -2379,7 +2594,7 @@ static int ex_aggregate(gns_ex *ex, const ExFilters &filters, uint32_t nf, gns_e
     if (nf == 0) return GNS_OK;
     GNS_TRY(set_device(ex->device));
     ExRead rd;
-    const int rc = ex_aggregate_on(ex, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, filters, nf, out);
+    const int rc = ex_aggregate_on(ex->kp, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, filters, nf, out);
     rd.free_all();
     return rc;
 }
@@ -2399,7 +2614,7 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
     if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
     GNS_TRY(set_device(ex->device));
     ExRead rd;
-    const int rc = ex_heavy_on(ex, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, metric, threshold,
+    const int rc = ex_heavy_on(ex->K, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, metric, threshold,
                                limit, keys, values, n_io);
     rd.free_all();
     return rc;
@@ -2516,7 +2731,7 @@ static int exv_aggregate(gns_ex_view *v, const ExFilters &filters, uint32_t nf, 
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(exv_rows(v));
     if (nf == 0) return GNS_OK;
-    return ex_aggregate_on(v->ex, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, filters, nf, out);
+    return ex_aggregate_on(v->ex->kp, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, filters, nf, out);
 }
 }  // namespace
 
@@ -2535,8 +2750,360 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
     GNS_TRY(set_device(v->ex->device));
     std::lock_guard<std::mutex> lk(v->mu);
     GNS_TRY(exv_rows(v));
-    return ex_heavy_on(v->ex, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, metric, threshold, limit, keys,
+    return ex_heavy_on(v->ex->K, ExTable{v->D, v->f, v->n}, v->stream, v->rd, nullptr, metric, threshold, limit, keys,
                        values, n_io);
+}
+
+// ---------------------------------------------------------------------------
+// History: the store behind the Querier's EndTime (`Timestamp <= ?`, querier.go:211-213,
+// 271-273, 344-346): every interval's view appended under one timestamp (manager.go:139-159),
+// every query answered as of the newest snapshot at or before its end time.
+// ---------------------------------------------------------------------------
+namespace {
+void exh_free_log(ExHistLog &g) {
+    dfree(g.L.rec); dfree(g.f.pkts); dfree(g.f.bytes); dfree(g.f.start); dfree(g.f.end);
+    dfree(g.written); dfree(g.superseded);
+    g.L.rec = nullptr;
+    g.f = FlowState{};
+    g.written = g.superseded = nullptr;
+    g.cap = 0;
+}
+
+void exh_free(gns_ex_hist *h) {
+    exh_free_log(h->log);
+    exv_free_rows(h->SD, h->sf);
+    dfree(h->D.rec); dfree(h->head); dfree(h->dctl); dfree(h->full); dfree(h->ids); dfree(h->mark); dfree(h->fresh);
+    dfree(h->scan); dfree(h->total);
+    h->dsc.free_all();
+    h->rsc.free_all();
+    h->rd.free_all();
+    h->destroy();
+}
+
+// Room for `need` log rows: allocate, copy the published rows, free (before an append links anything).
+int exh_reserve_log(gns_ex_hist *h, uint64_t need) {
+    if (need <= h->log.cap) return GNS_OK;
+    const uint64_t cap = hist_row_capacity(h->log.cap, need), rows = h->plan.rows;
+    const uint32_t RW = h->log.L.RW;
+    ExHistLog g = h->log;
+    g.L.rec = nullptr;
+    g.f = FlowState{};
+    g.written = g.superseded = nullptr;
+    g.cap = cap;
+    int rc;
+    if ((rc = dalloc_t(&g.L.rec, cap * RW)) || (rc = dalloc_t(&g.f.pkts, cap)) || (rc = dalloc_t(&g.f.bytes, cap)) ||
+        (rc = dalloc_t(&g.f.start, cap)) || (rc = dalloc_t(&g.f.end, cap)) || (rc = dalloc_t(&g.written, cap)) ||
+        (rc = dalloc_t(&g.superseded, cap))) {
+        exh_free_log(g);
+        return rc;
+    }
+    hipError_t e = hipSuccess;
+    if (rows) {
+        hipStream_t s = h->stream;
+        const ExHistLog &o = h->log;
+        e = hipMemcpyAsync(g.L.rec, o.L.rec, rows * RW * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.f.pkts, o.f.pkts, rows * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.f.bytes, o.f.bytes, rows * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.f.start, o.f.start, rows * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.f.end, o.f.end, rows * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.written, o.written, rows * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(g.superseded, o.superseded, rows * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        exh_free_log(g);
+        set_error("history log growth: %s", hipGetErrorString(e));
+        return GNS_E_HIP;
+    }
+    if (h->log.cap) h->n_log_grow++;
+    exh_free_log(h->log);
+    h->log = g;
+    return GNS_OK;
+}
+
+// The index rebuilt into at least `want` slots.  Kept: the keys of the published snapshots
+// (a head word) and the `done` ids the running append has resolved, which are renumbered; the
+// claims of a piece that overflowed are dropped.  The head words follow their records.
+int exh_grow_index(gns_ex_hist *h, uint64_t want, uint64_t done) {
+    const uint64_t old_slots = h->slots;
+    uint64_t new_slots = old_slots * 2;
+    while (new_slots < want) new_slots *= 2;
+    if (new_slots > kDictMaxSlots) {
+        set_error("history key index cannot grow beyond 2^30 slots (%llu keys)", (unsigned long long)h->keys);
+        return GNS_E_FULL;
+    }
+    hipStream_t s = h->stream;
+    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
+    uint32_t *nh = nullptr;
+    GNS_TRY(dalloc_t(&nh, new_slots));
+    hipLaunchKernelGGL(k_exh_heads, dim3((unsigned)((old_slots + 255) / 256)), dim3(256), 0, s, h->head, old_slots,
+                       h->mark);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemsetAsync(nh, 0xFF, new_slots * 4, s);
+    if (e != hipSuccess) { dfree(nh); set_error("history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    DictIds marks[2] = {{h->mark, old_slots}, {h->ids, done}};
+    DictIds remaps[1] = {{h->ids, done}};
+    uint64_t slots = old_slots, live = 0;
+    const int rc = dict_rebuild(h->D, slots, marks, 2, nullptr, remaps, 1, new_slots, s, h->dsc, &live, nullptr);
+    if (rc != GNS_OK) { dfree(nh); return rc; }
+    hipLaunchKernelGGL(k_exh_permute, dim3((unsigned)((old_slots + 255) / 256)), dim3(256), 0, s, h->head, old_slots,
+                       h->dsc.remap, nh);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    // (the table is the new one whatever the permute did: the old head words no longer fit it)
+    dfree(h->head);
+    h->head = nh;
+    h->slots = slots;
+    h->D.cap = (uint32_t)(slots - slots / 4);
+    h->claimed = live;
+    h->n_index_grow++;
+    if (e != hipSuccess) { set_error("history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+// query side, under h->mu: the snapshot a query as of *end_ns sees (-1: none) and its policy
+int64_t exh_as_of(const gns_ex_hist *h, const int64_t *end_ns, ExSelAsOf *sel, ExTable *T) {
+    const int64_t s = h->plan.as_of(end_ns);
+    sel->written = h->log.written;
+    sel->superseded = h->log.superseded;
+    sel->s = s < 0 ? 0u : (uint32_t)s;
+    *T = ExTable{h->log.L, h->log.f, h->plan.rows_as_of(s)};
+    return s;
+}
+
+int exh_aggregate(gns_ex_hist *h, const int64_t *end_ns, const ExFilters &filters, uint32_t nf, gns_ex_summary *out) {
+    if (!h || (nf && (!filters.base || !out))) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(ex_filters_check(filters, nf));
+    if (nf == 0) return GNS_OK;
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    ExSelAsOf sel;
+    ExTable T;
+    (void)exh_as_of(h, end_ns, &sel, &T);  // (no snapshot: no rows, every answer is the initial one)
+    return ex_aggregate_on(h->kp, T, h->stream, h->rd, nullptr, filters, nf, out, &sel);
+}
+}  // namespace
+
+int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out) {
+    if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
+    *out = nullptr;
+    GNS_TRY(check_device(p->device));
+    if (p->key.n_fields == 0) { set_error("history needs key fields"); return GNS_E_ARG; }
+    for (uint32_t i = 0; i < p->key.n_fields; i++)
+        if (p->key.fields[i] < GNS_F_SRCIP || p->key.fields[i] > GNS_F_PROTO) {
+            set_error("unknown key field id %u (task.go:363 rejects it)", p->key.fields[i]);
+            return GNS_E_ARG;
+        }
+    if (p->max_rows > kHistMax || p->max_flows > kDictMaxSlots / 2) { set_error("history capacity too large"); return GNS_E_ARG; }
+    gns_ex_hist *h = new gns_ex_hist();
+    h->device = p->device;
+    int rc = GNS_OK;
+    do {
+        if ((rc = set_device(h->device)) != GNS_OK) break;
+        if ((rc = make_plan(p->key, 0, &h->kp)) != GNS_OK) break;
+        h->K = h->kp.K;
+        if ((rc = h->init()) != GNS_OK || (rc = h->rd.init_keep()) != GNS_OK) break;
+        h->slots = hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10));
+        h->D.mask = (uint32_t)(h->slots - 1);
+        h->D.K = h->K;
+        h->D.RW = dict_record_words(h->K);
+        h->D.seed = 0x5BD1E995u;
+        h->D.cap = (uint32_t)(h->slots - h->slots / 4);
+        h->log.L = h->D;
+        h->log.L.rec = nullptr; h->log.L.ctl = nullptr; h->log.L.mask = 0; h->log.L.cap = 0;
+        h->SD = h->log.L;
+        if ((rc = dalloc_t(&h->D.rec, h->slots * h->D.RW)) || (rc = dalloc_t(&h->head, h->slots)) ||
+            (rc = dalloc_t(&h->dctl, 4)) || (rc = dalloc_t(&h->full, 1)) || (rc = dalloc_t(&h->fresh, 4)) ||
+            (rc = dalloc_t(&h->total, 4)))
+            break;
+        h->D.ctl = h->dctl;
+        if ((rc = exh_reserve_log(h, p->max_rows ? p->max_rows : (1ull << 20))) != GNS_OK) break;
+        hipStream_t s = h->stream;
+        if (hipMemsetAsync(h->D.rec, 0, h->slots * h->D.RW * 4, s) != hipSuccess ||
+            hipMemsetAsync(h->head, 0xFF, h->slots * 4, s) != hipSuccess ||
+            hipMemsetAsync(h->dctl, 0, 16, s) != hipSuccess || hipMemsetAsync(h->full, 0, 8, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            set_error("history create: device clear failed");
+            rc = GNS_E_HIP;
+        }
+    } while (0);
+    if (rc != GNS_OK) { exh_free(h); delete h; return rc; }
+    *out = h;
+    return GNS_OK;
+}
+
+int gns_ex_hist_destroy(gns_ex_hist *h) {
+    if (!h) return GNS_OK;
+    (void)hipSetDevice(h->device);
+    h->quiesce();
+    exh_free(h);
+    delete h;
+    return GNS_OK;
+}
+
+int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uint64_t out[2]) {
+    if (!h || !v) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lv(v->mu);  // a reader call on the view: a refresh waits for the append
+    if (!v->fresh) { set_error("history append: view never refreshed"); return GNS_E_ARG; }
+    if (!hist_same_layout(h->kp.src, h->kp.K, v->ex->kp.src, v->ex->kp.K)) {
+        set_error("history append: the view's key layout (%u bytes) is not the history's (%u bytes)", v->ex->kp.K, h->kp.K);
+        return GNS_E_ARG;
+    }
+    if (v->ex->device != h->device) {
+        set_error("history append: the view is on device %d, the history on device %d", v->ex->device, h->device);
+        return GNS_E_ARG;
+    }
+    int chk = h->plan.append_check(timestamp_ns, 0);
+    if (chk == HIST_E_TIME) {
+        set_error("history append: timestamp %lld is not after the last snapshot's %lld", (long long)timestamp_ns,
+                  (long long)h->plan.ts.back());
+        return GNS_E_ARG;
+    }
+    if (chk != HIST_OK) { set_error("history holds 2^32 - 2 snapshots"); return GNS_E_FULL; }
+    GNS_TRY(set_device(h->device));
+    GNS_TRY(exv_rows(v));
+    const uint64_t n = v->n;
+    if (h->plan.append_check(timestamp_ns, n) != HIST_OK) {
+        set_error("history log cannot grow beyond 2^32 - 2 rows (%llu held, %llu appended)", (unsigned long long)h->plan.rows,
+                  (unsigned long long)n);
+        return GNS_E_FULL;
+    }
+    hipStream_t s = h->stream;
+    const uint32_t S = (uint32_t)h->plan.ts.size();
+    uint64_t fresh = 0;
+    if (n) {
+        GNS_TRY(exh_reserve_log(h, h->plan.rows + n));
+        if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+        GNS_TRY(stream_wait_now(s, v->stream, "history append"));  // behind the refresh the view answers for
+        // A1: every row's index slot, piece by piece, before anything is linked
+        for (uint64_t off = 0; off < n; off += kResolvePiece) {
+            const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
+            if (h->claimed >= h->slots / 2) GNS_TRY(exh_grow_index(h, 0, off));  // keep the load <= ~1/2
+            KeyResolve r{};
+            r.keys = reinterpret_cast<const uint8_t *>(v->D.rec + off * v->D.RW + 1);  // key words follow the tag
+            r.stride = 4 * v->D.RW; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + off;
+            r.full_word = h->full;
+            for (;;) {
+                const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
+                if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+                GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
+                // room for the piece if every key of it is new, at most 8 times the table per step
+                GNS_TRY(exh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->keys + off + m), 8 * h->slots), off));
+            }
+        }
+        // A2
+        GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
+        hipLaunchKernelGGL(k_exh_link, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v->D, v->f, n, h->ids, h->head,
+                           (uint32_t)h->slots, h->log, h->plan.rows, S, h->fresh);
+        GNS_HIP(hipGetLastError());
+        uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
+        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));  // the view's rows are read: a refresh may replace them
+        fresh = *hp;
+    }
+    h->keys += fresh;
+    h->plan.publish(timestamp_ns, n);  // last: the snapshot exists from here on
+    if (out) { out[0] = n; out[1] = fresh; }
+    return GNS_OK;
+}
+
+int gns_ex_hist_times(gns_ex_hist *h, int64_t *ts, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t n = h->plan.ts.size(), m = std::min<uint64_t>(*n_io, n);
+    *n_io = n;
+    if (ts && m) memcpy(ts, h->plan.ts.data(), m * sizeof(int64_t));
+    return GNS_OK;
+}
+
+int gns_ex_hist_stats(gns_ex_hist *h, uint64_t out[8]) {
+    if (!h || !out) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->plan.ts.size(); out[1] = h->plan.rows; out[2] = h->keys; out[3] = h->log.cap;
+    out[4] = h->slots; out[5] = h->n_index_grow; out[6] = h->n_log_grow; out[7] = 0;
+    return GNS_OK;
+}
+
+int gns_ex_hist_aggregate(gns_ex_hist *h, const int64_t *end_ns, const gns_ex_filter *f, uint32_t nf, gns_ex_summary *out) {
+    return exh_aggregate(h, end_ns, ExFilters(f), nf, out);
+}
+
+int gns_ex_hist_aggregate_cidr(gns_ex_hist *h, const int64_t *end_ns, const gns_ex_cidr *f, uint32_t nf,
+                               gns_ex_summary *out) {
+    return exh_aggregate(h, end_ns, ExFilters(f), nf, out);
+}
+
+int gns_ex_hist_heavy_hitters(gns_ex_hist *h, const int64_t *end_ns, int metric, uint64_t threshold, uint64_t limit,
+                              uint8_t *keys, uint64_t *values, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    ExSelAsOf sel;
+    ExTable T;
+    (void)exh_as_of(h, end_ns, &sel, &T);
+    return ex_heavy_on(h->K, T, h->stream, h->rd, nullptr, metric, threshold, limit, keys, values, n_io, &sel);
+}
+
+int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, int64_t *start_ns, int64_t *end_out_ns,
+                         uint64_t *pkts, uint64_t *bytes, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    ExSelAsOf sel;
+    ExTable T;
+    (void)exh_as_of(h, end_ns, &sel, &T);
+    const uint64_t cap = *n_io;
+    if (T.rows == 0) { *n_io = 0; return GNS_OK; }
+    // V1-V3 over the log: the live rows compacted in log order
+    hipStream_t s = h->stream;
+    const uint32_t nblk = (uint32_t)((T.rows + 255) / 256);
+    const uint32_t nb = (nblk + kVBins - 1) / kVBins, ngrp = (nb + kTGrp - 1) / kTGrp;
+    const uint64_t words = (uint64_t)nb * kVBins + (uint64_t)ngrp * kVBins + kVBins;
+    if (words > h->scan_n) GNS_TRY(grow_buf(&h->scan, h->scan_n, words));
+    uint32_t *cnt = h->scan, *part = cnt + (uint64_t)nb * kVBins, *tot = part + (uint64_t)ngrp * kVBins;
+    hipLaunchKernelGGL(k_exhv_count, dim3(nb * kVBins), dim3(256), 0, s, T.D, T.rows, T.f, sel, nb, cnt);
+    hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part);
+    hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, s, part, ngrp, kVBins, tot);
+    hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, s, tot, kVBins, h->total);
+    hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part, tot);
+    GNS_HIP(hipGetLastError());
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
+    GNS_HIP(hipMemcpyAsync(hp, h->total, 4, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    const uint64_t live = *hp, m = std::min<uint64_t>(cap, live);
+    *n_io = live;
+    if (m == 0 || !(keys || start_ns || end_out_ns || pkts || bytes)) return GNS_OK;
+    if (live > h->scap) {
+        exv_free_rows(h->SD, h->sf);
+        h->scap = 0;
+        const uint64_t c = 2 * live;
+        int rc;
+        if ((rc = dalloc_t(&h->SD.rec, c * h->SD.RW)) || (rc = dalloc_t(&h->sf.pkts, c)) || (rc = dalloc_t(&h->sf.bytes, c)) ||
+            (rc = dalloc_t(&h->sf.start, c)) || (rc = dalloc_t(&h->sf.end, c))) {
+            exv_free_rows(h->SD, h->sf);
+            return rc;
+        }
+        h->scap = c;
+    }
+    hipLaunchKernelGGL(k_exhv_write, dim3(nblk), dim3(256), 0, s, T.D, T.rows, T.f, sel, nb, cnt, h->SD, h->sf, h->scap);
+    GNS_HIP(hipGetLastError());
+    ExRead &rd = h->rd;
+    if (keys) {
+        GNS_TRY(rd.buf(&rd.dk, rd.dk_n, m * h->K));
+        hipLaunchKernelGGL(k_ex_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)nullptr, m,
+                           h->SD, h->sf, rd.dk, (long long *)nullptr, (long long *)nullptr,
+                           (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+        GNS_HIP(hipGetLastError());
+        GNS_TRY(rd.copy_out(keys, rd.dk, m * h->K, s));
+    }
+    if (start_ns) GNS_TRY(rd.copy_out(start_ns, h->sf.start, m * 8, s));
+    if (end_out_ns) GNS_TRY(rd.copy_out(end_out_ns, h->sf.end, m * 8, s));
+    if (pkts) GNS_TRY(rd.copy_out(pkts, h->sf.pkts, m * 8, s));
+    if (bytes) GNS_TRY(rd.copy_out(bytes, h->sf.bytes, m * 8, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
 }
 
 int gns_ex_merge(gns_ex *ex, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,

@@ -1,0 +1,83 @@
+// gns_histplan.hpp -- the host bookkeeping of an exact history (gns_ex_hist_*, gns_exact.hip):
+// the table of snapshot timestamps, s(T) = the newest snapshot at or before a query time, the
+// checks an append passes before any device call, and the capacity arithmetic of the log and
+// of the key index.  The device side holds rows and version words only; which snapshot a
+// query sees is decided here.
+// No HIP here: the header compiles in a host-only driver (tests/test_exact_history_cpu.py).
+// Internal: not part of the C ABI.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace gns {
+
+// Log rows and snapshots are numbered in 32-bit version words whose all-ones value means
+// "not superseded": both stay at or below 2^32 - 2.
+constexpr uint64_t kHistMax = 0xFFFFFFFEull;
+constexpr uint32_t kHistOpen = 0xFFFFFFFFu;
+
+enum HistCheck { HIST_OK = 0, HIST_E_TIME = 1, HIST_E_SNAPSHOTS = 2, HIST_E_ROWS = 3 };
+
+struct HistPlan {
+    std::vector<int64_t> ts;         // strictly increasing
+    std::vector<uint64_t> end_rows;  // log rows of snapshots 0..i: rows are in snapshot order
+    uint64_t rows = 0;               // log rows of the published snapshots
+
+    // s(T): the largest i with ts[i] <= T, -1 when there is none; end == nullptr: the newest
+    int64_t as_of(const int64_t *end) const {
+        if (!end) return (int64_t)ts.size() - 1;
+        size_t lo = 0, hi = ts.size();  // ts[i] <= *end for i < lo, > *end for i >= hi
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (ts[mid] <= *end) lo = mid + 1;
+            else hi = mid;
+        }
+        return (int64_t)lo - 1;
+    }
+
+    // an append of n rows under timestamp t: HIST_E_TIME when t does not lie after the last
+    // snapshot's, HIST_E_SNAPSHOTS / HIST_E_ROWS when the log would pass kHistMax
+    int append_check(int64_t t, uint64_t n) const {
+        if (!ts.empty() && t <= ts.back()) return HIST_E_TIME;
+        if (ts.size() >= kHistMax) return HIST_E_SNAPSHOTS;
+        if (n > kHistMax - rows) return HIST_E_ROWS;
+        return HIST_OK;
+    }
+
+    // the rows a query as of snapshot s scans: every row of a later snapshot lies behind them
+    uint64_t rows_as_of(int64_t s) const { return s < 0 ? 0 : end_rows[(size_t)s]; }
+
+    // the append is complete: snapshot ts.size() exists
+    void publish(int64_t t, uint64_t n) {
+        ts.push_back(t);
+        rows += n;
+        end_rows.push_back(rows);
+    }
+};
+
+// Row capacity of a log of `cap` rows that is to hold `need`: unchanged when it fits, else
+// doubled (from at least 1) until it does, never beyond kHistMax.  need <= kHistMax.
+inline uint64_t hist_row_capacity(uint64_t cap, uint64_t need) {
+    if (need <= cap) return cap;
+    uint64_t c = cap ? cap : 1;
+    while (c < need) c = c > kHistMax / 2 ? kHistMax : c * 2;
+    return c;
+}
+
+// Slots of a key index that holds `flows` distinct keys at a load of at most 1/2: a power of
+// two, at least 64.
+inline uint64_t hist_index_slots(uint64_t flows) {
+    uint64_t s = 64;
+    while (s < 2 * flows) s <<= 1;
+    return s;
+}
+
+// two layouts name the same key bytes (src: the tuple byte of every key byte, make_plan's numbering)
+inline bool hist_same_layout(const uint8_t *a, uint32_t ka, const uint8_t *b, uint32_t kb) {
+    if (ka != kb) return false;
+    for (uint32_t i = 0; i < ka; i++)
+        if (a[i] != b[i]) return false;
+    return true;
+}
+
+}  // namespace gns

@@ -550,6 +550,100 @@ class ExactView:
         return _heavy_hitters(self._L.gns_ex_view_heavy_hitters, self._h, self.key_bytes, metric, threshold, limit)
 
 
+def _int64_ns(what: str, t) -> int:
+    t = int(t)
+    if not -(1 << 63) <= t < (1 << 63):
+        raise ValueError(f"{what} {t} is not an int64 of nanoseconds")
+    return t
+
+
+def _end_ptr(end_time):
+    """The end_ns argument of a gns_ex_hist_* query: NULL (the newest snapshot) or an int64."""
+    if end_time is None:
+        return None, None
+    c = ct.c_int64(_int64_ns("end_time", end_time))
+    return c, ct.byref(c)
+
+
+class ExactHistory:
+    """The store behind the Querier's EndTime (gns_ex_hist_*): an append-only, device-resident
+    log of the rows of refreshed ExactViews, each ``append`` one snapshot under a strictly
+    increasing timestamp (ns, signed).  A query with ``end_time=T`` answers as of the newest
+    snapshot at or before T -- per flow the latest row stored by then, the reference's
+    argMax(..., Timestamp) with `Timestamp <= ?` -- and as an empty table when there is none;
+    ``end_time=None`` is the newest snapshot.  Whole views and delta views (refresh(cursor))
+    give the same answers.  Flows are never forgotten: rows stored before a reset of the
+    aggregator stay, and a flow that returns supersedes its old row."""
+
+    def __init__(self, key_fields: Sequence[str], max_rows: int = 0, max_flows: int = 0, device: int = 0):
+        if max_rows < 0 or max_flows < 0:
+            raise ValueError("max_rows and max_flows are unsigned (initial capacities; both grow)")
+        self._L = _lib.load()
+        self.key_fields = list(key_fields)
+        self.key_bytes = sum(_lib.FIELD_SIZE.get(f, 0) for f in self.key_fields)
+        self.device = device
+        p = _lib.ExHistParams()
+        p.key = _lib.Layout.of(self.key_fields)
+        p.max_rows, p.max_flows, p.device = max_rows, max_flows, device
+        h = ct.c_void_p()
+        check(self._L.gns_ex_hist_create(ct.byref(p), ct.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.gns_ex_hist_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, view: ExactView, timestamp_ns: int):
+        """The rows of a refreshed view as the next snapshot; may run on the snapshotter's thread
+        while the aggregator ingests.  Returns (rows appended, keys new to the history)."""
+        if not isinstance(view, ExactView):
+            raise TypeError("append takes an ExactView")
+        out = (ct.c_uint64 * 2)()
+        check(self._L.gns_ex_hist_append(self._h, view._h, _int64_ns("timestamp_ns", timestamp_ns), out))
+        return int(out[0]), int(out[1])
+
+    def times(self) -> List[int]:
+        n = ct.c_uint64(0)
+        check(self._L.gns_ex_hist_times(self._h, None, ct.byref(n)))
+        ts = np.zeros(max(n.value, 1), np.int64)
+        n2 = ct.c_uint64(n.value)
+        check(self._L.gns_ex_hist_times(self._h, ts.ctypes.data, ct.byref(n2)))
+        return [int(t) for t in ts[:min(n.value, n2.value)]]
+
+    STATS = ["snapshots", "rows", "keys", "row_capacity", "index_slots", "index_growths", "log_growths", "_"]
+
+    def stats(self) -> dict:
+        s = (ct.c_uint64 * 8)()
+        check(self._L.gns_ex_hist_stats(self._h, s))
+        return {k: int(s[i]) for i, k in enumerate(self.STATS) if k != "_"}
+
+    def _bind(self, name: str, end_time):
+        """fn(h, ...) as the live calls have it from gns_ex_hist_<name>(h, end_ns, ...)."""
+        keep, ptr = _end_ptr(end_time)
+        return lambda h, *a: getattr(self._L, "gns_ex_hist_" + name)(h, ptr, *a)
+
+    def aggregate(self, filters, end_time=None) -> List[Summary]:
+        """ExactAggregator.aggregate as of ``end_time``: flows / packets / bytes over each flow's
+        latest row, first_ns / last_ns / max_packets / max_bytes over every row stored by then."""
+        return _aggregate(self._bind("aggregate", end_time), self._bind("aggregate_cidr", end_time), self._h, filters)
+
+    def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0, end_time=None):
+        """ExactAggregator.heavy_hitters over each flow's latest row as of ``end_time``."""
+        return _heavy_hitters(self._bind("heavy_hitters", end_time), self._h, self.key_bytes, metric, threshold, limit)
+
+    def snapshot_arrays(self, end_time=None):
+        """(keys, start, end, packets, bytes) of each flow's latest row as of ``end_time``, in
+        log order (snapshot, then the view's row order)."""
+        return _snapshot_arrays(self._bind("snapshot", end_time), self._h, self.key_bytes)
+
+
 class ExactAggregator:
     """One exact task's device state (gns_ex handle)."""
 
@@ -931,17 +1025,60 @@ class ExactTask:
         from . import checkpoint
         checkpoint.restore(self.agg, path)
 
-    # --- query.Querier (internal/query/querier.go) on the live table ---
+    # --- the history behind end_time (gns_ex_hist_*) ---
+    def keep_history(self, **kw) -> ExactHistory:
+        """Attach an ExactHistory of this task's layout (``kw``: its max_rows / max_flows), a view
+        and a cursor: ``record`` then stores an interval, and the Querier calls below answer
+        ``end_time`` from it.  Returns the history (the one already attached, if any)."""
+        if getattr(self, "history", None) is None:
+            kw.setdefault("device", self.agg.device)
+            self.history = ExactHistory(self.key_fields, **kw)
+            self._hist_view = self.agg.view()
+            self._hist_cursor = 0
+        return self.history
+
+    def record(self, timestamp_ns: int, full: bool = False):
+        """One interval of the snapshotter (manager.go:139-159): refresh the history's view -- the
+        flows touched since the last record, or the whole table with ``full`` -- and append it
+        under ``timestamp_ns``.  Returns (rows appended, keys new to the history)."""
+        h = getattr(self, "history", None)
+        if h is None:
+            raise ValueError("record: no history attached (keep_history first)")
+        cur = self._hist_view.refresh(0 if full else self._hist_cursor)
+        out = h.append(self._hist_view, timestamp_ns)
+        self._hist_cursor = cur  # (after the append: a rejected timestamp loses no interval)
+        return out
+
+    def _as_of(self, end_time):
+        """The history an end_time query answers from; ValueError without one."""
+        h = getattr(self, "history", None)
+        if h is None:
+            _no_end_time(end_time)
+        return h
+
+    # --- query.Querier (internal/query/querier.go) on the live table, or as of end_time ---
     def aggregate_flows_many(self, requests) -> List[TaskSummary]:
-        """AggregateFlows (querier.go:251-319) for a batch of AggregationRequests in ONE device
-        call.  A request is a dict of src_ip / dst_ip / src_port / dst_port / protocol (absent or
-        None: no constraint); an end_time raises ValueError."""
-        flt = []
+        """AggregateFlows (querier.go:251-319) for a batch of AggregationRequests.  A request is a
+        dict of src_ip / dst_ip / src_port / dst_port / protocol (absent or None: no constraint)
+        and end_time.  The requests without end_time are answered from the live table in ONE
+        device call; those with one from the attached history, one device call per distinct
+        end_time (ValueError when no history is attached)."""
+        flt, at = [], []
         for req in requests:
             req = dict(req)
-            _no_end_time(req.pop("end_time", None))
+            t = req.pop("end_time", None)
+            if t is not None:
+                self._as_of(t)
+            at.append(t)
             flt.append(make_filter(**req))
-        return [TaskSummary(self.name_, s.bytes, s.packets, s.flows) for s in self.agg.aggregate(flt)]
+        out: List[Optional[Summary]] = [None] * len(flt)
+        for t in dict.fromkeys(at):  # distinct end times, in order of appearance
+            idx = [i for i, x in enumerate(at) if x == t]
+            sub = [flt[i] for i in idx]
+            res = self.agg.aggregate(sub) if t is None else self.history.aggregate(sub, end_time=t)
+            for i, r in zip(idx, res):
+                out[i] = r
+        return [TaskSummary(self.name_, s.bytes, s.packets, s.flows) for s in out]
 
     def aggregate_flows(self, src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None,
                         end_time=None) -> TaskSummary:
@@ -953,20 +1090,25 @@ class ExactTask:
         max(ByteCount) of the flows equal to ``flow_keys`` on every key given (all zero when
         none is)."""
         flt = filter_from_flow_keys(flow_keys)
-        _no_end_time(end_time)
-        s = self.agg.aggregate([flt])[0]
+        if end_time is not None:
+            s = self._as_of(end_time).aggregate([flt], end_time=end_time)[0]
+        else:
+            s = self.agg.aggregate([flt])[0]
         return FlowLifecycle(s.first_ns, s.last_ns, s.max_packets, s.max_bytes)
 
     def heavy_hitters(self, type: int, limit: int, end_time=None) -> List[HeavyHitter]:
         """QueryHeavyHitters (querier.go:191-248): Type 0 PacketCount, 1 ByteCount, ORDER BY value
         DESC LIMIT ``limit`` (ties by key bytes; LIMIT 0 and an unknown Type select no row, as
         in the reference)."""
-        _no_end_time(end_time)
+        hist = self._as_of(end_time) if end_time is not None else None
         if limit < 0:
             raise ValueError("negative limit")
         if type not in (0, 1) or limit == 0:
             return []
-        keys, vals = self.agg.heavy_hitters(type, 0, limit)
+        if hist is not None:
+            keys, vals = hist.heavy_hitters(type, 0, limit, end_time=end_time)
+        else:
+            keys, vals = self.agg.heavy_hitters(type, 0, limit)
         return [HeavyHitter(key_string(bytes(k), self.key_fields)[0], int(v)) for k, v in zip(keys, vals)]
 
     def alerter_msg(self, rules) -> str:

@@ -130,6 +130,20 @@ class Manager:
         process() keeps feeding the tasks."""
         return {t.name(): t.snapshot_from(v) for t, v in zip(self.tasks(), views)}
 
+    def keep_history(self, **kw) -> Dict[str, object]:
+        """ExactTask.keep_history for every exact task: name -> ExactHistory."""
+        return {t.name(): t.keep_history(**kw) for t in self.tasks() if hasattr(t, "keep_history")}
+
+    def record(self, timestamp_ns: int, full: bool = False) -> Dict[str, object]:
+        """One snapshot interval: every exact task's changed flows into its history under ONE
+        timestamp, as the reference's snapshotter writes them (manager.go:140).  name -> (rows
+        appended, keys new to the history)."""
+        tasks = [t for t in self.tasks() if hasattr(t, "record")]
+        for t in tasks:
+            if getattr(t, "history", None) is None:
+                raise ValueError(f"record: task {t.name()} has no history (keep_history first)")
+        return {t.name(): t.record(timestamp_ns, full=full) for t in tasks}
+
     def reset_all(self) -> None:  # resetAllTasks, manager.go:179-193
         for t in self.tasks():
             t.reset()

@@ -818,6 +818,64 @@ int gns_ex_view_aggregate_cidr(gns_ex_view *v, const gns_ex_cidr *f, uint32_t nf
 int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, uint64_t limit,
                               uint8_t *keys, uint64_t *values, uint64_t *n_io);
 
+/* History: the store behind the Querier's EndTime.  Every request of query.Querier carries
+ * an EndTime and each query adds `Timestamp <= ?` on the snapshot time (querier.go:211-213,
+ * 271-273, 344-346); the reference answers from the per-interval snapshot rows its writer
+ * stored under one Timestamp (manager.go:139-159).  A history is that store on the device: an
+ * append-only log of the rows of refreshed views, each append one snapshot.
+ *   - Snapshots 0..S-1 carry strictly increasing timestamps (int64 ns, negative values are
+ *     legal).  gns_ex_hist_append adds the rows of one refreshed gns_ex_view -- whole
+ *     (since == 0) or a delta, the store answers the same either way -- as snapshot S.  It is
+ *     a reader call on the view: a concurrent refresh of the view waits, the handle keeps
+ *     ingesting, and the call may run on the snapshotter's thread.  out[0] = rows appended,
+ *     out[1] = keys new to the history (out may be NULL).  A view without rows is legal and
+ *     registers the timestamp.
+ *   - A query names a time by end_ns: NULL is the newest snapshot, else s(T) = the newest
+ *     snapshot with timestamp <= *end_ns; with none the query answers as an empty table.  A
+ *     row written by snapshot a is SEEN when a <= s(T) and LIVE when no later row of the same
+ *     key is seen too: the argMax(..., Timestamp) of the reference.  The store never forgets
+ *     a flow: rows written before a gns_ex_reset of the source handle stay, and a flow that
+ *     comes back after it supersedes its old row with its new, smaller counts.
+ *   - gns_ex_hist_aggregate[_cidr] take the filters of gns_ex_aggregate[_cidr] unchanged (a
+ *     masked field outside the layout matches nothing).  flows, packets, bytes are COUNT / SUM
+ *     over the matching LIVE rows (AggregateFlows); first_ns, last_ns, max_packets, max_bytes
+ *     are min / max over the matching SEEN rows, superseded ones included (TraceFlow has no
+ *     argMax); all zero when no seen row matches.  A history holding one whole view answers
+ *     bit-equal to gns_ex_view_aggregate of that view.
+ *   - gns_ex_hist_heavy_hitters lists the LIVE rows under the rules and the *n_io protocol of
+ *     gns_ex_heavy_hitters.  gns_ex_hist_snapshot returns the LIVE rows in log order
+ *     (snapshot, then the view's row order) under the protocol of gns_ex_snapshot.
+ *   - gns_ex_hist_times: *n_io capacity in, the number of snapshots out; ts may be NULL.
+ *     gns_ex_hist_stats: snapshots, rows, distinct keys, row capacity, index slots, index
+ *     growths, log growths, 0.
+ *   - max_rows / max_flows are only the INITIAL capacities of the log and of the key index
+ *     (0: 2^20 rows, 2^16 keys); both grow.  GNS_E_FULL is left only for a log beyond
+ *     2^32 - 2 rows or snapshots (and the dictionary's 2^30 slots).
+ *   - GNS_E_ARG with the history untouched, checked before any device call: a null handle, a
+ *     view that was never refreshed, a view whose handle's key layout differs from the
+ *     history's, a view on another device, timestamp_ns <= the last snapshot's, and the
+ *     filter / metric errors of the live calls.  Nothing of a snapshot is visible to a query
+ *     before its append has returned GNS_OK.
+ *   - Threads: any, serialised by the history's mutex; its stream and pinned staging are its
+ *     own and no query allocates or frees once warm.  A history does not refer to the
+ *     handle or the view after the append returns: either may be destroyed first.
+ * Memory: a record plus 40 bytes per log row (32 of state, 8 of version words); per index
+ * slot a record plus 4 bytes; 8 MB of pinned host staging.  Not offered: trimming old
+ * snapshots, exporting the log, roll-ups of a history. */
+typedef struct gns_ex_hist gns_ex_hist;
+typedef struct gns_ex_hist_params { gns_layout key; uint64_t max_rows, max_flows; int device; } gns_ex_hist_params;
+int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out);
+int gns_ex_hist_destroy(gns_ex_hist *h);
+int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uint64_t out[2]);
+int gns_ex_hist_times(gns_ex_hist *h, int64_t *ts, uint64_t *n_io);
+int gns_ex_hist_stats(gns_ex_hist *h, uint64_t out[8]);
+int gns_ex_hist_aggregate(gns_ex_hist *h, const int64_t *end_ns, const gns_ex_filter *f, uint32_t nf, gns_ex_summary *out);
+int gns_ex_hist_aggregate_cidr(gns_ex_hist *h, const int64_t *end_ns, const gns_ex_cidr *f, uint32_t nf, gns_ex_summary *out);
+int gns_ex_hist_heavy_hitters(gns_ex_hist *h, const int64_t *end_ns, int metric, uint64_t threshold, uint64_t limit,
+                              uint8_t *keys, uint64_t *values, uint64_t *n_io);
+int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, int64_t *start_ns, int64_t *end_out_ns,
+                         uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
+
 /* ------------------------------------------------------------------ */
 /* Exact spread: the device ground truth of SuperSpread                */
 /* ------------------------------------------------------------------ */

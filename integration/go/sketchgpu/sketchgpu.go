@@ -1181,6 +1181,140 @@ func (w *ExactView) HeavyHitters(metric int, threshold, limit uint64) (keys []by
 // Close releases the view.
 func (w *ExactView) Close() { C.gns_ex_view_destroy(w.v) }
 
+// History is the store behind the Querier's EndTime (gns_ex_hist_*): an append-only log, on
+// the device, of the rows the snapshotter hands to the writer each interval
+// (manager.go:139-159).  Append stores one refreshed ExactView -- whole or delta -- under a
+// Timestamp; every query takes an end time and answers as of the newest snapshot at or
+// before it (`Timestamp <= ?`, querier.go:211-213, 271-273, 344-346): per flow its latest row
+// by then, argMax(..., Timestamp).  A nil end time is the newest snapshot.  Calls may come
+// from any goroutine.
+type History struct {
+	h        *C.gns_ex_hist
+	keyBytes int
+}
+
+// NewHistory allocates a history for views of an Exact with the same key fields.  maxRows and
+// maxFlows are initial capacities (0: defaults); both grow.
+func NewHistory(keyFields []string, maxRows, maxFlows uint64, device int) (*History, error) {
+	var p C.gns_ex_hist_params
+	p.key.n_fields = C.uint32_t(len(keyFields))
+	kb := 0
+	for i, f := range keyFields {
+		p.key.fields[i] = fieldIDs[f]
+		kb += map[string]int{"SrcIP": 16, "DstIP": 16, "SrcPort": 2, "DstPort": 2, "Protocol": 1}[f]
+	}
+	p.max_rows, p.max_flows, p.device = C.uint64_t(maxRows), C.uint64_t(maxFlows), C.int(device)
+	var h *C.gns_ex_hist
+	if err := lastErr(C.gns_ex_hist_create(&p, &h)); err != nil {
+		return nil, err
+	}
+	return &History{h: h, keyBytes: kb}, nil
+}
+
+func endNs(end *int64) *C.int64_t { return (*C.int64_t)(unsafe.Pointer(end)) }
+
+// Append stores the view's rows as the next snapshot; tsNano must lie after the last one's.
+// A reader call on the view: it may run on the snapshotter goroutine while the Exact ingests.
+func (y *History) Append(w *ExactView, tsNano int64) (rows, newKeys uint64, err error) {
+	var out [2]C.uint64_t
+	err = lastErr(C.gns_ex_hist_append(y.h, w.v, C.int64_t(tsNano), &out[0]))
+	return uint64(out[0]), uint64(out[1]), err
+}
+
+// Times returns the snapshots' timestamps.
+func (y *History) Times() ([]int64, error) {
+	var n C.uint64_t
+	if err := lastErr(C.gns_ex_hist_times(y.h, nil, &n)); err != nil || n == 0 {
+		return nil, err
+	}
+	ts := make([]int64, int(n))
+	err := lastErr(C.gns_ex_hist_times(y.h, (*C.int64_t)(unsafe.Pointer(&ts[0])), &n))
+	if int(n) < len(ts) {
+		ts = ts[:int(n)]
+	}
+	return ts, err
+}
+
+// Stats returns snapshots, rows, distinct keys, row capacity, index slots, index growths, log growths, 0.
+func (y *History) Stats() (out [8]uint64, err error) {
+	err = lastErr(C.gns_ex_hist_stats(y.h, (*C.uint64_t)(unsafe.Pointer(&out[0]))))
+	return
+}
+
+// Aggregate is Exact.Aggregate as of end: counts and sums over each flow's latest row, first /
+// last / max over every row stored by then (AggregateFlows and TraceFlow).
+func (y *History) Aggregate(end *int64, filters []ExactFilter) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cf, err := exactFilters(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_hist_aggregate(y.h, endNs(end), &cf[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
+}
+
+// AggregateCIDR is Exact.AggregateCIDR as of end (gns_ex_hist_aggregate_cidr).
+func (y *History) AggregateCIDR(end *int64, filters []ExactCIDR) ([]ExactSummary, error) {
+	n := len(filters)
+	if n == 0 {
+		return nil, nil
+	}
+	cc, err := exactCIDRs(filters)
+	if err != nil {
+		return nil, err
+	}
+	cs := make([]C.gns_ex_summary, n)
+	if err := lastErr(C.gns_ex_hist_aggregate_cidr(y.h, endNs(end), &cc[0], C.uint32_t(n), &cs[0])); err != nil {
+		return nil, err
+	}
+	return exactSummaries(cs), nil
+}
+
+// HeavyHitters is Exact.HeavyHitters over each flow's latest row as of end (QueryHeavyHitters).
+func (y *History) HeavyHitters(end *int64, metric int, threshold, limit uint64) (keys []byte, values []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_hist_heavy_hitters(y.h, endNs(end), C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		nil, nil, &n)); err != nil || n == 0 {
+		return nil, nil, err
+	}
+	m := int(n)
+	keys, values = make([]byte, m*y.keyBytes+1), make([]uint64, m)
+	err = lastErr(C.gns_ex_hist_heavy_hitters(y.h, endNs(end), C.int(metric), C.uint64_t(threshold), C.uint64_t(limit),
+		(*C.uint8_t)(unsafe.Pointer(&keys[0])), (*C.uint64_t)(unsafe.Pointer(&values[0])), &n))
+	if int(n) < m { // (an Append in between only adds rows; a shorter list cannot happen, but never read past it)
+		m = int(n)
+	}
+	return keys[:m*y.keyBytes], values[:m], err
+}
+
+// Flows returns each flow's latest row as of end, in log order, in the layout of Exact.Flows.
+func (y *History) Flows(end *int64) (keys []byte, start, last []int64, pkts, bytes []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_hist_snapshot(y.h, endNs(end), nil, nil, nil, nil, nil, &n)); err != nil {
+		return
+	}
+	m := int(n)
+	keys = make([]byte, m*y.keyBytes+1)
+	start, last = make([]int64, m+1), make([]int64, m+1)
+	pkts, bytes = make([]uint64, m+1), make([]uint64, m+1)
+	err = lastErr(C.gns_ex_hist_snapshot(y.h, endNs(end), (*C.uint8_t)(unsafe.Pointer(&keys[0])),
+		(*C.int64_t)(unsafe.Pointer(&start[0])), (*C.int64_t)(unsafe.Pointer(&last[0])),
+		(*C.uint64_t)(unsafe.Pointer(&pkts[0])), (*C.uint64_t)(unsafe.Pointer(&bytes[0])), &n))
+	if int(n) < m {
+		m = int(n)
+	}
+	return keys[:m*y.keyBytes], start[:m], last[:m], pkts[:m], bytes[:m], err
+}
+
+// Close releases the history.
+func (y *History) Close() { C.gns_ex_hist_destroy(y.h) }
+
 // ThriftDecoder holds the device buffers one batch of NATS messages decodes into
 // (ns-engine's live path: stream_aggregator.go:85 decodes one PacketInfo message
 // at a time with probe.UnmarshalPacketInfo, packetcodec.go:97-108; here a whole
