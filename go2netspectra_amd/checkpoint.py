@@ -3,9 +3,9 @@
 The reference keeps a measurement period's state in process memory only (SURVEY
 §5 "Checkpoint/resume: no"); here it lives in HBM.  ``save`` exports it through
 the engines' read side (gns_cm_export_state, gns_ss_export_state or a
-SuperSpread view's gns_ss_view_export_state, gns_ex_snapshot, gns_pairs_export), ``restore`` puts it back through the write
+SuperSpread view's gns_ss_view_export_state, gns_ex_snapshot, gns_pairs_export, gns_ex_hist_export), ``restore`` puts it back through the write
 side (gns_cm_import_state, gns_ss_import_state, gns_ex_merge / gns_pairs_merge
-into an emptied table).
+into an emptied table, gns_ex_hist_append_rows per snapshot into a cleared history).
 
 A file holds the state arrays plus one metadata record (JSON): the class and
 the parameters a state depends on -- geometry, key layout, thresholds, row seeds
@@ -36,6 +36,7 @@ PARAMS = {
                     "m", "size", "base", "b", "hll_master", "rng_seed"],
     "ExactAggregator": ["key_fields", "key_bytes"],
     "ExactSpread": ["flow_fields", "elem_fields", "flow_bytes", "elem_bytes"],
+    "ExactHistory": ["key_fields", "key_bytes"],
 }
 # the arrays a file of each class holds
 ARRAYS = {
@@ -43,7 +44,20 @@ ARRAYS = {
     "SuperSpread": ["values", "keys", "regs", "pbits"],
     "ExactAggregator": ["keys", "start", "end", "pkts", "bytes"],
     "ExactSpread": ["flows", "elems"],
+    # the log rows in log order with the snapshot that wrote each, and the snapshot times (int64)
+    "ExactHistory": ["keys", "start", "end", "pkts", "bytes", "written", "times"],
 }
+
+
+def history_slices(written: np.ndarray, n_snapshots: int):
+    """[(lo, hi)] per snapshot: the rows of one snapshot are contiguous in an exported log
+    (``written`` never decreases); a snapshot without rows gets an empty range.  ValueError
+    for a ``written`` that is not sorted or names a snapshot that ``times`` lacks."""
+    w = np.asarray(written, np.int64)
+    if w.size and (np.any(np.diff(w) < 0) or w[0] < 0 or w[-1] >= n_snapshots):
+        raise ValueError("history file: 'written' is not a sorted list of snapshot numbers below len(times)")
+    edges = np.searchsorted(w, np.arange(n_snapshots + 1), side="left")
+    return [(int(edges[i]), int(edges[i + 1])) for i in range(n_snapshots)]
 
 
 def write(path, meta: dict, arrays: Dict[str, np.ndarray]) -> None:
@@ -82,7 +96,8 @@ def _plain(v):
 
 
 def describe(obj) -> dict:
-    """The metadata record of a live CountMin / SuperSpread / ExactAggregator / ExactSpread (no state)."""
+    """The metadata record of a live CountMin / SuperSpread / ExactAggregator / ExactSpread /
+    ExactHistory (no state)."""
     cls = type(obj).__name__
     if cls not in PARAMS:
         raise TypeError(f"no checkpoint format for {cls}")
@@ -139,6 +154,10 @@ def save(obj, path) -> None:
     elif cls == "ExactSpread":  # the pair set is the whole state; counters are not part of the file
         f, e, _ = obj.export_pairs()
         arrays = {"flows": np.ascontiguousarray(f), "elems": np.ascontiguousarray(e)}
+    elif cls == "ExactHistory":  # the whole log: restore re-appends it snapshot by snapshot
+        k, st, en, pk, by, wr, ts = obj.export_log()
+        arrays = {"keys": np.ascontiguousarray(k), "start": st, "end": en, "pkts": pk, "bytes": by, "written": wr,
+                  "times": np.asarray(ts, np.int64)}
     else:
         k, st, en, pk, by = obj.snapshot_arrays()
         arrays = {"keys": np.ascontiguousarray(k), "start": st, "end": en, "pkts": pk, "bytes": by}
@@ -163,6 +182,13 @@ def restore(obj, path) -> None:
     elif cls == "ExactSpread":
         obj.reset()
         obj.merge_pairs(arrays["flows"], arrays["elems"])
+    elif cls == "ExactHistory":
+        ts = np.asarray(arrays["times"], np.int64)
+        cuts = history_slices(arrays["written"], len(ts))  # (checked before anything is cleared)
+        obj.clear()
+        for t, (lo, hi) in zip(ts.tolist(), cuts):  # a snapshot without rows still registers its time
+            obj.append_rows(arrays["keys"][lo:hi], arrays["start"][lo:hi], arrays["end"][lo:hi], arrays["pkts"][lo:hi],
+                            arrays["bytes"][lo:hi], t)
     else:
         obj.reset()
         obj.merge(arrays["keys"], arrays["start"], arrays["end"], arrays["pkts"], arrays["bytes"])

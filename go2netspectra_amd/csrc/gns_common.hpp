@@ -224,9 +224,12 @@ struct DictScratch {
 };
 // grow_max != 0: the table also doubles (up to grow_max slots) while the live
 // flows exceed a quarter of it.
+// replace: the table is always a new allocation of new_slots slots, fewer than before
+// allowed (GNS_E_FULL when the live flows pass 7/8 of them), so the old table is read only
+// and a caller that passes a copy of its DictDev keeps it intact when the rebuild fails.
 int dict_rebuild(DictDev &D, uint64_t &slots, const DictIds *mark, int nmark, const unsigned long long *keep_nz,
                  DictIds *remap_arrays, int nremap, uint64_t new_slots, hipStream_t s, DictScratch &sc,
-                 uint64_t *live_out, uint32_t **old_rec_out, uint64_t grow_max = 0);
+                 uint64_t *live_out, uint32_t **old_rec_out, uint64_t grow_max = 0, bool replace = false);
 // Keys -> flow ids, claiming the absent ones (gns_dict.hip): the write side of
 // the state interface (gns_cm_import_state, gns_ss_import_state, gns_ex_merge)
 // names flows by key bytes, as the exports do.  ids[i] = the slot of key i, or

@@ -276,8 +276,8 @@ void DictScratch::free_all() {
 
 int dict_rebuild(DictDev &D, uint64_t &slots, const DictIds *mark, int nmark, const unsigned long long *keep_nz,
                  DictIds *remap_arrays, int nremap, uint64_t new_slots, hipStream_t s, DictScratch &sc,
-                 uint64_t *live_out, uint32_t **old_rec_out, uint64_t grow_max) {
-    if (new_slots < slots) new_slots = slots;
+                 uint64_t *live_out, uint32_t **old_rec_out, uint64_t grow_max, bool replace) {
+    if (!replace && new_slots < slots) new_slots = slots;
     if (!sc.cnt) GNS_TRY(dalloc_t(&sc.cnt, 4));
     if (!sc.h_cnt && hipHostMalloc(reinterpret_cast<void **>(&sc.h_cnt), 16, 0) != hipSuccess) {
         sc.h_cnt = nullptr;
@@ -326,7 +326,7 @@ int dict_rebuild(DictDev &D, uint64_t &slots, const DictIds *mark, int nmark, co
     // the new table: the same one cleared, or a larger one
     DictDev N = D;
     uint32_t *old_rec = nullptr;
-    if (new_slots != slots) {
+    if (new_slots != slots || replace) {
         GNS_TRY(dalloc_t(&N.rec, new_slots * D.RW));
         N.mask = (uint32_t)(new_slots - 1);
         old_rec = D.rec;

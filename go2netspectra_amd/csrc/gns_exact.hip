@@ -36,6 +36,10 @@
 //   HH  k_exq_hh_*     flows above a threshold, ordered, cut to a limit (gns_ex_heavy_hitters)
 //   A   k_exh_link     a view's rows appended to a history's log (gns_ex_hist_append); Q, HH
 //                      and V answer over the log as of a snapshot (gns_ex_hist_*)
+//   AR  k_exh_link_rows  host rows appended to the log (gns_ex_hist_append_rows; k_exh_own /
+//                      k_exh_dup refuse a key that occurs twice in the call)
+//   TR  k_exh_trim_*   expired snapshots dropped or folded into a base snapshot: the kept rows
+//                      moved into a new log, the head words remapped (gns_ex_hist_trim)
 // A Zipf batch touches a flow in many places; per-block LDS aggregation of
 // every flow left the tail flows to global atomics, three per packet; sorting
 // every packet (rocPRIM radix sort of 100M words) made the sort the largest
@@ -1461,6 +1465,130 @@ __global__ __launch_bounds__(256) void k_exh_heads(const uint32_t *head, uint64_
     ids[s] = head[s] != kHistOpen ? (uint32_t)s : GNS_ID_NONE;
 }
 
+// gns_ex_hist_append_rows: host rows instead of a view's.  The state words already lie in the
+// log at base + i (copied there behind the published rows); the record is the one the resolve
+// found or claimed in the index.  Two rows of one call with one key would share a head word,
+// which the link must not meet: every row names itself in its slot's owner word, and a row that
+// then reads another's name there is a duplicate (one of the equal rows wins the word, every
+// other one sees it).
+__global__ __launch_bounds__(256) void k_exh_own(const uint32_t *ids, uint64_t n, uint32_t slots, uint32_t *owner) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id < slots) owner[id] = (uint32_t)i;
+}
+__global__ __launch_bounds__(256) void k_exh_dup(const uint32_t *ids, uint64_t n, uint32_t slots, const uint32_t *owner,
+                                                 uint32_t *dup) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const uint32_t id = ids[i];
+        bad = id >= slots || owner[id] != (uint32_t)i;
+    }
+    if (bad) *dup = 1u;  // (every writer stores the same word)
+}
+__global__ __launch_bounds__(256) void k_exh_link_rows(DictDev I, uint64_t n, const uint32_t *ids, uint32_t *head,
+                                                       uint32_t slots, ExHistLog G, uint64_t base, uint32_t S,
+                                                       uint32_t *fresh) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t r = base + i;
+    bool isnew = false;
+    if (i < n && r < G.cap) {
+        const uint32_t id = ids[i];
+        if (id < slots) {  // (always: every id of the append was resolved before the link)
+            const uint4 *q = reinterpret_cast<const uint4 *>(I.rec + (uint64_t)id * I.RW);
+            uint4 *o = reinterpret_cast<uint4 *>(G.L.rec + r * I.RW);
+#pragma unroll
+            for (int w = 0; w < 4; w++)
+                if (4u * w < I.RW) o[w] = w < 3 ? q[w] : make_uint4(0, 0, 0, 0);
+            G.written[r] = S;
+            G.superseded[r] = kHistOpen;
+            const uint32_t old = head[id];
+            head[id] = (uint32_t)r;
+            if (old == kHistOpen) isnew = true;
+            else if (old < base) G.superseded[old] = S;
+        }
+    }
+    const uint64_t m = __ballot(isnew);
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(fresh, (uint32_t)__popcll(m));
+}
+
+// gns_ex_hist_trim.  The kept rows of the old log O -- of the expired prefix [0, R) those still
+// live as of snapshot s_last (fold; their ranks come from k_exhv_count over the prefix and the
+// scan, as V1 / V2), and every row from R on -- move stably into the new log G: a prefix row to
+// its rank, a suffix row to r - R + nbase.  Version words lose d; a word below d belongs to the
+// base and becomes 0.  row0: the first row of the grid (0 whenever prefix rows are ranked: block
+// b is then the count's block b).  newrow[r] = where prefix row r went (kHistOpen: dropped), for
+// the head words.  O is only read: a failed trim leaves it as it was.
+struct ExHistTrim {
+    uint64_t rows, R, nbase, row0;
+    uint32_t s_last, d, nb;
+    int fold;
+};
+__global__ __launch_bounds__(256) void k_exh_trim_move(ExHistLog O, ExHistTrim t, const uint32_t *off, ExHistLog G,
+                                                       uint32_t *newrow) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t r = t.row0 + (uint64_t)blockIdx.x * 256 + tid;
+    const bool prefix = r < t.R;
+    const bool sel = prefix && t.fold && O.superseded[r] > t.s_last;
+    const uint64_t m = __ballot(sel);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (r >= t.rows) return;
+    uint64_t nr = r - t.R + t.nbase;
+    if (prefix) {
+        nr = kHistOpen;
+        if (sel) {
+            nr = off[exv_cell(blockIdx.x, t.nb)] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            for (uint32_t w = 0; w < wave; w++) nr += s_w[w];
+        }
+        if (newrow) newrow[r] = (uint32_t)nr;
+        if (!sel) return;
+    }
+    if (nr >= G.cap) return;
+    const uint32_t RW = O.L.RW;
+    const uint4 *q = reinterpret_cast<const uint4 *>(O.L.rec + r * RW);
+    uint4 *o = reinterpret_cast<uint4 *>(G.L.rec + nr * RW);
+#pragma unroll
+    for (int w = 0; w < 4; w++)
+        if (4u * w < RW) o[w] = q[w];
+    G.f.pkts[nr] = O.f.pkts[r]; G.f.bytes[nr] = O.f.bytes[r]; G.f.start[nr] = O.f.start[r]; G.f.end[nr] = O.f.end[r];
+    const uint32_t a = O.written[r], b = O.superseded[r];
+    G.written[nr] = max(a, t.d) - t.d;
+    G.superseded[nr] = b == kHistOpen ? kHistOpen : b - t.d;
+}
+// where the row a head word names went
+__device__ __forceinline__ uint32_t exh_trim_head(uint32_t h, const ExHistTrim &t, const uint32_t *newrow) {
+    if (h == kHistOpen) return kHistOpen;
+    if (h >= t.R) return (uint32_t)(h - t.R + t.nbase);
+    return newrow ? newrow[h] : kHistOpen;
+}
+// the slots whose key keeps a row name themselves (dict_rebuild's mark list); the others are counted
+__global__ __launch_bounds__(256) void k_exh_trim_marks(const uint32_t *head, uint64_t slots, ExHistTrim t,
+                                                        const uint32_t *newrow, uint32_t *ids, uint32_t *forgot) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool gone = false;
+    if (s < slots) {
+        const uint32_t h = head[s], n = exh_trim_head(h, t, newrow);
+        ids[s] = n != kHistOpen ? (uint32_t)s : GNS_ID_NONE;
+        gone = h != kHistOpen && n == kHistOpen;
+    }
+    const uint64_t m = __ballot(gone);
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(forgot, (uint32_t)__popcll(m));
+}
+// the new head words: at the slot the rebuild gave the key (remap == nullptr: the slot it has)
+__global__ __launch_bounds__(256) void k_exh_trim_heads(const uint32_t *head, uint64_t slots, ExHistTrim t,
+                                                        const uint32_t *newrow, const uint32_t *remap, uint32_t *nh) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= slots) return;
+    const uint32_t n = exh_trim_head(head[s], t, newrow);
+    if (!remap) { nh[s] = n; return; }
+    const uint32_t to = remap[s];
+    if (to >= kDictMarked) return;
+    nh[to] = n;
+}
+
 // gns_ex_merge: row i is one pseudo-record at stream position base + i.  Counts add
 // (u64 wrap); first / last keep the stream-order rule among the rows of one call and
 // against the table (an existing flow's first lies below base), and the rows that
@@ -1807,7 +1935,7 @@ struct gns_ex_hist : ViewCore {
     uint32_t *mark = nullptr;  // k_exh_heads' list during an index growth
     uint64_t mark_n = 0;
     uint32_t *fresh = nullptr; // keys the running append added
-    uint64_t n_index_grow = 0, n_log_grow = 0;
+    uint64_t n_index_grow = 0, n_log_grow = 0, rows_trimmed = 0;
     // as-of snapshot: V1's counts and the scan's sums, the total, the compacted rows
     uint32_t *scan = nullptr, *total = nullptr;
     uint64_t scan_n = 0;
@@ -2780,10 +2908,8 @@ void exh_free(gns_ex_hist *h) {
     h->destroy();
 }
 
-// Room for `need` log rows: allocate, copy the published rows, free (before an append links anything).
-int exh_reserve_log(gns_ex_hist *h, uint64_t need) {
-    if (need <= h->log.cap) return GNS_OK;
-    const uint64_t cap = hist_row_capacity(h->log.cap, need), rows = h->plan.rows;
+// An empty log of the history's record layout with room for cap rows (cap == 0: no memory).
+int exh_alloc_log(const gns_ex_hist *h, uint64_t cap, ExHistLog *out) {
     const uint32_t RW = h->log.L.RW;
     ExHistLog g = h->log;
     g.L.rec = nullptr;
@@ -2791,12 +2917,23 @@ int exh_reserve_log(gns_ex_hist *h, uint64_t need) {
     g.written = g.superseded = nullptr;
     g.cap = cap;
     int rc;
-    if ((rc = dalloc_t(&g.L.rec, cap * RW)) || (rc = dalloc_t(&g.f.pkts, cap)) || (rc = dalloc_t(&g.f.bytes, cap)) ||
-        (rc = dalloc_t(&g.f.start, cap)) || (rc = dalloc_t(&g.f.end, cap)) || (rc = dalloc_t(&g.written, cap)) ||
-        (rc = dalloc_t(&g.superseded, cap))) {
+    if (cap && ((rc = dalloc_t(&g.L.rec, cap * RW)) || (rc = dalloc_t(&g.f.pkts, cap)) || (rc = dalloc_t(&g.f.bytes, cap)) ||
+                (rc = dalloc_t(&g.f.start, cap)) || (rc = dalloc_t(&g.f.end, cap)) || (rc = dalloc_t(&g.written, cap)) ||
+                (rc = dalloc_t(&g.superseded, cap)))) {
         exh_free_log(g);
         return rc;
     }
+    *out = g;
+    return GNS_OK;
+}
+
+// Room for `need` log rows: allocate, copy the published rows, free (before an append links anything).
+int exh_reserve_log(gns_ex_hist *h, uint64_t need) {
+    if (need <= h->log.cap) return GNS_OK;
+    const uint64_t cap = hist_row_capacity(h->log.cap, need), rows = h->plan.rows;
+    const uint32_t RW = h->log.L.RW;
+    ExHistLog g;
+    GNS_TRY(exh_alloc_log(h, cap, &g));
     hipError_t e = hipSuccess;
     if (rows) {
         hipStream_t s = h->stream;
@@ -2858,6 +2995,51 @@ int exh_grow_index(gns_ex_hist *h, uint64_t want, uint64_t done) {
     h->claimed = live;
     h->n_index_grow++;
     if (e != hipSuccess) { set_error("history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+// A1: h->ids[i] = the index slot of key i (device, n keys at `stride` bytes), piece by piece,
+// before anything is linked
+int exh_resolve(gns_ex_hist *h, const uint8_t *keys, uint32_t stride, uint64_t n) {
+    hipStream_t s = h->stream;
+    for (uint64_t off = 0; off < n; off += kResolvePiece) {
+        const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
+        if (h->claimed >= h->slots / 2) GNS_TRY(exh_grow_index(h, 0, off));  // keep the load <= ~1/2
+        KeyResolve r{};
+        r.keys = keys + off * stride;
+        r.stride = stride; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + off;
+        r.full_word = h->full;
+        for (;;) {
+            const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
+            if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+            GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
+            // room for the piece if every key of it is new, at most 8 times the table per step
+            GNS_TRY(exh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->keys + off + m), 8 * h->slots), off));
+        }
+    }
+    return GNS_OK;
+}
+
+// V1 / V2 over the first `rows` log rows: cnt[exv_cell(block)] = the rank of the block's first
+// row among those live under sel, *live the number of them.  Synchronizes the stream.
+int exh_rank(gns_ex_hist *h, const ExTable &T, const ExSelAsOf &sel, uint32_t *nb_out, uint64_t *live) {
+    hipStream_t s = h->stream;
+    const uint32_t nblk = (uint32_t)((T.rows + 255) / 256);
+    const uint32_t nb = (nblk + kVBins - 1) / kVBins, ngrp = (nb + kTGrp - 1) / kTGrp;
+    const uint64_t words = (uint64_t)nb * kVBins + (uint64_t)ngrp * kVBins + kVBins;
+    if (words > h->scan_n) GNS_TRY(grow_buf(&h->scan, h->scan_n, words));
+    uint32_t *cnt = h->scan, *part = cnt + (uint64_t)nb * kVBins, *tot = part + (uint64_t)ngrp * kVBins;
+    hipLaunchKernelGGL(k_exhv_count, dim3(nb * kVBins), dim3(256), 0, s, T.D, T.rows, T.f, sel, nb, cnt);
+    hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part);
+    hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, s, part, ngrp, kVBins, tot);
+    hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, s, tot, kVBins, h->total);
+    hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part, tot);
+    GNS_HIP(hipGetLastError());
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
+    GNS_HIP(hipMemcpyAsync(hp, h->total, 4, hipMemcpyDeviceToHost, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    *nb_out = nb;
+    *live = *hp;
     return GNS_OK;
 }
 
@@ -2976,22 +3158,8 @@ int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uin
         GNS_TRY(exh_reserve_log(h, h->plan.rows + n));
         if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
         GNS_TRY(stream_wait_now(s, v->stream, "history append"));  // behind the refresh the view answers for
-        // A1: every row's index slot, piece by piece, before anything is linked
-        for (uint64_t off = 0; off < n; off += kResolvePiece) {
-            const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
-            if (h->claimed >= h->slots / 2) GNS_TRY(exh_grow_index(h, 0, off));  // keep the load <= ~1/2
-            KeyResolve r{};
-            r.keys = reinterpret_cast<const uint8_t *>(v->D.rec + off * v->D.RW + 1);  // key words follow the tag
-            r.stride = 4 * v->D.RW; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + off;
-            r.full_word = h->full;
-            for (;;) {
-                const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
-                if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
-                GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
-                // room for the piece if every key of it is new, at most 8 times the table per step
-                GNS_TRY(exh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->keys + off + m), 8 * h->slots), off));
-            }
-        }
+        // A1 (key words follow the tag)
+        GNS_TRY(exh_resolve(h, reinterpret_cast<const uint8_t *>(v->D.rec + 1), 4 * v->D.RW, n));
         // A2
         GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
         hipLaunchKernelGGL(k_exh_link, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v->D, v->f, n, h->ids, h->head,
@@ -3008,6 +3176,214 @@ int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uin
     return GNS_OK;
 }
 
+namespace {
+// Host bytes -> device through the two halves of the history's pinned staging, one being
+// filled while the other's copy runs.  Complete on return.
+int exh_copy_in(gns_ex_hist *h, void *dst, const void *src, size_t bytes, hipStream_t s) {
+    PinnedOut &po = h->rd.po;
+    int half = 0;
+    for (size_t off = 0; off < bytes; off += kPinChunk, half ^= 1) {
+        const size_t m = std::min(kPinChunk, bytes - off);
+        uint8_t *p = po.pin + (size_t)half * kPinChunk;
+        if (off >= 2 * kPinChunk) GNS_HIP(hipEventSynchronize(po.ev[half]));  // the half's last copy has landed
+        memcpy(p, static_cast<const uint8_t *>(src) + off, m);
+        GNS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, p, m, hipMemcpyHostToDevice, s));
+        GNS_HIP(hipEventRecord(po.ev[half], s));
+    }
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+}  // namespace
+
+int gns_ex_hist_append_rows(gns_ex_hist *h, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
+                            const uint64_t *pkts, const uint64_t *bytes, uint64_t n, int64_t timestamp_ns,
+                            uint64_t out[2]) {
+    if (!h || (n && (!keys || !start_ns || !end_ns || !pkts || !bytes))) { set_error("null argument"); return GNS_E_ARG; }
+    for (uint64_t i = 0; i < n; i++)
+        if (pkts[i] == 0) {
+            set_error("history append: row %llu has no packets", (unsigned long long)i);
+            return GNS_E_ARG;
+        }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int chk = h->plan.append_check(timestamp_ns, n);
+    if (chk == HIST_E_TIME) {
+        set_error("history append: timestamp %lld is not after the last snapshot's %lld", (long long)timestamp_ns,
+                  (long long)h->plan.ts.back());
+        return GNS_E_ARG;
+    }
+    if (chk == HIST_E_SNAPSHOTS) { set_error("history holds 2^32 - 2 snapshots"); return GNS_E_FULL; }
+    if (chk != HIST_OK) {
+        set_error("history log cannot grow beyond 2^32 - 2 rows (%llu held, %llu appended)", (unsigned long long)h->plan.rows,
+                  (unsigned long long)n);
+        return GNS_E_FULL;
+    }
+    GNS_TRY(set_device(h->device));
+    hipStream_t s = h->stream;
+    const uint32_t S = (uint32_t)h->plan.ts.size();
+    const uint64_t base = h->plan.rows;
+    uint64_t fresh = 0;
+    if (n) {
+        if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+        ExRead &rd = h->rd;
+        GNS_TRY(rd.buf(&rd.dk, rd.dk_n, n * h->K));
+        GNS_TRY(exh_copy_in(h, rd.dk, keys, n * h->K, s));
+        GNS_TRY(exh_resolve(h, rd.dk, h->K, n));
+        // no two rows of the call in one index slot, decided before anything is linked
+        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
+        const dim3 grid((unsigned)((n + 255) / 256));
+        uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
+        GNS_HIP(hipMemsetAsync(h->fresh, 0, 8, s));
+        hipLaunchKernelGGL(k_exh_own, grid, dim3(256), 0, s, h->ids, n, (uint32_t)h->slots, h->mark);
+        hipLaunchKernelGGL(k_exh_dup, grid, dim3(256), 0, s, h->ids, n, (uint32_t)h->slots, h->mark, h->fresh + 1);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->fresh + 1, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        if (*hp) { set_error("history append: two rows of the call have the same key"); return GNS_E_ARG; }
+        // the state words go straight behind the published rows, which no query scans
+        GNS_TRY(exh_reserve_log(h, base + n));
+        GNS_TRY(exh_copy_in(h, h->log.f.start + base, start_ns, n * 8, s));
+        GNS_TRY(exh_copy_in(h, h->log.f.end + base, end_ns, n * 8, s));
+        GNS_TRY(exh_copy_in(h, h->log.f.pkts + base, pkts, n * 8, s));
+        GNS_TRY(exh_copy_in(h, h->log.f.bytes + base, bytes, n * 8, s));
+        // A2
+        hipLaunchKernelGGL(k_exh_link_rows, grid, dim3(256), 0, s, h->D, n, h->ids, h->head, (uint32_t)h->slots, h->log,
+                           base, S, h->fresh);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        fresh = *hp;
+    }
+    h->keys += fresh;
+    h->plan.publish(timestamp_ns, n);  // last: the snapshot exists from here on
+    if (out) { out[0] = n; out[1] = fresh; }
+    return GNS_OK;
+}
+
+int gns_ex_hist_export(gns_ex_hist *h, uint8_t *keys, int64_t *start_ns, int64_t *end_ns, uint64_t *pkts,
+                       uint64_t *bytes, uint32_t *written, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t rows = h->plan.rows, m = std::min<uint64_t>(*n_io, rows);
+    *n_io = rows;
+    if (m == 0 || !(keys || start_ns || end_ns || pkts || bytes || written)) return GNS_OK;
+    hipStream_t s = h->stream;
+    ExRead &rd = h->rd;
+    const ExHistLog &g = h->log;
+    if (keys) {  // every published row, in log order
+        GNS_TRY(rd.buf(&rd.dk, rd.dk_n, m * h->K));
+        hipLaunchKernelGGL(k_ex_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)nullptr, m,
+                           g.L, g.f, rd.dk, (long long *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr,
+                           (unsigned long long *)nullptr);
+        GNS_HIP(hipGetLastError());
+        GNS_TRY(rd.copy_out(keys, rd.dk, m * h->K, s));
+    }
+    if (start_ns) GNS_TRY(rd.copy_out(start_ns, g.f.start, m * 8, s));
+    if (end_ns) GNS_TRY(rd.copy_out(end_ns, g.f.end, m * 8, s));
+    if (pkts) GNS_TRY(rd.copy_out(pkts, g.f.pkts, m * 8, s));
+    if (bytes) GNS_TRY(rd.copy_out(bytes, g.f.bytes, m * 8, s));
+    if (written) GNS_TRY(rd.copy_out(written, g.written, m * 4, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4]) {
+    if (!h) { set_error("null argument"); return GNS_E_ARG; }
+    if (fold != 0 && fold != 1) { set_error("history trim: fold %d (0: drop, 1: fold)", fold); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const HistPlan::Trim tp = h->plan.trim_plan(before_ns, fold != 0);
+    if (out) { out[0] = out[1] = out[2] = 0; out[3] = h->plan.rows; }
+    if (tp.noop) return GNS_OK;
+    GNS_TRY(set_device(h->device));
+    hipStream_t s = h->stream;
+    const uint64_t old_slots = h->slots;
+    ExHistTrim t{};
+    t.rows = h->plan.rows; t.R = tp.R; t.fold = tp.fold ? 1 : 0; t.d = tp.d; t.s_last = (uint32_t)(tp.c - 1);
+    const bool ranked = tp.fold && tp.R != 0;  // prefix rows may stay
+    t.row0 = ranked ? 0 : tp.R;
+    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
+    if (ranked) {  // flag and rank the prefix: V1 / V2 as of the last expired snapshot
+        ExSelAsOf sel;
+        ExTable T;
+        sel.written = h->log.written; sel.superseded = h->log.superseded; sel.s = t.s_last;
+        T = ExTable{h->log.L, h->log.f, tp.R};
+        GNS_TRY(exh_rank(h, T, sel, &t.nb, &t.nbase));
+    }
+    const uint64_t kept = t.nbase + (t.rows - t.R);
+    // everything new is built beside the history, which stays as it is until the end
+    ExHistLog g;
+    uint32_t *newrow = nullptr, *nh = nullptr, *old_rec = nullptr;
+    DictDev Dn = h->D;
+    uint64_t slots_n = old_slots, live = h->claimed, forgot = 0;
+    bool rebuilt = false;
+    GNS_TRY(exh_alloc_log(h, hist_row_capacity(0, kept), &g));
+    auto run = [&]() -> int {
+        if (ranked) GNS_TRY(dalloc_t(&newrow, tp.R));
+        const uint64_t span = t.rows - t.row0;
+        if (span) {
+            hipLaunchKernelGGL(k_exh_trim_move, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, s, h->log, t,
+                               (const uint32_t *)h->scan, g, newrow);
+            GNS_HIP(hipGetLastError());
+        }
+        const dim3 sgrid((unsigned)((old_slots + 255) / 256));
+        uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
+        GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
+        hipLaunchKernelGGL(k_exh_trim_marks, sgrid, dim3(256), 0, s, (const uint32_t *)h->head, old_slots, t,
+                           (const uint32_t *)newrow, h->mark, h->fresh);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        forgot = *hp;
+        const uint32_t *remap = nullptr;
+        if (forgot) {  // the index rebuilt from the keys that keep a row, into a table of their number
+            const uint64_t want = hist_index_slots(h->keys - forgot);
+            GNS_TRY(dalloc_t(&nh, want));
+            GNS_HIP(hipMemsetAsync(nh, 0xFF, want * 4, s));
+            DictIds marks[1] = {{h->mark, old_slots}};
+            GNS_TRY(dict_rebuild(Dn, slots_n, marks, 1, nullptr, nullptr, 0, want, s, h->dsc, &live, &old_rec, 0, true));
+            rebuilt = true;
+            remap = h->dsc.remap;
+        } else {
+            GNS_TRY(dalloc_t(&nh, old_slots));
+        }
+        hipLaunchKernelGGL(k_exh_trim_heads, sgrid, dim3(256), 0, s, (const uint32_t *)h->head, old_slots, t,
+                           (const uint32_t *)newrow, remap, nh);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipStreamSynchronize(s));
+        return GNS_OK;
+    };
+    const int rc = run();
+    if (rc != GNS_OK) {
+        (void)hipStreamSynchronize(s);
+        if (rebuilt) dfree(Dn.rec);
+        if (forgot) {  // a rebuild restarts the claim counter: back to what the old table holds
+            const uint32_t ctl[2] = {(uint32_t)h->claimed, 0u};
+            (void)hipMemcpy(h->dctl, ctl, 8, hipMemcpyHostToDevice);
+        }
+        exh_free_log(g);
+        dfree(newrow); dfree(nh);
+        return rc;
+    }
+    dfree(newrow);
+    // publish: the log, the index and its head words, then the plan
+    exh_free_log(h->log);
+    h->log = g;
+    dfree(h->head);
+    h->head = nh;
+    if (rebuilt) {
+        dfree(old_rec);
+        h->D = Dn;
+        h->slots = slots_n;
+        h->D.cap = (uint32_t)(slots_n - slots_n / 4);
+        h->claimed = live;
+    }
+    h->keys -= forgot;
+    h->rows_trimmed += t.R - t.nbase;
+    h->plan = h->plan.trimmed(tp, t.nbase);
+    if (out) { out[0] = tp.fold ? tp.c - 1 : tp.c; out[1] = t.R - t.nbase; out[2] = forgot; out[3] = h->plan.rows; }
+    return GNS_OK;
+}
+
 int gns_ex_hist_times(gns_ex_hist *h, int64_t *ts, uint64_t *n_io) {
     if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
@@ -3021,7 +3397,7 @@ int gns_ex_hist_stats(gns_ex_hist *h, uint64_t out[8]) {
     if (!h || !out) { set_error("null argument"); return GNS_E_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
     out[0] = h->plan.ts.size(); out[1] = h->plan.rows; out[2] = h->keys; out[3] = h->log.cap;
-    out[4] = h->slots; out[5] = h->n_index_grow; out[6] = h->n_log_grow; out[7] = 0;
+    out[4] = h->slots; out[5] = h->n_index_grow; out[6] = h->n_log_grow; out[7] = h->rows_trimmed;
     return GNS_OK;
 }
 
@@ -3059,20 +3435,11 @@ int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, i
     // V1-V3 over the log: the live rows compacted in log order
     hipStream_t s = h->stream;
     const uint32_t nblk = (uint32_t)((T.rows + 255) / 256);
-    const uint32_t nb = (nblk + kVBins - 1) / kVBins, ngrp = (nb + kTGrp - 1) / kTGrp;
-    const uint64_t words = (uint64_t)nb * kVBins + (uint64_t)ngrp * kVBins + kVBins;
-    if (words > h->scan_n) GNS_TRY(grow_buf(&h->scan, h->scan_n, words));
-    uint32_t *cnt = h->scan, *part = cnt + (uint64_t)nb * kVBins, *tot = part + (uint64_t)ngrp * kVBins;
-    hipLaunchKernelGGL(k_exhv_count, dim3(nb * kVBins), dim3(256), 0, s, T.D, T.rows, T.f, sel, nb, cnt);
-    hipLaunchKernelGGL(k_tscan_part, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part);
-    hipLaunchKernelGGL(k_tscan_mid, dim3(1), dim3(256), 0, s, part, ngrp, kVBins, tot);
-    hipLaunchKernelGGL(k_tscan_bins, dim3(1), dim3(1024), 0, s, tot, kVBins, h->total);
-    hipLaunchKernelGGL(k_tscan_down, dim3(1, ngrp), dim3(256), 0, s, cnt, nb, kVBins, part, tot);
-    GNS_HIP(hipGetLastError());
-    uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
-    GNS_HIP(hipMemcpyAsync(hp, h->total, 4, hipMemcpyDeviceToHost, s));
-    GNS_HIP(hipStreamSynchronize(s));
-    const uint64_t live = *hp, m = std::min<uint64_t>(cap, live);
+    uint32_t nb = 0;
+    uint64_t live = 0;
+    GNS_TRY(exh_rank(h, T, sel, &nb, &live));
+    const uint32_t *cnt = h->scan;
+    const uint64_t m = std::min<uint64_t>(cap, live);
     *n_io = live;
     if (m == 0 || !(keys || start_ns || end_out_ns || pkts || bytes)) return GNS_OK;
     if (live > h->scap) {

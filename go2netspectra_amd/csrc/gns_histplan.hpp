@@ -1,9 +1,10 @@
 // gns_histplan.hpp -- the host bookkeeping of an exact history (gns_ex_hist_*, gns_exact.hip):
 // the table of snapshot timestamps, s(T) = the newest snapshot at or before a query time, the
-// checks an append passes before any device call, and the capacity arithmetic of the log and
-// of the key index.  The device side holds rows and version words only; which snapshot a
-// query sees is decided here.
-// No HIP here: the header compiles in a host-only driver (tests/test_exact_history_cpu.py).
+// checks an append passes before any device call, what a trim expires and the table it leaves
+// (trim_plan / trimmed), and the capacity arithmetic of the log and of the key index.  The
+// device side holds rows and version words only; which snapshot a query sees is decided here.
+// No HIP here: the header compiles in host-only drivers (tests/test_exact_history_cpu.py,
+// tests/test_exact_history_trim_cpu.py).
 // Internal: not part of the C ABI.
 #pragma once
 #include <cstdint>
@@ -52,6 +53,46 @@ struct HistPlan {
         ts.push_back(t);
         rows += n;
         end_rows.push_back(rows);
+    }
+
+    // A trim (gns_ex_hist_trim): the c snapshots with ts < before expire, a prefix of the log
+    // of R rows.  Drop removes them; fold keeps of them the rows live as of snapshot c - 1 as
+    // the new snapshot 0 under ts[c - 1].  d: what every version word of a remaining row
+    // loses (a word below d becomes 0: the row then belongs to the base).  A plan with c == 0,
+    // or with c == 1 under fold (the base is snapshot 0 itself), moves nothing.
+    struct Trim {
+        uint64_t c, R;
+        uint32_t d;
+        bool fold, noop;
+    };
+    Trim trim_plan(int64_t before, bool fold) const {
+        size_t lo = 0, hi = ts.size();  // ts[i] < before for i < lo, >= before for i >= hi
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (ts[mid] < before) lo = mid + 1;
+            else hi = mid;
+        }
+        Trim t;
+        t.c = lo;
+        t.R = lo ? end_rows[lo - 1] : 0;
+        t.fold = fold;
+        t.d = (uint32_t)(fold && lo ? lo - 1 : lo);
+        t.noop = lo == 0 || (fold && lo == 1);
+        return t;
+    }
+    // the plan after trim t (not a noop) kept nbase rows of the prefix (drop: 0)
+    HistPlan trimmed(const Trim &t, uint64_t nbase) const {
+        HistPlan p;
+        if (t.fold) {
+            p.ts.push_back(ts[t.c - 1]);
+            p.end_rows.push_back(nbase);
+        }
+        for (size_t i = t.c; i < ts.size(); i++) {
+            p.ts.push_back(ts[i]);
+            p.end_rows.push_back(end_rows[i] - t.R + nbase);
+        }
+        p.rows = rows - t.R + nbase;
+        return p;
     }
 };
 

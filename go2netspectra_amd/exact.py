@@ -369,18 +369,23 @@ def _is_dev(a) -> bool:
     return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
 
 
-def _snapshot_arrays(fn, h, key_bytes: int):
+def _snapshot_arrays(fn, h, key_bytes: int, retry: bool = False):
     """The two calls of a snapshot export (length, then rows) through gns_ex_snapshot or
-    gns_ex_view_snapshot."""
-    n = ct.c_uint64(0)
-    check(fn(h, None, None, None, None, None, ct.byref(n)))
-    m = n.value
-    K = max(key_bytes, 1)
-    keys = np.zeros((max(m, 1), K), np.uint8)
-    st, en = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
-    pk, by = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
-    n2 = ct.c_uint64(m)
-    check(fn(h, keys.ctypes.data, st.ctypes.data, en.ctypes.data, pk.ctypes.data, by.ctypes.data, ct.byref(n2)))
+    gns_ex_view_snapshot.  retry: a writer on another thread may add rows between the two calls
+    (a history's newest snapshot); the rows are then taken again instead of cut at the first
+    call's length."""
+    while True:
+        n = ct.c_uint64(0)
+        check(fn(h, None, None, None, None, None, ct.byref(n)))
+        m = n.value
+        K = max(key_bytes, 1)
+        keys = np.zeros((max(m, 1), K), np.uint8)
+        st, en = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+        pk, by = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+        n2 = ct.c_uint64(m)
+        check(fn(h, keys.ctypes.data, st.ctypes.data, en.ctypes.data, pk.ctypes.data, by.ctypes.data, ct.byref(n2)))
+        if not retry or n2.value <= m:
+            break
     m = min(m, n2.value)
     return keys[:m, :key_bytes], st[:m], en[:m], pk[:m], by[:m]
 
@@ -572,8 +577,10 @@ class ExactHistory:
     snapshot at or before T -- per flow the latest row stored by then, the reference's
     argMax(..., Timestamp) with `Timestamp <= ?` -- and as an empty table when there is none;
     ``end_time=None`` is the newest snapshot.  Whole views and delta views (refresh(cursor))
-    give the same answers.  Flows are never forgotten: rows stored before a reset of the
-    aggregator stay, and a flow that returns supersedes its old row."""
+    give the same answers.  Flows are never forgotten by a reset: rows stored before a reset of
+    the aggregator stay, and a flow that returns supersedes its old row.  ``trim`` expires old
+    snapshots (dropped, or folded into one base snapshot), ``export_log`` / ``append_rows`` and
+    ``save`` / ``restore`` carry the whole log to a file and back."""
 
     def __init__(self, key_fields: Sequence[str], max_rows: int = 0, max_flows: int = 0, device: int = 0):
         if max_rows < 0 or max_flows < 0:
@@ -617,7 +624,8 @@ class ExactHistory:
         check(self._L.gns_ex_hist_times(self._h, ts.ctypes.data, ct.byref(n2)))
         return [int(t) for t in ts[:min(n.value, n2.value)]]
 
-    STATS = ["snapshots", "rows", "keys", "row_capacity", "index_slots", "index_growths", "log_growths", "_"]
+    STATS = ["snapshots", "rows", "keys", "row_capacity", "index_slots", "index_growths", "log_growths",
+             "rows_trimmed"]
 
     def stats(self) -> dict:
         s = (ct.c_uint64 * 8)()
@@ -641,7 +649,81 @@ class ExactHistory:
     def snapshot_arrays(self, end_time=None):
         """(keys, start, end, packets, bytes) of each flow's latest row as of ``end_time``, in
         log order (snapshot, then the view's row order)."""
-        return _snapshot_arrays(self._bind("snapshot", end_time), self._h, self.key_bytes)
+        return _snapshot_arrays(self._bind("snapshot", end_time), self._h, self.key_bytes, retry=True)
+
+    # --- retention and the log as data (gns_ex_hist_trim / _export / _append_rows) ---
+    TRIM = ["snapshots_removed", "rows_released", "keys_forgotten", "rows"]
+
+    def trim(self, before, fold: bool = True) -> dict:
+        """Expire the snapshots with timestamp < ``before`` (int64 ns).  ``fold=True`` keeps of
+        them each flow's latest row as one base snapshot under the last expired timestamp, so
+        every answer with end_time at or after it is unchanged (earlier end times then answer
+        as an empty table, and first_ns / last_ns / max_* range over the rows that remain);
+        ``fold=False`` drops them with all their rows, and a flow seen only in them is
+        forgotten.  Returns snapshots_removed, rows_released, keys_forgotten and the rows now
+        held.  The kept rows move into a new, smaller log: the memory is returned."""
+        before, out = _int64_ns("before", before), (ct.c_uint64 * 4)()
+        check(self._L.gns_ex_hist_trim(self._h, before, int(fold), out))
+        return {k: int(out[i]) for i, k in enumerate(self.TRIM)}
+
+    def clear(self) -> dict:
+        """Forget every snapshot: ``trim`` past the last timestamp with ``fold=False``.  Timestamps
+        may start anew afterwards."""
+        ts = self.times()
+        if ts and ts[-1] == (1 << 63) - 1:
+            raise ValueError("clear: no int64 lies past the last snapshot's timestamp")
+        return self.trim(ts[-1] + 1 if ts else 0, fold=False)
+
+    def export_log(self):
+        """(keys, start, end, packets, bytes, written, times): every log row in log order --
+        ``written[i]`` the number of the snapshot that stored row i, ``times[j]`` snapshot j's
+        timestamp (int64 array).  ``append_rows`` of each snapshot's rows into an empty history
+        rebuilds this one."""
+        L, K = self._L, max(self.key_bytes, 1)
+        while True:
+            ts = np.asarray(self.times(), np.int64)
+            n = ct.c_uint64(0)
+            check(L.gns_ex_hist_export(self._h, None, None, None, None, None, None, ct.byref(n)))
+            m = n.value
+            keys = np.zeros((max(m, 1), K), np.uint8)
+            st, en = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+            pk, by = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+            wr = np.zeros(max(m, 1), np.uint32)
+            n2 = ct.c_uint64(m)
+            check(L.gns_ex_hist_export(self._h, keys.ctypes.data, st.ctypes.data, en.ctypes.data, pk.ctypes.data,
+                                       by.ctypes.data, wr.ctypes.data, ct.byref(n2)))
+            # (another thread appended or trimmed between the calls: take the log again)
+            if n2.value == m and self.times() == ts.tolist():
+                return keys[:m, :self.key_bytes], st[:m], en[:m], pk[:m], by[:m], wr[:m], ts
+
+    def append_rows(self, keys, start, end, packets, bytes, timestamp_ns: int):
+        """One snapshot from host arrays of the form ``snapshot_arrays`` / ``export_log`` give, as
+        ``append`` takes it from a view.  Every row carries packets and no key occurs twice
+        (GnsError otherwise, the history's answers unchanged); no rows register the timestamp.
+        Returns (rows appended, keys new to the history)."""
+        st, en = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+        pk, by = np.ascontiguousarray(packets, np.uint64), np.ascontiguousarray(bytes, np.uint64)
+        n = int(st.shape[0])
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(n, -1) if n else np.zeros((0, self.key_bytes), np.uint8)
+        if n and keys.shape[1] != self.key_bytes:
+            raise ValueError(f"append_rows: keys must be [n, {self.key_bytes}]")
+        if not (en.shape[0] == pk.shape[0] == by.shape[0] == n):
+            raise ValueError("append_rows: row arrays differ in length")
+        out, t = (ct.c_uint64 * 2)(), _int64_ns("timestamp_ns", timestamp_ns)
+        ptrs = [a.ctypes.data if n else None for a in (keys, st, en, pk, by)]
+        check(self._L.gns_ex_hist_append_rows(self._h, *ptrs, n, t, out))
+        return int(out[0]), int(out[1])
+
+    def save(self, path) -> None:
+        """The whole log as one checkpoint file (checkpoint.save)."""
+        from . import checkpoint
+        checkpoint.save(self, path)
+
+    def restore(self, path) -> None:
+        """Replace the log by a checkpoint's (checkpoint.restore): cleared, then one append_rows
+        per saved snapshot."""
+        from . import checkpoint
+        checkpoint.restore(self, path)
 
 
 class ExactAggregator:
@@ -1026,11 +1108,20 @@ class ExactTask:
         checkpoint.restore(self.agg, path)
 
     # --- the history behind end_time (gns_ex_hist_*) ---
-    def keep_history(self, **kw) -> ExactHistory:
+    def keep_history(self, retain=None, **kw) -> ExactHistory:
         """Attach an ExactHistory of this task's layout (``kw``: its max_rows / max_flows), a view
         and a cursor: ``record`` then stores an interval, and the Querier calls below answer
-        ``end_time`` from it.  Returns the history (the one already attached, if any)."""
+        ``end_time`` from it.  Returns the history (the one already attached, if any).
+
+        ``retain=N`` (N >= 1; None: keep everything): after each record the history is folded
+        (``ExactHistory.trim(fold=True)``) down to at most N snapshots, the base included, so
+        answers reach back N - 1 intervals and the log stops growing with time."""
+        if retain is not None:
+            if isinstance(retain, bool) or int(retain) != retain or retain < 1:
+                raise ValueError(f"retain {retain!r}: a number of snapshots >= 1, or None")
+            retain = int(retain)
         if getattr(self, "history", None) is None:
+            self._hist_retain = retain
             kw.setdefault("device", self.agg.device)
             self.history = ExactHistory(self.key_fields, **kw)
             self._hist_view = self.agg.view()
@@ -1047,7 +1138,28 @@ class ExactTask:
         cur = self._hist_view.refresh(0 if full else self._hist_cursor)
         out = h.append(self._hist_view, timestamp_ns)
         self._hist_cursor = cur  # (after the append: a rejected timestamp loses no interval)
+        keep = getattr(self, "_hist_retain", None)
+        if keep is not None:
+            ts = h.times()
+            if len(ts) > keep:  # fold all but the newest keep - 1 into the base
+                h.trim(ts[-(keep - 1)] if keep > 1 else ts[-1] + 1, fold=True)
         return out
+
+    def save_history(self, path) -> None:
+        """The attached history's log as one checkpoint file (ExactHistory.save)."""
+        self._history("save_history").save(path)
+
+    def restore_history(self, path) -> None:
+        """Replace the attached history's log by a checkpoint's (ExactHistory.restore).  The next
+        delta ``record`` after a ``restore`` of the flow table stores every restored flow again
+        -- the merge touched them all -- which is correct, only larger."""
+        self._history("restore_history").restore(path)
+
+    def _history(self, what: str) -> ExactHistory:
+        h = getattr(self, "history", None)
+        if h is None:
+            raise ValueError(f"{what}: no history attached (keep_history first)")
+        return h
 
     def _as_of(self, end_time):
         """The history an end_time query answers from; ValueError without one."""

@@ -130,9 +130,10 @@ class Manager:
         process() keeps feeding the tasks."""
         return {t.name(): t.snapshot_from(v) for t, v in zip(self.tasks(), views)}
 
-    def keep_history(self, **kw) -> Dict[str, object]:
-        """ExactTask.keep_history for every exact task: name -> ExactHistory."""
-        return {t.name(): t.keep_history(**kw) for t in self.tasks() if hasattr(t, "keep_history")}
+    def keep_history(self, retain=None, **kw) -> Dict[str, object]:
+        """ExactTask.keep_history for every exact task: name -> ExactHistory.  ``retain=N``: each
+        record folds the task's history down to at most N snapshots (None: keep everything)."""
+        return {t.name(): t.keep_history(retain=retain, **kw) for t in self.tasks() if hasattr(t, "keep_history")}
 
     def record(self, timestamp_ns: int, full: bool = False) -> Dict[str, object]:
         """One snapshot interval: every exact task's changed flows into its history under ONE
@@ -149,21 +150,33 @@ class Manager:
             t.reset()
 
     def checkpoint(self, dir) -> List[str]:
-        """Every task's state into ``dir``, one file per task name (task.save); returns the paths."""
+        """Every task's state into ``dir``, one file per task name (task.save), then
+        ``<name>.history.npz`` for each task that has a history attached (its whole log);
+        returns the paths, the history files after the task files."""
         import os
         os.makedirs(dir, exist_ok=True)
         paths = []
         for t in self.tasks():
             paths.append(os.path.join(dir, t.name() + ".npz"))
             t.save(paths[-1])
+        for t in self.tasks():
+            if getattr(t, "history", None) is not None:
+                paths.append(os.path.join(dir, t.name() + ".history.npz"))
+                t.save_history(paths[-1])
         return paths
 
     def restore(self, dir) -> None:
         """Every task's state from the files ``checkpoint`` wrote into ``dir`` (task.restore):
-        the tasks must be configured as the saved ones were."""
+        the tasks must be configured as the saved ones were.  A task with a history attached
+        also takes back ``<name>.history.npz`` when that file exists, so ``end_time`` answers
+        survive the restart.  The next delta ``record`` then stores every restored flow again
+        -- the merge that restored the table touched them all -- which is correct, only larger."""
         import os
         for t in self.tasks():
             t.restore(os.path.join(dir, t.name() + ".npz"))
+            hp = os.path.join(dir, t.name() + ".history.npz")
+            if getattr(t, "history", None) is not None and os.path.exists(hp):
+                t.restore_history(hp)
 
     def stop(self) -> Dict[str, object]:
         """Drain (flush every stream) and take the final snapshot (manager.go:196-216)."""

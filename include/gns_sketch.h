@@ -834,8 +834,9 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
  *     snapshot with timestamp <= *end_ns; with none the query answers as an empty table.  A
  *     row written by snapshot a is SEEN when a <= s(T) and LIVE when no later row of the same
  *     key is seen too: the argMax(..., Timestamp) of the reference.  The store never forgets
- *     a flow: rows written before a gns_ex_reset of the source handle stay, and a flow that
- *     comes back after it supersedes its old row with its new, smaller counts.
+ *     a flow by itself (only gns_ex_hist_trim removes rows): rows written before a
+ *     gns_ex_reset of the source handle stay, and a flow that comes back after it supersedes
+ *     its old row with its new, smaller counts.
  *   - gns_ex_hist_aggregate[_cidr] take the filters of gns_ex_aggregate[_cidr] unchanged (a
  *     masked field outside the layout matches nothing).  flows, packets, bytes are COUNT / SUM
  *     over the matching LIVE rows (AggregateFlows); first_ns, last_ns, max_packets, max_bytes
@@ -847,26 +848,60 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
  *     (snapshot, then the view's row order) under the protocol of gns_ex_snapshot.
  *   - gns_ex_hist_times: *n_io capacity in, the number of snapshots out; ts may be NULL.
  *     gns_ex_hist_stats: snapshots, rows, distinct keys, row capacity, index slots, index
- *     growths, log growths, 0.
+ *     growths, log growths, rows released by trims (cumulative).
+ *   - gns_ex_hist_trim expires the c snapshots with timestamp < before_ns, a prefix of the log.
+ *     fold == 0 drops them with all their rows (the reference's DROP PARTITION): the history
+ *     then equals one to which only the later snapshots were ever appended, a flow whose
+ *     every row expired is forgotten (appended again it counts as a new key), and with every
+ *     snapshot expired the history is empty.  fold == 1 folds them into one base snapshot:
+ *     of their rows those LIVE as of the last expired snapshot stay, in log order, as
+ *     snapshot 0 under that snapshot's timestamp, followed by the later snapshots unchanged;
+ *     every aggregate, heavy-hitter and snapshot answer with end time at or after that
+ *     timestamp is unchanged, earlier end times answer as an empty table, and the min / max
+ *     members of a summary (taken over SEEN rows) range over the rows that remain.  Nothing
+ *     expired (c == 0), or fold with c == 1, is a no-op that moves and allocates nothing.
+ *     out[0] = snapshots removed (fold: c - 1, the base replaces them), out[1] = rows
+ *     released, out[2] = keys forgotten, out[3] = rows now held (out may be NULL).  The kept
+ *     rows move into a new log sized for them and the key index is rebuilt (smaller when keys
+ *     were forgotten); the new state is published last, so on any failure the history is
+ *     untouched.  Queries from other threads wait for the trim and then see the trimmed store.
+ *   - gns_ex_hist_export writes every log row in log order under the *n_io protocol of
+ *     gns_ex_snapshot: canonical key bytes, start, end, pkts, bytes and the number of the
+ *     snapshot that wrote the row (any array may be NULL); timestamps come from
+ *     gns_ex_hist_times.  gns_ex_hist_append_rows appends one snapshot from host arrays of that
+ *     form, as gns_ex_hist_append does from a view (n == 0 registers the timestamp); feeding
+ *     an empty history the exported rows snapshot by snapshot restores it.  GNS_E_ARG with
+ *     every answer unchanged: a row without packets, and two rows of one call with the same
+ *     key (found on the device before anything is linked; the key index may have grown).
  *   - max_rows / max_flows are only the INITIAL capacities of the log and of the key index
  *     (0: 2^20 rows, 2^16 keys); both grow.  GNS_E_FULL is left only for a log beyond
  *     2^32 - 2 rows or snapshots (and the dictionary's 2^30 slots).
  *   - GNS_E_ARG with the history untouched, checked before any device call: a null handle, a
  *     view that was never refreshed, a view whose handle's key layout differs from the
- *     history's, a view on another device, timestamp_ns <= the last snapshot's, and the
- *     filter / metric errors of the live calls.  Nothing of a snapshot is visible to a query
+ *     history's, a view on another device, timestamp_ns <= the last snapshot's, a trim's
+ *     fold outside {0, 1}, and the filter / metric errors of the live calls.  Nothing of a snapshot is visible to a query
  *     before its append has returned GNS_OK.
  *   - Threads: any, serialised by the history's mutex; its stream and pinned staging are its
  *     own and no query allocates or frees once warm.  A history does not refer to the
  *     handle or the view after the append returns: either may be destroyed first.
  * Memory: a record plus 40 bytes per log row (32 of state, 8 of version words); per index
- * slot a record plus 4 bytes; 8 MB of pinned host staging.  Not offered: trimming old
- * snapshots, exporting the log, roll-ups of a history. */
+ * slot a record plus 4 bytes; 8 MB of pinned host staging.  A trim builds the new log beside
+ * the old one (blocks of one launch would otherwise read rows that others had overwritten):
+ * its peak is the old log plus the new, plus 4 bytes per expired row under fold and a second
+ * index while keys are forgotten; the old log is freed when the trim returns.
+ * gns_ex_hist_append_rows stages the call's key rows on the device.  Not offered: roll-ups
+ * of a history, a history of the sketch tasks' heavy-hitter lists. */
 typedef struct gns_ex_hist gns_ex_hist;
 typedef struct gns_ex_hist_params { gns_layout key; uint64_t max_rows, max_flows; int device; } gns_ex_hist_params;
 int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out);
 int gns_ex_hist_destroy(gns_ex_hist *h);
 int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uint64_t out[2]);
+int gns_ex_hist_append_rows(gns_ex_hist *h, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
+                            const uint64_t *pkts, const uint64_t *bytes, uint64_t n, int64_t timestamp_ns,
+                            uint64_t out[2]);
+int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4]);
+int gns_ex_hist_export(gns_ex_hist *h, uint8_t *keys, int64_t *start_ns, int64_t *end_ns, uint64_t *pkts,
+                       uint64_t *bytes, uint32_t *written, uint64_t *n_io);
 int gns_ex_hist_times(gns_ex_hist *h, int64_t *ts, uint64_t *n_io);
 int gns_ex_hist_stats(gns_ex_hist *h, uint64_t out[8]);
 int gns_ex_hist_aggregate(gns_ex_hist *h, const int64_t *end_ns, const gns_ex_filter *f, uint32_t nf, gns_ex_summary *out);

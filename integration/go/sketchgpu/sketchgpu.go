@@ -1312,6 +1312,62 @@ func (y *History) Flows(end *int64) (keys []byte, start, last []int64, pkts, byt
 	return keys[:m*y.keyBytes], start[:m], last[:m], pkts[:m], bytes[:m], err
 }
 
+// Trim expires the snapshots with timestamp < before (gns_ex_hist_trim).  fold keeps of them
+// each flow's latest row as one base snapshot under the last expired timestamp, so answers at
+// or after it are unchanged; without fold they are dropped with all their rows, as the
+// reference drops a partition.  out: snapshots removed, rows released, keys forgotten, rows held.
+func (y *History) Trim(before int64, fold bool) (out [4]uint64, err error) {
+	f := C.int(0)
+	if fold {
+		f = 1
+	}
+	err = lastErr(C.gns_ex_hist_trim(y.h, C.int64_t(before), f, (*C.uint64_t)(unsafe.Pointer(&out[0]))))
+	return
+}
+
+// Export returns every log row in log order (gns_ex_hist_export) in the layout of Exact.Flows,
+// with the number of the snapshot that wrote each row; Times gives the snapshots' timestamps.
+func (y *History) Export() (keys []byte, start, last []int64, pkts, bytes []uint64, written []uint32, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_ex_hist_export(y.h, nil, nil, nil, nil, nil, nil, &n)); err != nil {
+		return
+	}
+	m := int(n)
+	keys = make([]byte, m*y.keyBytes+1)
+	start, last = make([]int64, m+1), make([]int64, m+1)
+	pkts, bytes = make([]uint64, m+1), make([]uint64, m+1)
+	written = make([]uint32, m+1)
+	err = lastErr(C.gns_ex_hist_export(y.h, (*C.uint8_t)(unsafe.Pointer(&keys[0])),
+		(*C.int64_t)(unsafe.Pointer(&start[0])), (*C.int64_t)(unsafe.Pointer(&last[0])),
+		(*C.uint64_t)(unsafe.Pointer(&pkts[0])), (*C.uint64_t)(unsafe.Pointer(&bytes[0])),
+		(*C.uint32_t)(unsafe.Pointer(&written[0])), &n))
+	if int(n) < m {
+		m = int(n)
+	}
+	return keys[:m*y.keyBytes], start[:m], last[:m], pkts[:m], bytes[:m], written[:m], err
+}
+
+// AppendRows stores one snapshot from host rows in the layout of Exact.Flows
+// (gns_ex_hist_append_rows): every row carries packets and no key occurs twice.  No rows
+// register the timestamp.  Feeding an empty history the rows Export gave, snapshot by
+// snapshot, restores it.
+func (y *History) AppendRows(keys []byte, start, last []int64, pkts, bytes []uint64, tsNano int64) (rows, newKeys uint64, err error) {
+	n := len(pkts)
+	if len(keys) != n*y.keyBytes || len(start) != n || len(last) != n || len(bytes) != n {
+		return 0, 0, errors.New("sketchgpu: AppendRows: row slices differ in length")
+	}
+	var out [2]C.uint64_t
+	if n == 0 {
+		err = lastErr(C.gns_ex_hist_append_rows(y.h, nil, nil, nil, nil, nil, 0, C.int64_t(tsNano), &out[0]))
+	} else {
+		err = lastErr(C.gns_ex_hist_append_rows(y.h, (*C.uint8_t)(unsafe.Pointer(&keys[0])),
+			(*C.int64_t)(unsafe.Pointer(&start[0])), (*C.int64_t)(unsafe.Pointer(&last[0])),
+			(*C.uint64_t)(unsafe.Pointer(&pkts[0])), (*C.uint64_t)(unsafe.Pointer(&bytes[0])),
+			C.uint64_t(n), C.int64_t(tsNano), &out[0]))
+	}
+	return uint64(out[0]), uint64(out[1]), err
+}
+
 // Close releases the history.
 func (y *History) Close() { C.gns_ex_hist_destroy(y.h) }
 
