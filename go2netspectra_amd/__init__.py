@@ -13,6 +13,7 @@ from .exact import (ExactAggregator, ExactHistory, ExactTask, ExactView, FlowLif
                     TaskSummary, apply_delta, discount_heavy_prefixes, make_filter, make_prefix, mask_keys, mask_prefix,
                     merge_summaries, prefix_plan, rollup_plan, spread_rollup_plan, to16_to_encodeflow)
 from .factory import Manager, TaskGroup, create, register_aggregator
+from .heavy_history import HeavyHistory
 from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
 from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread, SuperSpreadView
@@ -27,5 +28,5 @@ __all__ = [
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "ExactHistory", "apply_delta", "CompactBatch",
     "SuperSpreadView", "rollup_plan", "spread_rollup_plan", "to16_to_encodeflow",
-    "mask_prefix", "mask_keys", "prefix_plan", "make_prefix", "discount_heavy_prefixes",
+    "mask_prefix", "mask_keys", "prefix_plan", "make_prefix", "discount_heavy_prefixes", "HeavyHistory",
 ]

@@ -59,6 +59,8 @@ EXPORTED = [
     "gns_ex_hist_create", "gns_ex_hist_destroy", "gns_ex_hist_append", "gns_ex_hist_times", "gns_ex_hist_stats",
     "gns_ex_hist_aggregate", "gns_ex_hist_aggregate_cidr", "gns_ex_hist_heavy_hitters", "gns_ex_hist_snapshot",
     "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows",
+    "gns_hh_hist_create", "gns_hh_hist_destroy", "gns_hh_hist_append", "gns_hh_hist_heavy_hitters",
+    "gns_hh_hist_heavy_rows", "gns_hh_hist_times", "gns_hh_hist_stats", "gns_hh_hist_export",
 ]
 
 
@@ -113,6 +115,14 @@ class ExParams(ct.Structure):
 
 class ExHistParams(ct.Structure):  # gns_ex_hist_params: initial capacities, both grow
     _fields_ = [("key", Layout), ("max_rows", ct.c_uint64), ("max_flows", ct.c_uint64), ("device", ct.c_int)]
+
+
+class HhHistParams(ct.Structure):  # gns_hh_hist_params: initial capacities, both grow
+    _fields_ = [("key_bytes", ct.c_uint32), ("max_rows", ct.c_uint64), ("max_flows", ct.c_uint64), ("device", ct.c_int)]
+
+
+class HhList(ct.Structure):  # gns_hh_list: packed rows [flow | u32 LE value] of one type
+    _fields_ = [("type", ct.c_uint32), ("rows", ct.c_void_p), ("n", ct.c_uint64)]
 
 
 class ExFilter(ct.Structure):  # gns_ex_filter: 44 bytes
@@ -276,6 +286,12 @@ def load() -> ct.CDLL:
         "gns_ex_hist_trim": ([vp, ct.c_int64, i32, vp], i32),
         "gns_ex_hist_export": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "gns_ex_hist_append_rows": ([vp, vp, vp, vp, vp, vp, u64, ct.c_int64, vp], i32),
+        "gns_hh_hist_create": ([vp, vp], i32), "gns_hh_hist_destroy": ([vp], i32),
+        "gns_hh_hist_append": ([vp, ct.c_int64, vp, u32, i32, vp], i32),
+        "gns_hh_hist_heavy_hitters": ([vp, vp, u32, u64, u64, vp, vp, vp], i32),
+        "gns_hh_hist_heavy_rows": ([vp, vp, u32, u64, u64, vp, vp], i32),
+        "gns_hh_hist_times": ([vp, vp, vp], i32), "gns_hh_hist_stats": ([vp, vp], i32),
+        "gns_hh_hist_export": ([vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,733 @@
+// gns_hhhist.hip -- the heavy-hitter history (gns_hh_hist_*): the store behind
+// QueryHeavyHitters' EndTime (internal/query/querier.go:191-248).  The reference's sketch
+// writer appends one row (Timestamp, TaskName, Flow, Value, Type) per list entry of every
+// interval's Snapshot() (internal/engine/impl/sketch/writer_clickhouse.go:86-138) and the
+// query takes, per Flow, argMax(Value, Timestamp) over the rows of one Type with
+// Timestamp <= EndTime.  Here that table lives on the device:
+//   - one key index of the history's own, a dictionary of K-byte flows (gns_dict.hip), shared
+//     by all types;
+//   - per type a LANE: a log of 16-byte rows {index slot, value, written, superseded} and one
+//     head word per index slot, the newest log row of that (type, flow).  Key bytes live only
+//     in the index.  written / superseded are snapshot numbers as in the exact history
+//     (gns_exact.hip): a row is live as of snapshot s when written <= s < superseded.
+// The timestamp table and s(T) are the host's (gns_hhplan.hpp over gns_histplan.hpp).
+//   A1  dict_resolve_keys   packed rows [flow | u32] at stride K + 4 -> index slots, piece by
+//                           piece, with the exact history's growth-and-retry loop
+//   A1b k_hhh_own / _dup    no two rows of one list in one index slot (over the whole list)
+//   A2  k_hhh_link          list row i -> lane row base + i, swapped into the head word; the
+//                           row it displaced is stamped superseded = S
+//   Q1  k_hhh_hist / _pick  limit != 0: a three-level radix select (11 + 11 + 10 bits) over
+//                           the live values fixes the cut value v*, the largest value with at
+//                           least `limit` live rows at or above it
+//   Q2  k_hhh_collect       live rows with value >= max(threshold, v*) -> packed rows
+//                           [flow | u32], key bytes from the index record
+//   Q3  hh_order_rows_dev   the canonical order (gns_hh.hip), then the cut to `limit`
+// Everything an append writes before the host publishes the snapshot lies outside every scan:
+// rows at and beyond a lane's published count, and superseded words that equal the new S.
+#include <mutex>
+#include <vector>
+
+#include "gns_common.hpp"
+#include "gns_hh.hpp"
+#include "gns_hhplan.hpp"
+
+namespace gns {
+
+namespace {
+constexpr uint32_t kSelBins = 2048;  // bins of one select level (LDS: 8 KB)
+
+// ids[i] -> owner word of its slot; a row that then reads another's name is a duplicate
+__global__ __launch_bounds__(256) void k_hhh_own(const uint32_t *ids, uint64_t n, uint32_t slots, uint32_t *owner) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id < slots) owner[id] = (uint32_t)i;
+}
+__global__ __launch_bounds__(256) void k_hhh_dup(const uint32_t *ids, uint64_t n, uint32_t slots, const uint32_t *owner,
+                                                 uint32_t *dup) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const uint32_t id = ids[i];
+        bad = id >= slots || owner[id] != (uint32_t)i;
+    }
+    if (bad) *dup = 1u;  // (every writer stores the same word)
+}
+
+// A2.  rows: packed [flow (K) | u32 LE value] at stride K + 4 (any alignment).
+__global__ __launch_bounds__(256) void k_hhh_link(const uint8_t *rows, uint32_t K, uint64_t n, const uint32_t *ids,
+                                                  uint32_t *head, uint32_t slots, uint4 *log, uint64_t cap, uint64_t base,
+                                                  uint32_t S, uint32_t *fresh) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t r = base + i;
+    bool isnew = false;
+    if (i < n && r < cap) {
+        const uint32_t id = ids[i];
+        if (id < slots) {  // (always: every id of the append was resolved before the link)
+            const uint8_t *p = rows + i * (uint64_t)(K + 4) + K;
+            const uint32_t v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+            log[r] = make_uint4(id, v, S, kHistOpen);
+            const uint32_t old = head[id];
+            head[id] = (uint32_t)r;
+            if (old == kHistOpen) isnew = true;
+            else if (old < base) log[old].w = S;
+        }
+    }
+    const uint64_t m = __ballot(isnew);  // (type, flow) pairs new to the lane: one add per wave
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(fresh, (uint32_t)__popcll(m));
+}
+
+// index growth: the slots some lane's head word names keep their record (dict_rebuild's mark
+// list), a head word follows its record (gns_dict.hip remap), and so does a log row's slot
+__global__ __launch_bounds__(256) void k_hhh_heads(const uint32_t *head, uint64_t slots, uint32_t *ids) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s < slots && head[s] != kHistOpen) ids[s] = (uint32_t)s;
+}
+__global__ __launch_bounds__(256) void k_hhh_permute(const uint32_t *oh, uint64_t slots, const uint32_t *remap,
+                                                     uint32_t *nh) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= slots) return;
+    const uint32_t t = remap[s];
+    if (t >= kDictMarked) return;
+    nh[t] = oh[s];
+}
+__global__ __launch_bounds__(256) void k_hhh_reslot(uint4 *log, uint64_t rows, uint64_t slots, const uint32_t *remap) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const uint32_t id = log[r].x;
+    if (id < slots) log[r].x = remap[id];  // (a published row's slot is marked: its key has a head word)
+}
+
+// Select control words: [0] the value bits fixed so far, [1] rows still wanted at or below the
+// band, [2] every row is wanted (fewer than `limit` qualify), [3] rows collected, [4] the cut
+enum { SEL_PREFIX = 0, SEL_REM = 1, SEL_ALL = 2, SEL_COUNT = 3, SEL_CUT = 4, SEL_WORDS = 8 };
+
+__global__ void k_hhh_sel_init(uint32_t *ctl, uint32_t limit, uint32_t thr, uint32_t *hist) {
+    const uint32_t t = threadIdx.x;
+    if (t == 0) {
+        ctl[SEL_PREFIX] = 0; ctl[SEL_REM] = limit; ctl[SEL_ALL] = 0; ctl[SEL_COUNT] = 0; ctl[SEL_CUT] = thr;
+    }
+    for (uint32_t b = t; b < kSelBins; b += blockDim.x) hist[b] = 0;
+}
+
+__device__ __forceinline__ bool hhh_live(const uint4 &q, uint32_t s) { return q.z <= s && s < q.w; }
+
+// Q1: one level's histogram of the live rows with value >= thr whose higher bits equal the
+// prefix; bin = (value >> shift) & (kSelBins - 1).  `above`: the bits over this level's.
+__global__ __launch_bounds__(256) void k_hhh_hist(const uint4 *log, uint64_t rows, uint32_t s, uint32_t thr,
+                                                  uint32_t shift, uint32_t above, const uint32_t *ctl, uint32_t *hist) {
+    __shared__ uint32_t s_h[kSelBins];
+    if (ctl[SEL_ALL]) return;  // (uniform)
+    const uint32_t prefix = ctl[SEL_PREFIX];
+    for (uint32_t b = threadIdx.x; b < kSelBins; b += 256) s_h[b] = 0;
+    __syncthreads();
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256) {
+        const uint4 q = log[r];
+        if (hhh_live(q, s) && q.y >= thr && ((q.y ^ prefix) & above) == 0)
+            atomicAdd(&s_h[(q.y >> shift) & (kSelBins - 1)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kSelBins; b += 256) {
+        const uint32_t c = s_h[b];
+        if (c) atomicAdd(&hist[b], c);
+    }
+}
+// the band that holds the rem-th largest value; the histogram is cleared for the next level
+__global__ __launch_bounds__(256) void k_hhh_pick(uint32_t *hist, uint32_t shift, uint32_t last, uint32_t thr,
+                                                  uint32_t *ctl) {
+    __shared__ uint32_t s_h[kSelBins];
+    for (uint32_t b = threadIdx.x; b < kSelBins; b += 256) {
+        s_h[b] = hist[b];
+        hist[b] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (!ctl[SEL_ALL]) {
+        const uint32_t rem = ctl[SEL_REM];
+        uint32_t acc = 0;
+        int band = -1;
+        for (int b = (int)kSelBins - 1; b >= 0; b--) {
+            const uint32_t c = s_h[b];
+            if (c >= rem - acc) { band = b; break; }  // acc < rem throughout
+            acc += c;
+        }
+        if (band < 0) {
+            ctl[SEL_ALL] = 1;  // fewer than `limit` rows qualify (decided at the first level)
+        } else {
+            ctl[SEL_PREFIX] |= (uint32_t)band << shift;
+            ctl[SEL_REM] = rem - acc;
+        }
+    }
+    if (last) ctl[SEL_CUT] = ctl[SEL_ALL] ? thr : max(thr, ctl[SEL_PREFIX]);
+}
+
+// Q2: ballot compaction, one global atomic per workgroup and round.  out: packed rows of
+// K + 4 bytes, `cap` of them; rows beyond cap are counted only (the host grows and re-runs).
+__global__ __launch_bounds__(256) void k_hhh_collect(const uint4 *log, uint64_t rows, uint32_t s, DictDev D, uint8_t *out,
+                                                     uint64_t cap, uint32_t *ctl) {
+    __shared__ uint32_t s_w[4], s_base;
+    const uint32_t cut = ctl[SEL_CUT], K = D.K, lane = __lane_id(), wv = threadIdx.x >> 6;
+    for (uint64_t b0 = (uint64_t)blockIdx.x * 256; b0 < rows; b0 += (uint64_t)gridDim.x * 256) {  // (block-uniform)
+        const uint64_t r = b0 + threadIdx.x;
+        uint4 q = make_uint4(0, 0, 0, 0);
+        bool take = false;
+        if (r < rows) {
+            q = log[r];
+            take = hhh_live(q, s) && q.y >= cut && q.x <= D.mask;
+        }
+        const uint64_t m = __ballot(take);
+        if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+            s_base = tot ? atomicAdd(&ctl[SEL_COUNT], tot) : 0u;
+        }
+        __syncthreads();
+        if (take) {
+            uint32_t pos = s_base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+            for (uint32_t w = 0; w < wv; w++) pos += s_w[w];
+            if (pos < cap) {
+                const uint32_t *rec = D.rec + (uint64_t)q.x * D.RW + 1;
+                uint8_t *o = out + (uint64_t)pos * (K + 4);
+                for (uint32_t j = 0; j < K; j++) o[j] = (uint8_t)(rec[j >> 2] >> (8 * (j & 3)));
+                o[K] = (uint8_t)q.y; o[K + 1] = (uint8_t)(q.y >> 8); o[K + 2] = (uint8_t)(q.y >> 16); o[K + 3] = (uint8_t)(q.y >> 24);
+            }
+        }
+        __syncthreads();  // s_w / s_base are rewritten by the next round
+    }
+}
+
+// ordered packed rows -> flows [m, K] and 64-bit values [m] (the host form of a list)
+__global__ __launch_bounds__(256) void k_hhh_split(const uint8_t *rows, uint32_t K, uint64_t m, uint8_t *flows,
+                                                   unsigned long long *vals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const uint8_t *p = rows + i * (uint64_t)(K + 4);
+    for (uint32_t j = 0; j < K; j++) flows[i * K + j] = p[j];
+    vals[i] = (uint32_t)p[K] | (uint32_t)p[K + 1] << 8 | (uint32_t)p[K + 2] << 16 | (uint32_t)p[K + 3] << 24;
+}
+
+// export: log rows [first, first + m) of a lane -> flow bytes, value, writing snapshot
+__global__ __launch_bounds__(256) void k_hhh_export(const uint4 *log, uint64_t m, DictDev D, uint8_t *flows,
+                                                    uint32_t *vals, uint32_t *written) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const uint4 q = log[i];
+    const uint32_t K = D.K;
+    if (q.x <= D.mask) {
+        const uint32_t *rec = D.rec + (uint64_t)q.x * D.RW + 1;
+        for (uint32_t j = 0; j < K; j++) flows[i * K + j] = (uint8_t)(rec[j >> 2] >> (8 * (j & 3)));
+    }
+    vals[i] = q.y;
+    written[i] = q.z;
+}
+
+struct HhLane {
+    uint4 *log = nullptr;      // cap rows of room
+    uint64_t cap = 0;
+    uint32_t *head = nullptr;  // [slots] newest log row of the slot's flow in this lane (kHistOpen: none)
+    uint64_t keys = 0;         // flows the lane has listed
+};
+}  // namespace
+}  // namespace gns
+
+using namespace gns;
+
+// The history of one task and one flow width.  Its stream, mutex and pinned staging are its
+// own, as a view's: appends and queries from any thread are serialised by the mutex and
+// allocate nothing once warm.
+struct gns_hh_hist : ViewCore {
+    int device = 0;
+    uint32_t K = 0;
+    uint64_t init_rows = 0;
+    HhHistPlan plan;            // timestamps, published rows per lane (host)
+    std::vector<HhLane> lanes;  // as plan.lanes
+    DictDev D{};                // the key index
+    uint64_t slots = 0, claimed = 0, pairs = 0;
+    uint32_t *dctl = nullptr;
+    unsigned long long *full = nullptr;
+    uint32_t epoch = 0;
+    DictScratch dsc;
+    KeyResolveScratch rsc;
+    uint32_t *ids = nullptr;   // the index slots of the rows being appended, list after list
+    uint64_t ids_n = 0;
+    uint32_t *mark = nullptr;  // [slots] k_hhh_heads' list during an index growth, owner words of A1b
+    uint64_t mark_n = 0;
+    uint32_t *fresh = nullptr;  // [0] pairs the running append added, [1] its duplicate flag
+    uint8_t *stage = nullptr;   // host lists staged for the append
+    uint64_t stage_n = 0;
+    uint64_t n_index_grow = 0, n_log_grow = 0;
+    // query side
+    uint32_t *ctl = nullptr, *hist = nullptr;
+    uint8_t *coll = nullptr, *ordered = nullptr;  // collected rows, then in canonical order
+    uint64_t coll_n = 0, ordered_n = 0;           // bytes
+    uint8_t *spl = nullptr;                       // split / export staging
+    uint64_t spl_n = 0;
+    HhScratch hh;
+    PinnedOut po;
+};
+
+namespace {
+
+void hhh_free(gns_hh_hist *h) {
+    for (HhLane &l : h->lanes) { dfree(l.log); dfree(l.head); }
+    h->lanes.clear();
+    dfree(h->D.rec); dfree(h->dctl); dfree(h->full); dfree(h->ids); dfree(h->mark); dfree(h->fresh); dfree(h->stage);
+    dfree(h->ctl); dfree(h->hist); dfree(h->coll); dfree(h->ordered); dfree(h->spl);
+    h->dsc.free_all();
+    h->rsc.free_all();
+    h->hh.free_all();
+    h->po.free_all();
+    h->destroy();
+}
+
+unsigned grid256(uint64_t n) { return (unsigned)((n + 255) / 256); }
+unsigned scan_grid(uint64_t rows) { return (unsigned)std::min<uint64_t>(2048, (rows + 255) / 256); }
+
+// device rows a caller hands in or takes out lie in device memory of the history's GPU
+int hhh_check_dev(const void *p, int device, const char *what) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("heavy history: %s is not device memory", what);
+        return GNS_E_ARG;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != device) {
+        set_error("heavy history: %s is not memory of device %d", what, device);
+        return GNS_E_ARG;
+    }
+    return GNS_OK;
+}
+
+// the lane of `type`, created empty when there is none
+int hhh_lane(gns_hh_hist *h, uint32_t type, int *out) {
+    int l = h->plan.lane(type);
+    if (l < 0) {
+        HhLane ln;
+        GNS_TRY(dalloc_t(&ln.head, h->slots));
+        if (hipMemsetAsync(ln.head, 0xFF, h->slots * 4, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+            dfree(ln.head);
+            set_error("heavy history: lane clear failed");
+            return GNS_E_HIP;
+        }
+        l = h->plan.add_lane(type);
+        h->lanes.push_back(ln);
+    }
+    *out = l;
+    return GNS_OK;
+}
+
+// Room for `need` rows in lane l: allocate, copy the published rows, free (before anything is linked).
+int hhh_reserve_log(gns_hh_hist *h, int l, uint64_t need) {
+    HhLane &ln = h->lanes[(size_t)l];
+    if (need <= ln.cap) return GNS_OK;
+    const uint64_t cap = hist_row_capacity(ln.cap ? ln.cap : std::min<uint64_t>(h->init_rows, kHistMax), need);
+    const uint64_t rows = h->plan.lanes[(size_t)l].rows;
+    uint4 *g = nullptr;
+    GNS_TRY(dalloc_t(&g, cap));
+    if (rows) {
+        hipError_t e = hipMemcpyAsync(g, ln.log, rows * sizeof(uint4), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            dfree(g);
+            set_error("heavy history log growth: %s", hipGetErrorString(e));
+            return GNS_E_HIP;
+        }
+    }
+    if (ln.cap) h->n_log_grow++;
+    dfree(ln.log);
+    ln.log = g;
+    ln.cap = cap;
+    return GNS_OK;
+}
+
+// The index rebuilt into at least `want` slots.  Kept: the flows some lane has listed (a head
+// word) and the `done` ids the running append has resolved, which are renumbered; claims of a
+// piece that overflowed, and of appends that were rejected, are dropped.  Every lane's head
+// words and the slot column of its log follow the records.
+int hhh_grow_index(gns_hh_hist *h, uint64_t want, uint64_t done) {
+    const uint64_t old_slots = h->slots;
+    uint64_t new_slots = old_slots * 2;
+    while (new_slots < want) new_slots *= 2;
+    if (new_slots > kDictMaxSlots) {
+        set_error("heavy history key index cannot grow beyond 2^30 slots");
+        return GNS_E_FULL;
+    }
+    hipStream_t s = h->stream;
+    if (h->mark_n < new_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, new_slots));
+    std::vector<uint32_t *> nh(h->lanes.size(), nullptr);
+    auto drop = [&]() { for (uint32_t *p : nh) dfree(p); };
+    for (size_t i = 0; i < nh.size(); i++) {
+        const int rc = dalloc_t(&nh[i], new_slots);
+        if (rc != GNS_OK) { drop(); return rc; }
+    }
+    hipError_t e = hipMemsetAsync(h->mark, 0xFF, old_slots * 4, s);  // GNS_ID_NONE
+    for (size_t i = 0; i < nh.size() && e == hipSuccess; i++) {
+        hipLaunchKernelGGL(k_hhh_heads, dim3(grid256(old_slots)), dim3(256), 0, s, h->lanes[i].head, old_slots, h->mark);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemsetAsync(nh[i], 0xFF, new_slots * 4, s);
+    }
+    if (e != hipSuccess) { drop(); set_error("heavy history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    DictIds marks[2] = {{h->mark, old_slots}, {h->ids, done}};
+    DictIds remaps[1] = {{h->ids, done}};
+    uint64_t slots = old_slots, live = 0;
+    const int rc = dict_rebuild(h->D, slots, marks, 2, nullptr, remaps, 1, new_slots, s, h->dsc, &live, nullptr);
+    if (rc != GNS_OK) { drop(); return rc; }
+    for (size_t i = 0; i < nh.size(); i++) {
+        HhLane &ln = h->lanes[i];
+        const uint64_t rows = h->plan.lanes[i].rows;
+        hipLaunchKernelGGL(k_hhh_permute, dim3(grid256(old_slots)), dim3(256), 0, s, ln.head, old_slots, h->dsc.remap, nh[i]);
+        if (rows) hipLaunchKernelGGL(k_hhh_reslot, dim3(grid256(rows)), dim3(256), 0, s, ln.log, rows, old_slots, h->dsc.remap);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    // (the table is the new one whatever the kernels did: the old head words no longer fit it)
+    for (size_t i = 0; i < nh.size(); i++) {
+        dfree(h->lanes[i].head);
+        h->lanes[i].head = nh[i];
+    }
+    h->slots = slots;
+    h->D.cap = (uint32_t)(slots - slots / 4);
+    h->claimed = live;
+    h->n_index_grow++;
+    if (e != hipSuccess) { set_error("heavy history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
+    return GNS_OK;
+}
+
+// A1: h->ids[at + i] = the index slot of row i's flow (device rows at stride K + 4), piece by
+// piece, before anything is linked.  `at` ids of earlier lists are renumbered by a growth.
+int hhh_resolve(gns_hh_hist *h, const uint8_t *rows, uint64_t n, uint64_t at) {
+    hipStream_t s = h->stream;
+    const uint32_t stride = h->K + 4;
+    for (uint64_t off = 0; off < n; off += kResolvePiece) {
+        const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
+        if (h->claimed >= h->slots / 2) GNS_TRY(hhh_grow_index(h, 0, at + off));  // keep the load <= ~1/2
+        KeyResolve r{};
+        r.keys = rows + off * stride;
+        r.stride = stride; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + at + off;
+        r.full_word = h->full;
+        for (;;) {
+            const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
+            if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
+            GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
+            // room for the piece if every flow of it is new, at most 8 times the table per step
+            GNS_TRY(hhh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->claimed + m), 8 * h->slots), at + off));
+        }
+    }
+    return GNS_OK;
+}
+
+// Host bytes -> device through the two halves of the pinned staging.  Complete on return.
+int hhh_copy_in(gns_hh_hist *h, void *dst, const void *src, size_t bytes) {
+    PinnedOut &po = h->po;
+    hipStream_t s = h->stream;
+    int half = 0;
+    for (size_t off = 0; off < bytes; off += kPinChunk, half ^= 1) {
+        const size_t m = std::min(kPinChunk, bytes - off);
+        uint8_t *p = po.pin + (size_t)half * kPinChunk;
+        if (off >= 2 * kPinChunk) GNS_HIP(hipEventSynchronize(po.ev[half]));  // the half's last copy has landed
+        memcpy(p, static_cast<const uint8_t *>(src) + off, m);
+        GNS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, p, m, hipMemcpyHostToDevice, s));
+        GNS_HIP(hipEventRecord(po.ev[half], s));
+    }
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+// Q1-Q3 under h->mu: the list of `type` as of *end_ns in h->ordered, *n rows of it (after the
+// cut to `limit`).  Synchronizes the stream.
+int hhh_list(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t threshold, uint64_t limit, uint64_t *n) {
+    *n = 0;
+    const int64_t sn = h->plan.t.as_of(end_ns);
+    const int l = h->plan.lane(type);
+    const uint64_t rows = h->plan.rows_as_of(l, sn);
+    if (rows == 0 || threshold > 0xFFFFFFFFull) return GNS_OK;  // (values are 32-bit)
+    hipStream_t st = h->stream;
+    const HhLane &ln = h->lanes[(size_t)l];
+    const uint32_t s = (uint32_t)sn, thr = (uint32_t)threshold, K = h->K;
+    const uint32_t lim = (uint32_t)std::min<uint64_t>(limit, 0xFFFFFFFFull);  // (a lane holds fewer rows)
+    const dim3 grid(scan_grid(rows));
+    hipLaunchKernelGGL(k_hhh_sel_init, dim3(1), dim3(256), 0, st, h->ctl, lim, thr, h->hist);
+    if (lim) {
+        const uint32_t shift[3] = {21, 10, 0}, above[3] = {0u, 0xFFE00000u, 0xFFFFFC00u};
+        for (int lv = 0; lv < 3; lv++) {
+            hipLaunchKernelGGL(k_hhh_hist, grid, dim3(256), 0, st, ln.log, rows, s, thr, shift[lv], above[lv], h->ctl, h->hist);
+            hipLaunchKernelGGL(k_hhh_pick, dim3(1), dim3(256), 0, st, h->hist, shift[lv], lv == 2 ? 1u : 0u, thr, h->ctl);
+        }
+    }
+    GNS_HIP(hipGetLastError());
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h->po.pin);
+    uint64_t got = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        const uint64_t cap = h->coll ? h->coll_n / (K + 4) : 0;
+        hipLaunchKernelGGL(k_hhh_collect, grid, dim3(256), 0, st, ln.log, rows, s, h->D, h->coll, cap, h->ctl);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->ctl + SEL_COUNT, 4, hipMemcpyDeviceToHost, st));
+        GNS_HIP(hipStreamSynchronize(st));
+        got = *hp;
+        if (got <= cap) break;
+        // more rows than the buffer holds: grow to the count and collect again (the cut stands)
+        GNS_TRY(grow_buf(&h->coll, h->coll_n, got * (K + 4)));
+        GNS_HIP(hipMemsetAsync(h->ctl + SEL_COUNT, 0, 4, st));
+    }
+    if (got == 0) return GNS_OK;
+    if (got >= (1ull << 31)) { set_error("heavy history: a list of %llu rows (max 2^31 - 1)", (unsigned long long)got); return GNS_E_RANGE; }
+    GNS_TRY(grow_buf(&h->ordered, h->ordered_n, got * (K + 4)));
+    GNS_TRY(hh_order_rows_dev(h->hh, st, h->coll, K, (uint32_t)got, h->ordered));
+    GNS_HIP(hipStreamSynchronize(st));
+    *n = limit ? std::min<uint64_t>(got, limit) : got;
+    return GNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gns_hh_hist_create(const gns_hh_hist_params *p, gns_hh_hist **out) {
+    if (!p || !out) { set_error("null argument"); return GNS_E_ARG; }
+    *out = nullptr;
+    if (p->key_bytes == 0 || p->key_bytes > 37) { set_error("heavy history: key_bytes %u (1..37)", p->key_bytes); return GNS_E_ARG; }
+    if (p->max_rows > kHistMax || p->max_flows > kDictMaxSlots / 2) { set_error("heavy history capacity too large"); return GNS_E_ARG; }
+    GNS_TRY(check_device(p->device));
+    gns_hh_hist *h = new gns_hh_hist();
+    h->device = p->device;
+    h->K = p->key_bytes;
+    h->init_rows = p->max_rows ? p->max_rows : (1ull << 20);
+    int rc = GNS_OK;
+    do {
+        if ((rc = set_device(h->device)) != GNS_OK) break;
+        if ((rc = h->init()) != GNS_OK || (rc = h->po.reserve(0)) != GNS_OK) break;
+        h->slots = hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10));
+        h->D.mask = (uint32_t)(h->slots - 1);
+        h->D.K = h->K;
+        h->D.RW = dict_record_words(h->K);
+        h->D.seed = 0x5BD1E995u;
+        h->D.cap = (uint32_t)(h->slots - h->slots / 4);
+        if ((rc = dalloc_t(&h->D.rec, h->slots * h->D.RW)) || (rc = dalloc_t(&h->dctl, 4)) || (rc = dalloc_t(&h->full, 1)) ||
+            (rc = dalloc_t(&h->fresh, 4)) || (rc = dalloc_t(&h->ctl, SEL_WORDS)) || (rc = dalloc_t(&h->hist, kSelBins)))
+            break;
+        h->D.ctl = h->dctl;
+        hipStream_t s = h->stream;
+        if (hipMemsetAsync(h->D.rec, 0, h->slots * h->D.RW * 4, s) != hipSuccess ||
+            hipMemsetAsync(h->dctl, 0, 16, s) != hipSuccess || hipMemsetAsync(h->full, 0, 8, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            set_error("heavy history create: device clear failed");
+            rc = GNS_E_HIP;
+        }
+    } while (0);
+    if (rc != GNS_OK) { hhh_free(h); delete h; return rc; }
+    *out = h;
+    return GNS_OK;
+}
+
+int gns_hh_hist_destroy(gns_hh_hist *h) {
+    if (!h) return GNS_OK;
+    (void)hipSetDevice(h->device);
+    h->quiesce();
+    hhh_free(h);
+    delete h;
+    return GNS_OK;
+}
+
+int gns_hh_hist_append(gns_hh_hist *h, int64_t timestamp_ns, const gns_hh_list *lists, uint32_t nlists, gns_mem where,
+                       uint64_t out[2]) {
+    if (!h || (nlists && !lists)) { set_error("null argument"); return GNS_E_ARG; }
+    if (nlists > kHhTypes) { set_error("heavy history append: %u lists (at most one per type)", nlists); return GNS_E_ARG; }
+    if (where != GNS_MEM_HOST && where != GNS_MEM_DEVICE) { set_error("heavy history append: unknown memory kind"); return GNS_E_ARG; }
+    uint32_t types[kHhTypes];
+    uint64_t ns[kHhTypes], total = 0;
+    for (uint32_t i = 0; i < nlists; i++) {
+        if (lists[i].n && !lists[i].rows) { set_error("null argument"); return GNS_E_ARG; }
+        types[i] = lists[i].type;
+        ns[i] = lists[i].n;
+        total += lists[i].n;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int chk = h->plan.append_check(timestamp_ns, types, ns, nlists);
+    switch (chk) {
+    case HIST_OK: break;
+    case HIST_E_TIME:
+        set_error("heavy history append: timestamp %lld is not after the last snapshot's %lld", (long long)timestamp_ns,
+                  (long long)h->plan.t.ts.back());
+        return GNS_E_ARG;
+    case HIST_E_SNAPSHOTS: set_error("heavy history holds 2^32 - 2 snapshots"); return GNS_E_FULL;
+    case HIST_E_ROWS: set_error("heavy history: a type's log cannot grow beyond 2^32 - 2 rows"); return GNS_E_FULL;
+    case HHH_E_TYPE: set_error("heavy history append: a list's type is outside 0..255"); return GNS_E_ARG;
+    default: set_error("heavy history append: two lists of one type"); return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(h->device));
+    hipStream_t s = h->stream;
+    const uint32_t W = h->K + 4, S = (uint32_t)h->plan.t.ts.size();
+    if (where == GNS_MEM_DEVICE)
+        for (uint32_t i = 0; i < nlists; i++)
+            if (lists[i].n) GNS_TRY(hhh_check_dev(lists[i].rows, h->device, "a list's rows"));
+    uint64_t fresh = 0;
+    if (total) {
+        // room first: lanes, their logs, the ids, and device copies of host lists
+        int lane[kHhTypes];
+        for (uint32_t i = 0; i < nlists; i++) {
+            if (ns[i] == 0) { lane[i] = -1; continue; }
+            GNS_TRY(hhh_lane(h, types[i], &lane[i]));
+            GNS_TRY(hhh_reserve_log(h, lane[i], h->plan.lanes[(size_t)lane[i]].rows + ns[i]));
+        }
+        if (h->ids_n < total) GNS_TRY(grow_buf(&h->ids, h->ids_n, total));
+        const uint8_t *rows[kHhTypes];
+        if (where == GNS_MEM_HOST) {
+            if (h->stage_n < total * W) GNS_TRY(grow_buf(&h->stage, h->stage_n, total * W));
+            uint64_t at = 0;
+            for (uint32_t i = 0; i < nlists; i++) {
+                rows[i] = h->stage + at * W;
+                if (ns[i]) GNS_TRY(hhh_copy_in(h, h->stage + at * W, lists[i].rows, ns[i] * W));
+                at += ns[i];
+            }
+        } else {
+            for (uint32_t i = 0; i < nlists; i++) rows[i] = lists[i].rows;
+        }
+        // A1: every list, before anything is checked or linked (a growth renumbers the ids)
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < nlists; i++) {
+            GNS_TRY(hhh_resolve(h, rows[i], ns[i], at));
+            at += ns[i];
+        }
+        // A1b: no two rows of a list in one index slot
+        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
+        uint32_t *hp = reinterpret_cast<uint32_t *>(h->po.pin);
+        GNS_HIP(hipMemsetAsync(h->fresh, 0, 8, s));
+        at = 0;
+        for (uint32_t i = 0; i < nlists; i++) {
+            if (ns[i] == 0) continue;
+            const dim3 grid(grid256(ns[i]));
+            hipLaunchKernelGGL(k_hhh_own, grid, dim3(256), 0, s, h->ids + at, ns[i], (uint32_t)h->slots, h->mark);
+            hipLaunchKernelGGL(k_hhh_dup, grid, dim3(256), 0, s, h->ids + at, ns[i], (uint32_t)h->slots, h->mark, h->fresh + 1);
+            at += ns[i];
+        }
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->fresh + 1, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        if (*hp) { set_error("heavy history append: two rows of a list name the same flow"); return GNS_E_ARG; }
+        // A2
+        at = 0;
+        uint64_t added[kHhTypes] = {};
+        for (uint32_t i = 0; i < nlists; i++) {
+            if (ns[i] == 0) continue;
+            HhLane &ln = h->lanes[(size_t)lane[i]];
+            GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
+            hipLaunchKernelGGL(k_hhh_link, dim3(grid256(ns[i])), dim3(256), 0, s, rows[i], h->K, ns[i], h->ids + at, ln.head,
+                               (uint32_t)h->slots, ln.log, ln.cap, h->plan.lanes[(size_t)lane[i]].rows, S, h->fresh);
+            GNS_HIP(hipGetLastError());
+            GNS_HIP(hipMemcpyAsync(hp + 1 + i, h->fresh, 4, hipMemcpyDeviceToHost, s));
+            at += ns[i];
+        }
+        GNS_HIP(hipStreamSynchronize(s));  // the caller's rows are read
+        for (uint32_t i = 0; i < nlists; i++) {
+            if (ns[i] == 0) continue;
+            added[i] = hp[1 + i];
+            h->lanes[(size_t)lane[i]].keys += added[i];
+            fresh += added[i];
+        }
+    }
+    h->pairs += fresh;
+    // (a list without rows names no lane: publish only what has one)
+    uint32_t pt[kHhTypes];
+    uint64_t pn[kHhTypes];
+    uint32_t np = 0;
+    for (uint32_t i = 0; i < nlists; i++)
+        if (ns[i]) { pt[np] = types[i]; pn[np] = ns[i]; np++; }
+    h->plan.publish(timestamp_ns, pt, pn, np);  // last: the snapshot exists from here on
+    if (out) { out[0] = total; out[1] = fresh; }
+    return GNS_OK;
+}
+
+int gns_hh_hist_heavy_rows(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t threshold, uint64_t limit,
+                           uint8_t *rows_dev, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    if (rows_dev && *n_io) GNS_TRY(hhh_check_dev(rows_dev, h->device, "rows_dev"));
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t cap = *n_io;
+    uint64_t n = 0;
+    GNS_TRY(hhh_list(h, end_ns, type, threshold, limit, &n));
+    *n_io = n;
+    if (n == 0 || n > cap || !rows_dev) return GNS_OK;
+    GNS_HIP(hipMemcpyAsync(rows_dev, h->ordered, n * (h->K + 4), hipMemcpyDeviceToDevice, h->stream));
+    GNS_HIP(hipStreamSynchronize(h->stream));
+    return GNS_OK;
+}
+
+int gns_hh_hist_heavy_hitters(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t threshold, uint64_t limit,
+                              uint8_t *flows, uint64_t *values, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t cap = *n_io;
+    uint64_t n = 0;
+    GNS_TRY(hhh_list(h, end_ns, type, threshold, limit, &n));
+    *n_io = n;
+    if (n == 0 || n > cap || !(flows || values)) return GNS_OK;
+    hipStream_t s = h->stream;
+    const uint32_t K = h->K;
+    if (h->spl_n < n * (K + 8)) GNS_TRY(grow_buf(&h->spl, h->spl_n, n * (K + 8)));
+    unsigned long long *dv = reinterpret_cast<unsigned long long *>(h->spl);
+    uint8_t *df = h->spl + n * 8;
+    hipLaunchKernelGGL(k_hhh_split, dim3(grid256(n)), dim3(256), 0, s, h->ordered, K, n, df, dv);
+    GNS_HIP(hipGetLastError());
+    if (flows) GNS_TRY(h->po.copy_out(flows, df, n * K, s));
+    if (values) GNS_TRY(h->po.copy_out(values, dv, n * 8, s));
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
+int gns_hh_hist_times(gns_hh_hist *h, int64_t *ts, uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t n = h->plan.t.ts.size(), m = std::min<uint64_t>(*n_io, n);
+    *n_io = n;
+    if (ts)
+        for (uint64_t i = 0; i < m; i++) ts[i] = h->plan.t.ts[(size_t)i];
+    return GNS_OK;
+}
+
+int gns_hh_hist_stats(gns_hh_hist *h, uint64_t out[8]) {
+    if (!h || !out) { set_error("null argument"); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    uint64_t cap = 0;
+    for (const HhLane &l : h->lanes) cap += l.cap;
+    out[0] = h->plan.t.ts.size(); out[1] = h->plan.t.rows; out[2] = h->pairs; out[3] = h->lanes.size();
+    out[4] = cap; out[5] = h->slots; out[6] = h->n_index_grow; out[7] = h->n_log_grow;
+    return GNS_OK;
+}
+
+int gns_hh_hist_export(gns_hh_hist *h, uint8_t *types, uint8_t *flows, uint32_t *values, uint32_t *written,
+                       uint64_t *n_io) {
+    if (!h || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    const uint64_t rows = h->plan.t.rows, room = std::min<uint64_t>(*n_io, rows);
+    *n_io = rows;
+    if (room == 0 || !(types || flows || values || written)) return GNS_OK;
+    hipStream_t s = h->stream;
+    const uint32_t K = h->K;
+    uint64_t at = 0;
+    for (uint32_t type = 0; type < kHhTypes && at < room; type++) {  // (type, log order)
+        const int l = h->plan.lane(type);
+        if (l < 0) continue;
+        const uint64_t m = std::min<uint64_t>(h->plan.lanes[(size_t)l].rows, room - at);
+        if (m == 0) continue;
+        if (types) memset(types + at, (int)type, m);
+        if (flows || values || written) {
+            if (h->spl_n < m * (K + 8)) GNS_TRY(grow_buf(&h->spl, h->spl_n, m * (K + 8)));
+            uint32_t *dv = reinterpret_cast<uint32_t *>(h->spl), *dw = dv + m;
+            uint8_t *df = h->spl + m * 8;
+            hipLaunchKernelGGL(k_hhh_export, dim3(grid256(m)), dim3(256), 0, s, h->lanes[(size_t)l].log, m, h->D, df, dv, dw);
+            GNS_HIP(hipGetLastError());
+            if (flows) GNS_TRY(h->po.copy_out(flows + at * K, df, m * K, s));
+            if (values) GNS_TRY(h->po.copy_out(values + at, dv, m * 4, s));
+            if (written) GNS_TRY(h->po.copy_out(written + at, dw, m * 4, s));
+            GNS_HIP(hipStreamSynchronize(s));
+        }
+        at += m;
+    }
+    return GNS_OK;
+}
+
+}  // extern "C"

@@ -145,14 +145,29 @@ class Manager:
                 raise ValueError(f"record: task {t.name()} has no history (keep_history first)")
         return {t.name(): t.record(timestamp_ns, full=full) for t in tasks}
 
+    def keep_heavy_history(self, **kw) -> Dict[str, object]:
+        """SketchTask.keep_heavy_history for every sketch task: name -> HeavyHistory."""
+        return {t.name(): t.keep_heavy_history(**kw) for t in self.tasks() if hasattr(t, "keep_heavy_history")}
+
+    def record_heavy(self, timestamp_ns: int) -> Dict[str, object]:
+        """One interval of the sketch writers: every sketch task's lists into its heavy history
+        under ONE timestamp.  The reference runs one snapshotter per writer, so this timestamp
+        is separate from the exact tasks' ``record``.  name -> (rows appended, pairs new)."""
+        tasks = [t for t in self.tasks() if hasattr(t, "record_heavy")]
+        for t in tasks:
+            if getattr(t, "heavy_history", None) is None:
+                raise ValueError(f"record_heavy: task {t.name()} has no heavy history (keep_heavy_history first)")
+        return {t.name(): t.record_heavy(timestamp_ns) for t in tasks}
+
     def reset_all(self) -> None:  # resetAllTasks, manager.go:179-193
         for t in self.tasks():
             t.reset()
 
     def checkpoint(self, dir) -> List[str]:
         """Every task's state into ``dir``, one file per task name (task.save), then
-        ``<name>.history.npz`` for each task that has a history attached (its whole log);
-        returns the paths, the history files after the task files."""
+        ``<name>.history.npz`` for each task that has a history attached (its whole log), then
+        ``<name>.heavy.npz`` for each sketch task that has a heavy history attached; returns the
+        paths, the history files after the task files."""
         import os
         os.makedirs(dir, exist_ok=True)
         paths = []
@@ -163,6 +178,10 @@ class Manager:
             if getattr(t, "history", None) is not None:
                 paths.append(os.path.join(dir, t.name() + ".history.npz"))
                 t.save_history(paths[-1])
+        for t in self.tasks():
+            if getattr(t, "heavy_history", None) is not None:
+                paths.append(os.path.join(dir, t.name() + ".heavy.npz"))
+                t.save_heavy_history(paths[-1])
         return paths
 
     def restore(self, dir) -> None:
@@ -177,6 +196,9 @@ class Manager:
             hp = os.path.join(dir, t.name() + ".history.npz")
             if getattr(t, "history", None) is not None and os.path.exists(hp):
                 t.restore_history(hp)
+            vp = os.path.join(dir, t.name() + ".heavy.npz")
+            if getattr(t, "heavy_history", None) is not None and os.path.exists(vp):
+                t.restore_heavy_history(vp)
 
     def stop(self) -> Dict[str, object]:
         """Drain (flush every stream) and take the final snapshot (manager.go:196-216)."""

@@ -168,6 +168,63 @@ class SketchTask:
         from . import checkpoint
         checkpoint.save(view, path)
 
+    # --- the history behind QueryHeavyHitters' end_time (gns_hh_hist_*) ---
+    def keep_heavy_history(self, **kw):
+        """Attach a HeavyHistory of this task's flow width (``kw``: its max_rows / max_flows) and
+        a view of the sketch: ``record_heavy`` then stores an interval's lists, and
+        ``query_heavy_hitters`` answers from it.  Returns the history (the one already
+        attached, if any)."""
+        if getattr(self, "heavy_history", None) is None:
+            from .heavy_history import HeavyHistory
+            kw.setdefault("device", self.sketch.device)
+            self.heavy_history = HeavyHistory(self.flow_size, **kw)
+            self._heavy_view = self.sketch.view()
+        return self.heavy_history
+
+    def _heavy(self, what: str):
+        h = getattr(self, "heavy_history", None)
+        if h is None:
+            raise ValueError(f"{what}: no heavy history attached (keep_heavy_history first)")
+        return h
+
+    def record_heavy(self, timestamp_ns: int, view=None):
+        """One interval of the sketch writer (writer_clickhouse.go:86-138): the lists as device
+        rows, appended under ``timestamp_ns`` -- types 0 (count) and 1 (size) for Count-Min,
+        type 2 for SuperSpread, the writer's branch on ``Size != nil``.  ``view``: a view the
+        caller refreshed on the ingest thread (the call may then run on the snapshotter's
+        thread while the task ingests); None refreshes a view of the task's own here.  Returns
+        (rows appended, (type, flow) pairs new to the history)."""
+        h = self._heavy("record_heavy")
+        if view is None:
+            view = self._heavy_view
+            view.refresh()
+        rows = view.heavy_hitters_rows_device()
+        if isinstance(self.sketch, CountMin):
+            return h.append(timestamp_ns, {0: rows[0], 1: rows[1]})
+        return h.append(timestamp_ns, {2: rows})
+
+    def query_heavy_hitters(self, type: int, limit: int, end_time=None):
+        """QueryHeavyHitters (querier.go:191-248) from the attached history: per flow the value
+        of its latest row of ``type`` with Timestamp <= ``end_time`` (None: no bound), ORDER BY
+        value DESC LIMIT ``limit`` (ties by flow bytes).  LIMIT 0 and a Type without rows select
+        nothing, as in the reference."""
+        from .exact import HeavyHitter
+        h = self._heavy("query_heavy_hitters")
+        if limit < 0:
+            raise ValueError("negative limit")
+        if limit == 0:
+            return []
+        flows, vals = h.heavy_hitters(type, 0, limit, end_time=end_time)
+        return [HeavyHitter(decode_flow(bytes(f), self.flow_fields), int(v)) for f, v in zip(flows, vals)]
+
+    def save_heavy_history(self, path) -> None:
+        """The attached heavy history's log as one file (HeavyHistory.save)."""
+        self._heavy("save_heavy_history").save(path)
+
+    def restore_heavy_history(self, path) -> None:
+        """Feed a saved log into the attached, still empty heavy history (HeavyHistory.restore)."""
+        self._heavy("restore_heavy_history").restore(path)
+
     def alerter_msg(self, rules, view=None) -> str:
         """AlerterMsg (task.go:187-243); rules: dicts with task_name/metric/operator/threshold/name.
         view: evaluate the rules on that view's snapshot instead of the live sketch's."""

@@ -890,7 +890,8 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
  * its peak is the old log plus the new, plus 4 bytes per expired row under fold and a second
  * index while keys are forgotten; the old log is freed when the trim returns.
  * gns_ex_hist_append_rows stages the call's key rows on the device.  Not offered: roll-ups
- * of a history, a history of the sketch tasks' heavy-hitter lists. */
+ * of a history.  (The sketch tasks' heavy-hitter lists have a history of their own:
+ * gns_hh_hist_*, below.) */
 typedef struct gns_ex_hist gns_ex_hist;
 typedef struct gns_ex_hist_params { gns_layout key; uint64_t max_rows, max_flows; int device; } gns_ex_hist_params;
 int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out);
@@ -910,6 +911,85 @@ int gns_ex_hist_heavy_hitters(gns_ex_hist *h, const int64_t *end_ns, int metric,
                               uint8_t *keys, uint64_t *values, uint64_t *n_io);
 int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, int64_t *start_ns, int64_t *end_out_ns,
                          uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
+
+/* ------------------------------------------------------------------ */
+/* Heavy-hitter history: QueryHeavyHitters' EndTime for the sketches   */
+/* ------------------------------------------------------------------ */
+/* QueryHeavyHitters (internal/query/querier.go:191-248) reads the heavy_hitters table, which only
+ * the sketch tasks write: one row (Timestamp, TaskName, Flow, Value, Type) per list entry of each
+ * interval's Snapshot() (internal/engine/impl/sketch/writer_clickhouse.go:86-138; Type 0 =
+ * Count-Min's count list, 1 = its size list, 2 = SuperSpread's list).  The query is
+ *   SELECT Flow, argMax(Value, Timestamp) ... WHERE TaskName = ? AND Type = ? [AND Timestamp <= ?]
+ *   GROUP BY Flow ORDER BY LatestValue DESC LIMIT ?
+ * A gns_hh_hist is that table on the device for one task (TaskName is fixed) and one flow width
+ * key_bytes (1..37): an append-only log per Type 0..255 over one key index; the types are
+ * independent tables that share the snapshot timestamps.
+ *   - Snapshots 0..S-1 carry STRICTLY increasing timestamps (int64 ns, negative values are
+ *     legal).  The reference's DateTime has second resolution and two snapshots within one second
+ *     tie in argMax; requiring strictly increasing timestamps is the defined behaviour here.  One
+ *     gns_hh_hist_append is one snapshot: zero or more lists of packed rows [flow (key_bytes) |
+ *     u32 LE value] -- the rows gns_cm_heavy_rows, gns_cm_view_heavy_rows and
+ *     gns_ss_view_heavy_rows give -- each under its type, at most one list per type.  `where`
+ *     names the memory of every list's rows: device memory of the history's GPU (no copy of the
+ *     list passes through the host), or host memory (staged to the device, then the same path: a
+ *     restore).  An append without rows registers its timestamp.  out[0] = rows appended,
+ *     out[1] = (type, flow) pairs new to the history (out may be NULL).
+ *   - A query names a time by end_ns: NULL is the newest snapshot, else s(T) = the newest
+ *     snapshot with timestamp <= *end_ns; with none every answer is empty.  For a type, a row is
+ *     SEEN when its snapshot is <= s(T) and LIVE when no later SEEN row of the same (type, flow)
+ *     exists.  There are NO TOMBSTONES: a flow that was listed once and is missing from every
+ *     later list stays LIVE with its last listed value (argMax only sees rows that exist), and a
+ *     flow listed again supersedes its old row even with a smaller value (the normal case after
+ *     the sketch's Reset).  GROUP BY Flow groups by the decoded string; DecodeFlow is injective on
+ *     the key bytes of a fixed layout, so the grouping is by key bytes.
+ *   - gns_hh_hist_heavy_hitters lists the LIVE rows of one type with value >= threshold, value
+ *     descending, then flow bytes ascending (ClickHouse leaves ties unordered: this is the
+ *     canonical list order of gns_ex_heavy_hitters), cut to `limit` rows when limit != 0, under
+ *     the *n_io protocol of gns_ex_heavy_hitters (capacity in, list length after the cut out; a
+ *     longer list is reported and not written; flows / values may be NULL).  Values are u32 in
+ *     the log, as every producer emits them, and 64-bit in the answer; value 0 is a legal row.  A
+ *     type that was never appended answers empty.  gns_hh_hist_heavy_rows gives the same list as
+ *     packed device rows (capacity *n_io rows of key_bytes + 4), e.g. for gns_hh_order_rows after
+ *     an all-gather of several GPUs' flow-disjoint histories.
+ *   - Rows of one list must name distinct flows (the engines' lists do).  They are caller memory
+ *     all the same, so the device checks every list before anything is linked.
+ *   - A rejected append leaves every answer, gns_hh_hist_times and the first three stats
+ *     unchanged (the key index may have grown).  GNS_E_ARG: a null handle, two rows of a list with
+ *     the same flow, two lists of one type, a type above 255, timestamp_ns <= the last
+ *     snapshot's, rows that are not device memory of the history's GPU.  GNS_E_FULL: a type's
+ *     log beyond 2^32 - 2 rows, 2^32 - 2 snapshots, the index beyond 2^30 slots.  All lists of a
+ *     snapshot are resolved and checked before any is linked, and nothing of a snapshot is
+ *     visible to a query before its append has returned GNS_OK.
+ *   - gns_hh_hist_times: as gns_ex_hist_times.  gns_hh_hist_stats: snapshots, rows, distinct
+ *     (type, flow) pairs, lanes (types that hold rows or had a lane made for them), row capacity
+ *     (all lanes), index slots, index growths, log growths.
+ *   - gns_hh_hist_export writes every log row in (type, log order) -- type, flow bytes, value,
+ *     the number of the snapshot that wrote the row; any array may be NULL -- under the *n_io
+ *     protocol of gns_ex_hist_export; timestamps come from gns_hh_hist_times.  Feeding an empty
+ *     history each snapshot's rows, as host lists, restores it.
+ *   - max_rows / max_flows are only the INITIAL capacities of a type's log and of the key index
+ *     (0: 2^20 rows, 2^16 flows); both grow.
+ *   - Threads: any, serialised by the history's mutex; its stream and pinned staging are its own
+ *     and no query allocates or frees once warm.  The history keeps no reference to the
+ *     caller's rows, handle or view after the append returns.
+ * Memory: 16 bytes per log row (key bytes live only in the index); per index slot a record plus
+ * 4 bytes per type in use; 8 MB of pinned host staging.
+ * Not offered: retention (trim / fold) for this store, per-flow point queries as of T, roll-ups. */
+typedef struct gns_hh_hist gns_hh_hist;
+typedef struct gns_hh_hist_params { uint32_t key_bytes; uint64_t max_rows, max_flows; int device; } gns_hh_hist_params;
+typedef struct gns_hh_list { uint32_t type; const uint8_t *rows; uint64_t n; } gns_hh_list;   /* packed [flow | u32 LE value] */
+int gns_hh_hist_create(const gns_hh_hist_params *p, gns_hh_hist **out);
+int gns_hh_hist_destroy(gns_hh_hist *h);
+int gns_hh_hist_append(gns_hh_hist *h, int64_t timestamp_ns, const gns_hh_list *lists, uint32_t nlists, gns_mem where,
+                       uint64_t out[2]);
+int gns_hh_hist_heavy_hitters(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t threshold, uint64_t limit,
+                              uint8_t *flows, uint64_t *values, uint64_t *n_io);
+int gns_hh_hist_heavy_rows(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t threshold, uint64_t limit,
+                           uint8_t *rows_dev, uint64_t *n_io);
+int gns_hh_hist_times(gns_hh_hist *h, int64_t *ts, uint64_t *n_io);
+int gns_hh_hist_stats(gns_hh_hist *h, uint64_t out[8]);
+int gns_hh_hist_export(gns_hh_hist *h, uint8_t *types, uint8_t *flows, uint32_t *values, uint32_t *written,
+                       uint64_t *n_io);
 
 /* ------------------------------------------------------------------ */
 /* Exact spread: the device ground truth of SuperSpread                */

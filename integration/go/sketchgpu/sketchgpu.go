@@ -1371,6 +1371,91 @@ func (y *History) AppendRows(keys []byte, start, last []int64, pkts, bytes []uin
 // Close releases the history.
 func (y *History) Close() { C.gns_ex_hist_destroy(y.h) }
 
+// HeavyHistory is the store behind QueryHeavyHitters' EndTime for the sketch tasks
+// (gns_hh_hist_*): it replaces the sketch ClickHouseWriter.Write (writer_clickhouse.go:86-138),
+// which appends one row per list entry of each interval's Snapshot(), and the query over
+// those rows (querier.go:191-248).  Append stores the lists of one interval as packed device
+// rows [flow | u32] -- what View.HeavyRows and SuperSpreadView.HeavyRows write -- under a
+// Timestamp; HeavyHitters answers, per flow, with the value of its latest row of one Type at
+// or before an end time (nil: the newest snapshot).  A flow that left the list keeps its
+// last listed value; one listed again supersedes its old row.  Calls may come from any
+// goroutine.
+type HeavyHistory struct {
+	h        *C.gns_hh_hist
+	keyBytes int
+}
+
+// HeavyList is one list of an interval: n packed device rows of keyBytes + 4 under a Type
+// (0: Count-Min's count list, 1: its size list, 2: SuperSpread's list).
+type HeavyList struct {
+	Type uint32
+	Rows unsafe.Pointer
+	N    uint64
+}
+
+// NewHeavyHistory allocates a history for flows of keyBytes bytes.  maxRows and maxFlows are
+// initial capacities (0: defaults); both grow.
+func NewHeavyHistory(keyBytes int, maxRows, maxFlows uint64, device int) (*HeavyHistory, error) {
+	var p C.gns_hh_hist_params
+	p.key_bytes = C.uint32_t(keyBytes)
+	p.max_rows, p.max_flows, p.device = C.uint64_t(maxRows), C.uint64_t(maxFlows), C.int(device)
+	var h *C.gns_hh_hist
+	if err := lastErr(C.gns_hh_hist_create(&p, &h)); err != nil {
+		return nil, err
+	}
+	return &HeavyHistory{h: h, keyBytes: keyBytes}, nil
+}
+
+// Append stores the lists (device rows, at most one list per Type) as the next snapshot;
+// tsNano must lie after the last one's.  No lists register the timestamp.
+func (y *HeavyHistory) Append(tsNano int64, lists []HeavyList) (rows, newPairs uint64, err error) {
+	var out [2]C.uint64_t
+	cl := make([]C.gns_hh_list, len(lists)+1)
+	for i, l := range lists {
+		cl[i]._type = C.uint32_t(l.Type)
+		cl[i].rows = (*C.uint8_t)(l.Rows)
+		cl[i].n = C.uint64_t(l.N)
+	}
+	err = lastErr(C.gns_hh_hist_append(y.h, C.int64_t(tsNano), &cl[0], C.uint32_t(len(lists)), C.GNS_MEM_DEVICE, &out[0]))
+	return uint64(out[0]), uint64(out[1]), err
+}
+
+// HeavyHitters lists the flows whose latest row of Type typ as of end has value >= threshold,
+// value descending then flow bytes ascending, cut to limit rows when limit != 0.
+func (y *HeavyHistory) HeavyHitters(end *int64, typ uint32, threshold, limit uint64) (flows []byte, values []uint64, err error) {
+	var n C.uint64_t
+	if err = lastErr(C.gns_hh_hist_heavy_hitters(y.h, endNs(end), C.uint32_t(typ), C.uint64_t(threshold), C.uint64_t(limit),
+		nil, nil, &n)); err != nil || n == 0 {
+		return nil, nil, err
+	}
+	m := int(n)
+	flows, values = make([]byte, m*y.keyBytes+1), make([]uint64, m)
+	err = lastErr(C.gns_hh_hist_heavy_hitters(y.h, endNs(end), C.uint32_t(typ), C.uint64_t(threshold), C.uint64_t(limit),
+		(*C.uint8_t)(unsafe.Pointer(&flows[0])), (*C.uint64_t)(unsafe.Pointer(&values[0])), &n))
+	if int(n) > m { // (an Append in between made the list longer: nothing was written)
+		return nil, nil, fmt.Errorf("heavy history: the list grew from %d to %d rows between the calls", m, int(n))
+	}
+	m = int(n)
+	return flows[:m*y.keyBytes], values[:m], err
+}
+
+// Times returns the snapshots' timestamps.
+func (y *HeavyHistory) Times() ([]int64, error) {
+	var n C.uint64_t
+	if err := lastErr(C.gns_hh_hist_times(y.h, nil, &n)); err != nil || n == 0 {
+		return nil, err
+	}
+	ts := make([]int64, int(n))
+	err := lastErr(C.gns_hh_hist_times(y.h, (*C.int64_t)(unsafe.Pointer(&ts[0])), &n))
+	if int(n) < len(ts) {
+		ts = ts[:int(n)]
+	}
+	return ts, err
+}
+
+// Close releases the history.
+func (y *HeavyHistory) Close() { C.gns_hh_hist_destroy(y.h) }
+
 // ThriftDecoder holds the device buffers one batch of NATS messages decodes into
 // (ns-engine's live path: stream_aggregator.go:85 decodes one PacketInfo message
 // at a time with probe.UnmarshalPacketInfo, packetcodec.go:97-108; here a whole
