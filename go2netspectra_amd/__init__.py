@@ -18,13 +18,13 @@ from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, 
                       read_pcap_compact, write_pcap, write_pcapgen, write_pcapng)
 from .sketch import CountMin, CountMinView, HeavyCount, HeavyRecord, HeavySize, SuperSpread, SuperSpreadView
 from .spread import ExactSpread
-from .task import New, SketchTask, decode_flow
+from .task import New, SketchTask, decode_flow, encode_flow
 
 __all__ = [
     "GnsError", "build", "load", "Config", "SketchTaskDef", "load_config", "parse_config", "Manager",
     "TaskGroup", "create", "register_aggregator", "HeaderBatch", "PacketBatch", "SyntheticTraffic",
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
-    "SuperSpread", "New", "SketchTask", "decode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
+    "SuperSpread", "New", "SketchTask", "decode_flow", "encode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
     "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "ExactHistory", "apply_delta", "CompactBatch",
     "SuperSpreadView", "rollup_plan", "spread_rollup_plan", "to16_to_encodeflow",

@@ -61,6 +61,7 @@ EXPORTED = [
     "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows",
     "gns_hh_hist_create", "gns_hh_hist_destroy", "gns_hh_hist_append", "gns_hh_hist_heavy_hitters",
     "gns_hh_hist_heavy_rows", "gns_hh_hist_times", "gns_hh_hist_stats", "gns_hh_hist_export",
+    "gns_hh_hist_trim", "gns_hh_hist_query",
 ]
 
 
@@ -292,6 +293,8 @@ def load() -> ct.CDLL:
         "gns_hh_hist_heavy_rows": ([vp, vp, u32, u64, u64, vp, vp], i32),
         "gns_hh_hist_times": ([vp, vp, vp], i32), "gns_hh_hist_stats": ([vp, vp], i32),
         "gns_hh_hist_export": ([vp, vp, vp, vp, vp, vp], i32),
+        "gns_hh_hist_trim": ([vp, ct.c_int64, i32, vp], i32),
+        "gns_hh_hist_query": ([vp, vp, u32, vp, u64, i32, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -22,6 +22,18 @@
 //   Q2  k_hhh_collect       live rows with value >= max(threshold, v*) -> packed rows
 //                           [flow | u32], key bytes from the index record
 //   Q3  hh_order_rows_dev   the canonical order (gns_hh.hip), then the cut to `limit`
+//   T1  k_hhh_trim_count    gns_hh_hist_trim, per lane: the rows of each 256-row block of the
+//                           expired prefix that a fold keeps
+//   T2  k_hhh_scan / _add   the exclusive scan of the block counts, 1,024 per workgroup and level
+//   T3  k_hhh_trim_move     the kept rows, stably, into a new log; k_hhh_trim_heads then reads
+//                           the new head words off it (the newest row of a slot is its open one)
+//   P1  k_hhh_q_lookup      gns_hh_hist_query: flows -> index slots (dict_lookup: no insert);
+//                           as of the newest snapshot the head word answers
+//   P2  k_hhh_own / _q_scan as of an older one: one pass over the lane's rows answers for the
+//                           live row of every wanted slot; P3 k_hhh_q_dup copies to duplicates
+// A fold keeps one row per (type, flow) pair ever listed, because the store has no tombstones: it
+// bounds the log by snapshots x list length + distinct pairs.  Only a drop bounds the index.
+// Not offered: roll-ups.
 // Everything an append writes before the host publishes the snapshot lies outside every scan:
 // rows at and beyond a lane's published count, and superseded words that equal the new S.
 #include <mutex>
@@ -98,6 +110,151 @@ __global__ __launch_bounds__(256) void k_hhh_reslot(uint4 *log, uint64_t rows, u
     if (id < slots) log[r].x = remap[id];  // (a published row's slot is marked: its key has a head word)
 }
 
+// a row is live as of snapshot s
+__device__ __forceinline__ bool hhh_live(const uint4 &q, uint32_t s) { return q.z <= s && s < q.w; }
+
+// gns_hh_hist_trim, lane by lane.  Of the expired prefix [0, R) of a lane's log the rows still
+// live as of the last expired snapshot s_last stay under a fold (superseded > s_last), none under
+// a drop; every row from R on stays.  T1 counts the staying rows of each 256-row block of the
+// prefix, T2 scans the counts, T3 moves the rows stably into the new log G: a prefix row to its
+// rank, a later row to r - R + nbase.  Version words lose d; a written word below d belongs to
+// the base and becomes 0.  The old log is only read: a failed trim leaves it as it was.
+struct HhTrim {
+    uint64_t rows, R, nbase, row0, cap;  // row0: the first row of T3's grid (0 when the prefix is ranked)
+    uint32_t s_last, d;
+    int fold;
+};
+__global__ __launch_bounds__(256) void k_hhh_trim_count(const uint4 *log, uint64_t R, uint32_t s_last, uint32_t *cnt) {
+    __shared__ uint32_t s_w[4];
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool sel = r < R && log[r].w > s_last;
+    const uint64_t m = __ballot(sel);
+    if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+// T2: a[0, n) -> its exclusive scan in place, 1,024 words per workgroup; the workgroup's sum goes
+// to sums[blockIdx.x] (the host scans those in turn and k_hhh_scan_add adds them back)
+constexpr uint32_t kScanTile = 1024;
+__global__ __launch_bounds__(256) void k_hhh_scan(uint32_t *a, uint64_t n, uint32_t *sums) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kScanTile + 4u * tid;
+    uint32_t v[4], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        v[j] = i0 + j < n ? a[i0 + j] : 0u;
+        sum += v[j];
+    }
+    uint32_t inc = sum;  // inclusive scan over the wave
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t x = __shfl_up(inc, o);
+        if (lane >= o) inc += x;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t run = inc - sum;
+    for (uint32_t w = 0; w < wave; w++) run += s_w[w];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        if (i0 + j < n) a[i0 + j] = run;
+        run += v[j];
+    }
+    if (tid == 0) sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+__global__ __launch_bounds__(256) void k_hhh_scan_add(uint32_t *a, uint64_t n, const uint32_t *sums) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] += sums[i / kScanTile];
+}
+// T3.  off: T2's scan of T1's counts (block b of this grid is T1's block b); nullptr: no prefix row stays
+__global__ __launch_bounds__(256) void k_hhh_trim_move(const uint4 *O, HhTrim t, const uint32_t *off, uint4 *G) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t r = t.row0 + (uint64_t)blockIdx.x * 256 + tid;
+    uint4 q = make_uint4(0, 0, 0, 0);
+    if (r < t.rows) q = O[r];
+    const bool prefix = r < t.R;
+    const bool sel = prefix && t.fold && q.w > t.s_last;
+    const uint64_t m = __ballot(sel);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (r >= t.rows || (prefix && !sel)) return;
+    uint64_t nr = r - t.R + t.nbase;
+    if (prefix) {
+        nr = off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; w++) nr += s_w[w];
+    }
+    if (nr >= t.cap) return;
+    G[nr] = make_uint4(q.x, q.y, max(q.z, t.d) - t.d, q.w == kHistOpen ? kHistOpen : q.w - t.d);
+}
+// The newest row of a (lane, slot) is the slot's only row that nothing superseded: the head words
+// of a new log, into an array cleared to kHistOpen
+__global__ __launch_bounds__(256) void k_hhh_trim_heads(const uint4 *log, uint64_t rows, uint64_t slots, uint32_t *nh) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const uint4 q = log[r];
+    if (q.w == kHistOpen && q.x < slots) nh[q.x] = (uint32_t)r;
+}
+// (type, flow) pairs a trim forgets: the old head word names a row, the new one none
+__global__ __launch_bounds__(256) void k_hhh_trim_forgot(const uint32_t *oh, const uint32_t *nh, uint64_t slots,
+                                                         uint32_t *forgot) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool gone = s < slots && oh[s] != kHistOpen && nh[s] == kHistOpen;
+    const uint64_t m = __ballot(gone);
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(forgot, (uint32_t)__popcll(m));
+}
+// the keys some lane still names (k_hhh_heads' list)
+__global__ __launch_bounds__(256) void k_hhh_trim_named(const uint32_t *ids, uint64_t slots, uint32_t *named) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t m = __ballot(s < slots && ids[s] != GNS_ID_NONE);
+    if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(named, (uint32_t)__popcll(m));
+}
+
+// gns_hh_hist_query.  P1: flow i -> its index slot (a read-only lookup: nothing is claimed) and
+// the answer "no live row"; as of the newest snapshot the lane's head word names the live row.
+__global__ __launch_bounds__(256) void k_hhh_q_lookup(const uint8_t *flows, uint64_t n, DictDev D, const uint32_t *head,
+                                                      const uint4 *log, uint64_t rows, uint32_t *ids,
+                                                      unsigned long long *values, uint8_t *found) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t kw[GNS_KWMAX];
+    load_key_bytes<GNS_KWMAX>(flows + i * D.K, D.K, false, kw);
+    const uint32_t id = dict_lookup(D, kw);
+    ids[i] = id;
+    unsigned long long v = 0;
+    uint8_t f = 0;
+    if (head && id != GNS_ID_NONE) {
+        const uint32_t r = head[id];
+        if (r < rows) { v = log[r].y; f = 1; }  // (kHistOpen lies beyond every log)
+    }
+    values[i] = v;
+    found[i] = f;
+}
+// P2, as of an older snapshot: every query has named itself in its slot's owner word (k_hhh_own;
+// the word is valid when ids[word] == slot, so nothing of index size is cleared per call); one
+// pass over the rows of snapshots 0..s answers for the live row of every wanted slot
+__global__ __launch_bounds__(256) void k_hhh_q_scan(const uint4 *log, uint64_t rows, uint32_t s, uint32_t slots,
+                                                    const uint32_t *owner, const uint32_t *ids, uint64_t n,
+                                                    unsigned long long *values, uint8_t *found) {
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256) {
+        const uint4 q = log[r];
+        if (!hhh_live(q, s) || q.x >= slots) continue;
+        const uint32_t i = owner[q.x];
+        if (i < n && ids[i] == q.x) { values[i] = q.y; found[i] = 1; }
+    }
+}
+// P3: a flow named more than once in the batch takes the answer of the query that owns the slot
+__global__ __launch_bounds__(256) void k_hhh_q_dup(const uint32_t *ids, uint64_t n, uint32_t slots, const uint32_t *owner,
+                                                   unsigned long long *values, uint8_t *found) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id >= slots) return;
+    const uint32_t o = owner[id];
+    if (o != (uint32_t)i && o < n) { values[i] = values[o]; found[i] = found[o]; }
+}
+
 // Select control words: [0] the value bits fixed so far, [1] rows still wanted at or below the
 // band, [2] every row is wanted (fewer than `limit` qualify), [3] rows collected, [4] the cut
 enum { SEL_PREFIX = 0, SEL_REM = 1, SEL_ALL = 2, SEL_COUNT = 3, SEL_CUT = 4, SEL_WORDS = 8 };
@@ -109,8 +266,6 @@ __global__ void k_hhh_sel_init(uint32_t *ctl, uint32_t limit, uint32_t thr, uint
     }
     for (uint32_t b = t; b < kSelBins; b += blockDim.x) hist[b] = 0;
 }
-
-__device__ __forceinline__ bool hhh_live(const uint4 &q, uint32_t s) { return q.z <= s && s < q.w; }
 
 // Q1: one level's histogram of the live rows with value >= thr whose higher bits equal the
 // prefix; bin = (value >> shift) & (kSelBins - 1).  `above`: the bits over this level's.
@@ -257,6 +412,8 @@ struct gns_hh_hist : ViewCore {
     uint8_t *stage = nullptr;   // host lists staged for the append
     uint64_t stage_n = 0;
     uint64_t n_index_grow = 0, n_log_grow = 0;
+    uint32_t *tsc = nullptr;  // a trim's counters, block counts and scan sums
+    uint64_t tsc_n = 0;
     // query side
     uint32_t *ctl = nullptr, *hist = nullptr;
     uint8_t *coll = nullptr, *ordered = nullptr;  // collected rows, then in canonical order
@@ -273,7 +430,7 @@ void hhh_free(gns_hh_hist *h) {
     for (HhLane &l : h->lanes) { dfree(l.log); dfree(l.head); }
     h->lanes.clear();
     dfree(h->D.rec); dfree(h->dctl); dfree(h->full); dfree(h->ids); dfree(h->mark); dfree(h->fresh); dfree(h->stage);
-    dfree(h->ctl); dfree(h->hist); dfree(h->coll); dfree(h->ordered); dfree(h->spl);
+    dfree(h->ctl); dfree(h->hist); dfree(h->coll); dfree(h->ordered); dfree(h->spl); dfree(h->tsc);
     h->dsc.free_all();
     h->rsc.free_all();
     h->hh.free_all();
@@ -477,6 +634,27 @@ int hhh_list(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t thre
     GNS_HIP(hipStreamSynchronize(st));
     *n = limit ? std::min<uint64_t>(got, limit) : got;
     return GNS_OK;
+}
+
+// T2 on the host side: a[0, n) -> its exclusive scan, the total to *tot.  sc: room for the tile
+// sums of every level below, hhh_scan_words(n) words.
+uint64_t hhh_scan_words(uint64_t n) {
+    uint64_t w = 0;
+    while (n > kScanTile) {
+        n = (n + kScanTile - 1) / kScanTile;
+        w += n;
+    }
+    return w;
+}
+void hhh_scan(hipStream_t s, uint32_t *a, uint64_t n, uint32_t *sc, uint32_t *tot) {
+    if (n <= kScanTile) {
+        hipLaunchKernelGGL(k_hhh_scan, dim3(1), dim3(256), 0, s, a, n, tot);
+        return;
+    }
+    const uint64_t nt = (n + kScanTile - 1) / kScanTile;
+    hipLaunchKernelGGL(k_hhh_scan, dim3((unsigned)nt), dim3(256), 0, s, a, n, sc);
+    hhh_scan(s, sc, nt, sc + nt, tot);
+    hipLaunchKernelGGL(k_hhh_scan_add, dim3(grid256(n)), dim3(256), 0, s, a, n, (const uint32_t *)sc);
 }
 
 }  // namespace
@@ -727,6 +905,211 @@ int gns_hh_hist_export(gns_hh_hist *h, uint8_t *types, uint8_t *flows, uint32_t 
         }
         at += m;
     }
+    return GNS_OK;
+}
+
+int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4]) {
+    if (!h) { set_error("null argument"); return GNS_E_ARG; }
+    if (fold != 0 && fold != 1) { set_error("heavy history trim: fold %d (0: drop, 1: fold)", fold); return GNS_E_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const HhHistPlan::Trim tp = h->plan.trim_plan(before_ns, fold != 0);
+    if (out) { out[0] = out[1] = out[2] = 0; out[3] = h->plan.t.rows; }
+    if (tp.t.noop) return GNS_OK;
+    GNS_TRY(set_device(h->device));
+    hipStream_t s = h->stream;
+    const size_t nl = h->lanes.size();
+    const uint64_t old_slots = h->slots;
+    const uint32_t s_last = (uint32_t)(tp.t.c - 1), d = tp.t.d;
+    // scratch: [0, nl) rows each lane's base keeps, [nl, 2 nl) pairs each lane forgets, [2 nl] keys
+    // still named; then per ranked lane its block counts and the scan's tile sums
+    std::vector<uint64_t> at(nl, 0), nblk(nl, 0), nbase(nl, 0);
+    uint64_t words = 2 * nl + 1;
+    bool ranked = false;
+    for (size_t l = 0; l < nl; l++) {
+        if (!tp.t.fold || tp.R[l] == 0) continue;  // prefix rows may stay
+        nblk[l] = (tp.R[l] + 255) / 256;
+        at[l] = words;
+        words += nblk[l] + hhh_scan_words(nblk[l]);
+        ranked = true;
+    }
+    if (h->tsc_n < words) GNS_TRY(grow_buf(&h->tsc, h->tsc_n, words));
+    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h->po.pin);
+    GNS_HIP(hipMemsetAsync(h->tsc, 0, (2 * nl + 1) * 4, s));
+    if (ranked) {  // T1 / T2 as of the last expired snapshot
+        for (size_t l = 0; l < nl; l++) {
+            if (!nblk[l]) continue;
+            uint32_t *cnt = h->tsc + at[l];
+            hipLaunchKernelGGL(k_hhh_trim_count, dim3((unsigned)nblk[l]), dim3(256), 0, s, (const uint4 *)h->lanes[l].log,
+                               tp.R[l], s_last, cnt);
+            hhh_scan(s, cnt, nblk[l], cnt + nblk[l], h->tsc + l);
+        }
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->tsc, nl * 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        for (size_t l = 0; l < nl; l++) nbase[l] = hp[l];
+    }
+    // everything new is built beside the history, which stays as it is until the end
+    std::vector<HhLane> nw(nl);
+    std::vector<uint32_t *> nh(nl, nullptr);  // the head words at the rebuilt index's slots
+    std::vector<uint64_t> forgot(nl, 0);
+    uint64_t forgot_all = 0, slots_n = old_slots, live = h->claimed;
+    uint32_t *old_rec = nullptr;
+    DictDev Dn = h->D;
+    bool rebuilt = false, ctl_touched = false;
+    auto run = [&]() -> int {
+        const dim3 sgrid(grid256(old_slots));
+        for (size_t l = 0; l < nl; l++) {
+            const uint64_t rows = h->plan.lanes[l].rows, kept = rows - tp.R[l] + nbase[l];
+            GNS_TRY(dalloc_t(&nw[l].head, old_slots));
+            GNS_HIP(hipMemsetAsync(nw[l].head, 0xFF, old_slots * 4, s));
+            if (kept) {
+                nw[l].cap = hist_row_capacity(0, kept);
+                GNS_TRY(dalloc_t(&nw[l].log, nw[l].cap));
+                HhTrim t{};
+                t.rows = rows; t.R = tp.R[l]; t.nbase = nbase[l]; t.row0 = nblk[l] ? 0 : tp.R[l]; t.cap = nw[l].cap;
+                t.s_last = s_last; t.d = d; t.fold = tp.t.fold ? 1 : 0;
+                hipLaunchKernelGGL(k_hhh_trim_move, dim3(grid256(rows - t.row0)), dim3(256), 0, s, (const uint4 *)h->lanes[l].log,
+                                   t, (const uint32_t *)(nblk[l] ? h->tsc + at[l] : nullptr), nw[l].log);
+                hipLaunchKernelGGL(k_hhh_trim_heads, dim3(grid256(kept)), dim3(256), 0, s, (const uint4 *)nw[l].log, kept,
+                                   old_slots, nw[l].head);
+            }
+            hipLaunchKernelGGL(k_hhh_trim_forgot, sgrid, dim3(256), 0, s, (const uint32_t *)h->lanes[l].head,
+                               (const uint32_t *)nw[l].head, old_slots, h->tsc + nl + l);
+            GNS_HIP(hipGetLastError());
+        }
+        GNS_HIP(hipMemsetAsync(h->mark, 0xFF, old_slots * 4, s));  // GNS_ID_NONE
+        for (size_t l = 0; l < nl; l++)
+            hipLaunchKernelGGL(k_hhh_heads, sgrid, dim3(256), 0, s, (const uint32_t *)nw[l].head, old_slots, h->mark);
+        hipLaunchKernelGGL(k_hhh_trim_named, sgrid, dim3(256), 0, s, (const uint32_t *)h->mark, old_slots, h->tsc + 2 * nl);
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipMemcpyAsync(hp, h->tsc + nl, (nl + 1) * 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipStreamSynchronize(s));
+        for (size_t l = 0; l < nl; l++) {
+            forgot[l] = hp[l];
+            forgot_all += forgot[l];
+        }
+        if (!forgot_all) return GNS_OK;
+        // the index rebuilt from the keys some lane still names, into a table of their number
+        // (never a larger one: the named keys fit the table they are in)
+        const uint64_t want = std::min<uint64_t>(hist_index_slots(hp[nl]), old_slots);
+        for (size_t l = 0; l < nl; l++) {
+            GNS_TRY(dalloc_t(&nh[l], want));
+            GNS_HIP(hipMemsetAsync(nh[l], 0xFF, want * 4, s));
+        }
+        DictIds marks[1] = {{h->mark, old_slots}};
+        ctl_touched = true;
+        GNS_TRY(dict_rebuild(Dn, slots_n, marks, 1, nullptr, nullptr, 0, want, s, h->dsc, &live, &old_rec, 0, true));
+        rebuilt = true;
+        for (size_t l = 0; l < nl; l++) {
+            const uint64_t kept = h->plan.lanes[l].rows - tp.R[l] + nbase[l];
+            hipLaunchKernelGGL(k_hhh_permute, sgrid, dim3(256), 0, s, (const uint32_t *)nw[l].head, old_slots,
+                               (const uint32_t *)h->dsc.remap, nh[l]);
+            if (kept) hipLaunchKernelGGL(k_hhh_reslot, dim3(grid256(kept)), dim3(256), 0, s, nw[l].log, kept, old_slots,
+                                         (const uint32_t *)h->dsc.remap);
+        }
+        GNS_HIP(hipGetLastError());
+        GNS_HIP(hipStreamSynchronize(s));
+        return GNS_OK;
+    };
+    const int rc = run();
+    if (rc != GNS_OK) {
+        (void)hipStreamSynchronize(s);
+        if (rebuilt) dfree(Dn.rec);
+        if (ctl_touched) {  // a rebuild restarts the claim counter: back to what the old table holds
+            const uint32_t ctl[2] = {(uint32_t)h->claimed, 0u};
+            (void)hipMemcpy(h->dctl, ctl, 8, hipMemcpyHostToDevice);
+        }
+        for (size_t l = 0; l < nl; l++) { dfree(nw[l].log); dfree(nw[l].head); dfree(nh[l]); }
+        return rc;
+    }
+    // publish: the logs, the index and the head words, then the plan
+    uint64_t removed = 0;
+    for (size_t l = 0; l < nl; l++) {
+        HhLane &ln = h->lanes[l];
+        dfree(ln.log);
+        dfree(ln.head);
+        ln.log = nw[l].log;
+        ln.cap = nw[l].cap;
+        if (rebuilt) { dfree(nw[l].head); ln.head = nh[l]; }
+        else ln.head = nw[l].head;
+        ln.keys -= forgot[l];
+        removed += tp.R[l] - nbase[l];
+    }
+    if (rebuilt) {
+        dfree(old_rec);
+        h->D = Dn;
+        h->slots = slots_n;
+        h->D.cap = (uint32_t)(slots_n - slots_n / 4);
+        h->claimed = live;
+    }
+    h->pairs -= forgot_all;
+    h->plan = h->plan.trimmed(tp, nbase);
+    if (out) { out[0] = tp.t.fold ? tp.t.c - 1 : tp.t.c; out[1] = removed; out[2] = forgot_all; out[3] = h->plan.t.rows; }
+    return GNS_OK;
+}
+
+int gns_hh_hist_query(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, const uint8_t *flows, uint64_t n, gns_mem where,
+                      uint64_t *values, uint8_t *found) {
+    if (!h || (n && !(flows && values && found))) { set_error("null argument"); return GNS_E_ARG; }
+    if (where != GNS_MEM_HOST && where != GNS_MEM_DEVICE) { set_error("heavy history query: unknown memory kind"); return GNS_E_ARG; }
+    if (n == 0) return GNS_OK;
+    if (n > kHistMax) { set_error("heavy history query: %llu flows in one call", (unsigned long long)n); return GNS_E_ARG; }
+    GNS_TRY(set_device(h->device));
+    const bool dev = where == GNS_MEM_DEVICE;
+    if (dev) {
+        GNS_TRY(hhh_check_dev(flows, h->device, "flows"));
+        GNS_TRY(hhh_check_dev(values, h->device, "values"));
+        GNS_TRY(hhh_check_dev(found, h->device, "found"));
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t s = h->stream;
+    const uint32_t K = h->K;
+    const int64_t sn = h->plan.t.as_of(end_ns);
+    const int l = h->plan.lane(type);
+    const uint64_t rows = h->plan.rows_as_of(l, sn);
+    if (rows == 0) {  // no row of this type by then: nothing is live
+        if (dev) {
+            GNS_HIP(hipMemsetAsync(values, 0, n * 8, s));
+            GNS_HIP(hipMemsetAsync(found, 0, n, s));
+            GNS_HIP(hipStreamSynchronize(s));
+        } else {
+            memset(values, 0, n * 8);
+            memset(found, 0, n);
+        }
+        return GNS_OK;
+    }
+    const uint8_t *df = flows;
+    unsigned long long *dv = reinterpret_cast<unsigned long long *>(values);
+    uint8_t *dfound = found;
+    if (!dev) {  // keys in, answers out through the history's own buffers
+        if (h->stage_n < n * K) GNS_TRY(grow_buf(&h->stage, h->stage_n, n * K));
+        if (h->spl_n < n * 9) GNS_TRY(grow_buf(&h->spl, h->spl_n, n * 9));
+        GNS_TRY(hhh_copy_in(h, h->stage, flows, n * K));
+        df = h->stage;
+        dv = reinterpret_cast<unsigned long long *>(h->spl);
+        dfound = h->spl + n * 8;
+    }
+    if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+    const HhLane &ln = h->lanes[(size_t)l];
+    const bool newest = sn == (int64_t)h->plan.t.ts.size() - 1;
+    const dim3 qgrid(grid256(n));
+    hipLaunchKernelGGL(k_hhh_q_lookup, qgrid, dim3(256), 0, s, df, n, h->D, (const uint32_t *)(newest ? ln.head : nullptr),
+                       (const uint4 *)ln.log, rows, h->ids, dv, dfound);
+    if (!newest) {
+        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
+        hipLaunchKernelGGL(k_hhh_own, qgrid, dim3(256), 0, s, (const uint32_t *)h->ids, n, (uint32_t)h->slots, h->mark);
+        hipLaunchKernelGGL(k_hhh_q_scan, dim3(scan_grid(rows)), dim3(256), 0, s, (const uint4 *)ln.log, rows, (uint32_t)sn,
+                           (uint32_t)h->slots, (const uint32_t *)h->mark, (const uint32_t *)h->ids, n, dv, dfound);
+        hipLaunchKernelGGL(k_hhh_q_dup, qgrid, dim3(256), 0, s, (const uint32_t *)h->ids, n, (uint32_t)h->slots,
+                           (const uint32_t *)h->mark, dv, dfound);
+    }
+    GNS_HIP(hipGetLastError());
+    if (!dev) {
+        GNS_TRY(h->po.copy_out(values, dv, n * 8, s));
+        GNS_TRY(h->po.copy_out(found, dfound, n, s));
+    }
+    GNS_HIP(hipStreamSynchronize(s));
     return GNS_OK;
 }
 

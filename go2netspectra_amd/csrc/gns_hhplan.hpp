@@ -2,8 +2,10 @@
 // gns_hhhist.hip): one table of snapshot timestamps (HistPlan, gns_histplan.hpp) shared by the
 // type lanes, and per lane the log rows of snapshots 0..i.  A lane is created by the first
 // append that names its type; for the snapshots before it the lane holds no rows.  Which rows
-// of a lane a query as of snapshot s scans is decided here; the device holds rows only.
-// No HIP here: the header compiles in a host-only driver (tests/test_heavy_history_cpu.py).
+// of a lane a query as of snapshot s scans is decided here, and so is what a trim expires in each
+// lane and the table it leaves (trim_plan / trimmed); the device holds rows only.
+// No HIP here: the header compiles in host-only drivers (tests/test_heavy_history_cpu.py,
+// tests/test_heavy_history_trim_cpu.py).
 // Internal: not part of the C ABI.
 #pragma once
 #include <cstdint>
@@ -69,6 +71,39 @@ struct HhHistPlan {
         }
         for (Lane &l : lanes) l.end_rows.push_back(l.rows);
         t.publish(ts, total);
+    }
+
+    // A trim (gns_hh_hist_trim): HistPlan's plan over the shared timestamps -- c, d, fold, noop;
+    // its R counts the expired rows of all lanes -- and per lane the expired prefix [0, R[l]) of
+    // its log: the rows of snapshots 0..c-1, none for a lane created after snapshot c - 1.
+    struct Trim {
+        HistPlan::Trim t;
+        std::vector<uint64_t> R;  // [lanes]
+    };
+    Trim trim_plan(int64_t before, bool fold) const {
+        Trim x;
+        x.t = t.trim_plan(before, fold);
+        for (const Lane &l : lanes) x.R.push_back(x.t.c ? l.end_rows[(size_t)x.t.c - 1] : 0);
+        return x;
+    }
+    // the plan after trim x (not a noop) kept nbase[l] rows of lane l's prefix (drop: zeros).
+    // Every lane stays a lane; one that was created after the base holds zeros up to its first rows.
+    HhHistPlan trimmed(const Trim &x, const std::vector<uint64_t> &nbase) const {
+        HhHistPlan p;
+        uint64_t total = 0;
+        for (uint64_t b : nbase) total += b;
+        p.t = t.trimmed(x.t, total);
+        for (int i = 0; i < (int)kHhTypes; i++) p.lane_of[i] = lane_of[i];
+        for (size_t l = 0; l < lanes.size(); l++) {
+            const Lane &o = lanes[l];
+            Lane n;
+            n.type = o.type;
+            if (x.t.fold) n.end_rows.push_back(nbase[l]);
+            for (size_t i = (size_t)x.t.c; i < o.end_rows.size(); i++) n.end_rows.push_back(o.end_rows[i] - x.R[l] + nbase[l]);
+            n.rows = o.rows - x.R[l] + nbase[l];
+            p.lanes.push_back(n);
+        }
+        return p;
     }
 };
 

@@ -145,9 +145,12 @@ class Manager:
                 raise ValueError(f"record: task {t.name()} has no history (keep_history first)")
         return {t.name(): t.record(timestamp_ns, full=full) for t in tasks}
 
-    def keep_heavy_history(self, **kw) -> Dict[str, object]:
-        """SketchTask.keep_heavy_history for every sketch task: name -> HeavyHistory."""
-        return {t.name(): t.keep_heavy_history(**kw) for t in self.tasks() if hasattr(t, "keep_heavy_history")}
+    def keep_heavy_history(self, retain=None, drop: bool = False, **kw) -> Dict[str, object]:
+        """SketchTask.keep_heavy_history for every sketch task: name -> HeavyHistory.  ``retain=N``:
+        each record_heavy trims the task's history to the newest N snapshots, folding the older
+        ones into a base (``drop=True``: dropping them); None keeps everything."""
+        return {t.name(): t.keep_heavy_history(retain=retain, drop=drop, **kw) for t in self.tasks()
+                if hasattr(t, "keep_heavy_history")}
 
     def record_heavy(self, timestamp_ns: int) -> Dict[str, object]:
         """One interval of the sketch writers: every sketch task's lists into its heavy history

@@ -55,7 +55,7 @@ def pack_rows(flows, values, key_bytes: int) -> np.ndarray:
 
 
 class HeavyHistory:
-    """An append-only, device-resident history of one task's heavy-hitter lists.  ``append`` is
+    """A device-resident history of one task's heavy-hitter lists, append-only but for ``trim``.  ``append`` is
     one snapshot under a strictly increasing timestamp (ns, signed): a dict type -> list, at most
     one list per type.  ``heavy_hitters(type, ..., end_time=T)`` answers as of the newest
     snapshot at or before T (``None``: the newest): per flow the value of its latest row of that
@@ -203,6 +203,89 @@ class HeavyHistory:
         check(self._L.gns_hh_hist_stats(self._h, s))
         return {k: int(s[i]) for i, k in enumerate(self.STATS)}
 
+    # --- per-flow queries as of T (gns_hh_hist_query) ---
+    def _end(self, end_time):
+        if end_time is None:
+            return None, None
+        c = ct.c_int64(_int64_ns("end_time", end_time))
+        return c, ct.byref(c)
+
+    def query(self, type: int, flows, end_time=None):
+        """(values uint64 [n], found bool [n]): for each of the host ``flows`` (uint8 [n, K], or n
+        bytes objects of K bytes) the value of its latest row of ``type`` as of ``end_time``,
+        the sketch-side counterpart of trace_flow(..., end_time=T).  ``found`` is False, and the
+        value 0, for a flow without such a row: never listed, listed only later, forgotten by a
+        drop.  Duplicates are each answered; nothing is inserted."""
+        type, K = _check_type(type), self.key_bytes
+        if isinstance(flows, (list, tuple)) and flows and isinstance(flows[0], (bytes, bytearray)):
+            if any(len(f) != K for f in flows):
+                raise ValueError(f"flows must be {K} bytes each")
+            flows = np.frombuffer(b"".join(bytes(f) for f in flows), np.uint8).reshape(-1, K)
+        flows = np.ascontiguousarray(flows, np.uint8)
+        if flows.size == 0:
+            flows = flows.reshape(0, K)
+        if flows.ndim != 2 or flows.shape[1] != K:
+            raise ValueError(f"flows must be [n, {K}]")
+        keep, end = self._end(end_time)
+        n = int(flows.shape[0])
+        values, found = np.zeros(n, np.uint64), np.zeros(n, np.uint8)
+        if n:
+            check(self._L.gns_hh_hist_query(self._h, end, type, flows.ctypes.data, n, _lib.MEM_HOST,
+                                            values.ctypes.data, found.ctypes.data))
+        return values, found.astype(bool)
+
+    def query_device(self, type: int, flows, end_time=None):
+        """``query`` for a DEVICE uint8 tensor [n, K] on the history's GPU: (values, found) as
+        device tensors, int64 [n] holding the uint64 answers and bool [n]; no host copy either way."""
+        import torch
+        type, K = _check_type(type), self.key_bytes
+        if not _lib.is_device(flows):
+            raise TypeError("query_device takes a device tensor (query takes host flows)")
+        if flows.dtype != torch.uint8:
+            raise TypeError(f"device flows must be uint8, not {flows.dtype}")
+        if flows.dim() != 2 or int(flows.shape[1]) != K:
+            raise ValueError(f"flows must be [n, {K}]")
+        if flows.device.index != self.device:
+            raise ValueError(f"flows are on device {flows.device.index}, the history on {self.device}")
+        keep, end = self._end(end_time)
+        n = int(flows.shape[0])
+        values = torch.zeros((n,), dtype=torch.int64, device=flows.device)
+        found = torch.zeros((n,), dtype=torch.uint8, device=flows.device)
+        if n:
+            flows = flows.contiguous()
+            _lib.device_ready(flows, values, found)
+            check(self._L.gns_hh_hist_query(self._h, end, type, flows.data_ptr(), n, _lib.MEM_DEVICE,
+                                            values.data_ptr(), found.data_ptr()))
+        return values, found.bool()
+
+    # --- retention (gns_hh_hist_trim) ---
+    TRIM = ["snapshots_removed", "rows_removed", "pairs_forgotten", "rows"]
+
+    def trim(self, before_ns, fold: bool = False) -> dict:
+        """Expire the snapshots with timestamp < ``before_ns``.  ``fold=False`` drops them with all
+        their rows, as the reference drops a partition of its table: a (type, flow) pair listed
+        only in them is forgotten, and the key index shrinks to the keys that are left.
+        ``fold=True`` keeps of them, per type, each flow's latest row as one base snapshot under
+        the last expired timestamp: every answer at or after it is unchanged, earlier end times
+        answer empty.  A fold keeps one row per pair ever listed (the store has no tombstones)
+        and never shrinks the index; only a drop bounds both.  Returns snapshots_removed,
+        rows_removed, pairs_forgotten and the rows now held.  The kept rows move into new,
+        smaller logs: the memory is returned."""
+        if not isinstance(fold, (bool, np.bool_)) and fold not in (0, 1):
+            raise ValueError(f"fold {fold!r}: False (drop) or True (fold)")
+        before, out = _int64_ns("before_ns", before_ns), (ct.c_uint64 * 4)()
+        check(self._L.gns_hh_hist_trim(self._h, before, int(bool(fold)), out))
+        self._hint.clear()
+        return {k: int(out[i]) for i, k in enumerate(self.TRIM)}
+
+    def clear(self) -> dict:
+        """Forget every snapshot: ``trim`` past the last timestamp with ``fold=False``.  The lanes
+        stay; timestamps may start anew afterwards."""
+        ts = self.times()
+        if ts and ts[-1] == (1 << 63) - 1:
+            raise ValueError("clear: no int64 lies past the last snapshot's timestamp")
+        return self.trim(ts[-1] + 1 if ts else 0, fold=False)
+
     # --- the log as data ---
     def export_log(self):
         """(types uint8 [m], flows uint8 [m, K], values uint32 [m], written uint32 [m], times
@@ -232,7 +315,8 @@ class HeavyHistory:
 
     def restore(self, path) -> None:
         """Feed a saved log back, snapshot by snapshot, as host lists.  The history must be
-        empty (this store has no trim)."""
+        empty (``clear`` makes it so).  A trimmed history's file holds its base snapshot as an
+        ordinary one."""
         with np.load(path, allow_pickle=False) as z:
             if str(z["kind"]) != "heavy_history":
                 raise ValueError(f"{path}: not a heavy-history file")

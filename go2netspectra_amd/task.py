@@ -75,6 +75,23 @@ def _check(value: float, threshold: float, op: str) -> bool:  # task.go:246-262
     return False
 
 
+def encode_flow(text: str, fields: Sequence[str]) -> bytes:
+    """The key bytes ``decode_flow`` prints as ``text``: its inverse on a fixed field layout."""
+    parts = text.split(" ")
+    if len(parts) != len(fields):
+        raise ValueError(f"flow {text!r}: {len(fields)} fields expected ({' '.join(fields)})")
+    out = b""
+    for f, p in zip(fields, parts):
+        if f in ("SrcIP", "DstIP"):
+            ip = ipaddress.ip_address(p)
+            out += bytes(10) + b"\xff\xff" + ip.packed if ip.version == 4 else ip.packed
+        elif f in ("SrcPort", "DstPort"):
+            out += struct.pack(">H", int(p))
+        elif f == "Protocol":
+            out += bytes([int(p)])
+    return out
+
+
 class SketchTask:
     """model.Task implementation for skt_type 0 (CountMin) and 1 (SuperSpread)."""
 
@@ -169,13 +186,27 @@ class SketchTask:
         checkpoint.save(view, path)
 
     # --- the history behind QueryHeavyHitters' end_time (gns_hh_hist_*) ---
-    def keep_heavy_history(self, **kw):
+    def keep_heavy_history(self, retain=None, drop: bool = False, **kw):
         """Attach a HeavyHistory of this task's flow width (``kw``: its max_rows / max_flows) and
         a view of the sketch: ``record_heavy`` then stores an interval's lists, and
-        ``query_heavy_hitters`` answers from it.  Returns the history (the one already
-        attached, if any)."""
+        ``query_heavy_hitters`` / ``query_heavy`` answer from it.  Returns the history (the one
+        already attached, if any).
+
+        ``retain=N`` (N >= 1; None: keep everything): after each ``record_heavy`` the history is
+        trimmed down to the newest N snapshots.  ``drop=False`` folds the older ones into a base
+        snapshot (the base counts as one of the N; answers at the kept times are unchanged, and a
+        flow that left the lists keeps its last value); ``drop=True`` drops them, as the reference
+        drops a partition: the history then answers over the N newest intervals' rows alone, and
+        the key index stays bounded too."""
+        if retain is not None:
+            if isinstance(retain, bool) or int(retain) != retain or retain < 1:
+                raise ValueError(f"retain {retain!r}: a number of snapshots >= 1, or None")
+            retain = int(retain)
+        if not isinstance(drop, bool):
+            raise ValueError(f"drop {drop!r}: False (fold) or True (drop)")
         if getattr(self, "heavy_history", None) is None:
             from .heavy_history import HeavyHistory
+            self._heavy_retain, self._heavy_drop = retain, drop
             kw.setdefault("device", self.sketch.device)
             self.heavy_history = HeavyHistory(self.flow_size, **kw)
             self._heavy_view = self.sketch.view()
@@ -200,8 +231,37 @@ class SketchTask:
             view.refresh()
         rows = view.heavy_hitters_rows_device()
         if isinstance(self.sketch, CountMin):
-            return h.append(timestamp_ns, {0: rows[0], 1: rows[1]})
-        return h.append(timestamp_ns, {2: rows})
+            out = h.append(timestamp_ns, {0: rows[0], 1: rows[1]})
+        else:
+            out = h.append(timestamp_ns, {2: rows})
+        keep = getattr(self, "_heavy_retain", None)
+        if keep is not None:
+            ts = h.times()
+            if len(ts) > keep:
+                if self._heavy_drop:  # the newest keep snapshots stay
+                    h.trim(ts[-keep], fold=False)
+                else:  # all but the newest keep - 1 fold into the base
+                    h.trim(ts[-(keep - 1)] if keep > 1 else ts[-1] + 1, fold=True)
+        return out
+
+    def query_heavy(self, flows, type: int, end_time=None):
+        """What these flows read at T: per flow the value of its latest row of ``type`` with
+        Timestamp <= ``end_time`` (None: no bound) in the attached history, the sketch-side
+        counterpart of trace_flow(..., end_time=T).  ``flows``: key bytes as ``query`` takes them,
+        or the decoded strings ``query_heavy_hitters`` returns, one or a list; a uint8 [n, K]
+        array is taken too.  Returns a list of int, None for a flow without such a row."""
+        h = self._heavy("query_heavy")
+        one = isinstance(flows, (str, bytes, bytearray))
+        if one:
+            flows = [flows]
+        if isinstance(flows, (list, tuple)):
+            flows = [encode_flow(f, self.flow_fields) if isinstance(f, str) else bytes(f) for f in flows]
+            if any(len(f) != self.flow_size for f in flows):
+                raise ValueError(f"flows must be {self.flow_size} bytes each")
+            flows = np.frombuffer(b"".join(flows), np.uint8).reshape(-1, self.flow_size)
+        values, found = h.query(type, flows, end_time=end_time)
+        out = [int(v) if f else None for v, f in zip(values, found)]
+        return out[0] if one else out
 
     def query_heavy_hitters(self, type: int, limit: int, end_time=None):
         """QueryHeavyHitters (querier.go:191-248) from the attached history: per flow the value

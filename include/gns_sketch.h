@@ -922,7 +922,7 @@ int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, i
  *   SELECT Flow, argMax(Value, Timestamp) ... WHERE TaskName = ? AND Type = ? [AND Timestamp <= ?]
  *   GROUP BY Flow ORDER BY LatestValue DESC LIMIT ?
  * A gns_hh_hist is that table on the device for one task (TaskName is fixed) and one flow width
- * key_bytes (1..37): an append-only log per Type 0..255 over one key index; the types are
+ * key_bytes (1..37): a log per Type 0..255 over one key index, append-only but for gns_hh_hist_trim; the types are
  * independent tables that share the snapshot timestamps.
  *   - Snapshots 0..S-1 carry STRICTLY increasing timestamps (int64 ns, negative values are
  *     legal).  The reference's DateTime has second resolution and two snapshots within one second
@@ -972,9 +972,43 @@ int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, i
  *   - Threads: any, serialised by the history's mutex; its stream and pinned staging are its own
  *     and no query allocates or frees once warm.  The history keeps no reference to the
  *     caller's rows, handle or view after the append returns.
+ *   - gns_hh_hist_trim expires the c snapshots with timestamp < before_ns: in every lane a prefix
+ *     of the log, the rows of snapshots 0..c-1 (none for a type first appended later).  out[0] =
+ *     snapshots removed, out[1] = rows removed over all lanes, out[2] = (type, flow) pairs
+ *     forgotten, out[3] = rows left (out may be NULL).
+ *       fold = 0 (drop): the snapshots and their rows are gone, as a dropped partition of the
+ *         reference's table (PARTITION BY toYYYYMM(Timestamp), writer_clickhouse.go:25-27): every
+ *         answer at every T is what the SQL gives over the table without the rows with
+ *         Timestamp < before_ns.  A (type, flow) pair whose newest row expired is forgotten (it
+ *         counts as new when appended again), a key no type names any more leaves the index, and
+ *         the index is rebuilt to the size of what is left.  A type that loses every row keeps
+ *         its lane: it answers empty and takes later appends.
+ *       fold = 1: the expired snapshots become ONE base snapshot under the timestamp of snapshot
+ *         c - 1, holding per type the expired rows that are live as of it, written = 0.  Every
+ *         answer at T >= that timestamp is unchanged, every answer below it is empty, and no pair
+ *         and no key is forgotten.  Because the store has no tombstones a fold keeps one row per
+ *         pair ever listed: it bounds the log by (snapshots kept) x (list length) + (distinct
+ *         pairs), and it never shrinks the index.  Only drop bounds the index.
+ *     c == 0, and c == 1 under fold (the base is snapshot 0 itself), change nothing and return
+ *     GNS_OK with out = {0, 0, 0, rows}.  The kept rows move stably into a new, smaller log per
+ *     type (log order stays snapshot order) and the snapshot numbers in them lose what was
+ *     removed; the new logs, head words and index are built beside the live ones and published
+ *     last, so a trim that fails leaves every answer, gns_hh_hist_times, _stats and _export as
+ *     they were.  The old logs are freed before the call returns.  GNS_E_ARG: a null handle, a
+ *     fold other than 0 / 1.
+ *   - gns_hh_hist_query answers a batch of n flows (key_bytes each; host memory, or device memory
+ *     of the history's GPU, as `where` says of flows, values and found alike) with the value of the
+ *     LIVE row of (type, flow) as of s(T): values[i] (u64) and found[i] = 1.  A flow without a
+ *     live row -- never listed, listed only later, forgotten by a drop, a type never appended, T
+ *     before the first snapshot -- answers found = 0, value = 0 (value 0 is a legal row, hence
+ *     found).  A flow named several times is answered each time; n == 0 is legal.  The call
+ *     never inserts into the index: gns_hh_hist_stats is the same after any number of queries.
+ *     As of the newest snapshot it reads head words; as of an older one it makes one pass over
+ *     the rows of snapshots 0..s(T) of that type, the cost class of gns_hh_hist_heavy_hitters
+ *     without a limit.
  * Memory: 16 bytes per log row (key bytes live only in the index); per index slot a record plus
  * 4 bytes per type in use; 8 MB of pinned host staging.
- * Not offered: retention (trim / fold) for this store, per-flow point queries as of T, roll-ups. */
+ * Not offered: roll-ups. */
 typedef struct gns_hh_hist gns_hh_hist;
 typedef struct gns_hh_hist_params { uint32_t key_bytes; uint64_t max_rows, max_flows; int device; } gns_hh_hist_params;
 typedef struct gns_hh_list { uint32_t type; const uint8_t *rows; uint64_t n; } gns_hh_list;   /* packed [flow | u32 LE value] */
@@ -990,6 +1024,9 @@ int gns_hh_hist_times(gns_hh_hist *h, int64_t *ts, uint64_t *n_io);
 int gns_hh_hist_stats(gns_hh_hist *h, uint64_t out[8]);
 int gns_hh_hist_export(gns_hh_hist *h, uint8_t *types, uint8_t *flows, uint32_t *values, uint32_t *written,
                        uint64_t *n_io);
+int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4]);
+int gns_hh_hist_query(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, const uint8_t *flows, uint64_t n, gns_mem where,
+                      uint64_t *values, uint8_t *found);
 
 /* ------------------------------------------------------------------ */
 /* Exact spread: the device ground truth of SuperSpread                */

@@ -1453,6 +1453,44 @@ func (y *HeavyHistory) Times() ([]int64, error) {
 	return ts, err
 }
 
+// Trim expires the snapshots with timestamp < before (gns_hh_hist_trim).  Without fold they are
+// dropped with all their rows, as the reference drops a partition of heavy_hitters
+// (writer_clickhouse.go:25-27): a (Type, flow) pair listed only in them is forgotten and the key
+// index shrinks.  fold keeps of them, per Type, each flow's latest row as one base snapshot
+// under the last expired timestamp, so answers at or after it are unchanged; it keeps one row per
+// pair ever listed and never shrinks the index.  out: snapshots removed, rows removed, pairs
+// forgotten, rows held.
+func (y *HeavyHistory) Trim(before int64, fold bool) (out [4]uint64, err error) {
+	f := C.int(0)
+	if fold {
+		f = 1
+	}
+	err = lastErr(C.gns_hh_hist_trim(y.h, C.int64_t(before), f, (*C.uint64_t)(unsafe.Pointer(&out[0]))))
+	return
+}
+
+// Query answers, for each of the len(flows)/keyBytes flows, with the value of its latest row of
+// Type typ as of end (gns_hh_hist_query); found[i] is false, and the value 0, for a flow without
+// such a row.  Nothing is inserted.
+func (y *HeavyHistory) Query(end *int64, typ uint32, flows []byte) (values []uint64, found []bool, err error) {
+	if len(flows)%y.keyBytes != 0 {
+		return nil, nil, errors.New("sketchgpu: Query: flows is not a multiple of the key width")
+	}
+	n := len(flows) / y.keyBytes
+	if n == 0 {
+		return nil, nil, nil
+	}
+	values = make([]uint64, n)
+	f8 := make([]uint8, n)
+	err = lastErr(C.gns_hh_hist_query(y.h, endNs(end), C.uint32_t(typ), (*C.uint8_t)(unsafe.Pointer(&flows[0])), C.uint64_t(n),
+		C.GNS_MEM_HOST, (*C.uint64_t)(unsafe.Pointer(&values[0])), (*C.uint8_t)(unsafe.Pointer(&f8[0]))))
+	found = make([]bool, n)
+	for i, b := range f8 {
+		found[i] = b != 0
+	}
+	return
+}
+
 // Close releases the history.
 func (y *HeavyHistory) Close() { C.gns_hh_hist_destroy(y.h) }
 
