@@ -194,6 +194,20 @@ int PinnedOut::copy_out(void *dst, const void *src, size_t bytes, hipStream_t s,
     return GNS_OK;
 }
 
+int PinnedOut::copy_in(void *dst, const void *src, size_t bytes, hipStream_t s) {
+    int half = 0;
+    for (size_t off = 0; off < bytes; off += kPinChunk, half ^= 1) {
+        const size_t m = std::min(kPinChunk, bytes - off);
+        uint8_t *p = pin + (size_t)half * kPinChunk;
+        if (off >= 2 * kPinChunk) GNS_HIP(hipEventSynchronize(ev[half]));  // the half's last copy has landed
+        memcpy(p, static_cast<const uint8_t *>(src) + off, m);
+        GNS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, p, m, hipMemcpyHostToDevice, s));
+        GNS_HIP(hipEventRecord(ev[half], s));
+    }
+    GNS_HIP(hipStreamSynchronize(s));
+    return GNS_OK;
+}
+
 void PinnedOut::free_all() {
     if (pin) (void)hipHostFree(pin);
     pin = nullptr;

@@ -343,6 +343,9 @@ struct PinnedOut {
     int reserve(size_t bytes);
     // complete on return.  sw != 0: rows of sw source bytes of which the first dw go out
     int copy_out(void *dst, const void *src, size_t bytes, hipStream_t s, size_t sw = 0, size_t dw = 0);
+    // host bytes -> device through the two halves, one being filled while the other's copy runs.
+    // Complete on return (synchronizes s).
+    int copy_in(void *dst, const void *src, size_t bytes, hipStream_t s);
     void free_all();
 };
 

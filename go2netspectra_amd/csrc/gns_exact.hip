@@ -36,8 +36,8 @@
 //   HH  k_exq_hh_*     flows above a threshold, ordered, cut to a limit (gns_ex_heavy_hitters)
 //   A   k_exh_link     a view's rows appended to a history's log (gns_ex_hist_append); Q, HH
 //                      and V answer over the log as of a snapshot (gns_ex_hist_*)
-//   AR  k_exh_link_rows  host rows appended to the log (gns_ex_hist_append_rows; k_exh_own /
-//                      k_exh_dup refuse a key that occurs twice in the call)
+//   AR  k_exh_link_rows  host rows appended to the log (gns_ex_hist_append_rows;
+//                      HistIndex::check_unique refuses a key that occurs twice in the call)
 //   TR  k_exh_trim_*   expired snapshots dropped or folded into a base snapshot: the kept rows
 //                      moved into a new log, the head words remapped (gns_ex_hist_trim)
 // A Zipf batch touches a flow in many places; per-block LDS aggregation of
@@ -56,7 +56,7 @@
 
 #include "gns_common.hpp"
 #include "gns_exsrc.hpp"
-#include "gns_histplan.hpp"
+#include "gns_histindex.hpp"
 #include "gns_scan.cuh"
 #include "gns_xcd.cuh"
 
@@ -1403,10 +1403,10 @@ __global__ __launch_bounds__(256) void k_ex_init(FlowState f, uint64_t slots) {
 // History (gns_ex_hist_*): an append-only log of snapshot rows.  A log row is a view's row
 // -- record at stride RW, start, end, pkts, bytes -- with two version words: the snapshot
 // that wrote it and the snapshot that next wrote the same key (kHistOpen: none yet).  The key
-// index is a dictionary of the history's own with one head word per slot, the newest log row
-// of that key.  "The latest row of each flow as of snapshot s" is then
+// index is a dictionary of the history's own (HistIndex, gns_histindex.hpp) with one head word
+// per slot, the newest log row of that key.  "The latest row of each flow as of snapshot s" is then
 // written <= s < superseded, tested in the scans of the query plane (ExSelAsOf).
-//   A1 dict_resolve_keys  the view's key words -> index slots (growth and retry as gns_ex_merge)
+//   A1 HistIndex::resolve the view's key words -> index slots (growth and retry as gns_ex_merge)
 //   A2 k_exh_link         view row i -> log row base + i, stamped written = S; the row is
 //                         swapped into its key's head word and the row it displaced is
 //                         stamped superseded = S.  Keys are distinct within a view, so no two
@@ -1448,45 +1448,10 @@ __global__ __launch_bounds__(256) void k_exh_link(DictDev V, FlowState vf, uint6
     const uint64_t m = __ballot(isnew);  // keys new to the history: one add per wave
     if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(fresh, (uint32_t)__popcll(m));
 }
-// index growth: a key's head word follows its record to the new slot (gns_dict.hip remap)
-__global__ __launch_bounds__(256) void k_exh_permute(const uint32_t *oh, uint64_t slots, const uint32_t *remap,
-                                                     uint32_t *nh) {
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= slots) return;
-    const uint32_t t = remap[s];
-    if (t >= kDictMarked) return;
-    nh[t] = oh[s];
-}
-// the slots that hold a key of a published snapshot name themselves (dict_rebuild's mark list);
-// a slot claimed by an append that did not complete names nothing and is dropped
-__global__ __launch_bounds__(256) void k_exh_heads(const uint32_t *head, uint64_t slots, uint32_t *ids) {
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= slots) return;
-    ids[s] = head[s] != kHistOpen ? (uint32_t)s : GNS_ID_NONE;
-}
-
 // gns_ex_hist_append_rows: host rows instead of a view's.  The state words already lie in the
 // log at base + i (copied there behind the published rows); the record is the one the resolve
 // found or claimed in the index.  Two rows of one call with one key would share a head word,
-// which the link must not meet: every row names itself in its slot's owner word, and a row that
-// then reads another's name there is a duplicate (one of the equal rows wins the word, every
-// other one sees it).
-__global__ __launch_bounds__(256) void k_exh_own(const uint32_t *ids, uint64_t n, uint32_t slots, uint32_t *owner) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t id = ids[i];
-    if (id < slots) owner[id] = (uint32_t)i;
-}
-__global__ __launch_bounds__(256) void k_exh_dup(const uint32_t *ids, uint64_t n, uint32_t slots, const uint32_t *owner,
-                                                 uint32_t *dup) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    bool bad = false;
-    if (i < n) {
-        const uint32_t id = ids[i];
-        bad = id >= slots || owner[id] != (uint32_t)i;
-    }
-    if (bad) *dup = 1u;  // (every writer stores the same word)
-}
+// which the link must not meet: HistIndex::check_unique refuses the call first.
 __global__ __launch_bounds__(256) void k_exh_link_rows(DictDev I, uint64_t n, const uint32_t *ids, uint32_t *head,
                                                        uint32_t slots, ExHistLog G, uint64_t base, uint32_t S,
                                                        uint32_t *fresh) {
@@ -1922,20 +1887,10 @@ struct gns_ex_hist : ViewCore {
     uint32_t K = 0;
     HistPlan plan;             // timestamps, published rows (host)
     ExHistLog log{};           // cap rows of room
-    DictDev D{};               // the key index
-    uint64_t slots = 0, claimed = 0, keys = 0;
-    uint32_t *head = nullptr;  // [slots] newest log row of the slot's key (kHistOpen: none)
-    uint32_t *dctl = nullptr;
-    unsigned long long *full = nullptr;  // the index's dictionary-full word
-    uint32_t epoch = 0;
-    DictScratch dsc;
-    KeyResolveScratch rsc;
-    uint32_t *ids = nullptr;   // the index slots of the rows being appended
-    uint64_t ids_n = 0;
-    uint32_t *mark = nullptr;  // k_exh_heads' list during an index growth
-    uint64_t mark_n = 0;
-    uint32_t *fresh = nullptr; // keys the running append added
-    uint64_t n_index_grow = 0, n_log_grow = 0, rows_trimmed = 0;
+    HistIndex ix;              // the key index
+    uint64_t keys = 0;
+    uint32_t *head = nullptr;  // [ix.slots] newest log row of the slot's key (kHistOpen: none)
+    uint64_t n_log_grow = 0, rows_trimmed = 0;
     // as-of snapshot: V1's counts and the scan's sums, the total, the compacted rows
     uint32_t *scan = nullptr, *total = nullptr;
     uint64_t scan_n = 0;
@@ -2900,10 +2855,8 @@ void exh_free_log(ExHistLog &g) {
 void exh_free(gns_ex_hist *h) {
     exh_free_log(h->log);
     exv_free_rows(h->SD, h->sf);
-    dfree(h->D.rec); dfree(h->head); dfree(h->dctl); dfree(h->full); dfree(h->ids); dfree(h->mark); dfree(h->fresh);
-    dfree(h->scan); dfree(h->total);
-    h->dsc.free_all();
-    h->rsc.free_all();
+    h->ix.free_all();
+    dfree(h->head); dfree(h->scan); dfree(h->total);
     h->rd.free_all();
     h->destroy();
 }
@@ -2958,66 +2911,19 @@ int exh_reserve_log(gns_ex_hist *h, uint64_t need) {
     return GNS_OK;
 }
 
-// The index rebuilt into at least `want` slots.  Kept: the keys of the published snapshots
-// (a head word) and the `done` ids the running append has resolved, which are renumbered; the
-// claims of a piece that overflowed are dropped.  The head words follow their records.
-int exh_grow_index(gns_ex_hist *h, uint64_t want, uint64_t done) {
-    const uint64_t old_slots = h->slots;
-    uint64_t new_slots = old_slots * 2;
-    while (new_slots < want) new_slots *= 2;
-    if (new_slots > kDictMaxSlots) {
-        set_error("history key index cannot grow beyond 2^30 slots (%llu keys)", (unsigned long long)h->keys);
-        return GNS_E_FULL;
-    }
+// A1: ix.ids[i] = the index slot of key i (device, n keys at `stride` bytes).  A growth keeps the
+// keys of the published snapshots (a head word) and the ids resolved so far; m != 0: room for a
+// piece of m keys if every one of them is new.
+int exh_slots_of(gns_ex_hist *h, const uint8_t *keys, uint32_t stride, uint64_t n) {
     hipStream_t s = h->stream;
-    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
-    uint32_t *nh = nullptr;
-    GNS_TRY(dalloc_t(&nh, new_slots));
-    hipLaunchKernelGGL(k_exh_heads, dim3((unsigned)((old_slots + 255) / 256)), dim3(256), 0, s, h->head, old_slots,
-                       h->mark);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemsetAsync(nh, 0xFF, new_slots * 4, s);
-    if (e != hipSuccess) { dfree(nh); set_error("history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    DictIds marks[2] = {{h->mark, old_slots}, {h->ids, done}};
-    DictIds remaps[1] = {{h->ids, done}};
-    uint64_t slots = old_slots, live = 0;
-    const int rc = dict_rebuild(h->D, slots, marks, 2, nullptr, remaps, 1, new_slots, s, h->dsc, &live, nullptr);
-    if (rc != GNS_OK) { dfree(nh); return rc; }
-    hipLaunchKernelGGL(k_exh_permute, dim3((unsigned)((old_slots + 255) / 256)), dim3(256), 0, s, h->head, old_slots,
-                       h->dsc.remap, nh);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    // (the table is the new one whatever the permute did: the old head words no longer fit it)
-    dfree(h->head);
-    h->head = nh;
-    h->slots = slots;
-    h->D.cap = (uint32_t)(slots - slots / 4);
-    h->claimed = live;
-    h->n_index_grow++;
-    if (e != hipSuccess) { set_error("history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
-}
-
-// A1: h->ids[i] = the index slot of key i (device, n keys at `stride` bytes), piece by piece,
-// before anything is linked
-int exh_resolve(gns_ex_hist *h, const uint8_t *keys, uint32_t stride, uint64_t n) {
-    hipStream_t s = h->stream;
-    for (uint64_t off = 0; off < n; off += kResolvePiece) {
-        const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
-        if (h->claimed >= h->slots / 2) GNS_TRY(exh_grow_index(h, 0, off));  // keep the load <= ~1/2
-        KeyResolve r{};
-        r.keys = keys + off * stride;
-        r.stride = stride; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + off;
-        r.full_word = h->full;
-        for (;;) {
-            const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
-            if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
-            GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
-            // room for the piece if every key of it is new, at most 8 times the table per step
-            GNS_TRY(exh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->keys + off + m), 8 * h->slots), off));
+    return h->ix.resolve(keys, stride, n, 0, s, [&](uint64_t m, uint64_t done) {
+        const uint64_t want = m ? h->ix.room_for(h->keys + done + m) : 0;
+        if (h->ix.grown(want) > kDictMaxSlots) {
+            set_error("history key index cannot grow beyond 2^30 slots (%llu keys)", (unsigned long long)h->keys);
+            return (int)GNS_E_FULL;
         }
-    }
-    return GNS_OK;
+        return h->ix.grow(want, done, {&h->head}, s);
+    });
 }
 
 // V1 / V2 over the first `rows` log rows: cnt[exv_cell(block)] = the rank of the block's first
@@ -3085,29 +2991,18 @@ int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out) {
         if ((rc = make_plan(p->key, 0, &h->kp)) != GNS_OK) break;
         h->K = h->kp.K;
         if ((rc = h->init()) != GNS_OK || (rc = h->rd.init_keep()) != GNS_OK) break;
-        h->slots = hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10));
-        h->D.mask = (uint32_t)(h->slots - 1);
-        h->D.K = h->K;
-        h->D.RW = dict_record_words(h->K);
-        h->D.seed = 0x5BD1E995u;
-        h->D.cap = (uint32_t)(h->slots - h->slots / 4);
-        h->log.L = h->D;
-        h->log.L.rec = nullptr; h->log.L.ctl = nullptr; h->log.L.mask = 0; h->log.L.cap = 0;
-        h->SD = h->log.L;
-        if ((rc = dalloc_t(&h->D.rec, h->slots * h->D.RW)) || (rc = dalloc_t(&h->head, h->slots)) ||
-            (rc = dalloc_t(&h->dctl, 4)) || (rc = dalloc_t(&h->full, 1)) || (rc = dalloc_t(&h->fresh, 4)) ||
-            (rc = dalloc_t(&h->total, 4)))
-            break;
-        h->D.ctl = h->dctl;
-        if ((rc = exh_reserve_log(h, p->max_rows ? p->max_rows : (1ull << 20))) != GNS_OK) break;
-        hipStream_t s = h->stream;
-        if (hipMemsetAsync(h->D.rec, 0, h->slots * h->D.RW * 4, s) != hipSuccess ||
-            hipMemsetAsync(h->head, 0xFF, h->slots * 4, s) != hipSuccess ||
-            hipMemsetAsync(h->dctl, 0, 16, s) != hipSuccess || hipMemsetAsync(h->full, 0, 8, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
+        const uint64_t slots = hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10));
+        if ((rc = dalloc_t(&h->head, slots)) || (rc = dalloc_t(&h->total, 4))) break;
+        if (hipMemsetAsync(h->head, 0xFF, slots * 4, h->stream) != hipSuccess) {
             set_error("history create: device clear failed");
             rc = GNS_E_HIP;
+            break;
         }
+        if ((rc = h->ix.init("history", h->K, slots, h->stream)) != GNS_OK) break;  // (waits for the head words' clear too)
+        h->log.L = h->ix.D;
+        h->log.L.rec = nullptr; h->log.L.ctl = nullptr; h->log.L.mask = 0; h->log.L.cap = 0;
+        h->SD = h->log.L;
+        rc = exh_reserve_log(h, p->max_rows ? p->max_rows : (1ull << 20));
     } while (0);
     if (rc != GNS_OK) { exh_free(h); delete h; return rc; }
     *out = h;
@@ -3156,17 +3051,18 @@ int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uin
     uint64_t fresh = 0;
     if (n) {
         GNS_TRY(exh_reserve_log(h, h->plan.rows + n));
-        if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+        HistIndex &ix = h->ix;
+        if (ix.ids_n < n) GNS_TRY(grow_buf(&ix.ids, ix.ids_n, n));
         GNS_TRY(stream_wait_now(s, v->stream, "history append"));  // behind the refresh the view answers for
         // A1 (key words follow the tag)
-        GNS_TRY(exh_resolve(h, reinterpret_cast<const uint8_t *>(v->D.rec + 1), 4 * v->D.RW, n));
+        GNS_TRY(exh_slots_of(h, reinterpret_cast<const uint8_t *>(v->D.rec + 1), 4 * v->D.RW, n));
         // A2
-        GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
-        hipLaunchKernelGGL(k_exh_link, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v->D, v->f, n, h->ids, h->head,
-                           (uint32_t)h->slots, h->log, h->plan.rows, S, h->fresh);
+        GNS_HIP(hipMemsetAsync(ix.fresh, 0, 4, s));
+        hipLaunchKernelGGL(k_exh_link, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v->D, v->f, n, ix.ids, h->head,
+                           (uint32_t)ix.slots, h->log, h->plan.rows, S, ix.fresh);
         GNS_HIP(hipGetLastError());
         uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
-        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipMemcpyAsync(hp, ix.fresh, 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));  // the view's rows are read: a refresh may replace them
         fresh = *hp;
     }
@@ -3175,25 +3071,6 @@ int gns_ex_hist_append(gns_ex_hist *h, gns_ex_view *v, int64_t timestamp_ns, uin
     if (out) { out[0] = n; out[1] = fresh; }
     return GNS_OK;
 }
-
-namespace {
-// Host bytes -> device through the two halves of the history's pinned staging, one being
-// filled while the other's copy runs.  Complete on return.
-int exh_copy_in(gns_ex_hist *h, void *dst, const void *src, size_t bytes, hipStream_t s) {
-    PinnedOut &po = h->rd.po;
-    int half = 0;
-    for (size_t off = 0; off < bytes; off += kPinChunk, half ^= 1) {
-        const size_t m = std::min(kPinChunk, bytes - off);
-        uint8_t *p = po.pin + (size_t)half * kPinChunk;
-        if (off >= 2 * kPinChunk) GNS_HIP(hipEventSynchronize(po.ev[half]));  // the half's last copy has landed
-        memcpy(p, static_cast<const uint8_t *>(src) + off, m);
-        GNS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, p, m, hipMemcpyHostToDevice, s));
-        GNS_HIP(hipEventRecord(po.ev[half], s));
-    }
-    GNS_HIP(hipStreamSynchronize(s));
-    return GNS_OK;
-}
-}  // namespace
 
 int gns_ex_hist_append_rows(gns_ex_hist *h, const uint8_t *keys, const int64_t *start_ns, const int64_t *end_ns,
                             const uint64_t *pkts, const uint64_t *bytes, uint64_t n, int64_t timestamp_ns,
@@ -3223,33 +3100,31 @@ int gns_ex_hist_append_rows(gns_ex_hist *h, const uint8_t *keys, const int64_t *
     const uint64_t base = h->plan.rows;
     uint64_t fresh = 0;
     if (n) {
-        if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+        HistIndex &ix = h->ix;
+        if (ix.ids_n < n) GNS_TRY(grow_buf(&ix.ids, ix.ids_n, n));
         ExRead &rd = h->rd;
+        PinnedOut &po = rd.po;
         GNS_TRY(rd.buf(&rd.dk, rd.dk_n, n * h->K));
-        GNS_TRY(exh_copy_in(h, rd.dk, keys, n * h->K, s));
-        GNS_TRY(exh_resolve(h, rd.dk, h->K, n));
+        GNS_TRY(po.copy_in(rd.dk, keys, n * h->K, s));
+        GNS_TRY(exh_slots_of(h, rd.dk, h->K, n));
         // no two rows of the call in one index slot, decided before anything is linked
-        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
-        const dim3 grid((unsigned)((n + 255) / 256));
-        uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
-        GNS_HIP(hipMemsetAsync(h->fresh, 0, 8, s));
-        hipLaunchKernelGGL(k_exh_own, grid, dim3(256), 0, s, h->ids, n, (uint32_t)h->slots, h->mark);
-        hipLaunchKernelGGL(k_exh_dup, grid, dim3(256), 0, s, h->ids, n, (uint32_t)h->slots, h->mark, h->fresh + 1);
-        GNS_HIP(hipGetLastError());
-        GNS_HIP(hipMemcpyAsync(hp, h->fresh + 1, 4, hipMemcpyDeviceToHost, s));
+        uint32_t *hp = reinterpret_cast<uint32_t *>(po.pin);
+        GNS_HIP(hipMemsetAsync(ix.fresh, 0, 8, s));
+        GNS_TRY(ix.check_unique(ix.ids, n, ix.fresh + 1, s));
+        GNS_HIP(hipMemcpyAsync(hp, ix.fresh + 1, 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));
         if (*hp) { set_error("history append: two rows of the call have the same key"); return GNS_E_ARG; }
         // the state words go straight behind the published rows, which no query scans
         GNS_TRY(exh_reserve_log(h, base + n));
-        GNS_TRY(exh_copy_in(h, h->log.f.start + base, start_ns, n * 8, s));
-        GNS_TRY(exh_copy_in(h, h->log.f.end + base, end_ns, n * 8, s));
-        GNS_TRY(exh_copy_in(h, h->log.f.pkts + base, pkts, n * 8, s));
-        GNS_TRY(exh_copy_in(h, h->log.f.bytes + base, bytes, n * 8, s));
+        GNS_TRY(po.copy_in(h->log.f.start + base, start_ns, n * 8, s));
+        GNS_TRY(po.copy_in(h->log.f.end + base, end_ns, n * 8, s));
+        GNS_TRY(po.copy_in(h->log.f.pkts + base, pkts, n * 8, s));
+        GNS_TRY(po.copy_in(h->log.f.bytes + base, bytes, n * 8, s));
         // A2
-        hipLaunchKernelGGL(k_exh_link_rows, grid, dim3(256), 0, s, h->D, n, h->ids, h->head, (uint32_t)h->slots, h->log,
-                           base, S, h->fresh);
+        hipLaunchKernelGGL(k_exh_link_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ix.D, n, ix.ids, h->head,
+                           (uint32_t)ix.slots, h->log, base, S, ix.fresh);
         GNS_HIP(hipGetLastError());
-        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipMemcpyAsync(hp, ix.fresh, 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));
         fresh = *hp;
     }
@@ -3296,12 +3171,13 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
     if (tp.noop) return GNS_OK;
     GNS_TRY(set_device(h->device));
     hipStream_t s = h->stream;
-    const uint64_t old_slots = h->slots;
+    HistIndex &ix = h->ix;
+    const uint64_t old_slots = ix.slots;
     ExHistTrim t{};
     t.rows = h->plan.rows; t.R = tp.R; t.fold = tp.fold ? 1 : 0; t.d = tp.d; t.s_last = (uint32_t)(tp.c - 1);
     const bool ranked = tp.fold && tp.R != 0;  // prefix rows may stay
     t.row0 = ranked ? 0 : tp.R;
-    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
+    GNS_TRY(ix.reserve_mark(old_slots));
     if (ranked) {  // flag and rank the prefix: V1 / V2 as of the last expired snapshot
         ExSelAsOf sel;
         ExTable T;
@@ -3312,10 +3188,8 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
     const uint64_t kept = t.nbase + (t.rows - t.R);
     // everything new is built beside the history, which stays as it is until the end
     ExHistLog g;
-    uint32_t *newrow = nullptr, *nh = nullptr, *old_rec = nullptr;
-    DictDev Dn = h->D;
-    uint64_t slots_n = old_slots, live = h->claimed, forgot = 0;
-    bool rebuilt = false;
+    uint32_t *newrow = nullptr, *nh = nullptr;
+    uint64_t forgot = 0;
     GNS_TRY(exh_alloc_log(h, hist_row_capacity(0, kept), &g));
     auto run = [&]() -> int {
         if (ranked) GNS_TRY(dalloc_t(&newrow, tp.R));
@@ -3327,11 +3201,11 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
         }
         const dim3 sgrid((unsigned)((old_slots + 255) / 256));
         uint32_t *hp = reinterpret_cast<uint32_t *>(h->rd.po.pin);
-        GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
+        GNS_HIP(hipMemsetAsync(ix.fresh, 0, 4, s));
         hipLaunchKernelGGL(k_exh_trim_marks, sgrid, dim3(256), 0, s, (const uint32_t *)h->head, old_slots, t,
-                           (const uint32_t *)newrow, h->mark, h->fresh);
+                           (const uint32_t *)newrow, ix.mark, ix.fresh);
         GNS_HIP(hipGetLastError());
-        GNS_HIP(hipMemcpyAsync(hp, h->fresh, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipMemcpyAsync(hp, ix.fresh, 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));
         forgot = *hp;
         const uint32_t *remap = nullptr;
@@ -3339,10 +3213,8 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
             const uint64_t want = hist_index_slots(h->keys - forgot);
             GNS_TRY(dalloc_t(&nh, want));
             GNS_HIP(hipMemsetAsync(nh, 0xFF, want * 4, s));
-            DictIds marks[1] = {{h->mark, old_slots}};
-            GNS_TRY(dict_rebuild(Dn, slots_n, marks, 1, nullptr, nullptr, 0, want, s, h->dsc, &live, &old_rec, 0, true));
-            rebuilt = true;
-            remap = h->dsc.remap;
+            GNS_TRY(ix.shrink_beside(want, s));
+            remap = ix.dsc.remap;
         } else {
             GNS_TRY(dalloc_t(&nh, old_slots));
         }
@@ -3355,11 +3227,7 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
     const int rc = run();
     if (rc != GNS_OK) {
         (void)hipStreamSynchronize(s);
-        if (rebuilt) dfree(Dn.rec);
-        if (forgot) {  // a rebuild restarts the claim counter: back to what the old table holds
-            const uint32_t ctl[2] = {(uint32_t)h->claimed, 0u};
-            (void)hipMemcpy(h->dctl, ctl, 8, hipMemcpyHostToDevice);
-        }
+        ix.rollback();
         exh_free_log(g);
         dfree(newrow); dfree(nh);
         return rc;
@@ -3370,13 +3238,7 @@ int gns_ex_hist_trim(gns_ex_hist *h, int64_t before_ns, int fold, uint64_t out[4
     h->log = g;
     dfree(h->head);
     h->head = nh;
-    if (rebuilt) {
-        dfree(old_rec);
-        h->D = Dn;
-        h->slots = slots_n;
-        h->D.cap = (uint32_t)(slots_n - slots_n / 4);
-        h->claimed = live;
-    }
+    ix.commit();
     h->keys -= forgot;
     h->rows_trimmed += t.R - t.nbase;
     h->plan = h->plan.trimmed(tp, t.nbase);
@@ -3397,7 +3259,7 @@ int gns_ex_hist_stats(gns_ex_hist *h, uint64_t out[8]) {
     if (!h || !out) { set_error("null argument"); return GNS_E_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
     out[0] = h->plan.ts.size(); out[1] = h->plan.rows; out[2] = h->keys; out[3] = h->log.cap;
-    out[4] = h->slots; out[5] = h->n_index_grow; out[6] = h->n_log_grow; out[7] = h->rows_trimmed;
+    out[4] = h->ix.slots; out[5] = h->ix.n_index_grow; out[6] = h->n_log_grow; out[7] = h->rows_trimmed;
     return GNS_OK;
 }
 

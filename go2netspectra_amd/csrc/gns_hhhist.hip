@@ -4,16 +4,16 @@
 // interval's Snapshot() (internal/engine/impl/sketch/writer_clickhouse.go:86-138) and the
 // query takes, per Flow, argMax(Value, Timestamp) over the rows of one Type with
 // Timestamp <= EndTime.  Here that table lives on the device:
-//   - one key index of the history's own, a dictionary of K-byte flows (gns_dict.hip), shared
-//     by all types;
+//   - one key index of the history's own (HistIndex, gns_histindex.hpp), a dictionary of K-byte
+//     flows shared by all types;
 //   - per type a LANE: a log of 16-byte rows {index slot, value, written, superseded} and one
 //     head word per index slot, the newest log row of that (type, flow).  Key bytes live only
 //     in the index.  written / superseded are snapshot numbers as in the exact history
 //     (gns_exact.hip): a row is live as of snapshot s when written <= s < superseded.
 // The timestamp table and s(T) are the host's (gns_hhplan.hpp over gns_histplan.hpp).
-//   A1  dict_resolve_keys   packed rows [flow | u32] at stride K + 4 -> index slots, piece by
-//                           piece, with the exact history's growth-and-retry loop
-//   A1b k_hhh_own / _dup    no two rows of one list in one index slot (over the whole list)
+//   A1  HistIndex::resolve  packed rows [flow | u32] at stride K + 4 -> index slots, piece by
+//                           piece; a growth renumbers the head words and k_hhh_reslot the logs
+//   A1b ::check_unique      no two rows of one list in one index slot (over the whole list)
 //   A2  k_hhh_link          list row i -> lane row base + i, swapped into the head word; the
 //                           row it displaced is stamped superseded = S
 //   Q1  k_hhh_hist / _pick  limit != 0: a three-level radix select (11 + 11 + 10 bits) over
@@ -29,7 +29,7 @@
 //                           the new head words off it (the newest row of a slot is its open one)
 //   P1  k_hhh_q_lookup      gns_hh_hist_query: flows -> index slots (dict_lookup: no insert);
 //                           as of the newest snapshot the head word answers
-//   P2  k_hhh_own / _q_scan as of an older one: one pass over the lane's rows answers for the
+//   P2  ::own / k_hhh_q_scan as of an older one: one pass over the lane's rows answers for the
 //                           live row of every wanted slot; P3 k_hhh_q_dup copies to duplicates
 // A fold keeps one row per (type, flow) pair ever listed, because the store has no tombstones: it
 // bounds the log by snapshots x list length + distinct pairs.  Only a drop bounds the index.
@@ -42,29 +42,12 @@
 #include "gns_common.hpp"
 #include "gns_hh.hpp"
 #include "gns_hhplan.hpp"
+#include "gns_histindex.hpp"
 
 namespace gns {
 
 namespace {
 constexpr uint32_t kSelBins = 2048;  // bins of one select level (LDS: 8 KB)
-
-// ids[i] -> owner word of its slot; a row that then reads another's name is a duplicate
-__global__ __launch_bounds__(256) void k_hhh_own(const uint32_t *ids, uint64_t n, uint32_t slots, uint32_t *owner) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t id = ids[i];
-    if (id < slots) owner[id] = (uint32_t)i;
-}
-__global__ __launch_bounds__(256) void k_hhh_dup(const uint32_t *ids, uint64_t n, uint32_t slots, const uint32_t *owner,
-                                                 uint32_t *dup) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    bool bad = false;
-    if (i < n) {
-        const uint32_t id = ids[i];
-        bad = id >= slots || owner[id] != (uint32_t)i;
-    }
-    if (bad) *dup = 1u;  // (every writer stores the same word)
-}
 
 // A2.  rows: packed [flow (K) | u32 LE value] at stride K + 4 (any alignment).
 __global__ __launch_bounds__(256) void k_hhh_link(const uint8_t *rows, uint32_t K, uint64_t n, const uint32_t *ids,
@@ -89,20 +72,7 @@ __global__ __launch_bounds__(256) void k_hhh_link(const uint8_t *rows, uint32_t 
     if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(fresh, (uint32_t)__popcll(m));
 }
 
-// index growth: the slots some lane's head word names keep their record (dict_rebuild's mark
-// list), a head word follows its record (gns_dict.hip remap), and so does a log row's slot
-__global__ __launch_bounds__(256) void k_hhh_heads(const uint32_t *head, uint64_t slots, uint32_t *ids) {
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s < slots && head[s] != kHistOpen) ids[s] = (uint32_t)s;
-}
-__global__ __launch_bounds__(256) void k_hhh_permute(const uint32_t *oh, uint64_t slots, const uint32_t *remap,
-                                                     uint32_t *nh) {
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= slots) return;
-    const uint32_t t = remap[s];
-    if (t >= kDictMarked) return;
-    nh[t] = oh[s];
-}
+// index growth: a log row's slot follows its record (HistIndex::grow's remap)
 __global__ __launch_bounds__(256) void k_hhh_reslot(uint4 *log, uint64_t rows, uint64_t slots, const uint32_t *remap) {
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
@@ -204,7 +174,7 @@ __global__ __launch_bounds__(256) void k_hhh_trim_forgot(const uint32_t *oh, con
     const uint64_t m = __ballot(gone);
     if (m && __lane_id() == (uint32_t)(__ffsll((unsigned long long)m) - 1)) atomicAdd(forgot, (uint32_t)__popcll(m));
 }
-// the keys some lane still names (k_hhh_heads' list)
+// the keys some lane still names (HistIndex::mark_heads' list)
 __global__ __launch_bounds__(256) void k_hhh_trim_named(const uint32_t *ids, uint64_t slots, uint32_t *named) {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t m = __ballot(s < slots && ids[s] != GNS_ID_NONE);
@@ -231,7 +201,7 @@ __global__ __launch_bounds__(256) void k_hhh_q_lookup(const uint8_t *flows, uint
     values[i] = v;
     found[i] = f;
 }
-// P2, as of an older snapshot: every query has named itself in its slot's owner word (k_hhh_own;
+// P2, as of an older snapshot: every query has named itself in its slot's owner word (HistIndex::own;
 // the word is valid when ids[word] == slot, so nothing of index size is cleared per call); one
 // pass over the rows of snapshots 0..s answers for the live row of every wanted slot
 __global__ __launch_bounds__(256) void k_hhh_q_scan(const uint4 *log, uint64_t rows, uint32_t s, uint32_t slots,
@@ -397,21 +367,11 @@ struct gns_hh_hist : ViewCore {
     uint64_t init_rows = 0;
     HhHistPlan plan;            // timestamps, published rows per lane (host)
     std::vector<HhLane> lanes;  // as plan.lanes
-    DictDev D{};                // the key index
-    uint64_t slots = 0, claimed = 0, pairs = 0;
-    uint32_t *dctl = nullptr;
-    unsigned long long *full = nullptr;
-    uint32_t epoch = 0;
-    DictScratch dsc;
-    KeyResolveScratch rsc;
-    uint32_t *ids = nullptr;   // the index slots of the rows being appended, list after list
-    uint64_t ids_n = 0;
-    uint32_t *mark = nullptr;  // [slots] k_hhh_heads' list during an index growth, owner words of A1b
-    uint64_t mark_n = 0;
-    uint32_t *fresh = nullptr;  // [0] pairs the running append added, [1] its duplicate flag
+    HistIndex ix;               // the key index (ids: list after list; fresh[0]: pairs the running append added)
+    uint64_t pairs = 0;
     uint8_t *stage = nullptr;   // host lists staged for the append
     uint64_t stage_n = 0;
-    uint64_t n_index_grow = 0, n_log_grow = 0;
+    uint64_t n_log_grow = 0;
     uint32_t *tsc = nullptr;  // a trim's counters, block counts and scan sums
     uint64_t tsc_n = 0;
     // query side
@@ -429,10 +389,8 @@ namespace {
 void hhh_free(gns_hh_hist *h) {
     for (HhLane &l : h->lanes) { dfree(l.log); dfree(l.head); }
     h->lanes.clear();
-    dfree(h->D.rec); dfree(h->dctl); dfree(h->full); dfree(h->ids); dfree(h->mark); dfree(h->fresh); dfree(h->stage);
-    dfree(h->ctl); dfree(h->hist); dfree(h->coll); dfree(h->ordered); dfree(h->spl); dfree(h->tsc);
-    h->dsc.free_all();
-    h->rsc.free_all();
+    h->ix.free_all();
+    dfree(h->stage); dfree(h->ctl); dfree(h->hist); dfree(h->coll); dfree(h->ordered); dfree(h->spl); dfree(h->tsc);
     h->hh.free_all();
     h->po.free_all();
     h->destroy();
@@ -461,8 +419,8 @@ int hhh_lane(gns_hh_hist *h, uint32_t type, int *out) {
     int l = h->plan.lane(type);
     if (l < 0) {
         HhLane ln;
-        GNS_TRY(dalloc_t(&ln.head, h->slots));
-        if (hipMemsetAsync(ln.head, 0xFF, h->slots * 4, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+        GNS_TRY(dalloc_t(&ln.head, h->ix.slots));
+        if (hipMemsetAsync(ln.head, 0xFF, h->ix.slots * 4, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
             dfree(ln.head);
             set_error("heavy history: lane clear failed");
             return GNS_E_HIP;
@@ -498,97 +456,18 @@ int hhh_reserve_log(gns_hh_hist *h, int l, uint64_t need) {
     return GNS_OK;
 }
 
-// The index rebuilt into at least `want` slots.  Kept: the flows some lane has listed (a head
-// word) and the `done` ids the running append has resolved, which are renumbered; claims of a
-// piece that overflowed, and of appends that were rejected, are dropped.  Every lane's head
-// words and the slot column of its log follow the records.
-int hhh_grow_index(gns_hh_hist *h, uint64_t want, uint64_t done) {
-    const uint64_t old_slots = h->slots;
-    uint64_t new_slots = old_slots * 2;
-    while (new_slots < want) new_slots *= 2;
-    if (new_slots > kDictMaxSlots) {
-        set_error("heavy history key index cannot grow beyond 2^30 slots");
-        return GNS_E_FULL;
-    }
+// HistIndex::resolve's growth: every lane's head words follow the records, and so does the slot
+// column of its log.  m != 0: room for a piece of m flows if every one of them is new.
+int hhh_grow(gns_hh_hist *h, uint64_t m, uint64_t done) {
+    std::vector<uint32_t **> heads;
+    for (HhLane &ln : h->lanes) heads.push_back(&ln.head);
     hipStream_t s = h->stream;
-    if (h->mark_n < new_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, new_slots));
-    std::vector<uint32_t *> nh(h->lanes.size(), nullptr);
-    auto drop = [&]() { for (uint32_t *p : nh) dfree(p); };
-    for (size_t i = 0; i < nh.size(); i++) {
-        const int rc = dalloc_t(&nh[i], new_slots);
-        if (rc != GNS_OK) { drop(); return rc; }
-    }
-    hipError_t e = hipMemsetAsync(h->mark, 0xFF, old_slots * 4, s);  // GNS_ID_NONE
-    for (size_t i = 0; i < nh.size() && e == hipSuccess; i++) {
-        hipLaunchKernelGGL(k_hhh_heads, dim3(grid256(old_slots)), dim3(256), 0, s, h->lanes[i].head, old_slots, h->mark);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemsetAsync(nh[i], 0xFF, new_slots * 4, s);
-    }
-    if (e != hipSuccess) { drop(); set_error("heavy history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    DictIds marks[2] = {{h->mark, old_slots}, {h->ids, done}};
-    DictIds remaps[1] = {{h->ids, done}};
-    uint64_t slots = old_slots, live = 0;
-    const int rc = dict_rebuild(h->D, slots, marks, 2, nullptr, remaps, 1, new_slots, s, h->dsc, &live, nullptr);
-    if (rc != GNS_OK) { drop(); return rc; }
-    for (size_t i = 0; i < nh.size(); i++) {
-        HhLane &ln = h->lanes[i];
-        const uint64_t rows = h->plan.lanes[i].rows;
-        hipLaunchKernelGGL(k_hhh_permute, dim3(grid256(old_slots)), dim3(256), 0, s, ln.head, old_slots, h->dsc.remap, nh[i]);
-        if (rows) hipLaunchKernelGGL(k_hhh_reslot, dim3(grid256(rows)), dim3(256), 0, s, ln.log, rows, old_slots, h->dsc.remap);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    // (the table is the new one whatever the kernels did: the old head words no longer fit it)
-    for (size_t i = 0; i < nh.size(); i++) {
-        dfree(h->lanes[i].head);
-        h->lanes[i].head = nh[i];
-    }
-    h->slots = slots;
-    h->D.cap = (uint32_t)(slots - slots / 4);
-    h->claimed = live;
-    h->n_index_grow++;
-    if (e != hipSuccess) { set_error("heavy history index growth: %s", hipGetErrorString(e)); return GNS_E_HIP; }
-    return GNS_OK;
-}
-
-// A1: h->ids[at + i] = the index slot of row i's flow (device rows at stride K + 4), piece by
-// piece, before anything is linked.  `at` ids of earlier lists are renumbered by a growth.
-int hhh_resolve(gns_hh_hist *h, const uint8_t *rows, uint64_t n, uint64_t at) {
-    hipStream_t s = h->stream;
-    const uint32_t stride = h->K + 4;
-    for (uint64_t off = 0; off < n; off += kResolvePiece) {
-        const uint64_t m = std::min<uint64_t>(kResolvePiece, n - off);
-        if (h->claimed >= h->slots / 2) GNS_TRY(hhh_grow_index(h, 0, at + off));  // keep the load <= ~1/2
-        KeyResolve r{};
-        r.keys = rows + off * stride;
-        r.stride = stride; r.n = m; r.live = KEYS_ALL; r.vals = nullptr; r.ids = h->ids + at + off;
-        r.full_word = h->full;
-        for (;;) {
-            const int rc = dict_resolve_keys(h->D, h->epoch, r, h->rsc, s, &h->claimed, nullptr, 0);
-            if (rc != GNS_E_FULL) { GNS_TRY(rc); break; }
-            GNS_HIP(hipMemsetAsync(h->full, 0, sizeof(unsigned long long), s));
-            // room for the piece if every flow of it is new, at most 8 times the table per step
-            GNS_TRY(hhh_grow_index(h, std::min<uint64_t>(hist_index_slots(h->claimed + m), 8 * h->slots), at + off));
+    return h->ix.grow(m ? h->ix.room_for(h->ix.claimed + m) : 0, done, heads, s, [&](const uint32_t *remap, uint64_t old_slots) {
+        for (size_t i = 0; i < h->lanes.size(); i++) {
+            const uint64_t rows = h->plan.lanes[i].rows;
+            if (rows) hipLaunchKernelGGL(k_hhh_reslot, dim3(grid256(rows)), dim3(256), 0, s, h->lanes[i].log, rows, old_slots, remap);
         }
-    }
-    return GNS_OK;
-}
-
-// Host bytes -> device through the two halves of the pinned staging.  Complete on return.
-int hhh_copy_in(gns_hh_hist *h, void *dst, const void *src, size_t bytes) {
-    PinnedOut &po = h->po;
-    hipStream_t s = h->stream;
-    int half = 0;
-    for (size_t off = 0; off < bytes; off += kPinChunk, half ^= 1) {
-        const size_t m = std::min(kPinChunk, bytes - off);
-        uint8_t *p = po.pin + (size_t)half * kPinChunk;
-        if (off >= 2 * kPinChunk) GNS_HIP(hipEventSynchronize(po.ev[half]));  // the half's last copy has landed
-        memcpy(p, static_cast<const uint8_t *>(src) + off, m);
-        GNS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, p, m, hipMemcpyHostToDevice, s));
-        GNS_HIP(hipEventRecord(po.ev[half], s));
-    }
-    GNS_HIP(hipStreamSynchronize(s));
-    return GNS_OK;
+    });
 }
 
 // Q1-Q3 under h->mu: the list of `type` as of *end_ns in h->ordered, *n rows of it (after the
@@ -617,7 +496,7 @@ int hhh_list(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, uint64_t thre
     uint64_t got = 0;
     for (int pass = 0; pass < 2; pass++) {
         const uint64_t cap = h->coll ? h->coll_n / (K + 4) : 0;
-        hipLaunchKernelGGL(k_hhh_collect, grid, dim3(256), 0, st, ln.log, rows, s, h->D, h->coll, cap, h->ctl);
+        hipLaunchKernelGGL(k_hhh_collect, grid, dim3(256), 0, st, ln.log, rows, s, h->ix.D, h->coll, cap, h->ctl);
         GNS_HIP(hipGetLastError());
         GNS_HIP(hipMemcpyAsync(hp, h->ctl + SEL_COUNT, 4, hipMemcpyDeviceToHost, st));
         GNS_HIP(hipStreamSynchronize(st));
@@ -675,23 +554,8 @@ int gns_hh_hist_create(const gns_hh_hist_params *p, gns_hh_hist **out) {
     do {
         if ((rc = set_device(h->device)) != GNS_OK) break;
         if ((rc = h->init()) != GNS_OK || (rc = h->po.reserve(0)) != GNS_OK) break;
-        h->slots = hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10));
-        h->D.mask = (uint32_t)(h->slots - 1);
-        h->D.K = h->K;
-        h->D.RW = dict_record_words(h->K);
-        h->D.seed = 0x5BD1E995u;
-        h->D.cap = (uint32_t)(h->slots - h->slots / 4);
-        if ((rc = dalloc_t(&h->D.rec, h->slots * h->D.RW)) || (rc = dalloc_t(&h->dctl, 4)) || (rc = dalloc_t(&h->full, 1)) ||
-            (rc = dalloc_t(&h->fresh, 4)) || (rc = dalloc_t(&h->ctl, SEL_WORDS)) || (rc = dalloc_t(&h->hist, kSelBins)))
-            break;
-        h->D.ctl = h->dctl;
-        hipStream_t s = h->stream;
-        if (hipMemsetAsync(h->D.rec, 0, h->slots * h->D.RW * 4, s) != hipSuccess ||
-            hipMemsetAsync(h->dctl, 0, 16, s) != hipSuccess || hipMemsetAsync(h->full, 0, 8, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_error("heavy history create: device clear failed");
-            rc = GNS_E_HIP;
-        }
+        if ((rc = dalloc_t(&h->ctl, SEL_WORDS)) || (rc = dalloc_t(&h->hist, kSelBins))) break;
+        rc = h->ix.init("heavy history", h->K, hist_index_slots(p->max_flows ? p->max_flows : (64ull << 10)), h->stream);
     } while (0);
     if (rc != GNS_OK) { hhh_free(h); delete h; return rc; }
     *out = h;
@@ -748,14 +612,15 @@ int gns_hh_hist_append(gns_hh_hist *h, int64_t timestamp_ns, const gns_hh_list *
             GNS_TRY(hhh_lane(h, types[i], &lane[i]));
             GNS_TRY(hhh_reserve_log(h, lane[i], h->plan.lanes[(size_t)lane[i]].rows + ns[i]));
         }
-        if (h->ids_n < total) GNS_TRY(grow_buf(&h->ids, h->ids_n, total));
+        HistIndex &ix = h->ix;
+        if (ix.ids_n < total) GNS_TRY(grow_buf(&ix.ids, ix.ids_n, total));
         const uint8_t *rows[kHhTypes];
         if (where == GNS_MEM_HOST) {
             if (h->stage_n < total * W) GNS_TRY(grow_buf(&h->stage, h->stage_n, total * W));
             uint64_t at = 0;
             for (uint32_t i = 0; i < nlists; i++) {
                 rows[i] = h->stage + at * W;
-                if (ns[i]) GNS_TRY(hhh_copy_in(h, h->stage + at * W, lists[i].rows, ns[i] * W));
+                if (ns[i]) GNS_TRY(h->po.copy_in(h->stage + at * W, lists[i].rows, ns[i] * W, s));
                 at += ns[i];
             }
         } else {
@@ -764,23 +629,18 @@ int gns_hh_hist_append(gns_hh_hist *h, int64_t timestamp_ns, const gns_hh_list *
         // A1: every list, before anything is checked or linked (a growth renumbers the ids)
         uint64_t at = 0;
         for (uint32_t i = 0; i < nlists; i++) {
-            GNS_TRY(hhh_resolve(h, rows[i], ns[i], at));
+            GNS_TRY(ix.resolve(rows[i], W, ns[i], at, s, [&](uint64_t m, uint64_t done) { return hhh_grow(h, m, done); }));
             at += ns[i];
         }
         // A1b: no two rows of a list in one index slot
-        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
         uint32_t *hp = reinterpret_cast<uint32_t *>(h->po.pin);
-        GNS_HIP(hipMemsetAsync(h->fresh, 0, 8, s));
+        GNS_HIP(hipMemsetAsync(ix.fresh, 0, 8, s));
         at = 0;
         for (uint32_t i = 0; i < nlists; i++) {
-            if (ns[i] == 0) continue;
-            const dim3 grid(grid256(ns[i]));
-            hipLaunchKernelGGL(k_hhh_own, grid, dim3(256), 0, s, h->ids + at, ns[i], (uint32_t)h->slots, h->mark);
-            hipLaunchKernelGGL(k_hhh_dup, grid, dim3(256), 0, s, h->ids + at, ns[i], (uint32_t)h->slots, h->mark, h->fresh + 1);
+            if (ns[i]) GNS_TRY(ix.check_unique(ix.ids + at, ns[i], ix.fresh + 1, s));
             at += ns[i];
         }
-        GNS_HIP(hipGetLastError());
-        GNS_HIP(hipMemcpyAsync(hp, h->fresh + 1, 4, hipMemcpyDeviceToHost, s));
+        GNS_HIP(hipMemcpyAsync(hp, ix.fresh + 1, 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));
         if (*hp) { set_error("heavy history append: two rows of a list name the same flow"); return GNS_E_ARG; }
         // A2
@@ -789,11 +649,11 @@ int gns_hh_hist_append(gns_hh_hist *h, int64_t timestamp_ns, const gns_hh_list *
         for (uint32_t i = 0; i < nlists; i++) {
             if (ns[i] == 0) continue;
             HhLane &ln = h->lanes[(size_t)lane[i]];
-            GNS_HIP(hipMemsetAsync(h->fresh, 0, 4, s));
-            hipLaunchKernelGGL(k_hhh_link, dim3(grid256(ns[i])), dim3(256), 0, s, rows[i], h->K, ns[i], h->ids + at, ln.head,
-                               (uint32_t)h->slots, ln.log, ln.cap, h->plan.lanes[(size_t)lane[i]].rows, S, h->fresh);
+            GNS_HIP(hipMemsetAsync(ix.fresh, 0, 4, s));
+            hipLaunchKernelGGL(k_hhh_link, dim3(grid256(ns[i])), dim3(256), 0, s, rows[i], h->K, ns[i], ix.ids + at, ln.head,
+                               (uint32_t)ix.slots, ln.log, ln.cap, h->plan.lanes[(size_t)lane[i]].rows, S, ix.fresh);
             GNS_HIP(hipGetLastError());
-            GNS_HIP(hipMemcpyAsync(hp + 1 + i, h->fresh, 4, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipMemcpyAsync(hp + 1 + i, ix.fresh, 4, hipMemcpyDeviceToHost, s));
             at += ns[i];
         }
         GNS_HIP(hipStreamSynchronize(s));  // the caller's rows are read
@@ -871,7 +731,7 @@ int gns_hh_hist_stats(gns_hh_hist *h, uint64_t out[8]) {
     uint64_t cap = 0;
     for (const HhLane &l : h->lanes) cap += l.cap;
     out[0] = h->plan.t.ts.size(); out[1] = h->plan.t.rows; out[2] = h->pairs; out[3] = h->lanes.size();
-    out[4] = cap; out[5] = h->slots; out[6] = h->n_index_grow; out[7] = h->n_log_grow;
+    out[4] = cap; out[5] = h->ix.slots; out[6] = h->ix.n_index_grow; out[7] = h->n_log_grow;
     return GNS_OK;
 }
 
@@ -896,7 +756,7 @@ int gns_hh_hist_export(gns_hh_hist *h, uint8_t *types, uint8_t *flows, uint32_t 
             if (h->spl_n < m * (K + 8)) GNS_TRY(grow_buf(&h->spl, h->spl_n, m * (K + 8)));
             uint32_t *dv = reinterpret_cast<uint32_t *>(h->spl), *dw = dv + m;
             uint8_t *df = h->spl + m * 8;
-            hipLaunchKernelGGL(k_hhh_export, dim3(grid256(m)), dim3(256), 0, s, h->lanes[(size_t)l].log, m, h->D, df, dv, dw);
+            hipLaunchKernelGGL(k_hhh_export, dim3(grid256(m)), dim3(256), 0, s, h->lanes[(size_t)l].log, m, h->ix.D, df, dv, dw);
             GNS_HIP(hipGetLastError());
             if (flows) GNS_TRY(h->po.copy_out(flows + at * K, df, m * K, s));
             if (values) GNS_TRY(h->po.copy_out(values + at, dv, m * 4, s));
@@ -918,7 +778,8 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
     GNS_TRY(set_device(h->device));
     hipStream_t s = h->stream;
     const size_t nl = h->lanes.size();
-    const uint64_t old_slots = h->slots;
+    HistIndex &ix = h->ix;
+    const uint64_t old_slots = ix.slots;
     const uint32_t s_last = (uint32_t)(tp.t.c - 1), d = tp.t.d;
     // scratch: [0, nl) rows each lane's base keeps, [nl, 2 nl) pairs each lane forgets, [2 nl] keys
     // still named; then per ranked lane its block counts and the scan's tile sums
@@ -933,7 +794,6 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
         ranked = true;
     }
     if (h->tsc_n < words) GNS_TRY(grow_buf(&h->tsc, h->tsc_n, words));
-    if (h->mark_n < old_slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, old_slots));
     uint32_t *hp = reinterpret_cast<uint32_t *>(h->po.pin);
     GNS_HIP(hipMemsetAsync(h->tsc, 0, (2 * nl + 1) * 4, s));
     if (ranked) {  // T1 / T2 as of the last expired snapshot
@@ -953,10 +813,7 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
     std::vector<HhLane> nw(nl);
     std::vector<uint32_t *> nh(nl, nullptr);  // the head words at the rebuilt index's slots
     std::vector<uint64_t> forgot(nl, 0);
-    uint64_t forgot_all = 0, slots_n = old_slots, live = h->claimed;
-    uint32_t *old_rec = nullptr;
-    DictDev Dn = h->D;
-    bool rebuilt = false, ctl_touched = false;
+    uint64_t forgot_all = 0;
     auto run = [&]() -> int {
         const dim3 sgrid(grid256(old_slots));
         for (size_t l = 0; l < nl; l++) {
@@ -978,10 +835,10 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
                                (const uint32_t *)nw[l].head, old_slots, h->tsc + nl + l);
             GNS_HIP(hipGetLastError());
         }
-        GNS_HIP(hipMemsetAsync(h->mark, 0xFF, old_slots * 4, s));  // GNS_ID_NONE
-        for (size_t l = 0; l < nl; l++)
-            hipLaunchKernelGGL(k_hhh_heads, sgrid, dim3(256), 0, s, (const uint32_t *)nw[l].head, old_slots, h->mark);
-        hipLaunchKernelGGL(k_hhh_trim_named, sgrid, dim3(256), 0, s, (const uint32_t *)h->mark, old_slots, h->tsc + 2 * nl);
+        std::vector<const uint32_t *> heads;
+        for (const HhLane &ln : nw) heads.push_back(ln.head);
+        GNS_TRY(ix.mark_heads(heads.data(), nl, s));
+        hipLaunchKernelGGL(k_hhh_trim_named, sgrid, dim3(256), 0, s, (const uint32_t *)ix.mark, old_slots, h->tsc + 2 * nl);
         GNS_HIP(hipGetLastError());
         GNS_HIP(hipMemcpyAsync(hp, h->tsc + nl, (nl + 1) * 4, hipMemcpyDeviceToHost, s));
         GNS_HIP(hipStreamSynchronize(s));
@@ -997,16 +854,12 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
             GNS_TRY(dalloc_t(&nh[l], want));
             GNS_HIP(hipMemsetAsync(nh[l], 0xFF, want * 4, s));
         }
-        DictIds marks[1] = {{h->mark, old_slots}};
-        ctl_touched = true;
-        GNS_TRY(dict_rebuild(Dn, slots_n, marks, 1, nullptr, nullptr, 0, want, s, h->dsc, &live, &old_rec, 0, true));
-        rebuilt = true;
+        GNS_TRY(ix.shrink_beside(want, s));
         for (size_t l = 0; l < nl; l++) {
             const uint64_t kept = h->plan.lanes[l].rows - tp.R[l] + nbase[l];
-            hipLaunchKernelGGL(k_hhh_permute, sgrid, dim3(256), 0, s, (const uint32_t *)nw[l].head, old_slots,
-                               (const uint32_t *)h->dsc.remap, nh[l]);
+            ix.permute(nw[l].head, old_slots, nh[l], s);
             if (kept) hipLaunchKernelGGL(k_hhh_reslot, dim3(grid256(kept)), dim3(256), 0, s, nw[l].log, kept, old_slots,
-                                         (const uint32_t *)h->dsc.remap);
+                                         (const uint32_t *)ix.dsc.remap);
         }
         GNS_HIP(hipGetLastError());
         GNS_HIP(hipStreamSynchronize(s));
@@ -1015,11 +868,7 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
     const int rc = run();
     if (rc != GNS_OK) {
         (void)hipStreamSynchronize(s);
-        if (rebuilt) dfree(Dn.rec);
-        if (ctl_touched) {  // a rebuild restarts the claim counter: back to what the old table holds
-            const uint32_t ctl[2] = {(uint32_t)h->claimed, 0u};
-            (void)hipMemcpy(h->dctl, ctl, 8, hipMemcpyHostToDevice);
-        }
+        ix.rollback();
         for (size_t l = 0; l < nl; l++) { dfree(nw[l].log); dfree(nw[l].head); dfree(nh[l]); }
         return rc;
     }
@@ -1031,18 +880,12 @@ int gns_hh_hist_trim(gns_hh_hist *h, int64_t before_ns, int fold, uint64_t out[4
         dfree(ln.head);
         ln.log = nw[l].log;
         ln.cap = nw[l].cap;
-        if (rebuilt) { dfree(nw[l].head); ln.head = nh[l]; }
+        if (nh[l]) { dfree(nw[l].head); ln.head = nh[l]; }  // (the index was rebuilt)
         else ln.head = nw[l].head;
         ln.keys -= forgot[l];
         removed += tp.R[l] - nbase[l];
     }
-    if (rebuilt) {
-        dfree(old_rec);
-        h->D = Dn;
-        h->slots = slots_n;
-        h->D.cap = (uint32_t)(slots_n - slots_n / 4);
-        h->claimed = live;
-    }
+    ix.commit();
     h->pairs -= forgot_all;
     h->plan = h->plan.trimmed(tp, nbase);
     if (out) { out[0] = tp.t.fold ? tp.t.c - 1 : tp.t.c; out[1] = removed; out[2] = forgot_all; out[3] = h->plan.t.rows; }
@@ -1085,24 +928,24 @@ int gns_hh_hist_query(gns_hh_hist *h, const int64_t *end_ns, uint32_t type, cons
     if (!dev) {  // keys in, answers out through the history's own buffers
         if (h->stage_n < n * K) GNS_TRY(grow_buf(&h->stage, h->stage_n, n * K));
         if (h->spl_n < n * 9) GNS_TRY(grow_buf(&h->spl, h->spl_n, n * 9));
-        GNS_TRY(hhh_copy_in(h, h->stage, flows, n * K));
+        GNS_TRY(h->po.copy_in(h->stage, flows, n * K, s));
         df = h->stage;
         dv = reinterpret_cast<unsigned long long *>(h->spl);
         dfound = h->spl + n * 8;
     }
-    if (h->ids_n < n) GNS_TRY(grow_buf(&h->ids, h->ids_n, n));
+    HistIndex &ix = h->ix;
+    if (ix.ids_n < n) GNS_TRY(grow_buf(&ix.ids, ix.ids_n, n));
     const HhLane &ln = h->lanes[(size_t)l];
     const bool newest = sn == (int64_t)h->plan.t.ts.size() - 1;
     const dim3 qgrid(grid256(n));
-    hipLaunchKernelGGL(k_hhh_q_lookup, qgrid, dim3(256), 0, s, df, n, h->D, (const uint32_t *)(newest ? ln.head : nullptr),
-                       (const uint4 *)ln.log, rows, h->ids, dv, dfound);
+    hipLaunchKernelGGL(k_hhh_q_lookup, qgrid, dim3(256), 0, s, df, n, ix.D, (const uint32_t *)(newest ? ln.head : nullptr),
+                       (const uint4 *)ln.log, rows, ix.ids, dv, dfound);
     if (!newest) {
-        if (h->mark_n < h->slots) GNS_TRY(grow_buf(&h->mark, h->mark_n, h->slots));
-        hipLaunchKernelGGL(k_hhh_own, qgrid, dim3(256), 0, s, (const uint32_t *)h->ids, n, (uint32_t)h->slots, h->mark);
+        GNS_TRY(ix.own(ix.ids, n, s));
         hipLaunchKernelGGL(k_hhh_q_scan, dim3(scan_grid(rows)), dim3(256), 0, s, (const uint4 *)ln.log, rows, (uint32_t)sn,
-                           (uint32_t)h->slots, (const uint32_t *)h->mark, (const uint32_t *)h->ids, n, dv, dfound);
-        hipLaunchKernelGGL(k_hhh_q_dup, qgrid, dim3(256), 0, s, (const uint32_t *)h->ids, n, (uint32_t)h->slots,
-                           (const uint32_t *)h->mark, dv, dfound);
+                           (uint32_t)ix.slots, (const uint32_t *)ix.mark, (const uint32_t *)ix.ids, n, dv, dfound);
+        hipLaunchKernelGGL(k_hhh_q_dup, qgrid, dim3(256), 0, s, (const uint32_t *)ix.ids, n, (uint32_t)ix.slots,
+                           (const uint32_t *)ix.mark, dv, dfound);
     }
     GNS_HIP(hipGetLastError());
     if (!dev) {
