@@ -58,7 +58,7 @@ EXPORTED = [
     "gns_ex_rollup_prefix", "gns_spread_rollup_prefix", "gns_ex_aggregate_cidr", "gns_ex_view_aggregate_cidr",
     "gns_ex_hist_create", "gns_ex_hist_destroy", "gns_ex_hist_append", "gns_ex_hist_times", "gns_ex_hist_stats",
     "gns_ex_hist_aggregate", "gns_ex_hist_aggregate_cidr", "gns_ex_hist_heavy_hitters", "gns_ex_hist_snapshot",
-    "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows",
+    "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows", "gns_ex_hist_rollup",
     "gns_hh_hist_create", "gns_hh_hist_destroy", "gns_hh_hist_append", "gns_hh_hist_heavy_hitters",
     "gns_hh_hist_heavy_rows", "gns_hh_hist_times", "gns_hh_hist_stats", "gns_hh_hist_export",
     "gns_hh_hist_trim", "gns_hh_hist_query",
@@ -287,6 +287,7 @@ def load() -> ct.CDLL:
         "gns_ex_hist_trim": ([vp, ct.c_int64, i32, vp], i32),
         "gns_ex_hist_export": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "gns_ex_hist_append_rows": ([vp, vp, vp, vp, vp, vp, u64, ct.c_int64, vp], i32),
+        "gns_ex_hist_rollup": ([vp, vp, vp, vp, vp], i32),
         "gns_hh_hist_create": ([vp, vp], i32), "gns_hh_hist_destroy": ([vp], i32),
         "gns_hh_hist_append": ([vp, ct.c_int64, vp, u32, i32, vp], i32),
         "gns_hh_hist_heavy_hitters": ([vp, vp, u32, u64, u64, vp, vp, vp], i32),

@@ -1757,6 +1757,167 @@ __global__ __launch_bounds__(256) void k_exr_times(ExrRows R, uint64_t n, unsign
     if (f.last[id] == B + R.last[i]) f.end[id] = R.end[i];
 }
 
+// ---------------------------------------------------------------------------
+// History roll-up (gns_ex_hist_rollup): the rows of a history's log LIVE as of snapshot
+// s -- the rows gns_ex_hist_snapshot lists, the reference's argMax(..., Timestamp) with
+// Timestamp <= T -- projected onto another handle's key layout and merged there as the
+// reference's GROUP BY over stored rows has it (querier.go:251-372): counts add, StartTime
+// is the group's minimum and EndTime its maximum.  Log rows carry no stream positions, so
+// the stream-order rule of gns_ex_rollup has nothing to order by; min / max does not depend
+// on the order of rows inside a snapshot.  Log row r stands at stream position B + r.
+// Per piece of log rows:
+//   H1 k_exh_project  live row -> dense row {projected key, pkts, bytes, r, start, end}
+//                     (R1 with ExSelAsOf as the selection and the log as the source)
+//   R2 ex_resolve_rows on the destination
+//   H2 k_exh_seed     a slot no row has reached yet (first == ~0: k_ex_init's, or a
+//                     growth's) gets start = int64 max, end = int64 min, so that the zeros
+//                     it was created with take no part in the min / max
+//   H3 k_exh_add      counts add, first / last = min / max of the positions, start / end
+//                     = signed min / max: R3 with two more columns, and no R4
+// H2 reads first and writes start / end, H3 is the first to write first: every row of a new
+// slot sees it as new and stores the same two seeds, whichever lanes get there.
+// ---------------------------------------------------------------------------
+// grid covers log rows [r0, r1), r1 <= the rows as of sel.s; at most r1 - r0 rows are appended
+// (R.cnt zeroed by the host).  A wave none of whose rows is live loads no record.  R.first[row]
+// = the log row; R.last is not written.
+template <bool PX>
+__global__ __launch_bounds__(256) void k_exh_project(DictDev L, FlowState lf, ExSelAsOf sel, uint64_t r0, uint64_t r1,
+                                                     ExrPlan<PX> pl, ExrRows R) {
+    __shared__ uint32_t s_k[GNS_KWMAX][256];  // proj_fill_column
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint8_t *t;
+    if constexpr (PX) {
+        __shared__ uint32_t s_pw[40];  // g, fld, m4, m6 (not kernel-argument scalars: see ExrPlan)
+        if (tid < 40) s_pw[tid] = pl.w[tid];
+        __syncthreads();  // before any wave leaves
+        t = reinterpret_cast<const uint8_t *>(s_pw);
+    } else {
+        t = pl.t;
+    }
+    const uint64_t r = r0 + (uint64_t)blockIdx.x * 256 + tid;
+    bool seen = false, live = false;
+    if (r < r1) sel.test(r, seen, live);
+    const uint64_t m = __ballot(live);
+    if (m == 0) return;
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(R.cnt, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    if (!live) return;
+    const uint64_t row = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    uint32_t w[12];
+    load_record(L, (uint32_t)r, w);
+    proj_fill_column(s_k, tid, w);
+    uint32_t v4 = 0;  // bit f: IP field f of this flow is IPv4
+    if constexpr (PX) {
+#pragma unroll
+        for (int f = 0; f < 2; f++)
+            if (pl.ipoff[f] != 0xFFu) v4 |= (px_is_v4(s_k, tid, pl.ipoff[f]) ? 1u : 0u) << f;
+    }
+#pragma unroll
+    for (int i = 0; i < GNS_KWMAX; i++) {
+        if ((uint32_t)i >= pl.KW) break;  // uniform
+        R.keys[row * pl.KW + i] = proj_word<PX>(s_k, tid, t, v4, pl.K, i);
+    }
+    R.pkts[row] = lf.pkts[r]; R.bytes[row] = lf.bytes[r]; R.first[row] = r;
+    R.start[row] = lf.start[r]; R.end[row] = lf.end[r];
+}
+
+__global__ __launch_bounds__(256) void k_exh_seed(const uint32_t *ids, uint64_t n, FlowState f) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    if (id == GNS_ID_NONE) return;
+    if (f.first[id] == ~0ull) { f.start[id] = INT64_MAX; f.end[id] = INT64_MIN; }
+}
+
+// H3's workgroup table: R3's, and the two time columns as unsigned words with the sign bit
+// flipped (kQSign, as the query plane reduces them), which keeps the signed order under the
+// unsigned wave reductions and LDS atomics.  They leave the CU as signed 64-bit atomics on the
+// raw words of the table.  ~26 KB.
+struct ExhLds {
+    uint32_t id[kExrTab];
+    unsigned long long pk[kExrTab], by[kExrTab], fi[kExrTab], la[kExrTab], st[kExrTab], en[kExrTab];
+};
+
+struct ExhRow {
+    unsigned long long pk, by, fi, la, st, en;  // st / en: sign-flipped
+};
+
+__device__ __forceinline__ void exh_global(const FlowState &f, uint32_t id, const ExhRow &v) {
+    atomicAdd(&f.pkts[id], v.pk);
+    atomicAdd(&f.bytes[id], v.by);
+    atomicMin(&f.first[id], v.fi);
+    atomicMax(&f.last[id], v.la);
+    atomicMin(&f.start[id], (long long)(v.st ^ kQSign));
+    atomicMax(&f.end[id], (long long)(v.en ^ kQSign));
+}
+
+__device__ __forceinline__ void exh_merge(ExhLds &t, const FlowState &f, uint32_t id, const ExhRow &v) {
+    uint32_t h = (id * 0x9E3779B1u) >> (32 - kExrTabBits);
+    for (int p = 0; p < 4; p++) {
+        const uint32_t old = atomicCAS(&t.id[h], GNS_ID_NONE, id);
+        if (old == GNS_ID_NONE || old == id) {
+            atomicAdd(&t.pk[h], v.pk);
+            atomicAdd(&t.by[h], v.by);
+            atomicMin(&t.fi[h], v.fi);
+            atomicMax(&t.la[h], v.la);
+            atomicMin(&t.st[h], v.st);
+            atomicMax(&t.en[h], v.en);
+            return;
+        }
+        h = (h + 1u) & (kExrTab - 1u);
+    }
+    exh_global(f, id, v);
+}
+
+// row i stands at stream position B + R.first[i]; the stored `last` word is one past it, as
+// everywhere (k_ex_merge_add)
+__global__ __launch_bounds__(256) void k_exh_add(ExrRows R, uint64_t n, unsigned long long B, FlowState f) {
+    __shared__ ExhLds t;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t i = tid; i < kExrTab; i += 256) {
+        t.id[i] = GNS_ID_NONE; t.pk[i] = 0; t.by[i] = 0; t.fi[i] = ~0ull; t.la[i] = 0; t.st[i] = ~0ull; t.en[i] = 0;
+    }
+    __syncthreads();
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < n; i0 += (uint64_t)gridDim.x * 256) {  // block-uniform
+        const uint64_t i = i0 + tid;
+        uint32_t id = GNS_ID_NONE;
+        ExhRow v{0, 0, ~0ull, 0, ~0ull, 0};
+        if (i < n) id = R.ids[i];
+        bool pending = id != GNS_ID_NONE;
+        if (pending) {
+            v.pk = R.pkts[i]; v.by = R.bytes[i]; v.fi = B + R.first[i]; v.la = v.fi + 1;
+            v.st = (unsigned long long)R.start[i] ^ kQSign; v.en = (unsigned long long)R.end[i] ^ kQSign;
+        }
+        uint64_t todo = __ballot(pending);
+        for (int round = 0; round < kExrPeel && todo; round++) {  // wave-uniform
+            const int lead = __ffsll((unsigned long long)todo) - 1;
+            const uint32_t lid = (uint32_t)__shfl((int)id, lead);
+            const bool in = pending && id == lid;
+            const uint64_t same = __ballot(in);
+            todo &= ~same;
+            if (__popcll(same) < 4) continue;  // these lanes merge their own rows below
+            ExhRow w;
+            w.pk = __ockl_wfred_add_u64(in ? v.pk : 0ull);
+            w.by = __ockl_wfred_add_u64(in ? v.by : 0ull);
+            w.fi = __ockl_wfred_min_u64(in ? v.fi : ~0ull);
+            w.la = __ockl_wfred_max_u64(in ? v.la : 0ull);
+            w.st = __ockl_wfred_min_u64(in ? v.st : ~0ull);
+            w.en = __ockl_wfred_max_u64(in ? v.en : 0ull);
+            if ((int)lane == lead) exh_merge(t, f, lid, w);
+            pending = pending && !in;
+        }
+        if (pending) exh_merge(t, f, id, v);
+    }
+    __syncthreads();
+    for (uint32_t h = tid; h < kExrTab; h += 256) {
+        const uint32_t id = t.id[h];
+        if (id == GNS_ID_NONE) continue;
+        exh_global(f, id, ExhRow{t.pk[h], t.by[h], t.fi[h], t.la[h], t.st[h], t.en[h]});
+    }
+}
+
 }  // namespace gns
 
 using namespace gns;
@@ -3392,6 +3553,28 @@ void exr_free(ExrRows &R) {
     R = ExrRows{};
 }
 
+// The projection plan from layout `from` onto layout `to`: *pl (px == nullptr) or *pp is filled.
+// GNS_E_ARG names the first field of `to` that `from` lacks.
+int exr_plans(const KeyPlanN &from, const KeyPlanN &to, const gns_prefix *px, const char *what, ExrPlan<false> *pl,
+              ExrPlan<true> *pp) {
+    pl->K = pp->K = to.K;
+    pl->KW = pp->KW = (to.K + 3) / 4;
+    int miss;
+    if (px) {
+        RollRow row;
+        memset(pp->ipoff, 0xFF, sizeof(pp->ipoff));
+        miss = roll_tables(from.src, from.K, to.src, to.K, px, false, &row, pp->ipoff);
+        memcpy(pp->t, &row, sizeof(pp->t));
+    } else {
+        miss = roll_gather(from.src, from.K, to.src, to.K, pl->t);
+    }
+    if (miss >= 0) {
+        set_error("%s: key field %s is not part of the source's layout", what, tuple_field_name(to.src[miss]));
+        return GNS_E_ARG;
+    }
+    return GNS_OK;
+}
+
 // gns_ex_rollup (px == nullptr) and gns_ex_rollup_prefix behind their argument checks
 static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t out[2]) {
     if (dst == src) { set_error("rollup: dst and src are the same handle"); return GNS_E_ARG; }
@@ -3401,21 +3584,7 @@ static int exr_rollup(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_t o
     }
     ExrPlan<false> pl{};  // the one the call takes is filled
     ExrPlan<true> pp{};
-    pl.K = pp.K = dst->kp.K;
-    pl.KW = pp.KW = (dst->kp.K + 3) / 4;
-    int miss;
-    if (px) {
-        RollRow row;
-        memset(pp.ipoff, 0xFF, sizeof(pp.ipoff));
-        miss = roll_tables(src->kp.src, src->kp.K, dst->kp.src, dst->kp.K, px, false, &row, pp.ipoff);
-        memcpy(pp.t, &row, sizeof(pp.t));
-    } else {
-        miss = roll_gather(src->kp.src, src->kp.K, dst->kp.src, dst->kp.K, pl.t);
-    }
-    if (miss >= 0) {
-        set_error("rollup: key field %s is not part of the source's layout", tuple_field_name(dst->kp.src[miss]));
-        return GNS_E_ARG;
-    }
+    GNS_TRY(exr_plans(src->kp, dst->kp, px, "rollup", &pl, &pp));
     GNS_TRY(set_device(dst->device));
     const uint64_t piece = std::min<uint64_t>(test_piece("GNS_EX_ROLLUP_PIECE", kResolvePiece), src->slots);
     if (out) out[0] = out[1] = 0;
@@ -3478,6 +3647,79 @@ int gns_ex_rollup_prefix(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_
     if (!dst || !src) { set_error("null argument"); return GNS_E_ARG; }
     GNS_TRY(px_check_prefix(px, "rollup"));
     return exr_rollup(dst, src, px, out);
+}
+
+int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const gns_prefix *px, uint64_t out[2]) {
+    if (!dst || !h) { set_error("null argument"); return GNS_E_ARG; }
+    if (px) GNS_TRY(px_check_prefix(px, "history rollup"));
+    if (dst->device != h->device) {
+        set_error("history rollup: dst is on device %d, the history on device %d", dst->device, h->device);
+        return GNS_E_ARG;
+    }
+    ExrPlan<false> pl{};
+    ExrPlan<true> pp{};
+    GNS_TRY(exr_plans(h->kp, dst->kp, px, "history rollup", &pl, &pp));
+    GNS_TRY(set_device(dst->device));
+    if (out) out[0] = out[1] = 0;
+    // a reader call on the history: held until dst's stream has drained, so no trim frees the
+    // log under the kernels and an append waits
+    std::lock_guard<std::mutex> lk(h->mu);
+    ExSelAsOf sel;
+    ExTable T;
+    (void)exh_as_of(h, end_ns, &sel, &T);
+    const uint64_t rows = T.rows;
+    if (rows == 0) return GNS_OK;  // no snapshot at or before the time (or none with rows): an empty source
+    const uint64_t piece = std::min<uint64_t>(test_piece("GNS_EX_ROLLUP_PIECE", kResolvePiece), rows);
+    hipStream_t s = dst->stream;
+    ExrRows R{};
+    KeyResolveScratch sc;
+    uint64_t projected = 0, added = 0;
+    bool wrote = false;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = dalloc_t(&R.keys, piece * pl.KW)) || (rc = dalloc_t(&R.ids, piece)) || (rc = dalloc_t(&R.cnt, 4)) ||
+            (rc = dalloc_t(&R.pkts, piece)) || (rc = dalloc_t(&R.bytes, piece)) || (rc = dalloc_t(&R.first, piece)) ||
+            (rc = dalloc_t(&R.start, piece)) || (rc = dalloc_t(&R.end, piece)))
+            return rc;
+        GNS_TRY(stream_wait_now(s, h->stream, "history rollup"));  // after the history's pending work
+        const unsigned long long B = dst->pkt + dst->merged;  // log row r stands at position B + r
+        for (uint64_t r0 = 0; r0 < rows; r0 += piece) {
+            const uint64_t r1 = std::min<uint64_t>(r0 + piece, rows);
+            GNS_HIP(hipMemsetAsync(R.cnt, 0, 4, s));
+            const dim3 grid((unsigned)((r1 - r0 + 255) / 256));
+            if (px) hipLaunchKernelGGL(k_exh_project<true>, grid, dim3(256), 0, s, T.D, T.f, sel, r0, r1, pp, R);
+            else hipLaunchKernelGGL(k_exh_project<false>, grid, dim3(256), 0, s, T.D, T.f, sel, r0, r1, pl, R);
+            GNS_HIP(hipGetLastError());
+            GNS_HIP(hipMemcpyAsync(dst->h_pin, R.cnt, 4, hipMemcpyDeviceToHost, s));
+            GNS_HIP(hipStreamSynchronize(s));
+            const uint64_t m = std::min<uint64_t>(dst->h_pin[0], r1 - r0);
+            if (m == 0) continue;
+            GNS_TRY(ex_resolve_rows(dst, reinterpret_cast<const uint8_t *>(R.keys), 4 * pl.KW, m, R.pkts, R.ids, sc, &added));
+            wrote = true;
+            hipLaunchKernelGGL(k_exh_seed, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)R.ids, m,
+                               dst->f);
+            hipLaunchKernelGGL(k_exh_add, dim3((unsigned)std::min<uint64_t>((m + 255) / 256, 1024)), dim3(256), 0, s, R, m,
+                               B, dst->f);
+            GNS_HIP(hipGetLastError());
+            projected += m;
+        }
+        return GNS_OK;
+    };
+    int rc = run();
+    if (rc == GNS_OK || wrote) {
+        // the positions handed out are spent, whatever happened after the first piece
+        dst->merged += rows;
+        const int rc2 = ex_hot_clear(dst);  // the next batch re-picks the designated flows
+        if (rc == GNS_OK) rc = rc2;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == GNS_OK) {
+        set_error("history rollup: stream synchronize failed");
+        rc = GNS_E_HIP;
+    }
+    exr_free(R);
+    sc.free_all();
+    if (rc == GNS_OK && out) { out[0] = projected; out[1] = added; }
+    return rc;
 }
 
 int gns_ex_reset(gns_ex *ex) {

@@ -651,6 +651,68 @@ class ExactHistory:
         log order (snapshot, then the view's row order)."""
         return _snapshot_arrays(self._bind("snapshot", end_time), self._h, self.key_bytes, retry=True)
 
+    # --- the table as of end_time, re-keyed on the device (gns_ex_hist_rollup) ---
+    def rollup(self, key_fields: Sequence[str], prefix=None, end_time=None, **kw) -> "ExactAggregator":
+        """A new aggregator on the history's device keyed on ``key_fields`` (fields of the
+        history's layout, in any order) and filled by ``rollup_from_history(self, end_time,
+        prefix)``: "bytes per source /24 as of T" without the rows leaving the GPU.  Empty when
+        no snapshot lies at or before ``end_time``.  ``kw`` as ExactAggregator's constructor."""
+        rollup_plan(self.key_fields, key_fields)
+        if prefix is not None:
+            make_prefix(prefix)
+        _end_ptr(end_time)
+        kw.setdefault("device", self.device)
+        dst = ExactAggregator(key_fields, **kw)
+        try:
+            dst.rollup_from_history(self, end_time=end_time, prefix=prefix)
+        except Exception:
+            dst.close()
+            raise
+        return dst
+
+    def table(self, end_time=None, **kw) -> "ExactAggregator":
+        """The table as of ``end_time`` as a live handle of the history's own layout: the rows of
+        ``snapshot_arrays(end_time)``, ready for rollup / spread / views / queries / merge."""
+        return self.rollup(self.key_fields, end_time=end_time, **kw)
+
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], flow_prefix=None, elem_prefix=None,
+               end_time=None, **kw):
+        """ExactAggregator.spread of the table as of ``end_time``: through ``table(end_time)``,
+        which is closed again (the log is not projected into a spread table directly)."""
+        spread_rollup_plan(self.key_fields, flow_fields, elem_fields)
+        for p in (flow_prefix, elem_prefix):
+            if p is not None:
+                make_prefix(p)
+        tab = self.table(end_time=end_time)
+        try:
+            return tab.spread(flow_fields, elem_fields, flow_prefix=flow_prefix, elem_prefix=elem_prefix, **kw)
+        finally:
+            tab.close()
+
+    def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int, end_time=None):
+        """ExactAggregator.hierarchical_heavy_hitters of the table as of ``end_time``.  The finest
+        level is rolled straight from the history, each coarser level from the one before it
+        (``ExactAggregator.rollup``); only counts are read, so the chain is exact."""
+        if field not in ("SrcIP", "DstIP"):
+            raise ValueError(f"hierarchical heavy hitters: {field!r} is not an IP field")
+        levels = check_levels(levels)
+        if threshold < 1:
+            raise ValueError("hierarchical heavy hitters: threshold must be at least 1")
+        _end_ptr(end_time)
+        lists, made, cur = [], [], None
+        try:
+            for lv in levels:
+                if cur is None:
+                    cur = self.rollup([field], prefix={field: lv}, end_time=end_time)
+                else:
+                    cur = cur.rollup([field], prefix={field: lv})
+                made.append(cur)
+                lists.append(cur.heavy_hitters(metric, threshold))
+        finally:
+            for a in made:
+                a.close()
+        return discount_heavy_prefixes(lists, levels, threshold)
+
     # --- retention and the log as data (gns_ex_hist_trim / _export / _append_rows) ---
     TRIM = ["snapshots_removed", "rows_released", "keys_forgotten", "rows"]
 
@@ -882,6 +944,28 @@ class ExactAggregator:
             check(self._L.gns_ex_rollup_prefix(self._h, src._h, ct.byref(px), out))
         return int(out[0]), int(out[1])
 
+    def rollup_from_history(self, hist: "ExactHistory", end_time=None, prefix=None):
+        """gns_ex_hist_rollup: re-key the table ``hist`` holds as of ``end_time`` -- each flow's
+        latest row stored by then, the rows ``hist.snapshot_arrays(end_time)`` lists -- onto this
+        handle's layout, on the device.  The reference's GROUP BY over stored rows: the flows that
+        share one projected key enter with summed counts (u64 wrap; a group whose packets sum to
+        0 is no flow), the smallest start and the largest end (signed) -- not ``rollup_from``'s
+        stream-order rule, log rows have no stream positions.  A key this handle already holds
+        adds its counts and keeps the smaller start and the larger end.  ``prefix`` as
+        ``rollup_from``'s.  hist is only read.  Returns (rows of hist projected, flows new in
+        this handle); (0, 0) when no snapshot lies at or before ``end_time``."""
+        if not isinstance(hist, ExactHistory):
+            raise TypeError("rollup_from_history takes an ExactHistory")
+        rollup_plan(hist.key_fields, self.key_fields)
+        px = make_prefix(prefix) if prefix is not None else None
+        keep, ptr = _end_ptr(end_time)
+        if hist.device != self.device:
+            raise ValueError(f"rollup_from_history: this handle is on device {self.device}, "
+                             f"the history on device {hist.device}")
+        out = (ct.c_uint64 * 2)()
+        check(self._L.gns_ex_hist_rollup(self._h, hist._h, ptr, ct.byref(px) if px is not None else None, out))
+        return int(out[0]), int(out[1])
+
     def rollup(self, key_fields: Sequence[str], prefix=None, **kw) -> "ExactAggregator":
         """A new aggregator on the same device keyed on ``key_fields`` (fields of this handle's
         layout, in any order) and filled by ``rollup_from(self, prefix)``; ``kw`` as the
@@ -1075,20 +1159,33 @@ class ExactTask:
         another thread while the task keeps ingesting."""
         return self.snapshot(view.snapshot_arrays())
 
-    def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, prefix=None, **kw) -> "ExactTask":
+    def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, prefix=None, end_time=None,
+               **kw) -> "ExactTask":
         """A full task keyed on ``key_fields`` (fields of this task's key, in any order) holding
         this task's flows re-keyed on the device (ExactAggregator.rollup): what a task configured
         with that key and fed the same packets -- their addresses masked by ``prefix``, when one is
-        given -- holds.  It takes packets, queries, views and checkpoints like any other task."""
-        return ExactTask(name, key_fields, num_shards, agg=self.agg.rollup(key_fields, prefix=prefix, **kw))
+        given -- holds.  It takes packets, queries, views and checkpoints like any other task.
+        ``end_time``: the table as of that time, from the attached history
+        (ExactHistory.rollup; ValueError when none is attached) instead of the live one."""
+        src = self.agg if end_time is None else self._as_of(end_time)
+        extra = {} if end_time is None else {"end_time": end_time}
+        return ExactTask(name, key_fields, num_shards, agg=src.rollup(key_fields, prefix=prefix, **extra, **kw))
 
-    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], flow_prefix=None, elem_prefix=None, **kw):
+    def spread(self, flow_fields: Sequence[str], elem_fields: Sequence[str], flow_prefix=None, elem_prefix=None,
+               end_time=None, **kw):
         """The exact spread table of this task's flows (ExactAggregator.spread): SuperSpread's
-        ground truth for those layouts without a spread engine on the ingest path."""
+        ground truth for those layouts without a spread engine on the ingest path.  ``end_time``:
+        of the table as of that time, from the attached history (ExactHistory.spread)."""
+        if end_time is not None:
+            return self._as_of(end_time).spread(flow_fields, elem_fields, flow_prefix=flow_prefix,
+                                                elem_prefix=elem_prefix, end_time=end_time, **kw)
         return self.agg.spread(flow_fields, elem_fields, flow_prefix=flow_prefix, elem_prefix=elem_prefix, **kw)
 
-    def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int):
-        """ExactAggregator.hierarchical_heavy_hitters of this task's table."""
+    def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int, end_time=None):
+        """ExactAggregator.hierarchical_heavy_hitters of this task's table, or with ``end_time``
+        of the table as of that time (ExactHistory.hierarchical_heavy_hitters)."""
+        if end_time is not None:
+            return self._as_of(end_time).hierarchical_heavy_hitters(field, levels, metric, threshold, end_time=end_time)
         return self.agg.hierarchical_heavy_hitters(field, levels, metric, threshold)
 
     def reset(self) -> None:

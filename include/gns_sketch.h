@@ -889,9 +889,43 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
  * the old one (blocks of one launch would otherwise read rows that others had overwritten):
  * its peak is the old log plus the new, plus 4 bytes per expired row under fold and a second
  * index while keys are forgotten; the old log is freed when the trim returns.
- * gns_ex_hist_append_rows stages the call's key rows on the device.  Not offered: roll-ups
- * of a history.  (The sketch tasks' heavy-hitter lists have a history of their own:
- * gns_hh_hist_*, below.) */
+ * gns_ex_hist_append_rows stages the call's key rows on the device.  (The sketch tasks'
+ * heavy-hitter lists have a history of their own: gns_hh_hist_*, below.)
+ *
+ * gns_ex_hist_rollup: the table as of end_ns re-keyed into dst, on the device -- the GROUP BY
+ * the reference would run over its stored rows (querier.go:251-372).  The source is the LIVE
+ * rows as of s(T), the rows gns_ex_hist_snapshot lists (none when no snapshot lies at or
+ * before *end_ns: GNS_OK, nothing moves); each is projected onto dst's layout, under px
+ * masked to a prefix, and merged into dst group by group:
+ *   - pkts / bytes: the sums over the group (u64 wrap).  A group whose packet sum wraps to
+ *     exactly 0 is not a flow, as in gns_ex_merge and gns_ex_rollup.
+ *   - start = min(StartTime), end = max(EndTime), both signed.  NOT the stream-order rule of
+ *     gns_ex_rollup: log rows carry no stream positions, and min / max is what TraceFlow and
+ *     AggregateFlows compute over stored rows, whatever the order of rows inside a snapshot.
+ *   - A key already in dst: counts add, start becomes the smaller and end the larger of the
+ *     two.  Two shards' histories rolled into one dst are their union, in either order.
+ *   - Positions: log row r enters dst at stream position B + r, B = dst's stream end at the
+ *     call; a group's first / last are the min / max of those, and dst's position advances
+ *     by the rows as of s(T).  As after gns_ex_rollup, later inserts come after every rolled-up
+ *     flow, a view cursor taken before the call selects exactly the groups, and dst is a full
+ *     handle: a source for gns_ex_rollup[_prefix] and gns_spread_rollup, views, queries, merge.
+ *   - Limit: a further gns_ex_rollup of such a table applies THAT call's stream-order rule
+ *     over these positions, so a chain keeps counts exact but keeps min / max times only for
+ *     timestamps monotone in the log.  Roll each level from the history when the times matter.
+ *   - Layouts as gns_ex_rollup: dst's fields may be fewer than the history's, equal to them, a
+ *     permutation of them, or repeated.  Prefixes as gns_ex_rollup_prefix (px == NULL: unmasked):
+ *     the class test runs on the unmasked bytes, a prefix for a field dst lacks is ignored.
+ *   - out (may be NULL): out[0] = live rows projected, out[1] = flows new in dst.
+ *   - GNS_E_ARG with dst untouched, checked before any device call: a null handle, a dst field
+ *     outside the history's layout (named in the error text), different devices, a prefix out
+ *     of range.
+ *   - Calling rules: a reader call on the history -- its mutex is held until dst's stream has
+ *     drained, so a concurrent trim cannot free the log under the kernels and a concurrent
+ *     append waits -- and an ingest-side call on dst.  The device work runs on dst's stream,
+ *     ordered after the history's, in pieces of 2^20 log rows.  An error after the first piece
+ *     leaves the pieces merged so far; the positions are spent.
+ * Not offered: a spread table straight from the log (go through a same-layout roll-up and
+ * gns_spread_rollup), a delta roll-up between two times. */
 typedef struct gns_ex_hist gns_ex_hist;
 typedef struct gns_ex_hist_params { gns_layout key; uint64_t max_rows, max_flows; int device; } gns_ex_hist_params;
 int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out);
@@ -911,6 +945,7 @@ int gns_ex_hist_heavy_hitters(gns_ex_hist *h, const int64_t *end_ns, int metric,
                               uint8_t *keys, uint64_t *values, uint64_t *n_io);
 int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, int64_t *start_ns, int64_t *end_out_ns,
                          uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
+int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const gns_prefix *px, uint64_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Heavy-hitter history: QueryHeavyHitters' EndTime for the sketches   */
