@@ -9,9 +9,9 @@ behind the C ABI in include/gns_sketch.h (libgns_sketch.so).
 from . import checkpoint
 from ._lib import GnsError, build, load
 from .config import Config, ExactTaskDef, SketchTaskDef, load_config, parse_config
-from .exact import (ExactAggregator, ExactHistory, ExactTask, ExactView, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
+from .exact import (Change, ExactAggregator, ExactHistory, ExactTask, ExactView, FlowLifecycle, HeavyHitter, NewExact, SnapshotData, Summary,
                     TaskSummary, apply_delta, discount_heavy_prefixes, make_filter, make_prefix, mask_keys, mask_prefix,
-                    merge_summaries, prefix_plan, rollup_plan, spread_rollup_plan, to16_to_encodeflow)
+                    merge_summaries, prefix_plan, rollup_plan, signed, spread_rollup_plan, to16_to_encodeflow)
 from .factory import Manager, TaskGroup, create, register_aggregator
 from .heavy_history import HeavyHistory
 from .packets import (CompactBatch, HeaderBatch, PacketBatch, SyntheticTraffic, compact_headers, ip_slot, read_pcap,
@@ -25,7 +25,7 @@ __all__ = [
     "TaskGroup", "create", "register_aggregator", "HeaderBatch", "PacketBatch", "SyntheticTraffic",
     "ip_slot", "read_pcap", "read_pcap_compact", "compact_headers", "write_pcap", "write_pcapgen", "write_pcapng", "CountMin", "CountMinView", "HeavyCount", "HeavyRecord", "HeavySize",
     "SuperSpread", "New", "SketchTask", "decode_flow", "encode_flow", "ExactTaskDef", "ExactAggregator", "ExactTask",
-    "NewExact", "SnapshotData", "ExactSpread", "Summary", "TaskSummary", "FlowLifecycle", "HeavyHitter",
+    "NewExact", "SnapshotData", "ExactSpread", "Summary", "Change", "signed", "TaskSummary", "FlowLifecycle", "HeavyHitter",
     "make_filter", "merge_summaries", "checkpoint", "ExactView", "ExactHistory", "apply_delta", "CompactBatch",
     "SuperSpreadView", "rollup_plan", "spread_rollup_plan", "to16_to_encodeflow",
     "mask_prefix", "mask_keys", "prefix_plan", "make_prefix", "discount_heavy_prefixes", "HeavyHistory",

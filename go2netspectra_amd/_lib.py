@@ -46,7 +46,7 @@ EXPORTED = [
     "gns_exs_create", "gns_exs_destroy", "gns_exs_insert_keys", "gns_exs_insert_tuples", "gns_exs_insert_headers",
     "gns_exs_flush", "gns_exs_query", "gns_exs_query_device", "gns_exs_heavy_hitters", "gns_exs_snapshot",
     "gns_exs_reset", "gns_exs_counters", "gns_exs_dict_stats", "gns_exs_set_timing", "gns_exs_stage_times",
-    "gns_ex_aggregate", "gns_ex_heavy_hitters",
+    "gns_ex_aggregate", "gns_ex_heavy_hitters", "gns_ex_movers",
     "gns_ex_view_create", "gns_ex_view_destroy", "gns_ex_view_refresh", "gns_ex_view_snapshot",
     "gns_ex_view_aggregate", "gns_ex_view_heavy_hitters",
     "gns_pairs_export", "gns_pairs_merge", "gns_pairs_merge_from",
@@ -58,7 +58,7 @@ EXPORTED = [
     "gns_ex_rollup_prefix", "gns_spread_rollup_prefix", "gns_ex_aggregate_cidr", "gns_ex_view_aggregate_cidr",
     "gns_ex_hist_create", "gns_ex_hist_destroy", "gns_ex_hist_append", "gns_ex_hist_times", "gns_ex_hist_stats",
     "gns_ex_hist_aggregate", "gns_ex_hist_aggregate_cidr", "gns_ex_hist_heavy_hitters", "gns_ex_hist_snapshot",
-    "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows", "gns_ex_hist_rollup",
+    "gns_ex_hist_trim", "gns_ex_hist_export", "gns_ex_hist_append_rows", "gns_ex_hist_rollup", "gns_ex_hist_rollup_between",
     "gns_hh_hist_create", "gns_hh_hist_destroy", "gns_hh_hist_append", "gns_hh_hist_heavy_hitters",
     "gns_hh_hist_heavy_rows", "gns_hh_hist_times", "gns_hh_hist_stats", "gns_hh_hist_export",
     "gns_hh_hist_trim", "gns_hh_hist_query",
@@ -247,6 +247,7 @@ def load() -> ct.CDLL:
         "gns_exs_set_timing": ([vp, i32], i32), "gns_exs_stage_times": ([vp, vp, vp, i32], i32),
         "gns_ex_aggregate": ([vp, vp, u32, vp], i32),
         "gns_ex_heavy_hitters": ([vp, i32, u64, u64, vp, vp, vp], i32),
+        "gns_ex_movers": ([vp, i32, i32, u64, u64, vp, vp, vp], i32),
         "gns_cm_import_state": ([vp, vp, vp, vp, vp, vp], i32),
         "gns_ss_import_state": ([vp, vp, vp, vp, vp, u64, vp], i32),
         "gns_ex_merge": ([vp, vp, vp, vp, vp, vp, u64, i32], i32),
@@ -288,6 +289,7 @@ def load() -> ct.CDLL:
         "gns_ex_hist_export": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "gns_ex_hist_append_rows": ([vp, vp, vp, vp, vp, vp, u64, ct.c_int64, vp], i32),
         "gns_ex_hist_rollup": ([vp, vp, vp, vp, vp], i32),
+        "gns_ex_hist_rollup_between": ([vp, vp, vp, vp, vp, vp], i32),
         "gns_hh_hist_create": ([vp, vp], i32), "gns_hh_hist_destroy": ([vp], i32),
         "gns_hh_hist_append": ([vp, ct.c_int64, vp, u32, i32, vp], i32),
         "gns_hh_hist_heavy_hitters": ([vp, vp, u32, u64, u64, vp, vp, vp], i32),

@@ -50,6 +50,7 @@
 #include <cstring>
 #include <mutex>
 #include <optional>
+#include <type_traits>
 #include <vector>
 
 #include <rocprim/device/device_merge_sort.hpp>
@@ -1019,6 +1020,7 @@ struct ExSelSince {
 };
 struct ExSelAsOf {
     static constexpr bool kVersioned = true;
+    static constexpr bool kSigned = false;
     const uint32_t *written, *superseded;
     uint32_t s;
     __device__ __forceinline__ void test(uint64_t row, bool &seen, bool &live) const {
@@ -1153,11 +1155,22 @@ __device__ __forceinline__ unsigned long long exq_lane_u64(unsigned long long v,
 // table's and the views' instantiations keep their argument list.
 struct ExSelOcc {
     static constexpr bool kVersioned = false;
+    static constexpr bool kSigned = false;
+};
+// HH1 / HH2 of gns_ex_movers: ExSelOcc over a table whose counts are two's-complement changes.
+// The value is the magnitude of the signed change (as u64: INT64_MIN has 2^63), taken when the
+// change is not 0 and its sign matches dir (+1 increases, -1 decreases, 0 either).
+struct ExSelSigned {
+    static constexpr bool kVersioned = false;
+    static constexpr bool kSigned = true;
+    int dir;
 };
 __device__ __forceinline__ ExSelOcc exq_sel() { return ExSelOcc{}; }
 __device__ __forceinline__ const ExSelAsOf &exq_sel(const ExSelAsOf &sel) { return sel; }
+__device__ __forceinline__ const ExSelSigned &exq_sel(const ExSelSigned &sel) { return sel; }
 template <class... SL> struct ExSelPick { using type = ExSelOcc; };
 template <> struct ExSelPick<ExSelAsOf> { using type = ExSelAsOf; };
+template <> struct ExSelPick<ExSelSigned> { using type = ExSelSigned; };
 template <class... SL>
 using ExSelOf = typename ExSelPick<SL...>::type;
 
@@ -1320,6 +1333,12 @@ __device__ __forceinline__ bool exq_hh_take(const DictDev &D, const FlowState &f
         if (!live) return false;
         v = metric ? f.bytes[s] : f.pkts[s];
         return v >= thr;
+    } else if constexpr (SEL::kSigned) {
+        const unsigned long long pk = f.pkts[s];
+        const unsigned long long c = metric ? f.bytes[s] : pk;
+        const bool neg = (long long)c < 0;
+        v = neg ? 0ull - c : c;  // |change|; thr >= 1 (the host's), so a change of 0 is not taken
+        return D.rec[s * D.RW] != 0u && pk != 0ull && v >= thr && (sel.dir == 0 || (sel.dir < 0) == neg);
     } else {
         const unsigned long long pk = f.pkts[s];
         v = metric ? f.bytes[s] : pk;
@@ -1365,6 +1384,8 @@ __global__ __launch_bounds__(256) void k_exq_hh_collect(DictDev D, uint64_t slot
             row.v = v;
 #pragma unroll
             for (int i = 0; i < GNS_KWMAX; i++) row.k[i] = __builtin_bswap32(r[1 + i] & tail_mask(D.K, i));
+            if constexpr (ExSelOf<SL...>::kSigned)  // the sign rides in key byte 39, which no key has (K <= 37):
+                row.k[GNS_KWMAX - 1] |= (long long)(metric ? f.bytes[s] : f.pkts[s]) < 0 ? 1u : 0u;  // below every key bit
             rows[q] = row;
         }
     }
@@ -1381,6 +1402,13 @@ __global__ __launch_bounds__(256) void k_exq_hh_out(const ExHhRow *rows, uint64_
         keys[p * K + j] = (uint8_t)(w >> (8u * (3u - (j & 3u))));
     }
     vals[p] = row.v;
+}
+
+// gns_ex_movers after HH4: the magnitudes become the signed changes (ExSelSigned's sign bit)
+__global__ __launch_bounds__(256) void k_exq_mv_sign(const ExHhRow *rows, uint64_t n, unsigned long long *vals) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    if (rows[p].k[GNS_KWMAX - 1] & 1u) vals[p] = 0ull - vals[p];
 }
 
 // table growth: per-flow state follows its record to the new slot (gns_dict.hip remap)
@@ -1777,12 +1805,32 @@ __global__ __launch_bounds__(256) void k_exr_times(ExrRows R, uint64_t n, unsign
 // H2 reads first and writes start / end, H3 is the first to write first: every row of a new
 // slot sees it as new and stores the same two seeds, whichever lanes get there.
 // ---------------------------------------------------------------------------
+// The selection of a window (T0, T1] (gns_ex_hist_rollup_between), HistPlan::between's: lo =
+// s0 + 1.  A row (written a, superseded b) is a PLUS row when s0 < a <= s1 < b and a MINUS row
+// when a <= s0 < b <= s1.  The log is in snapshot order, so a row below minus_end has a <= s0
+// and a row from there to the scan's end s0 < a <= s1: one version word per row decides, and a
+// row live at both times (the common one) is never loaded.
+struct ExSelBetween {
+    const uint32_t *superseded;
+    uint32_t lo, s1;
+    uint64_t minus_end;
+    __device__ __forceinline__ void pick(uint64_t row, bool &take, bool &minus) const {
+        const uint32_t b = superseded[row];
+        minus = row < minus_end;
+        take = minus ? (lo <= b && b <= s1) : s1 < b;
+    }
+};
+
+// H1.  SEL = ExSelAsOf (the live rows) or ExSelBetween (plus and minus rows, r1 <= the rows as of
+// sel.s1; a minus row enters as {-pkts, -bytes, start = int64 max, end = int64 min}: it subtracts
+// under H3's wrapping adds and takes no part in its min / max, so H2 and H3 run unchanged).
 // grid covers log rows [r0, r1), r1 <= the rows as of sel.s; at most r1 - r0 rows are appended
-// (R.cnt zeroed by the host).  A wave none of whose rows is live loads no record.  R.first[row]
-// = the log row; R.last is not written.
-template <bool PX>
-__global__ __launch_bounds__(256) void k_exh_project(DictDev L, FlowState lf, ExSelAsOf sel, uint64_t r0, uint64_t r1,
+// (R.cnt zeroed by the host).  A wave none of whose rows is selected loads no record.
+// R.first[row] = the log row; R.last is not written.
+template <bool PX, class SEL = ExSelAsOf>
+__global__ __launch_bounds__(256) void k_exh_project(DictDev L, FlowState lf, SEL sel, uint64_t r0, uint64_t r1,
                                                      ExrPlan<PX> pl, ExrRows R) {
+    constexpr bool kBetween = std::is_same<SEL, ExSelBetween>::value;
     __shared__ uint32_t s_k[GNS_KWMAX][256];  // proj_fill_column
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint8_t *t;
@@ -1795,8 +1843,14 @@ __global__ __launch_bounds__(256) void k_exh_project(DictDev L, FlowState lf, Ex
         t = pl.t;
     }
     const uint64_t r = r0 + (uint64_t)blockIdx.x * 256 + tid;
-    bool seen = false, live = false;
-    if (r < r1) sel.test(r, seen, live);
+    bool live = false;
+    [[maybe_unused]] bool minus = false;
+    if constexpr (kBetween) {
+        if (r < r1) sel.pick(r, live, minus);
+    } else {
+        bool seen = false;
+        if (r < r1) sel.test(r, seen, live);
+    }
     const uint64_t m = __ballot(live);
     if (m == 0) return;
     const int leader = __ffsll((unsigned long long)m) - 1;
@@ -1819,8 +1873,14 @@ __global__ __launch_bounds__(256) void k_exh_project(DictDev L, FlowState lf, Ex
         if ((uint32_t)i >= pl.KW) break;  // uniform
         R.keys[row * pl.KW + i] = proj_word<PX>(s_k, tid, t, v4, pl.K, i);
     }
-    R.pkts[row] = lf.pkts[r]; R.bytes[row] = lf.bytes[r]; R.first[row] = r;
-    R.start[row] = lf.start[r]; R.end[row] = lf.end[r];
+    if constexpr (kBetween) {
+        const unsigned long long pk = lf.pkts[r], by = lf.bytes[r];
+        R.pkts[row] = minus ? 0ull - pk : pk; R.bytes[row] = minus ? 0ull - by : by; R.first[row] = r;
+        R.start[row] = minus ? INT64_MAX : lf.start[r]; R.end[row] = minus ? INT64_MIN : lf.end[r];
+    } else {
+        R.pkts[row] = lf.pkts[r]; R.bytes[row] = lf.bytes[r]; R.first[row] = r;
+        R.start[row] = lf.start[r]; R.end[row] = lf.end[r];
+    }
 }
 
 __global__ __launch_bounds__(256) void k_exh_seed(const uint32_t *ids, uint64_t n, FlowState f) {
@@ -2232,7 +2292,10 @@ int ex_geometry(gns_ex *ex) {
 // grows a Go map): when the dictionary fills, the table doubles.  Flows with
 // packets are reinserted (gns_dict.hip) and their state follows them; the
 // claims of an aborted batch (flows without packets yet) are dropped.
-int ex_grow(gns_ex *ex) {
+// keep_reached (gns_ex_hist_rollup_between): the slots that move are those some row has reached
+// (last != 0), not those with packets -- between two pieces of a window a group's packet change
+// may stand at 0 with a byte change and times that the next piece's rows still add to.
+int ex_grow(gns_ex *ex, bool keep_reached = false) {
     const uint64_t old_slots = ex->slots, new_slots = old_slots * 2;
     if (new_slots > (1ull << 30)) {
         set_error("exact flow dictionary cannot grow beyond 2^30 slots (%llu flows)", (unsigned long long)ex->claimed);
@@ -2248,7 +2311,7 @@ int ex_grow(gns_ex *ex) {
         return rc;
     }
     uint64_t slots = ex->slots, live = 0;
-    rc = dict_rebuild(ex->D, slots, nullptr, 0, ex->f.pkts, nullptr, 0, new_slots, ex->stream, ex->dsc, &live, nullptr);
+    rc = dict_rebuild(ex->D, slots, nullptr, 0, keep_reached ? ex->f.last : ex->f.pkts, nullptr, 0, new_slots, ex->stream, ex->dsc, &live, nullptr);
     if (rc != GNS_OK) {
         dfree(nf.pkts); dfree(nf.bytes); dfree(nf.first); dfree(nf.last); dfree(nf.start); dfree(nf.end);
         return rc;
@@ -2484,7 +2547,7 @@ int ex_aggregate_on(const KeyPlanN &kp, const ExTable &T, hipStream_t s, ExRead 
 // gns_ex_heavy_hitters over table T (the argument checks are the caller's)
 int ex_heavy_on(uint32_t K, const ExTable &T, hipStream_t s, ExRead &rd, StageTimer *timer, int metric,
                 uint64_t threshold, uint64_t limit, uint8_t *keys, uint64_t *values, uint64_t *n_io,
-                const ExSelAsOf *asof = nullptr) {
+                const ExSelAsOf *asof = nullptr, const ExSelSigned *mv = nullptr) {
     if (T.rows == 0) {  // a view without rows
         *n_io = 0;
         return GNS_OK;
@@ -2507,6 +2570,9 @@ int ex_heavy_on(uint32_t K, const ExTable &T, hipStream_t s, ExRead &rd, StageTi
         if (asof)
             hipLaunchKernelGGL(k_exq_hh_hist<ExSelAsOf>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
                                (unsigned long long)threshold, dh, *asof);
+        else if (mv)
+            hipLaunchKernelGGL(k_exq_hh_hist<ExSelSigned>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, dh, *mv);
         else
             hipLaunchKernelGGL(k_exq_hh_hist<>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
                                (unsigned long long)threshold, dh);
@@ -2541,6 +2607,9 @@ int ex_heavy_on(uint32_t K, const ExTable &T, hipStream_t s, ExRead &rd, StageTi
         if (asof)
             hipLaunchKernelGGL(k_exq_hh_collect<ExSelAsOf>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
                                (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows, *asof);
+        else if (mv)
+            hipLaunchKernelGGL(k_exq_hh_collect<ExSelSigned>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
+                               (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows, *mv);
         else
             hipLaunchKernelGGL(k_exq_hh_collect<>, dim3(grid), dim3(256), 0, s, T.D, T.rows, T.f, metric,
                                (unsigned long long)threshold, band, rd.rows[0], dh + kQBands, (uint32_t)nrows);
@@ -2550,6 +2619,9 @@ int ex_heavy_on(uint32_t K, const ExTable &T, hipStream_t s, ExRead &rd, StageTi
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_exq_hh_out, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, rd.rows[1], len,
                                K, rd.dk, rd.dv);
+            if (mv)
+                hipLaunchKernelGGL(k_exq_mv_sign, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, rd.rows[1], len,
+                                   rd.dv);
             e = hipGetLastError();
         }
     }
@@ -2615,9 +2687,9 @@ int exv_rows(gns_ex_view *v) {
 // vals[i] != 0) on ex's table, which grows as the rows need: no state is written before every
 // id of the piece is known.  *added, when given, grows by the slots the piece claimed.
 int ex_resolve_rows(gns_ex *ex, const uint8_t *keys, uint32_t stride, uint64_t m, const unsigned long long *vals,
-                    uint32_t *ids, KeyResolveScratch &sc, uint64_t *added) {
+                    uint32_t *ids, KeyResolveScratch &sc, uint64_t *added, bool keep_reached = false) {
     hipStream_t s = ex->stream;
-    if (ex->claimed >= ex->slots / 2) GNS_TRY(ex_grow(ex));  // keep the load <= ~1/2
+    if (ex->claimed >= ex->slots / 2) GNS_TRY(ex_grow(ex, keep_reached));  // keep the load <= ~1/2
     KeyResolve r{};
     r.keys = keys; r.stride = stride; r.n = m; r.live = KEYS_VAL64; r.vals = vals; r.ids = ids;
     r.full_word = ex->stats + 3;
@@ -2628,7 +2700,7 @@ int ex_resolve_rows(gns_ex *ex, const uint8_t *keys, uint32_t stride, uint64_t m
         if (rc != GNS_E_FULL) return rc;
         GNS_HIP(hipMemsetAsync(ex->stats + 3, 0, sizeof(unsigned long long), s));
         ex->n_retry++;
-        GNS_TRY(ex_grow(ex));  // the state already written follows the table; the piece's claims are dropped
+        GNS_TRY(ex_grow(ex, keep_reached));  // the state already written follows the table; the piece's claims are dropped
     }
 }
 }  // namespace
@@ -2860,6 +2932,24 @@ int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t li
     ExRead rd;
     const int rc = ex_heavy_on(ex->K, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, metric, threshold,
                                limit, keys, values, n_io);
+    rd.free_all();
+    return rc;
+}
+
+int gns_ex_movers(gns_ex *ex, int metric, int direction, uint64_t threshold, uint64_t limit, uint8_t *keys,
+                  int64_t *values, uint64_t *n_io) {
+    if (!ex || !n_io) { set_error("null argument"); return GNS_E_ARG; }
+    if (metric != 0 && metric != 1) { set_error("metric %d (0: PacketCount, 1: ByteCount)", metric); return GNS_E_ARG; }
+    if (direction < -1 || direction > 1) {
+        set_error("movers: direction %d (+1: increases, -1: decreases, 0: either)", direction);
+        return GNS_E_ARG;
+    }
+    GNS_TRY(set_device(ex->device));
+    ExRead rd;
+    const ExSelSigned mv{direction};
+    const int rc = ex_heavy_on(ex->K, ExTable{ex->D, ex->f, ex->slots}, ex->stream, rd, &ex->timer, metric,
+                               std::max<uint64_t>(threshold, 1), limit, keys, reinterpret_cast<uint64_t *>(values), n_io,
+                               nullptr, &mv);
     rd.free_all();
     return rc;
 }
@@ -3649,8 +3739,16 @@ int gns_ex_rollup_prefix(gns_ex *dst, gns_ex *src, const gns_prefix *px, uint64_
     return exr_rollup(dst, src, px, out);
 }
 
-int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const gns_prefix *px, uint64_t out[2]) {
+namespace {
+// gns_ex_hist_rollup (window == false: the rows live as of end_ns) and gns_ex_hist_rollup_between
+// (the plus and minus rows of the window (start_ns, end_ns]): one body, two H1 selections
+int exh_rollup(gns_ex *dst, gns_ex_hist *h, bool window, const int64_t *start_ns, const int64_t *end_ns,
+               const gns_prefix *px, uint64_t out[2]) {
     if (!dst || !h) { set_error("null argument"); return GNS_E_ARG; }
+    if (window && start_ns && end_ns && *start_ns > *end_ns) {
+        set_error("history rollup: the window starts at %lld, after its end %lld", (long long)*start_ns, (long long)*end_ns);
+        return GNS_E_ARG;
+    }
     if (px) GNS_TRY(px_check_prefix(px, "history rollup"));
     if (dst->device != h->device) {
         set_error("history rollup: dst is on device %d, the history on device %d", dst->device, h->device);
@@ -3665,10 +3763,17 @@ int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const
     // log under the kernels and an append waits
     std::lock_guard<std::mutex> lk(h->mu);
     ExSelAsOf sel;
+    ExSelBetween bsel{};
     ExTable T;
-    (void)exh_as_of(h, end_ns, &sel, &T);
+    if (window) {
+        const HistPlan::Between b = h->plan.between(start_ns, end_ns);
+        bsel = ExSelBetween{h->log.superseded, (uint32_t)(b.s0 + 1), (uint32_t)b.s1, b.minus_end};
+        T = ExTable{h->log.L, h->log.f, b.empty ? 0 : b.scan_end};  // (bad: checked above)
+    } else {
+        (void)exh_as_of(h, end_ns, &sel, &T);
+    }
     const uint64_t rows = T.rows;
-    if (rows == 0) return GNS_OK;  // no snapshot at or before the time (or none with rows): an empty source
+    if (rows == 0) return GNS_OK;  // no snapshot at or before the time (or none with rows; no snapshot in the window): an empty source
     const uint64_t piece = std::min<uint64_t>(test_piece("GNS_EX_ROLLUP_PIECE", kResolvePiece), rows);
     hipStream_t s = dst->stream;
     ExrRows R{};
@@ -3687,14 +3792,17 @@ int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const
             const uint64_t r1 = std::min<uint64_t>(r0 + piece, rows);
             GNS_HIP(hipMemsetAsync(R.cnt, 0, 4, s));
             const dim3 grid((unsigned)((r1 - r0 + 255) / 256));
-            if (px) hipLaunchKernelGGL(k_exh_project<true>, grid, dim3(256), 0, s, T.D, T.f, sel, r0, r1, pp, R);
+            if (window && px) hipLaunchKernelGGL((k_exh_project<true, ExSelBetween>), grid, dim3(256), 0, s, T.D, T.f, bsel, r0, r1, pp, R);
+            else if (window) hipLaunchKernelGGL((k_exh_project<false, ExSelBetween>), grid, dim3(256), 0, s, T.D, T.f, bsel, r0, r1, pl, R);
+            else if (px) hipLaunchKernelGGL(k_exh_project<true>, grid, dim3(256), 0, s, T.D, T.f, sel, r0, r1, pp, R);
             else hipLaunchKernelGGL(k_exh_project<false>, grid, dim3(256), 0, s, T.D, T.f, sel, r0, r1, pl, R);
             GNS_HIP(hipGetLastError());
             GNS_HIP(hipMemcpyAsync(dst->h_pin, R.cnt, 4, hipMemcpyDeviceToHost, s));
             GNS_HIP(hipStreamSynchronize(s));
             const uint64_t m = std::min<uint64_t>(dst->h_pin[0], r1 - r0);
             if (m == 0) continue;
-            GNS_TRY(ex_resolve_rows(dst, reinterpret_cast<const uint8_t *>(R.keys), 4 * pl.KW, m, R.pkts, R.ids, sc, &added));
+            GNS_TRY(ex_resolve_rows(dst, reinterpret_cast<const uint8_t *>(R.keys), 4 * pl.KW, m, R.pkts, R.ids, sc, &added,
+                                    window));
             wrote = true;
             hipLaunchKernelGGL(k_exh_seed, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)R.ids, m,
                                dst->f);
@@ -3720,6 +3828,16 @@ int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const
     sc.free_all();
     if (rc == GNS_OK && out) { out[0] = projected; out[1] = added; }
     return rc;
+}
+}  // namespace
+
+int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const gns_prefix *px, uint64_t out[2]) {
+    return exh_rollup(dst, h, false, nullptr, end_ns, px, out);
+}
+
+int gns_ex_hist_rollup_between(gns_ex *dst, gns_ex_hist *h, const int64_t *start_ns, const int64_t *end_ns,
+                               const gns_prefix *px, uint64_t out[2]) {
+    return exh_rollup(dst, h, true, start_ns, end_ns, px, out);
 }
 
 int gns_ex_reset(gns_ex *ex) {

@@ -48,6 +48,35 @@ struct HistPlan {
     // the rows a query as of snapshot s scans: every row of a later snapshot lies behind them
     uint64_t rows_as_of(int64_t s) const { return s < 0 ? 0 : end_rows[(size_t)s]; }
 
+    // A window (T0, T1] (gns_ex_hist_rollup_between): s0 = s(T0), -1 for a null start; s1 =
+    // s(T1), the newest for a null end.  Rows are in snapshot order, so a row below minus_end
+    // = rows_as_of(s0) was written at or before s0 and can only be a MINUS row (live at T0,
+    // displaced in the window), a row from there to scan_end = rows_as_of(s1) was written in
+    // the window and can only be a PLUS row (live at T1), and nothing beyond is scanned.
+    // bad: both times given and T0 > T1.  empty: no snapshot at or before T1, or none in the
+    // window (s0 == s1) -- nothing is scanned, whatever the row counts.
+    struct Between {
+        int64_t s0, s1;
+        uint64_t minus_end, scan_end;
+        bool bad, empty;
+    };
+    Between between(const int64_t *start, const int64_t *end) const {
+        Between b{-1, -1, 0, 0, false, true};
+        if (start && end && *start > *end) {
+            b.bad = true;
+            return b;
+        }
+        b.s1 = as_of(end);
+        b.s0 = start ? as_of(start) : -1;
+        if (b.s0 > b.s1) b.s0 = b.s1;  // a null end with a start after the newest snapshot
+        b.empty = b.s1 < 0 || b.s0 == b.s1;
+        if (!b.empty) {
+            b.minus_end = rows_as_of(b.s0);
+            b.scan_end = rows_as_of(b.s1);
+        }
+        return b;
+    }
+
     // the append is complete: snapshot ts.size() exists
     void publish(int64_t t, uint64_t n) {
         ts.push_back(t);

@@ -60,6 +60,13 @@ class Summary:  # gns_ex_summary: one filter's answer
 
 
 @dataclass
+class Change:  # one filter's totals over a window: summary(T1) - summary(T0), signed
+    flows: int = 0
+    packets: int = 0  # the difference of the two u64 sums, read as int64
+    bytes: int = 0
+
+
+@dataclass
 class TaskSummary:  # query.TaskSummary (querier.go:29-34)
     TaskName: str
     TotalBytes: int
@@ -361,6 +368,15 @@ def _no_end_time(end_time) -> None:
         raise ValueError("end_time is not supported: a live handle holds one point in time, no history of snapshots")
 
 
+def signed(a):
+    """The u64 count columns of a table of changes (``ExactHistory.delta(...).snapshot_arrays()``)
+    as the int64 changes they store in two's complement; an int as a Python int."""
+    if isinstance(a, (int, np.integer)):
+        v = int(a) & ((1 << 64) - 1)
+        return v - (1 << 64) if v >> 63 else v
+    return np.asarray(a, np.uint64).view(np.int64)
+
+
 def _ptr(a):
     return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
 
@@ -423,6 +439,17 @@ def _heavy_hitters(fn, h, key_bytes: int, metric: int, threshold: int, limit: in
         check(fn(h, metric, threshold, limit, keys.ctypes.data, vals.ctypes.data, ct.byref(n)))
     m = min(cap, n.value)
     return keys[:m, :key_bytes], vals[:m]
+
+
+def _movers(fn, h, key_bytes: int, metric: int, direction: int, threshold: int, limit: int):
+    if metric not in (0, 1):
+        raise ValueError(f"metric {metric}: 0 (PacketCount) or 1 (ByteCount)")
+    if direction not in (-1, 0, 1):
+        raise ValueError(f"direction {direction}: +1 (increases), -1 (decreases) or 0 (either)")
+    if threshold < 0 or limit < 0 or threshold >= 1 << 64 or limit >= 1 << 64:
+        raise ValueError("threshold and limit are unsigned 64-bit")
+    keys, vals = _heavy_hitters(lambda hh, m, t, l, *a: fn(hh, m, direction, t, l, *a), h, key_bytes, metric, threshold, limit)
+    return keys, vals.view(np.int64)
 
 
 def apply_delta(state: dict, arrays) -> dict:
@@ -562,12 +589,22 @@ def _int64_ns(what: str, t) -> int:
     return t
 
 
-def _end_ptr(end_time):
+def _end_ptr(end_time, what: str = "end_time"):
     """The end_ns argument of a gns_ex_hist_* query: NULL (the newest snapshot) or an int64."""
     if end_time is None:
         return None, None
-    c = ct.c_int64(_int64_ns("end_time", end_time))
+    c = ct.c_int64(_int64_ns(what, end_time))
     return c, ct.byref(c)
+
+
+def _window(start_time, end_time):
+    """The (start_ns, end_ns) arguments of gns_ex_hist_rollup_between, checked: (keep, start
+    pointer, end pointer)."""
+    k0, p0 = _end_ptr(start_time, "start_time")
+    k1, p1 = _end_ptr(end_time)
+    if k0 is not None and k1 is not None and k0.value > k1.value:
+        raise ValueError(f"start_time {k0.value} lies after end_time {k1.value}")
+    return (k0, k1), p0, p1
 
 
 class ExactHistory:
@@ -637,10 +674,17 @@ class ExactHistory:
         keep, ptr = _end_ptr(end_time)
         return lambda h, *a: getattr(self._L, "gns_ex_hist_" + name)(h, ptr, *a)
 
-    def aggregate(self, filters, end_time=None) -> List[Summary]:
+    def aggregate(self, filters, end_time=None, start_time=None):
         """ExactAggregator.aggregate as of ``end_time``: flows / packets / bytes over each flow's
-        latest row, first_ns / last_ns / max_packets / max_bytes over every row stored by then."""
-        return _aggregate(self._bind("aggregate", end_time), self._bind("aggregate_cidr", end_time), self._h, filters)
+        latest row, first_ns / last_ns / max_packets / max_bytes over every row stored by then.
+        With ``start_time``: one ``Change(flows, packets, bytes)`` per filter, summary(end_time) -
+        summary(start_time) as signed ints -- two device scans and a subtraction here."""
+        if start_time is None:
+            return _aggregate(self._bind("aggregate", end_time), self._bind("aggregate_cidr", end_time), self._h, filters)
+        _window(start_time, end_time)
+        filters = list(filters)
+        new, old = self.aggregate(filters, end_time=end_time), self.aggregate(filters, end_time=start_time)
+        return [Change(a.flows - b.flows, signed(a.packets - b.packets), signed(a.bytes - b.bytes)) for a, b in zip(new, old)]
 
     def heavy_hitters(self, metric: int, threshold: int = 0, limit: int = 0, end_time=None):
         """ExactAggregator.heavy_hitters over each flow's latest row as of ``end_time``."""
@@ -669,6 +713,46 @@ class ExactHistory:
             dst.close()
             raise
         return dst
+
+    # --- what changed in a window (gns_ex_hist_rollup_between, gns_ex_movers) ---
+    def delta(self, key_fields=None, prefix=None, start_time=None, end_time=None, **kw) -> "ExactAggregator":
+        """A new aggregator keyed on ``key_fields`` (None: the history's own layout) whose counts
+        are the CHANGES between ``start_time`` and ``end_time``: per group sum(T1) - sum(T0) in
+        two's complement (``signed`` reads the u64 columns), filled by
+        ``rollup_from_history(self, end_time, prefix, start_time)`` from the rows that differ
+        between the two snapshots only.  ``start_time=None``: from before the first snapshot, the
+        table as of ``end_time``.  A group whose packet change is 0 is no flow and is not listed,
+        whatever its byte change.  Times: min start / max end over the group's rows stored in the
+        window and current at ``end_time``."""
+        key_fields = self.key_fields if key_fields is None else list(key_fields)
+        rollup_plan(self.key_fields, key_fields)
+        if prefix is not None:
+            make_prefix(prefix)
+        _window(start_time, end_time)
+        kw.setdefault("device", self.device)
+        dst = ExactAggregator(key_fields, **kw)
+        try:
+            dst.rollup_from_history(self, end_time=end_time, prefix=prefix, start_time=start_time)
+        except Exception:
+            dst.close()
+            raise
+        return dst
+
+    def movers(self, key_fields, metric: int, direction: int = 0, threshold: int = 1, limit: int = 0, start_time=None,
+               end_time=None, prefix=None):
+        """The groups whose count changed most in the window: ``delta(key_fields, ...)``, its
+        ``ExactAggregator.movers`` list, and the table closed again."""
+        if metric not in (0, 1):
+            raise ValueError(f"metric {metric}: 0 (PacketCount) or 1 (ByteCount)")
+        if direction not in (-1, 0, 1):
+            raise ValueError(f"direction {direction}: +1 (increases), -1 (decreases) or 0 (either)")
+        if threshold < 0 or limit < 0 or threshold >= 1 << 64 or limit >= 1 << 64:
+            raise ValueError("threshold and limit are unsigned 64-bit")
+        tab = self.delta(key_fields, prefix=prefix, start_time=start_time, end_time=end_time)
+        try:
+            return tab.movers(metric, direction, threshold, limit)
+        finally:
+            tab.close()
 
     def table(self, end_time=None, **kw) -> "ExactAggregator":
         """The table as of ``end_time`` as a live handle of the history's own layout: the rows of
@@ -944,7 +1028,7 @@ class ExactAggregator:
             check(self._L.gns_ex_rollup_prefix(self._h, src._h, ct.byref(px), out))
         return int(out[0]), int(out[1])
 
-    def rollup_from_history(self, hist: "ExactHistory", end_time=None, prefix=None):
+    def rollup_from_history(self, hist: "ExactHistory", end_time=None, prefix=None, start_time=None):
         """gns_ex_hist_rollup: re-key the table ``hist`` holds as of ``end_time`` -- each flow's
         latest row stored by then, the rows ``hist.snapshot_arrays(end_time)`` lists -- onto this
         handle's layout, on the device.  The reference's GROUP BY over stored rows: the flows that
@@ -953,17 +1037,27 @@ class ExactAggregator:
         stream-order rule, log rows have no stream positions.  A key this handle already holds
         adds its counts and keeps the smaller start and the larger end.  ``prefix`` as
         ``rollup_from``'s.  hist is only read.  Returns (rows of hist projected, flows new in
-        this handle); (0, 0) when no snapshot lies at or before ``end_time``."""
+        this handle); (0, 0) when no snapshot lies at or before ``end_time``.
+
+        ``start_time`` (gns_ex_hist_rollup_between): only what changed after it enters -- the
+        rows stored in the window that are current at ``end_time`` add, the rows current at
+        ``start_time`` that were displaced in the window subtract (two's complement; ``signed``),
+        and times are the min / max over the former.  Returns (rows selected, flows new in this
+        handle); (0, 0) and no position spent when no snapshot lies in the window."""
         if not isinstance(hist, ExactHistory):
             raise TypeError("rollup_from_history takes an ExactHistory")
         rollup_plan(hist.key_fields, self.key_fields)
         px = make_prefix(prefix) if prefix is not None else None
-        keep, ptr = _end_ptr(end_time)
+        keep, sptr, ptr = _window(start_time, end_time)
         if hist.device != self.device:
             raise ValueError(f"rollup_from_history: this handle is on device {self.device}, "
                              f"the history on device {hist.device}")
         out = (ct.c_uint64 * 2)()
-        check(self._L.gns_ex_hist_rollup(self._h, hist._h, ptr, ct.byref(px) if px is not None else None, out))
+        pxp = ct.byref(px) if px is not None else None
+        if start_time is None:  # (a NULL start is the same call, bit for bit)
+            check(self._L.gns_ex_hist_rollup(self._h, hist._h, ptr, pxp, out))
+        else:
+            check(self._L.gns_ex_hist_rollup_between(self._h, hist._h, sptr, ptr, pxp, out))
         return int(out[0]), int(out[1])
 
     def rollup(self, key_fields: Sequence[str], prefix=None, **kw) -> "ExactAggregator":
@@ -1012,6 +1106,13 @@ class ExactAggregator:
         with PacketCount (metric 0) / ByteCount (metric 1) >= threshold, value descending, ties
         by key bytes ascending, cut to ``limit`` rows when limit != 0."""
         return _heavy_hitters(self._L.gns_ex_heavy_hitters, self._h, self.key_bytes, metric, threshold, limit)
+
+    def movers(self, metric: int, direction: int = 0, threshold: int = 1, limit: int = 0):
+        """gns_ex_movers on a table of changes (``ExactHistory.delta``): (keys [n, K], values
+        int64 [n]) of the groups whose packet (metric 0) / byte (metric 1) change v is not 0, has
+        the sign of ``direction`` (+1 increases, -1 decreases, 0 either) and |v| >= max(threshold,
+        1); |v| descending, ties by key bytes ascending, cut to ``limit`` rows when limit != 0."""
+        return _movers(lambda *a: self._L.gns_ex_movers(*a), self._h, self.key_bytes, metric, direction, threshold, limit)
 
     def hierarchical_heavy_hitters(self, field: str, levels, metric: int, threshold: int):
         """Exact hierarchical heavy hitters of one IP field: ``levels`` is a list of (IPv4 bits,
@@ -1160,13 +1261,19 @@ class ExactTask:
         return self.snapshot(view.snapshot_arrays())
 
     def rollup(self, name: str, key_fields: Sequence[str], num_shards: int = 0, prefix=None, end_time=None,
-               **kw) -> "ExactTask":
+               start_time=None, **kw) -> "ExactTask":
         """A full task keyed on ``key_fields`` (fields of this task's key, in any order) holding
         this task's flows re-keyed on the device (ExactAggregator.rollup): what a task configured
         with that key and fed the same packets -- their addresses masked by ``prefix``, when one is
         given -- holds.  It takes packets, queries, views and checkpoints like any other task.
         ``end_time``: the table as of that time, from the attached history
-        (ExactHistory.rollup; ValueError when none is attached) instead of the live one."""
+        (ExactHistory.rollup; ValueError when none is attached) instead of the live one.
+        ``start_time``: the changes from then to ``end_time`` (None: the newest snapshot) from the
+        attached history (ExactHistory.delta) -- counts are signed changes."""
+        if start_time is not None:
+            agg = self._window_history(start_time).delta(key_fields, prefix=prefix, start_time=start_time,
+                                                         end_time=end_time, **kw)
+            return ExactTask(name, key_fields, num_shards, agg=agg)
         src = self.agg if end_time is None else self._as_of(end_time)
         extra = {} if end_time is None else {"end_time": end_time}
         return ExactTask(name, key_fields, num_shards, agg=src.rollup(key_fields, prefix=prefix, **extra, **kw))
@@ -1265,34 +1372,49 @@ class ExactTask:
             _no_end_time(end_time)
         return h
 
+    def _window_history(self, start_time):
+        """The history a start_time query answers from; ValueError without one."""
+        h = getattr(self, "history", None)
+        if h is None:
+            raise ValueError("start_time is not supported: no history attached (keep_history first)")
+        return h
+
     # --- query.Querier (internal/query/querier.go) on the live table, or as of end_time ---
     def aggregate_flows_many(self, requests) -> List[TaskSummary]:
         """AggregateFlows (querier.go:251-319) for a batch of AggregationRequests.  A request is a
-        dict of src_ip / dst_ip / src_port / dst_port / protocol (absent or None: no constraint)
-        and end_time.  The requests without end_time are answered from the live table in ONE
-        device call; those with one from the attached history, one device call per distinct
-        end_time (ValueError when no history is attached)."""
+        dict of src_ip / dst_ip / src_port / dst_port / protocol (absent or None: no constraint),
+        end_time and start_time.  The requests without either are answered from the live table in
+        ONE device call; those with an end_time from the attached history, one device call per
+        distinct end_time (ValueError when no history is attached).  A request with start_time
+        answers with the signed changes of the window (ExactHistory.aggregate's Change; end_time
+        None: the newest snapshot), always from the history."""
         flt, at = [], []
         for req in requests:
             req = dict(req)
-            t = req.pop("end_time", None)
-            if t is not None:
+            t, t0 = req.pop("end_time", None), req.pop("start_time", None)
+            if t0 is not None:
+                self._window_history(t0)
+                _window(t0, t)
+            elif t is not None:
                 self._as_of(t)
-            at.append(t)
+            at.append((t0, t))
             flt.append(make_filter(**req))
-        out: List[Optional[Summary]] = [None] * len(flt)
-        for t in dict.fromkeys(at):  # distinct end times, in order of appearance
-            idx = [i for i, x in enumerate(at) if x == t]
+        out = [None] * len(flt)
+        for t0, t in dict.fromkeys(at):  # distinct windows / end times, in order of appearance
+            idx = [i for i, x in enumerate(at) if x == (t0, t)]
             sub = [flt[i] for i in idx]
-            res = self.agg.aggregate(sub) if t is None else self.history.aggregate(sub, end_time=t)
+            if t0 is not None:
+                res = self.history.aggregate(sub, end_time=t, start_time=t0)
+            else:
+                res = self.agg.aggregate(sub) if t is None else self.history.aggregate(sub, end_time=t)
             for i, r in zip(idx, res):
                 out[i] = r
         return [TaskSummary(self.name_, s.bytes, s.packets, s.flows) for s in out]
 
     def aggregate_flows(self, src_ip=None, dst_ip=None, src_port=None, dst_port=None, protocol=None,
-                        end_time=None) -> TaskSummary:
+                        end_time=None, start_time=None) -> TaskSummary:
         return self.aggregate_flows_many([dict(src_ip=src_ip, dst_ip=dst_ip, src_port=src_port, dst_port=dst_port,
-                                               protocol=protocol, end_time=end_time)])[0]
+                                               protocol=protocol, end_time=end_time, start_time=start_time)])[0]
 
     def trace_flow(self, flow_keys, end_time=None) -> FlowLifecycle:
         """TraceFlow (querier.go:322-372): min(StartTime), max(EndTime), max(PacketCount),
@@ -1318,6 +1440,23 @@ class ExactTask:
             keys, vals = hist.heavy_hitters(type, 0, limit, end_time=end_time)
         else:
             keys, vals = self.agg.heavy_hitters(type, 0, limit)
+        return [HeavyHitter(key_string(bytes(k), self.key_fields)[0], int(v)) for k, v in zip(keys, vals)]
+
+    def movers(self, type: int, limit: int, start_time=None, end_time=None, direction: int = 0) -> List[HeavyHitter]:
+        """The flows of this task's key whose PacketCount (Type 0) / ByteCount (Type 1) changed
+        most between ``start_time`` and ``end_time`` in the attached history
+        (ExactHistory.movers): ORDER BY abs(change) DESC LIMIT ``limit``, ties by key bytes;
+        ``Value`` is the signed change.  LIMIT 0 and an unknown Type select no row, as in
+        ``heavy_hitters``."""
+        hist = self._window_history(start_time)
+        if limit < 0:
+            raise ValueError("negative limit")
+        _window(start_time, end_time)
+        if direction not in (-1, 0, 1):
+            raise ValueError(f"direction {direction}: +1 (increases), -1 (decreases) or 0 (either)")
+        if type not in (0, 1) or limit == 0:
+            return []
+        keys, vals = hist.movers(self.key_fields, type, direction, 1, limit, start_time=start_time, end_time=end_time)
         return [HeavyHitter(key_string(bytes(k), self.key_fields)[0], int(v)) for k, v in zip(keys, vals)]
 
     def alerter_msg(self, rules) -> str:

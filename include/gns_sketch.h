@@ -770,6 +770,14 @@ int gns_ex_aggregate_cidr(gns_ex *ex, const gns_ex_cidr *filters, uint32_t nf, g
  * gns_ex_snapshot, values 64-bit.  threshold 0 lists every flow.  keys / values may be NULL. */
 int gns_ex_heavy_hitters(gns_ex *ex, int metric, uint64_t threshold, uint64_t limit,
                          uint8_t *keys, uint64_t *values, uint64_t *n_io);
+/* The signed heavy changers of a table whose counts are changes (gns_ex_hist_rollup_between):
+ * v = the packet (metric 0) or byte (metric 1) word read as int64.  A group is listed when it
+ * is a flow (pkts != 0), v != 0, the sign of v matches direction (+1: increases, -1: decreases,
+ * 0: either) and |v| >= max(threshold, 1), |v| as u64 (INT64_MIN has magnitude 2^63).  Order:
+ * |v| descending, key bytes ascending, cut to `limit` rows when limit != 0; values[] holds v
+ * itself.  *n_io, keys, values as gns_ex_heavy_hitters; GNS_E_ARG also for another direction. */
+int gns_ex_movers(gns_ex *ex, int metric, int direction, uint64_t threshold, uint64_t limit,
+                  uint8_t *keys, int64_t *values, uint64_t *n_io);
 
 /* Snapshot view: the table, or the flows touched since a cursor, exported and queried
  * CONCURRENTLY with ingest.  The reference's snapshotter hands every flow of every exact
@@ -924,8 +932,42 @@ int gns_ex_view_heavy_hitters(gns_ex_view *v, int metric, uint64_t threshold, ui
  *     append waits -- and an ingest-side call on dst.  The device work runs on dst's stream,
  *     ordered after the history's, in pieces of 2^20 log rows.  An error after the first piece
  *     leaves the pieces merged so far; the positions are spent.
+ *
+ * gns_ex_hist_rollup_between: what changed between two times, re-keyed into dst on the device.
+ * s0 = s(*start_ns) (-1 for NULL and before the first snapshot), s1 = s(*end_ns) (NULL: the
+ * newest).  A log row with version words (a, b) = (written, superseded) is a PLUS row when
+ * s0 < a <= s1 < b (live at T1, stored in the window), a MINUS row when a <= s0 < b <= s1 (live
+ * at T0, displaced in the window) and takes no part otherwise -- the row live at both times,
+ * the common one, is never loaded: rows are in snapshot order, so the rows below those as of
+ * s0 can only be minus rows and the rows from there to those as of s1 only plus rows, one
+ * version word per row decides, and nothing beyond is scanned.  Selected rows are projected
+ * (under px masked) and merged per projected key as in gns_ex_hist_rollup, with
+ *   - pkts / bytes: plus rows add, minus rows subtract (u64 wrap): the stored words are the
+ *     two's-complement signed change sum v(T1) - sum v(T0); read them as int64.  A group whose
+ *     packet change is exactly 0 is not a flow (the rule above), so its byte change is NOT
+ *     reported even when it is not 0.
+ *   - start = min(StartTime), end = max(EndTime) over the group's PLUS rows: the times of the
+ *     rows stored in the window and still current at T1.  Minus rows take no part; the store
+ *     has no tombstones, so every key with a minus row has a plus row.  A history stored as
+ *     whole views (not deltas) stores a row per flow and snapshot, so an unchanged flow yields
+ *     a plus and a minus row of equal counts: they cancel in the counts and the plus row widens
+ *     a coarser group's times.
+ *   - A key already in dst, positions (dst advances by the rows as of s1 when the scan runs),
+ *     layouts, prefixes, calling rules, pieces and error behaviour: gns_ex_hist_rollup's.  When
+ *     s1 < 0 or s0 == s1 nothing is scanned, no position is spent and out = {0, 0}.
+ *   - s0 = -1: gns_ex_hist_rollup(dst, h, end_ns, px), bit for bit.
+ *   - out (may be NULL): out[0] = rows selected (plus + minus), out[1] = slots claimed in dst:
+ *     the projected keys new to it, those of groups whose packet change is 0 included.
+ *   - Such a no-flow group keeps its slot, byte change and times while window calls follow one
+ *     another into dst (table growth inside this call moves every slot a row has reached), and
+ *     loses them at the next growth of dst in any other call (insert, merge, the as-of roll-up):
+ *     what a later row of that key adds to is history-dependent.  Do not rely on it.
+ *   - GNS_E_ARG before any device call also for *start_ns > *end_ns (both given).
+ * There is no counter-reset rule: a flow that came back smaller after a reset of the task
+ * reports a negative change, the honest table(T1) - table(T0).  gns_ex_movers (above) lists the
+ * heavy changers of such a table.
  * Not offered: a spread table straight from the log (go through a same-layout roll-up and
- * gns_spread_rollup), a delta roll-up between two times. */
+ * gns_spread_rollup), movers on views or straight off the log. */
 typedef struct gns_ex_hist gns_ex_hist;
 typedef struct gns_ex_hist_params { gns_layout key; uint64_t max_rows, max_flows; int device; } gns_ex_hist_params;
 int gns_ex_hist_create(const gns_ex_hist_params *p, gns_ex_hist **out);
@@ -946,6 +988,8 @@ int gns_ex_hist_heavy_hitters(gns_ex_hist *h, const int64_t *end_ns, int metric,
 int gns_ex_hist_snapshot(gns_ex_hist *h, const int64_t *end_ns, uint8_t *keys, int64_t *start_ns, int64_t *end_out_ns,
                          uint64_t *pkts, uint64_t *bytes, uint64_t *n_io);
 int gns_ex_hist_rollup(gns_ex *dst, gns_ex_hist *h, const int64_t *end_ns, const gns_prefix *px, uint64_t out[2]);
+int gns_ex_hist_rollup_between(gns_ex *dst, gns_ex_hist *h, const int64_t *start_ns, const int64_t *end_ns,
+                               const gns_prefix *px, uint64_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Heavy-hitter history: QueryHeavyHitters' EndTime for the sketches   */
