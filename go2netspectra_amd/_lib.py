@@ -9,6 +9,8 @@ import ctypes as ct
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GNS_LIB") or os.path.join(_HERE, "libgns_sketch.so")
 CSRC = os.path.join(_HERE, "csrc")
@@ -62,6 +64,7 @@ EXPORTED = [
     "gns_hh_hist_create", "gns_hh_hist_destroy", "gns_hh_hist_append", "gns_hh_hist_heavy_hitters",
     "gns_hh_hist_heavy_rows", "gns_hh_hist_times", "gns_hh_hist_stats", "gns_hh_hist_export",
     "gns_hh_hist_trim", "gns_hh_hist_query",
+    "gns_gomath_eval",
 ]
 
 
@@ -298,6 +301,7 @@ def load() -> ct.CDLL:
         "gns_hh_hist_export": ([vp, vp, vp, vp, vp, vp], i32),
         "gns_hh_hist_trim": ([vp, ct.c_int64, i32, vp], i32),
         "gns_hh_hist_query": ([vp, vp, u32, vp, u64, i32, vp, vp], i32),
+        "gns_gomath_eval": ([i32, vp, vp, u64, vp, vp, u64, i32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -375,6 +379,23 @@ def check(code: int) -> None:
     if code != GNS_OK:
         msg = (load().gns_last_error() or b"").decode(errors="replace")
         raise GnsError(code, msg)
+
+
+GM_POW, GM_LDEXP, GM_FREXP, GM_LOG, GM_LOG1M, GM_UNIFORM, GM_HLL_SEEDS = range(7)
+
+
+def gomath_eval(op: int, x, y=None, seed: int = 0, device: int = 0):
+    """Self-test hook (gns_gomath_eval): gns_gomath.cuh's device helpers over float64
+    arrays, integer arguments as bit patterns.  -> out, or (out, exponents) for GM_FREXP."""
+    x = np.ascontiguousarray(x, np.float64).reshape(-1)
+    y = None if y is None else np.ascontiguousarray(y, np.float64).reshape(-1)
+    if y is not None and y.size != x.size:
+        raise ValueError("gomath_eval: x and y differ in length")
+    out = np.empty(x.size, np.float64)
+    out2 = np.zeros(x.size, np.int32)
+    check(load().gns_gomath_eval(op, x.ctypes.data, None if y is None else y.ctypes.data, x.size,
+                                 out.ctypes.data, out2.ctypes.data, seed, device))
+    return (out, out2) if op == GM_FREXP else out
 
 
 def layout_bytes(fields) -> int:

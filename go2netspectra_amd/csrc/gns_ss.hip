@@ -598,7 +598,7 @@ __device__ __forceinline__ uint64_t rl64(uint64_t v, int j) {
 
 // one sampled encode: vv repeats of the MV step for flow f (state in val/key)
 struct MvState {
-    uint32_t val, key, mval;
+    uint32_t val, key, mval;  // mval: the val mppp / ml1m belong to; 0 = none yet (a foreign step never sees val 0)
     double mppp, ml1m;
 };
 // b^-val and log1m(b^-val) for val < kSsMvTab, computed once per workgroup into LDS
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(256) void k_ss_walk_mv(SsApplyArgs a) {
         const uint32_t k0 = a.heads[hi];
         const uint64_t cell = a.skey[k0] >> kSsPktBits;
         const uint32_t row = (uint32_t)(cell / a.g.w);
-        MvState st{a.values[cell], a.keys[cell], 0xFFFFFFFFu, 0.0, 0.0};
+        MvState st{a.values[cell], a.keys[cell], 0u, 0.0, 0.0};
         uint64_t kc = a.skey[k0], vc = a.sval[k0];
         int64_t rc = a.rep[k0];
         double lc = a.tp[k0];
@@ -690,7 +690,7 @@ __global__ __launch_bounds__(256) void k_ss_walk_mv(SsApplyArgs a) {
         const uint32_t k0 = a.heads[hj];
         const uint64_t cell = a.skey[k0] >> kSsPktBits;
         const uint32_t row = (uint32_t)(cell / a.g.w);
-        MvState st{a.values[cell], a.keys[cell], 0xFFFFFFFFu, 0.0, 0.0};
+        MvState st{a.values[cell], a.keys[cell], 0u, 0.0, 0.0};
         // windows of 64 encodes, three loads ahead of the one being stepped (a
         // superspreader's chain is thousands of encodes: the step is short, the load is not)
         struct Win { uint64_t k, v; int64_t r; double l; };

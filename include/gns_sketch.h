@@ -372,10 +372,12 @@ int gns_ss_export_state(gns_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *re
  * position, gns_ss_counters' [6] (records since create, dropped ones included):
  * it is part of the state -- without it a restored sketch draws other uniforms.
  * counters: NULL or the new [0..2].  pbits is taken as bit patterns.  A cell's key
- * is live when its bytes or its value are non-zero.  A register above 2^size - 1
- * is GNS_E_ARG: it would index past the power tables; the check runs on the device
- * before any state is written, and the handle stays untouched (as for a null
- * pointer).  Any later error leaves the handle as after gns_ss_reset. */
+ * is live when its bytes or its value are non-zero.  A key in a cell it does not
+ * hash to -- no stream produces one -- is never read by a query but counts in
+ * gns_ss_heavy_hitters (a flow's max over the cells that hold it).  A register
+ * above 2^size - 1 is GNS_E_ARG: it would index past the power tables; the check
+ * runs on the device before any state is written, and the handle stays untouched
+ * (as for a null pointer).  Any later error leaves the handle as after gns_ss_reset. */
 int gns_ss_import_state(gns_ss *ss, const uint32_t *values, const uint8_t *keys, const uint8_t *regs,
                         const double *pbits, uint64_t records, const uint64_t *counters /* [3] or NULL */);
 int gns_ss_stats(gns_ss *ss, uint64_t stats[4]);
@@ -1308,6 +1310,23 @@ int gns_spread_rollup_prefix(gns_exs *dst, gns_ex *src, const gns_prefix *flow_p
  * gns_*_insert_headers then reads with GNS_MEM_DEVICE). */
 int gns_device_alloc(uint64_t bytes, int device, void **out);
 int gns_device_free(void *p, int device);
+
+/* ---- self-test hooks ---- */
+/* The device float64 helpers SuperSpread's sequential step inlines (csrc/gns_gomath.cuh),
+ * evaluated over host arrays and returned to host arrays, so their roundings can be compared
+ * with another restatement bit for bit.  Integers travel as the bit patterns of the doubles:
+ *   GNS_GM_POW        out = go_pow_int(x, y)               Go math.Pow, integer y
+ *   GNS_GM_LDEXP      out = go_ldexp(x, (int)(int64)bits(y))
+ *   GNS_GM_FREXP      out, out2 = go_frexp(x)              out2 [n] int32, required
+ *   GNS_GM_LOG        out = gm_log(x)                      x in (0, 1]
+ *   GNS_GM_LOG1M      out = gm_log1m(x)                    0 < x < 1
+ *   GNS_GM_UNIFORM    out = ss_uniform(seed, pkt = bits(x), row = bits(y) >> 32, draw = (u32)bits(y))
+ *   GNS_GM_HLL_SEEDS  bits(out) = s1 << 32 | s0 of ss_hll_seeds(master = seed, cell = bits(x))
+ * y is read by POW, LDEXP and UNIFORM only, out2 by FREXP only (NULL otherwise).
+ * GNS_E_ARG: an unknown op, a null array the op needs, n > 2^30. */
+enum { GNS_GM_POW = 0, GNS_GM_LDEXP, GNS_GM_FREXP, GNS_GM_LOG, GNS_GM_LOG1M, GNS_GM_UNIFORM, GNS_GM_HLL_SEEDS };
+int gns_gomath_eval(int op, const double *x, const double *y, uint64_t n, double *out, int32_t *out2,
+                    uint64_t seed, int device);
 
 const char *gns_last_error(void);
 const char *gns_version(void);

@@ -578,6 +578,40 @@ double or_det_log1m(double p) {
     return or_det_log(1.0 - p);
 }
 
+/* Go math.Frexp (src/math/frexp.go): libm's frexp but for the special values. */
+double or_go_frexp(double x, int *e) {
+    if (x == 0 || isinf(x) || isnan(x)) { *e = 0; return x; }
+    return frexp(x, e);
+}
+
+/* The helpers over arrays (gns_gomath_eval's ops and packing: integers travel as the
+ * bit patterns of the doubles). */
+int or_gomath_eval(int op, const double *x, const double *y, uint64_t n, double *out, int32_t *out2, uint64_t seed) {
+    if (((op == 0 || op == 1 || op == 5) && !y) || (op == 2 && !out2)) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t xb, yb = 0;
+        memcpy(&xb, &x[i], 8);
+        if (y) memcpy(&yb, &y[i], 8);
+        switch (op) {
+        case 0: out[i] = or_go_pow(x[i], y[i]); break;
+        case 1: out[i] = or_go_ldexp(x[i], (int)(int64_t)yb); break;
+        case 2: { int e; out[i] = or_go_frexp(x[i], &e); out2[i] = e; break; }
+        case 3: out[i] = or_det_log(x[i]); break;
+        case 4: out[i] = or_det_log1m(x[i]); break;
+        case 5: out[i] = or_ss_uniform(seed, xb, (uint32_t)(yb >> 32), (uint32_t)yb); break;
+        case 6: {
+            uint32_t s0, s1;
+            or_ss_hll_seeds(seed, xb, &s0, &s1);
+            uint64_t r = (uint64_t)s1 << 32 | s0;
+            memcpy(&out[i], &r, 8);
+            break;
+        }
+        default: return -1;
+        }
+    }
+    return 0;
+}
+
 /* super_spread.go:207-233 for one (packet, row) after sampling passed.
  * Owner (or empty) counter: every remaining iteration increments (:211-220).
  * Foreign counter: iteration t decrements with probability b^-val (:222-227);
@@ -761,6 +795,18 @@ void or_ss_export(const or_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *reg
     if (keys) memcpy(keys, ss->keys, cells * ss->Kf);
     if (regs) memcpy(regs, ss->regs, cells * ss->m);
     if (pbits) memcpy(pbits, ss->pbits, cells * sizeof(double));
+}
+
+/* Host twin of gns_ss_import_state: the whole state replaced, pbits as bit
+ * patterns, records = the declared generator's position. */
+void or_ss_import(or_ss *ss, const uint32_t *values, const uint8_t *keys, const uint8_t *regs, const double *pbits,
+                  uint64_t records) {
+    size_t cells = (size_t)ss->d * ss->w;
+    memcpy(ss->values, values, cells * 4);
+    memcpy(ss->keys, keys, cells * ss->Kf);
+    memcpy(ss->regs, regs, cells * ss->m);
+    memcpy(ss->pbits, pbits, cells * sizeof(double));
+    ss->pkt = records;
 }
 
 /* super_spread.go:297-311 (pbits is not reset by the reference either) */

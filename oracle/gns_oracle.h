@@ -107,6 +107,10 @@ uint32_t or_ss_heavy(const or_ss *ss, uint8_t *flows, uint32_t *vals, uint32_t c
 void or_ss_export(const or_ss *ss, uint32_t *values, uint8_t *keys, uint8_t *regs, double *pbits);
 void or_ss_reset(or_ss *ss);
 uint64_t or_ss_packets(const or_ss *ss);
+/* host twin of gns_ss_import_state: arrays shaped as or_ss_export's, pbits copied as
+ * bit patterns, records = the declared generator's position (or_ss_packets) */
+void or_ss_import(or_ss *ss, const uint32_t *values, const uint8_t *keys, const uint8_t *regs, const double *pbits,
+                  uint64_t records);
 
 /* declared generator + Go helpers (exposed for tests) */
 uint64_t or_mix64(uint64_t x);
@@ -116,6 +120,10 @@ double or_go_pow(double x, double y);
 double or_det_log(double x);    /* deterministic log, x in (0, 1] */
 double or_det_log1m(double p);  /* log(1 - p), 0 < p < 1 */
 double or_go_ldexp(double frac, int e);
+double or_go_frexp(double x, int *e); /* Go math.Frexp: (x, 0) for 0, inf and NaN */
+/* The functions above over arrays, op and argument packing as gns_gomath_eval's
+ * (include/gns_sketch.h GNS_GM_*): the host side of tests/test_gomath_gpu.py. */
+int or_gomath_eval(int op, const double *x, const double *y, uint64_t n, double *out, int32_t *out2, uint64_t seed);
 
 /* splitmix64 stream (BASELINE/SURVEY §8d seeds) */
 uint64_t or_splitmix64_next(uint64_t *state);

@@ -101,6 +101,13 @@ def lib():
     L.or_ss_uniform.argtypes = [ct.c_uint64, ct.c_uint64, ct.c_uint32, ct.c_uint32]
     L.or_go_pow.restype = ct.c_double
     L.or_go_pow.argtypes = [ct.c_double, ct.c_double]
+    L.or_ss_import.argtypes = [ct.c_void_p] + [ct.c_void_p] * 4 + [ct.c_uint64]
+    L.or_go_ldexp.restype = ct.c_double
+    L.or_go_ldexp.argtypes = [ct.c_double, ct.c_int]
+    L.or_ss_hll_seeds.argtypes = [ct.c_uint64, ct.c_uint64, ct.c_void_p, ct.c_void_p]
+    L.or_gomath_eval.restype = ct.c_int
+    L.or_gomath_eval.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_uint64, ct.c_void_p, ct.c_void_p,
+                                 ct.c_uint64]
     _lib = L
     return L
 
@@ -278,6 +285,36 @@ class SuperSpread:
 
     def reset(self):
         self.L.or_ss_reset(self.h)
+
+    def import_state(self, values, keys, regs, pbits, records):
+        """Replace the whole state (or_ss_import): the arrays export() returns, pbits as
+        float64 or its uint64 bit patterns, records = the generator's position."""
+        n = self.d * self.w
+        values = np.ascontiguousarray(values, np.uint32).reshape(-1)
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        regs = np.ascontiguousarray(regs, np.uint8).reshape(-1)
+        pbits = np.ascontiguousarray(pbits).reshape(-1)
+        if pbits.dtype != np.float64:
+            pbits = pbits.view(np.float64) if pbits.dtype == np.uint64 else pbits.astype(np.float64)
+        if values.size != n or keys.size != n * self.kf or regs.size != n * self.m or pbits.size != n:
+            raise ValueError("import_state: arrays do not match the geometry")
+        self.L.or_ss_import(self.h, _p(values), _p(keys), _p(regs), _p(pbits), int(records))
+
+
+GM_POW, GM_LDEXP, GM_FREXP, GM_LOG, GM_LOG1M, GM_UNIFORM, GM_HLL_SEEDS = range(7)
+
+
+def gomath_eval(op, x, y=None, seed=0):
+    """or_gomath_eval: the Go-math helpers over arrays, packed as gns_gomath_eval packs
+    them (float64 arrays whose integer arguments are bit patterns).  -> out, or
+    (out, exponents) for GM_FREXP."""
+    x = np.ascontiguousarray(x, np.float64)
+    y = None if y is None else np.ascontiguousarray(y, np.float64)
+    out = np.empty(x.shape[0], np.float64)
+    out2 = np.zeros(x.shape[0], np.int32)
+    if lib().or_gomath_eval(op, _p(x), None if y is None else _p(y), x.shape[0], _p(out), _p(out2), seed) != 0:
+        raise ValueError(f"gomath_eval: unknown op {op}")
+    return (out, out2) if op == GM_FREXP else out
 
 
 class Exact:

@@ -223,6 +223,23 @@ def det_log1m(p: float) -> float:
     return det_log(1.0 - p)
 
 
+def _fdiv(a: float, b: float) -> float:
+    """IEEE-754 a / b, as Go and C divide: +-inf at a zero divisor, NaN at 0/0 and inf/inf."""
+    if b != 0:
+        return a / b  # inf / inf is NaN in Python too
+    if a == 0 or a != a:
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def _fceil(x: float) -> float:
+    """math.Ceil as a float64: inf stays, and -1 < x < 0 gives -0.0."""
+    if not math.isfinite(x):
+        return x
+    c = float(math.ceil(x))
+    return -0.0 if c == 0 and x < 0 else c
+
+
 class SuperSpreadSeq:
     """super_spread.go with injected HLL seeds and the declared generator."""
 
@@ -245,6 +262,29 @@ class SuperSpreadSeq:
         self.keys = [bytes(kf)] * n
         self.pkt = 0
 
+    def set_state(self, values, keys, regs, pbits, records) -> None:
+        """Replace the whole state (the twin of or_ss_import): per-cell lists, pbits as
+        Python floats, records = the generator's position."""
+        n = self.d * self.w
+        self.values = [int(v) for v in values]
+        self.keys = [bytes(k) for k in keys]
+        self.regs = [[int(r) for r in row] for row in regs]
+        self.pbits = [float(p) for p in pbits]
+        assert len(self.values) == len(self.keys) == len(self.regs) == len(self.pbits) == n
+        self.pkt = int(records)
+
+    def reset(self) -> None:
+        """super_spread.go:297-311: registers, keys and values; pbits stays."""
+        n = self.d * self.w
+        self.regs = [[0] * self.m for _ in range(n)]
+        self.values = [0] * n
+        self.keys = [bytes(self.kf)] * n
+
+    def _note(self, what: str, cell: int = -1, val: int = -1) -> None:
+        """Called in every branch with the branch's name (and, where it matters, the cell
+        and the counter value the step saw); a subclass counts them (tests/ss_regimes.py).
+        No effect on the state."""
+
     def _encode(self, cell, merged):
         s0, s1 = hll_seeds(self.hm, cell)
         h = mm3(merged, s0)
@@ -259,6 +299,11 @@ class SuperSpreadSeq:
         self.pbits[cell] = self.pbits[cell] + (-go_pow_int(self.base, float(old)) / float(self.m))
         if lz < self.maxv:
             self.pbits[cell] = self.pbits[cell] + go_pow_int(self.base, float(lz)) / float(self.m)
+        else:
+            self._note("lz_sat")
+        self._note("encode", cell)
+        if res == -1.0:
+            self._note("real_at_m1")  # a real update the caller's :196 test drops
         return res
 
     def insert(self, flow: bytes, elem: bytes) -> None:
@@ -270,38 +315,68 @@ class SuperSpreadSeq:
             p = self._encode(cell, merged)
             if p == -1.0:
                 continue
-            inv = 1.0 / p if p != 0 else math.inf
-            cv = math.ceil(inv) if math.isfinite(inv) else math.inf
-            pcu = inv / cv if math.isfinite(inv) else math.nan
+            if p == 0:
+                self._note("tempP_zero")
+            elif p < 0:
+                self._note("tempP_neg")
+                if p < -1:
+                    self._note("tempP_lt_m1")
+            inv = _fdiv(1.0, p)                 # +-inf at tempP == +-0
+            cv = _fceil(inv)                    # -0.0 for -1 < inv < 0
+            pcu = _fdiv(inv, cv)                # NaN at inf / inf, +inf at x / -0.0 (x < 0)
             if ss_uniform(self.rs, pkt, i, 0) >= pcu:
                 continue
-            vv = int(cv) if cv < 2.0 ** 63 else -(1 << 63)
+            # int(math.Ceil(..)) on amd64: out of range (and inf) -> MinInt64
+            vv = int(cv) if -(2.0 ** 63) <= cv < 2.0 ** 63 else -(1 << 63)
+            if vv <= 0:
+                self._note("vv_nonpos")
+            elif vv >= 1 << 31:
+                self._note("vv_big")
             self._mv(cell, flow, vv, pkt, i)
 
     def _mv(self, cell, flow, vv, pkt, row):
         """super_spread.go:207-233; foreign decrements as geometric waiting times."""
         draw = 1
+        dec = False  # a decrement happened inside this encode (census only)
         while vv > 0:
             if self.values[cell] == 0 or self.keys[cell] == flow:
                 if self.values[cell] == 0:
                     self.keys[cell] = flow
+                    if dec:
+                        self._note("takeover_after_dec")
+                if self.values[cell] + vv > M32:
+                    self._note("wrap")
                 self.values[cell] = (self.values[cell] + vv) & M32
                 return
-            ppp = go_pow_int(self.b, -float(self.values[cell]))
+            val = self.values[cell]
+            self._note("foreign", cell, val)
+            ppp = go_pow_int(self.b, -float(val))
+            if ppp < 1e-4:
+                self._note("ppp_series")
             if not ppp > 0:
+                self._note("ppp_zero")
                 return
+            if ppp < 2.2250738585072014e-308:
+                self._note("ppp_subnormal")
             if ppp >= 1:
-                k = min(self.values[cell], vv)
+                self._note("ppp_ge1", cell, val)  # decrements min(val, vv) >= 1 at once
+                k = min(val, vv)
                 self.values[cell] -= k
                 vv -= k
+                dec = True
                 continue
             u = ss_uniform(self.rs, pkt, row, draw)
+            if draw > 1:
+                self._note("draw_later")
             draw += 1
             q = det_log(1.0 - u) / det_log1m(ppp)
             if not q < float(vv):
+                self._note("wait_past")
                 return
             vv -= int(math.floor(q)) + 1
             self.values[cell] -= 1
+            dec = True
+            self._note("decrement", cell, val)
 
     def estimate(self, flow: bytes) -> int:
         est = 0

@@ -152,6 +152,52 @@ def test_det_log_c_python_and_accuracy(oracle):
         assert abs(c - math.log1p(-p)) <= 1e-12 * abs(math.log1p(-p))
 
 
+def _same_bits(c, py, what):
+    py = np.array(py, np.float64)
+    bad = np.nonzero(c.view(np.uint64) != py.view(np.uint64))[0]
+    assert len(bad) == 0, f"{what}: {len(bad)} differ, first at {bad[0]}: C={c[bad[0]]!r} pyref={py[bad[0]]!r}"
+
+
+def test_gomath_grids_c_vs_python(oracle):
+    """The grids the device helpers are compared on (gomath_grids.py, test_gomath_gpu.py): the C
+    oracle's side of that comparison equals pyref, the second restatement, bit for bit -- b^+-v
+    up to v = 12000 into the subnormal band and underflow, ldexp / frexp around their thresholds,
+    the log at its reduction boundary and the powers of two, log1m around its series cut, the
+    generator at packet indices around 2^27, 2^32 and 2^63."""
+    import math
+
+    import gomath_grids as G
+    x, y = G.pow_grid()
+    _same_bits(oracle.gomath_eval(oracle.GM_POW, x, y), [pyref.go_pow_int(a, b) for a, b in zip(x.tolist(), y.tolist())],
+               "go_pow")
+    x, e = G.ldexp_grid()
+
+    def py_ldexp(f, k):
+        try:
+            return math.ldexp(f, k)
+        except OverflowError:
+            return math.copysign(math.inf, f)
+    c = oracle.gomath_eval(oracle.GM_LDEXP, x, G.as_f64(e.view(np.uint64)))
+    _same_bits(c, [py_ldexp(f, k) for f, k in zip(x.tolist(), e.tolist())], "go_ldexp")
+    fx = np.unique(np.concatenate([x, c]))
+    cf, ce = oracle.gomath_eval(oracle.GM_FREXP, fx)
+    pf = [math.frexp(v) for v in fx.tolist()]
+    _same_bits(cf, [f for f, _ in pf], "go_frexp")
+    assert ce.tolist() == [k for _, k in pf]
+    x = G.log_grid()
+    _same_bits(oracle.gomath_eval(oracle.GM_LOG, x), [pyref.det_log(v) for v in x.tolist()], "det_log")
+    p = G.log1m_grid()
+    _same_bits(oracle.gomath_eval(oracle.GM_LOG1M, p), [pyref.det_log1m(v) for v in p.tolist()], "det_log1m")
+    pk, rd = G.uniform_grid()
+    c = oracle.gomath_eval(oracle.GM_UNIFORM, G.as_f64(pk), G.as_f64(rd), seed=G.UNIFORM_SEED)
+    _same_bits(c, [pyref.ss_uniform(G.UNIFORM_SEED, a, b >> 32, b & 0xFFFFFFFF) for a, b in zip(pk.tolist(), rd.tolist())],
+               "ss_uniform")
+    cells = G.cells_grid()
+    c = oracle.gomath_eval(oracle.GM_HLL_SEEDS, G.as_f64(cells), seed=G.HLL_MASTER).view(np.uint64)
+    want = [s1 << 32 | s0 for s0, s1 in (pyref.hll_seeds(G.HLL_MASTER, v) for v in cells.tolist())]
+    assert c.tolist() == want
+
+
 def _ipv6_zero_runs(rng, n):
     """IPv6 slots with random runs of zero groups (RFC 5952 '::' selection cases)."""
     out = rng.integers(0, 256, (n, 16), dtype=np.uint8)
